@@ -23,7 +23,18 @@ relaxation launch over the group's residues; a run of K steps is cut into groups
 inside the timed region.  `--group 1` is the per-step schedule of rounds 1-2 (every step launches its own fits, `--depth`
 steps in flight).
 
-One JSON line is printed by rank 0 (contract in the task statement) with extra objects:
+A plain run does only what the headline needs: set-up, W warm-up steps and the spin-up, ONE timed region of exactly K steps
+(`ms_per_step` = its wall time / K, `value` = triples / that), the outputs of its last step if `--dump-outputs DIR` is given, and
+the JSON line (metric, value, unit, ms_per_step, dtype, config, fit tallies).  Everything else -- three timed regions and their
+median (`--repeats`), the steady-state and random-dispatch regions, the upload-inclusive stream, the per-kernel and roofline
+figures, the checksummed extra batch, the CPU baseline and the CLI chain -- runs with `--full` only.
+
+`--dump-outputs DIR`: the results the last timed step computed (C(t), dC(t), the histogram of
+the anisotropic workloads, the selected model of every residue -- order index, components, S2, amplitudes, times -- and the
+R1/R2/NOE table), one float64 `DIR/<name>.npy` each, all ranks' vectors gathered.  Above 64 MB in all, a fixed, seeded sample of
+the vectors is written (its indices as `DIR/vector_index.npy`).  The inputs are seeded: the same arguments give the same inputs.
+
+With `--full`, one JSON line is printed by rank 0 (contract in the task statement) with extra objects:
   kernels       one entry per kernel of a step, every `frac` a fraction of a bound THAT kernel can reach, from what it
                 executes:  k_ct_rfft / k_ct_fft -- executed float64 flop / duration against the FP64 vector peak;  k_ct_palmer (the
                 direct formulation, timed alone as a second line) -- 8 flop x exact triples against the FP32 vector peak;
@@ -132,9 +143,11 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100, help='timed batches (the pipeline keeps --depth of them in flight; its fill and drain are inside the timed region)')
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--repeats', type=int, default=3, help='the timed region (exactly --steps steps between two synchronisations) is run this many times; value / ms_per_step are the MEDIAN, every sample is listed')
-    ap.add_argument('--spinup-s', type=float, default=1.0, help='untimed seconds of the same pipeline before the warm-up steps: a fresh box needs about a second under load before the clocks settle (5 warm-up steps are 15 ms)')
-    ap.add_argument('--steady-steps', type=int, default=120, help='steps of the extra (untimed for the headline) long run behind ms_per_step_steady; 0 = skip')
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline: three timed regions, steady-state and random-dispatch regions, the upload-inclusive stream, per-kernel / roofline figures, checksums, the CPU baseline and the CLI chain')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of the vectors above 64 MB in all)')
+    ap.add_argument('--repeats', type=int, default=None, help='the timed region (exactly --steps steps between two synchronisations) is run this many times; value / ms_per_step are the MEDIAN, every sample is listed (default 1; 3 with --full)')
+    ap.add_argument('--spinup-s', type=float, default=1.0, help='untimed seconds of the same pipeline after the warm-up steps, right before the timed region: a fresh box needs about a second under load before the clocks settle (5 warm-up steps are 15 ms)')
+    ap.add_argument('--steady-steps', type=int, default=120, help='--full: steps of the extra (untimed for the headline) long run behind ms_per_step_steady; 0 = skip')
     ap.add_argument('--workload', type=str, default='cfg3', choices=['cfg2', 'cfg3', 'cfg4'])
     ap.add_argument('--scaling', type=str, default='strong', choices=['strong', 'weak'],
                     help='strong (default): the workload\'s vectors are fixed and sharded over the ranks (N = 1 is the BENCH run); weak: every rank owns the full vector count')
@@ -163,15 +176,52 @@ def parse():
                     help='grouped schedule, order of the merged launch\'s residues: history = longest first by the evaluation counts of the last collected batch (a prediction; exact here because the benchmark repeats one shard -- the random-order figure is reported beside the headline), random = fixed pseudo-random order')
     ap.add_argument('--depth', type=int, default=5, help='batches in flight: the straggler tail of the last fit order of batch k overlaps batches k+1 .. k+depth-1 (1 = strictly serial steps)')
     ap.add_argument('--shard', type=str, default=None, help='r/N: time the vector range rank r of N would own under --scaling strong, alone on this GPU and without a process group (per-rank figures behind the scaling prediction of DESIGN.md section 7)')
-    ap.add_argument('--no-h2d-stream', action='store_true', help='skip the upload-inclusive figure (value_with_h2d: every step\'s shard from pinned host memory)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-cli-wall', action='store_true', help='skip the wall-clock run of the drop-in CLI chain (run-all.bash Step 3 + Step 4) on the same workload')
-    ap.add_argument('--no-kernel-profile', action='store_true', help='skip the per-kernel alone / saturated timings after the timed region (the `kernels` entries then only carry in-pipeline durations)')
+    ap.add_argument('--no-h2d-stream', action='store_true', help='--full: skip the upload-inclusive figure (value_with_h2d: every step\'s shard from pinned host memory)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-cli-wall', action='store_true', help='--full: skip the wall-clock run of the drop-in CLI chain (run-all.bash Step 3 + Step 4) on the same workload')
+    ap.add_argument('--no-kernel-profile', action='store_true', help='--full: skip the per-kernel alone / saturated timings after the timed region (the `kernels` entries then only carry in-pipeline durations)')
     ap.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend for N > 1 (nccl = RCCL; gloo only for rehearsals)')
     ap.add_argument('--all-ranks-on-device0', action='store_true', help='rehearsal on a 1-GPU box: every rank uses cuda:0 (needs --backend gloo)')
     ap.add_argument('--cpu-sample-vectors', type=int, default=6, help='vectors of the 1-thread reference-equivalent CPU sample (6: about 12 s of CPU work, run BEFORE the GPU is initialised)')
     ap.add_argument('--cpu-allcore-vectors', type=int, default=64, help='vectors of the all-core / CPU-FFT samples (>= 64: not cache-resident)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    return args
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20240917
+# the host results written: the selected model of every residue (index of its order in the search, number of components, S2,
+# amplitudes and times padded with 0 / 1 beyond K) and the R1/R2/NOE table.  The search's per-order trials (popt, dP, chisq,
+# status, nfev) and the selected chi^2 are not outputs of the path: their entries for orders the search did not attempt, for
+# parameters beyond an order's own and for a residue without an accepted model are NaN / inf markers, not computed values.
+DUMP_RESULTS = ('best', 'K', 'S2', 'C', 'tau', 'relax')
+# axis of the vector (residue) index in every array written: C(t) / dC(t) are (L, V), the histogram (V, bins); the host
+# results follow spinrelax_amd/pipeline.py's layouts (the table (fields, V, 4, 2))
+DUMP_VECTOR_AXIS = {'Ct': 1, 'dCt': 1, 'hist': 0, 'S2': 0, 'C': 0, 'tau': 0, 'relax': 1, 'best': 0, 'K': 0}
+
+
+def write_outputs(outdir, arrays):
+    """arrays: name -> host array with the vectors of the whole workload on DUMP_VECTOR_AXIS[name].  Writes float64 .npy files;
+    above DUMP_LIMIT_BYTES the same fixed, seeded sample of vectors from every array (indices in vector_index.npy)."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    V = arrays['Ct'].shape[1]
+    total = sum(a.nbytes for a in arrays.values())
+    index = None
+    if total > DUMP_LIMIT_BYTES:
+        keep = int((DUMP_LIMIT_BYTES - 2 ** 20) // (total / V + 8))          # room for the headers and the index file
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(V, size=keep, replace=False))
+        arrays = {k: np.take(a, index, axis=DUMP_VECTOR_AXIS[k]) for k, a in arrays.items()}
+        arrays['vector_index'] = index.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), np.ascontiguousarray(a))
+    return {'dir': outdir, 'files': sorted(n + '.npy' for n in arrays), 'bytes': int(sum(a.nbytes for a in arrays.values())),
+            'vectors': V, 'sampled_vectors': None if index is None else int(index.size)}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -441,7 +491,7 @@ def main():
     # ---- CPU baseline (rank 0, N = 1), also before the GPU is touched: it needs nothing from the device, and run first it
     # does not sit between the GPU phases of the run ----
     cpu_res = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu_res = cpu_baseline(vecs_host, s, cfg, min(args.cpu_sample_vectors, V), min(args.cpu_allcore_vectors, V))
 
     if args.all_ranks_on_device0:
@@ -535,12 +585,37 @@ def main():
                 ev.record(gstream)
             return ev
 
-        def run_batches(nb, events=None):
+        def run_batches(nb, events=None, on_finished=None):
             if grouped:
-                pipe.run(vecs, nb, events, on_enqueued=gather_results, on_part=gather_part)
+                pipe.run(vecs, nb, events, on_finished=on_finished, on_enqueued=gather_results, on_part=gather_part)
             else:
-                pipe.run(vecs, nb, events, on_enqueued=gather_results)
+                pipe.run(vecs, nb, events, on_finished=on_finished, on_enqueued=gather_results)
             torch.cuda.synchronize()
+
+        # --dump-outputs: the last batch the pipeline hands back in a run (its host results; its C(t), dC(t) and histogram stay
+        # in the pipeline's buffers until the next run)
+        last_batch = []
+
+        def keep_last(b):
+            last_batch[:] = [b]
+
+        def take_outputs():
+            """the last timed step's arrays on the host, every rank's vectors (all-gathered for N > 1); called by every rank"""
+            b = last_batch[0]
+            parts = {'Ct': b.Ct, 'dCt': b.dCt}
+            if q is not None:                                    # the isotropic workloads compute no histogram
+                parts['hist'] = b.hist
+            for name in DUMP_RESULTS if b.result is not None else ():
+                parts[name] = torch.from_numpy(np.ascontiguousarray(b.result[name])).to(dev)
+            out = {}
+            for name, tns in parts.items():
+                tns = tns.contiguous()
+                if world > 1:
+                    pieces = [torch.empty_like(tns) for _ in range(world)]
+                    dist.all_gather(pieces, tns)
+                    tns = torch.cat(pieces, dim=DUMP_VECTOR_AXIS[name])
+                out[name] = tns.cpu().numpy()
+            return out
 
         pipe.prime(vecs)                 # set-up (code objects, first touch of every in-flight slot), not a warm-up step
         if world > 1:                    # set-up: communicator and gather buffers exist before anything is timed
@@ -548,14 +623,18 @@ def main():
                 gather_results(sl)
             torch.cuda.synchronize()
             dist.barrier()
-        # clock spin-up (untimed, same work as the timed steps): run until --spinup-s seconds have passed
+        run_batches(args.warmup)
+        # clock spin-up (untimed, same work as the timed steps): run until --spinup-s seconds have passed.  After the warm-up steps,
+        # so that the timed region follows a run of its own length (behind the W-step run it was 2 % slower per step)
         spin_steps, t_spin = 0, time.perf_counter()
         spin_chunk = args.steps if grouped else 10     # grouped: the spin-up runs groups of the size the timed region uses
+        # ... and records the same per-kernel timing events (re-recorded every chunk), so that their first use is not in the timed region
+        spin_events = None if args.dev_no_events else [[torch.cuda.Event(enable_timing=True) for _ in range(6)] for _ in range(spin_chunk)]
         while time.perf_counter() - t_spin < args.spinup_s:
-            run_batches(spin_chunk)
+            run_batches(spin_chunk, spin_events)
             spin_steps += spin_chunk
+        del spin_events
         spin_s = time.perf_counter() - t_spin
-        run_batches(args.warmup)
         nfev0 = pipe.nfev_total
         samples = []
         events = None
@@ -566,17 +645,23 @@ def main():
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            run_batches(args.steps, None if args.dev_no_events else events)
+            run_batches(args.steps, None if args.dev_no_events else events, keep_last if args.dump_outputs else None)
             torch.cuda.synchronize()
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
             samples.append(time.perf_counter() - t0)
         nfev_timed = pipe.nfev_total - nfev0
+        dumped = None
+        if args.dump_outputs:            # before anything else reuses the pipeline's buffers
+            outputs = take_outputs()
+            if rank == 0:
+                dumped = write_outputs(args.dump_outputs, outputs)
+            del outputs
         # the same timed region with the prediction switched off (pseudo-random dispatch order of the merged launch), once: what a
         # stream of unrelated trajectories would see
         random_dispatch = None
-        if grouped and args.dispatch == 'history' and not args.no_permute:
+        if args.full and grouped and args.dispatch == 'history' and not args.no_permute:
             pipe.dispatch = 'random'
             run_batches(args.steps)
             torch.cuda.synchronize()
@@ -587,7 +672,7 @@ def main():
             run_batches(args.steps)                   # (re-establishes the history for what follows)
         # steady state: one long run, fill and drain amortised (reported beside the headline, never as it)
         steady = None
-        if args.steady_steps > 0:
+        if args.full and args.steady_steps > 0:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             run_batches(args.steady_steps)
@@ -595,7 +680,7 @@ def main():
 
     # ---- the same K steps with every step's shard coming from page-locked HOST memory (upload-inclusive stream) ----
     with_h2d = None
-    if grouped and not args.no_h2d_stream:
+    if args.full and grouped and not args.no_h2d_stream:
         shard_bytes = int(vecs_host.nbytes)
         haddr = ctx.host_alloc(shard_bytes)
         import ctypes
@@ -646,9 +731,10 @@ def main():
     def keep(b):
         last['Ct'], last['dCt'], last['hist'] = b.Ct.clone(), b.dCt.clone(), b.hist.clone()
         last['relax'] = torch.from_numpy(np.ascontiguousarray(b.result['relax'])).to(dev)
-    with torch.cuda.stream(stream):
-        pipe.run(vecs, 1, None, keep, None)
-    torch.cuda.synchronize()
+    if args.full:
+        with torch.cuda.stream(stream):
+            pipe.run(vecs, 1, None, keep, None)
+        torch.cuda.synchronize()
     checksums = None
     if last:
         import hashlib
@@ -678,7 +764,7 @@ def main():
 
     # ---- after the timed region: one batch at a time on the whole chip -- latency, every kernel alone, the fit saturated ----
     alone, latency = {}, None
-    if rank == 0 and not args.no_kernel_profile and not args.dev_skip_fits:
+    if args.full and rank == 0 and not args.no_kernel_profile and not args.dev_skip_fits:
         p1 = DevicePipeline(ctx, dev, s['frames'], V, s['R'], s['F'], s['dt'], depth=1, stream=torch.cuda.Stream(device=dev), **pkw)
         st1 = p1.main
         p1.step(vecs)
@@ -773,192 +859,194 @@ def main():
         use_rfft = use_fft and args.ct_fft in (-1, 2, 3, 4) and s['F'] + s['L'] > 4096
         use_f32 = use_fft and use_rfft32_bench(args, s)
         kname = 'k_ct_rfft32' if use_f32 else ('k_ct_rfft' if use_rfft else ('k_ct_fft' if use_fft else 'k_ct_palmer'))
-        prof, prof_src = committed_profile() if cfg == 3 and V == 512 else ({}, None)
-        stale, build_id = profile_staleness() if prof else (None, None)
-        stale_txt = ' -- STALE: collected with library build %s, this run loaded build %s (re-run scripts/profile_round.sh)' % (PROFILE_BUILD_ID, build_id) if stale else ''
-        N, R, L = s['N'], s['R'], s['L']
-        kernels = {}
+        kernels, roofline = {}, None
+        if args.full:
+            prof, prof_src = committed_profile() if cfg == 3 and V == 512 else ({}, None)
+            stale, build_id = profile_staleness() if prof else (None, None)
+            stale_txt = ' -- STALE: collected with library build %s, this run loaded build %s (re-run scripts/profile_round.sh)' % (PROFILE_BUILD_ID, build_id) if stale else ''
+            N, R, L = s['N'], s['R'], s['L']
+            kernels = {}
 
-        def entry(name, bound, work, unit_scale, peak, unit, t_pipe, t_alone, t_sat=None, **extra):
-            """work per launch (flop or bytes); achieved = work / duration; frac against `peak`."""
-            e = dict(bound=bound, work_per_launch=float(work), peak=peak, unit=unit)
-            if t_pipe:
-                e['in_pipeline_ms'] = t_pipe
-                e['achieved'] = work / (t_pipe * 1e-3) / unit_scale
-                e['frac'] = e['achieved'] / peak
-            if t_alone:
-                e['alone_ms'] = t_alone
-                e['achieved_alone'] = work / (t_alone * 1e-3) / unit_scale
-                e['frac_alone'] = e['achieved_alone'] / peak
-                if 'achieved' not in e:
-                    e['achieved'], e['frac'] = e['achieved_alone'], e['frac_alone']
-            sat = t_sat if t_sat else t_alone
-            if sat:
-                e['cu_ms_per_batch'] = sat * N_CU
-            pe = prof_entry(prof, name)
-            e['traffic'] = pe['hbm_bytes_corrected'] if pe else None
-            e['traffic_note'] = ('HBM bytes per launch (PMC 2*FETCH_SIZE + WRITE_SIZE) from the committed profile %s -- '
-                                 'not measured in this run%s' % (prof_src, stale_txt)) if pe else 'no committed PMC profile for this kernel / configuration'
-            e.update(extra)
-            kernels[name] = e
-            return e
+            def entry(name, bound, work, unit_scale, peak, unit, t_pipe, t_alone, t_sat=None, **extra):
+                """work per launch (flop or bytes); achieved = work / duration; frac against `peak`."""
+                e = dict(bound=bound, work_per_launch=float(work), peak=peak, unit=unit)
+                if t_pipe:
+                    e['in_pipeline_ms'] = t_pipe
+                    e['achieved'] = work / (t_pipe * 1e-3) / unit_scale
+                    e['frac'] = e['achieved'] / peak
+                if t_alone:
+                    e['alone_ms'] = t_alone
+                    e['achieved_alone'] = work / (t_alone * 1e-3) / unit_scale
+                    e['frac_alone'] = e['achieved_alone'] / peak
+                    if 'achieved' not in e:
+                        e['achieved'], e['frac'] = e['achieved_alone'], e['frac_alone']
+                sat = t_sat if t_sat else t_alone
+                if sat:
+                    e['cu_ms_per_batch'] = sat * N_CU
+                pe = prof_entry(prof, name)
+                e['traffic'] = pe['hbm_bytes_corrected'] if pe else None
+                e['traffic_note'] = ('HBM bytes per launch (PMC 2*FETCH_SIZE + WRITE_SIZE) from the committed profile %s -- '
+                                     'not measured in this run%s' % (prof_src, stale_txt)) if pe else 'no committed PMC profile for this kernel / configuration'
+                e.update(extra)
+                kernels[name] = e
+                return e
 
-        if use_f32:
-            M, xflop = fft32_exec_flop(s, V)
-            xflop_formula = float(xflop)
-            pe = prof_entry(prof, kname)
-            xsrc = 'formula (bench.py:fft32_exec_flop)'
-            if pe and pe.get('fp32_flop_per_launch'):
-                xflop, xsrc = pe['fp32_flop_per_launch'], 'PMC float32 instruction counts of the committed profile %s%s' % (prof_src, stale_txt)
-            entry(kname, 'valu-fp32 (packed float32 vector arithmetic; LDS-exchange- and latency-limited)', xflop, 1e12, PEAK_FP32_TFLOPS, 'TFLOP/s',
-                  ct_ms, alone.get('ct'),
-                  formulation='Wiener-Khinchin on real input in the reference\'s arithmetic type: 5 + 1 FLOAT32 complex transforms of %d points on the '
-                              'mean-removed traceless components (packed v_pk_*_f32 complex arithmetic), the mean terms restored in float64 by one scan '
-                              'per series; three workgroups per CU (spinrelax_amd/csrc/sr_ct32.hip)' % (M // 2),
-                  work_source=xsrc, work_per_launch_textbook=xflop_formula, executed_over_textbook=float(xflop) / xflop_formula,
-                  algorithmic_bytes=12 * N * V + 8 * R * L * V,
-                  float64_transform_kernel_alone_ms=alone.get('ct_rfft_f64'),
-                  accuracy='C(t) 4e-8 relative, dC(t) 3e-9 absolute against the float64 oracle on this workload (tests/test_gpu_pipeline.py); the reference itself computes C(t) in float32',
-                  note='in the pipeline the kernel is confined to %d of %d CUs' % (N_CU - reserve_used, N_CU))
-            if alone.get('ct_direct'):
-                entry('k_ct_palmer', 'valu-fp32 (non-MFMA vector FMA; FP32 MFMA peak is the same)', 8.0 * triples, 1e12, PEAK_FP32_TFLOPS, 'TFLOP/s',
-                      None, alone['ct_direct'], formulation='direct shifted products, 8 flop per (frame, vector, lag) triple (SURVEY 8(d)); second line, timed alone',
-                      algorithmic_bytes=12 * N * V + 8 * R * L * V)
-        elif use_fft:
-            M, xflop = fft_exec_flop(s, V, use_rfft, bool(args.ct_traceless))
-            xflop_formula = float(xflop)
-            pe = prof_entry(prof, kname)
-            xsrc = 'formula (bench.py:fft_exec_flop)'
-            if pe and pe.get('fp64_flop_per_launch'):
-                xflop, xsrc = pe['fp64_flop_per_launch'], 'PMC float64 instruction counts of the committed profile %s%s' % (prof_src, stale_txt)
-            form = ('Wiener-Khinchin on real input: %s float64 complex transforms of %d points (half the padded length), two workgroups per CU'
-                    % ('5 (traceless components; the trace term from window sums) + 1' if (bool(args.ct_traceless) and M == 6144) else '6 + 1', M // 2)
-                    if use_rfft else 'Wiener-Khinchin: 6 float64 autocorrelations by FFT, whole %d-point transform resident in LDS' % M)
-            entry(kname, 'valu-fp64 (float64 vector FMA; latency- and LDS-exchange-limited)', xflop, 1e12, PEAK_FP64_TFLOPS, 'TFLOP/s',
-                  ct_ms, alone.get('ct'), formulation=form, work_source=xsrc,
-                  work_per_launch_textbook=xflop_formula, executed_over_textbook=float(xflop) / xflop_formula,
-                  work_textbook_note='textbook operation count of the same transforms (5 N log2 N per complex N-point transform, 6 flop '
-                                     'per twiddle, 24 per frequency of the spectrum step; bench.py:fft_exec_flop) -- an upper bound: the '
-                                     'radix-12 / 16 register transforms have trivial twiddles and the zero blocks of the padded input are pruned, '
-                                     'so the kernel executes less (work_per_launch, PMC)',
-                  algorithmic_bytes=12 * N * V + 8 * R * L * V,
-                  note='in the pipeline the kernel is confined to %d of %d CUs' % (N_CU - reserve_used, N_CU))
-            if alone.get('ct_direct'):
-                entry('k_ct_palmer', 'valu-fp32 (non-MFMA vector FMA; FP32 MFMA peak is the same)', 8.0 * triples, 1e12, PEAK_FP32_TFLOPS, 'TFLOP/s',
-                      None, alone['ct_direct'], formulation='direct shifted products, 8 flop per (frame, vector, lag) triple (SURVEY 8(d)); second line, timed alone',
-                      algorithmic_bytes=12 * N * V + 8 * R * L * V)
-        else:
-            entry('k_ct_palmer', 'valu-fp32 (non-MFMA vector FMA; FP32 MFMA peak is the same)', 8.0 * triples, 1e12, PEAK_FP32_TFLOPS, 'TFLOP/s',
-                  ct_ms, alone.get('ct'), formulation='direct shifted products, 8 flop per triple', algorithmic_bytes=12 * N * V + 8 * R * L * V)
-        if q is not None:
-            entry('k_vechist', 'hbm', 12.0 * N * V + 8.0 * V * 2592, 1e9, PEAK_HBM_GBS, 'GB/s', hist_ms, alone.get('hist'),
-                  formulation='one pass over the planes: rotation + Lambert histogram + mean vector + S2 sums; bytes = 12 N V + 8 V 2592 (SURVEY 8(d))')
-        if alone.get('pack'):
-            entry('k_pack_soa', 'hbm', 24.0 * s['frames'] * V, 1e9, PEAK_HBM_GBS, 'GB/s', None, alone['pack'],
-                  formulation='frame-major -> per-vector planes: 12 B read + 12 B written per (frame, vector)')
-        if fit_ms is not None:
-            pe = prof_entry(prof, 'k_order_search')
-            fflop = pe.get('fp64_flop_per_launch') if pe else None
-            sat = alone.get('fit_saturated_per_batch')
-            tref = sat or alone.get('fit') or fit_ms
-            e = dict(bound='valu-fp64 issue + latency (one workgroup per residue, hundreds of dependent solver iterations)',
-                     in_pipeline_ms=fit_ms, in_pipeline_batches_per_launch=group_used,
-                     in_pipeline_ms_per_batch=fit_ms / group_used, alone_ms=alone.get('fit'), saturated_ms_per_batch=sat,
-                     cu_ms_per_batch=sat * N_CU if sat else None, residues=V, evaluations_per_batch=nfev_step,
-                     residues_per_s=V / (tref * 1e-3), evaluations_per_s=nfev_step / (tref * 1e-3),
-                     peak=PEAK_FP64_TFLOPS, unit='TFLOP/s',
-                     note='rates over the saturated duration (32 batches, longest residues first, in one launch / 32): the time the chip needs per batch when '
-                          'it is full of fits; a lone launch lasts as long as its slowest residue (alone_ms)')
-            if fflop:
-                e['work_per_launch'] = float(fflop)
-                e['achieved'] = fflop / (tref * 1e-3) / 1e12
-                e['frac'] = e['achieved'] / PEAK_FP64_TFLOPS
-                e['work_note'] = 'executed float64 flop per launch from the PMC pass of the committed profile %s (deterministic data)' % prof_src
-                if fit_ms:
-                    # the launch as it ran inside the timed region: merged over the group, residues in permuted order -- its
-                    # duration includes the tail in which only the last-started expensive residues are still running
-                    e['achieved_in_pipeline'] = fflop * group_used / (fit_ms * 1e-3) / 1e12
-                    e['frac_in_pipeline'] = e['achieved_in_pipeline'] / PEAK_FP64_TFLOPS
-                e['work_note'] += stale_txt
+            if use_f32:
+                M, xflop = fft32_exec_flop(s, V)
+                xflop_formula = float(xflop)
+                pe = prof_entry(prof, kname)
+                xsrc = 'formula (bench.py:fft32_exec_flop)'
+                if pe and pe.get('fp32_flop_per_launch'):
+                    xflop, xsrc = pe['fp32_flop_per_launch'], 'PMC float32 instruction counts of the committed profile %s%s' % (prof_src, stale_txt)
+                entry(kname, 'valu-fp32 (packed float32 vector arithmetic; LDS-exchange- and latency-limited)', xflop, 1e12, PEAK_FP32_TFLOPS, 'TFLOP/s',
+                      ct_ms, alone.get('ct'),
+                      formulation='Wiener-Khinchin on real input in the reference\'s arithmetic type: 5 + 1 FLOAT32 complex transforms of %d points on the '
+                                  'mean-removed traceless components (packed v_pk_*_f32 complex arithmetic), the mean terms restored in float64 by one scan '
+                                  'per series; three workgroups per CU (spinrelax_amd/csrc/sr_ct32.hip)' % (M // 2),
+                      work_source=xsrc, work_per_launch_textbook=xflop_formula, executed_over_textbook=float(xflop) / xflop_formula,
+                      algorithmic_bytes=12 * N * V + 8 * R * L * V,
+                      float64_transform_kernel_alone_ms=alone.get('ct_rfft_f64'),
+                      accuracy='C(t) 4e-8 relative, dC(t) 3e-9 absolute against the float64 oracle on this workload (tests/test_gpu_pipeline.py); the reference itself computes C(t) in float32',
+                      note='in the pipeline the kernel is confined to %d of %d CUs' % (N_CU - reserve_used, N_CU))
+                if alone.get('ct_direct'):
+                    entry('k_ct_palmer', 'valu-fp32 (non-MFMA vector FMA; FP32 MFMA peak is the same)', 8.0 * triples, 1e12, PEAK_FP32_TFLOPS, 'TFLOP/s',
+                          None, alone['ct_direct'], formulation='direct shifted products, 8 flop per (frame, vector, lag) triple (SURVEY 8(d)); second line, timed alone',
+                          algorithmic_bytes=12 * N * V + 8 * R * L * V)
+            elif use_fft:
+                M, xflop = fft_exec_flop(s, V, use_rfft, bool(args.ct_traceless))
+                xflop_formula = float(xflop)
+                pe = prof_entry(prof, kname)
+                xsrc = 'formula (bench.py:fft_exec_flop)'
+                if pe and pe.get('fp64_flop_per_launch'):
+                    xflop, xsrc = pe['fp64_flop_per_launch'], 'PMC float64 instruction counts of the committed profile %s%s' % (prof_src, stale_txt)
+                form = ('Wiener-Khinchin on real input: %s float64 complex transforms of %d points (half the padded length), two workgroups per CU'
+                        % ('5 (traceless components; the trace term from window sums) + 1' if (bool(args.ct_traceless) and M == 6144) else '6 + 1', M // 2)
+                        if use_rfft else 'Wiener-Khinchin: 6 float64 autocorrelations by FFT, whole %d-point transform resident in LDS' % M)
+                entry(kname, 'valu-fp64 (float64 vector FMA; latency- and LDS-exchange-limited)', xflop, 1e12, PEAK_FP64_TFLOPS, 'TFLOP/s',
+                      ct_ms, alone.get('ct'), formulation=form, work_source=xsrc,
+                      work_per_launch_textbook=xflop_formula, executed_over_textbook=float(xflop) / xflop_formula,
+                      work_textbook_note='textbook operation count of the same transforms (5 N log2 N per complex N-point transform, 6 flop '
+                                         'per twiddle, 24 per frequency of the spectrum step; bench.py:fft_exec_flop) -- an upper bound: the '
+                                         'radix-12 / 16 register transforms have trivial twiddles and the zero blocks of the padded input are pruned, '
+                                         'so the kernel executes less (work_per_launch, PMC)',
+                      algorithmic_bytes=12 * N * V + 8 * R * L * V,
+                      note='in the pipeline the kernel is confined to %d of %d CUs' % (N_CU - reserve_used, N_CU))
+                if alone.get('ct_direct'):
+                    entry('k_ct_palmer', 'valu-fp32 (non-MFMA vector FMA; FP32 MFMA peak is the same)', 8.0 * triples, 1e12, PEAK_FP32_TFLOPS, 'TFLOP/s',
+                          None, alone['ct_direct'], formulation='direct shifted products, 8 flop per (frame, vector, lag) triple (SURVEY 8(d)); second line, timed alone',
+                          algorithmic_bytes=12 * N * V + 8 * R * L * V)
             else:
-                e['achieved'] = e['frac'] = None
-                e['work_note'] = 'no committed float64-instruction PMC pass: flop rate not stated'
-            if fit_ms and sat:
-                # merged launch = bulk (the chip full of fits: saturated time per batch x batches) + tail (the last-started
-                # expensive residues finishing while nothing takes the freed slots; the group's histograms run there)
-                bulk = sat * group_used
-                e['in_pipeline_bulk_ms'] = bulk
-                e['in_pipeline_tail_ms'] = max(0.0, fit_ms - bulk)
-                e['in_pipeline_tail_frac'] = max(0.0, fit_ms - bulk) / fit_ms
-            e['traffic'] = pe['hbm_bytes_corrected'] if pe else None
-            e['traffic_note'] = 'from the committed profile %s -- not measured in this run%s' % (prof_src, stale_txt) if pe else None
-            e['algorithmic_bytes'] = 24 * V * L + 1024 * V
-            kernels['k_order_search'] = e
-        # how close the two float64 kernels are to what their occupancy lets the vector pipe issue (both hold 2 waves per SIMD)
-        probe = fp64_issue_probe()
-        if probe and prof:
-            ceil2 = probe['instr_per_us_per_simd_by_waves'].get('2')
-            for kn, dur_ms in ((kname, alone.get('ct')), ('k_order_search', alone.get('fit_saturated_per_batch'))):
-                pe = prof_entry(prof, kn)
-                if not (pe and pe.get('fp64_wave_instructions') and dur_ms and ceil2 and kn in kernels):
-                    continue
-                n64 = float(sum(pe['fp64_wave_instructions'].values()))
-                rate = n64 / 1024.0 / (dur_ms * 1e3)
-                kernels[kn]['fp64_issue'] = {
-                    'fp64_wave_instructions_per_launch': n64, 'duration_ms': dur_ms, 'waves_per_simd': 2,
-                    'fp64_instr_per_us_per_simd': rate, 'two_wave_ceiling': ceil2, 'frac_of_two_wave_ceiling': rate / ceil2,
-                    'note': 'float64 VALU wave-instructions (PMC) per SIMD and microsecond over the kernel alone / saturated, against what a '
-                            'SIMD holding two waves issues in the probe (%s): the other VALU instructions of the kernel are not '
-                            'counted, so the true figure is higher%s' % (probe['source'], stale_txt)}
-        # the kernel that occupies most of the chip per batch
-        off_step = {'k_ct_palmer'} if use_fft else set()
-        ranked = sorted(((v.get('cu_ms_per_batch') or 0.0, k) for k, v in kernels.items() if k not in off_step), reverse=True)
-        top = ranked[0][1] if ranked and ranked[0][0] > 0 else kname
-        tk = kernels[top]
-        roofline = {'kernel': top, 'bound': tk['bound'], 'achieved': tk.get('achieved'), 'peak': tk['peak'], 'unit': tk['unit'],
-                    'frac': tk.get('frac'), 'traffic': tk.get('traffic'), 'traffic_note': tk.get('traffic_note'),
-                    'selection': 'largest cu_ms_per_batch among the kernels of a step: ' + ', '.join('%s %.0f' % (k, c) for c, k in ranked),
-                    'kernel_ms': tk.get('saturated_ms_per_batch') or tk.get('in_pipeline_ms') or tk.get('alone_ms'),
-                    'direct_equivalent': {'note': 'for comparison only, NOT a roofline: the reference formulation (8 flop, 24 B streamed per triple) '
-                                                  'credited to the duration of the kernel that computes C(t)',
-                                          'kernel': kname, 'kernel_ms': ct_ms, 'TFLOPs_equiv': 8.0 * triples / (ct_ms * 1e-3) / 1e12,
-                                          'streaming_equiv_GBps': 24.0 * triples / (ct_ms * 1e-3) / 1e9}}
-        # what the whole chip does per step: executed float64 work of every kernel of a batch over the step time (the
-        # per-kernel `frac` of an overlapped pipeline is diluted by sharing: two C(t) launches, the pack, the histogram and the
-        # chunk statistics run at the same time -- per-step schedule: the fits of three batches as well --, so a launch's own
-        # duration says little about the chip)
-        prof_all, _ = committed_profile()
-        step_flop = sum(float(v.get('fp64_flop_per_launch') or 0.0) * (2 if k.startswith('k_transpose') else 1) for k, v in prof_all.items()
-                        if not k.startswith('k_fft_init'))
-        roofline['traffic_stale'] = stale
-        roofline['library_build_id'] = build_id
-        roofline['profile_build_id'] = PROFILE_BUILD_ID if prof else None
-        step_bytes = sum(float(v.get('hbm_bytes_corrected') or 0.0) * (2 if k.startswith('k_transpose') else 1) for k, v in prof_all.items()
-                         if not k.startswith('k_fft_init')) if prof else 0.0
-        if step_bytes > 0:
-            compulsory = 12.0 * s['frames'] * V + 16.0 * L * V + 8.0 * V * 2592
-            roofline['hbm_bytes_per_step'] = {'pmc': step_bytes, 'compulsory': compulsory, 'ratio': step_bytes / compulsory,
-                                              'GBps': step_bytes / (ms_per_step * 1e-3) / 1e9,
-                                              'note': 'sum over the kernels of a batch of the committed PMC pass (2*FETCH_SIZE + WRITE_SIZE: requests the L2s send to the '
-                                                      'fabric, Infinity-Cache hits included) against vectors in once + C(t), dC(t), histogram out; not measured in this run. '
-                                                      'The pack writes the planes once and they are read by kernel 1 and kernel 2 (1.84 GB of it); k_ct_rfft32 re-reads its '
-                                                      'planes per pass and, at four workgroups per CU, 128 x 48 KB per XCD exceed its 4 MB L2: 0.9 GB of re-reads come from the '
-                                                      'Infinity Cache (DESIGN.md section 4)%s' % stale_txt}
-        roofline['fp64_issue_probe'] = probe
-        roofline['frac_alone'] = tk.get('frac_alone')
-        roofline['launches_of_this_kernel_in_flight'] = (tk.get('in_pipeline_ms') or 0.0) / ms_per_step if ms_per_step else None
-        step_flop32 = sum(float(v.get('fp32_flop_per_launch') or 0.0) for k, v in prof_all.items() if not k.startswith('k_fft_init') and not k.startswith('k_ct32_init'))
-        roofline['chip'] = None if not (cfg == 3 and V == 512 and step_flop > 0) else {
-            'fp64_flop_per_step': step_flop, 'fp32_flop_per_step': step_flop32,
-            'TFLOPs_fp64': step_flop / (ms_per_step * 1e-3) / 1e12, 'TFLOPs_fp32': step_flop32 / (ms_per_step * 1e-3) / 1e12,
-            'frac': (step_flop / PEAK_FP64_TFLOPS + step_flop32 / PEAK_FP32_TFLOPS) / 1e12 / (ms_per_step * 1e-3),
-            'note': 'executed float64 and float32 flop of all kernels of a batch (committed PMC pass) over ms_per_step, each against its vector '
-                    'peak: the share of the step during which the vector pipes would be busy at their peak rates' + stale_txt, 'stale': stale}
+                entry('k_ct_palmer', 'valu-fp32 (non-MFMA vector FMA; FP32 MFMA peak is the same)', 8.0 * triples, 1e12, PEAK_FP32_TFLOPS, 'TFLOP/s',
+                      ct_ms, alone.get('ct'), formulation='direct shifted products, 8 flop per triple', algorithmic_bytes=12 * N * V + 8 * R * L * V)
+            if q is not None:
+                entry('k_vechist', 'hbm', 12.0 * N * V + 8.0 * V * 2592, 1e9, PEAK_HBM_GBS, 'GB/s', hist_ms, alone.get('hist'),
+                      formulation='one pass over the planes: rotation + Lambert histogram + mean vector + S2 sums; bytes = 12 N V + 8 V 2592 (SURVEY 8(d))')
+            if alone.get('pack'):
+                entry('k_pack_soa', 'hbm', 24.0 * s['frames'] * V, 1e9, PEAK_HBM_GBS, 'GB/s', None, alone['pack'],
+                      formulation='frame-major -> per-vector planes: 12 B read + 12 B written per (frame, vector)')
+            if fit_ms is not None:
+                pe = prof_entry(prof, 'k_order_search')
+                fflop = pe.get('fp64_flop_per_launch') if pe else None
+                sat = alone.get('fit_saturated_per_batch')
+                tref = sat or alone.get('fit') or fit_ms
+                e = dict(bound='valu-fp64 issue + latency (one workgroup per residue, hundreds of dependent solver iterations)',
+                         in_pipeline_ms=fit_ms, in_pipeline_batches_per_launch=group_used,
+                         in_pipeline_ms_per_batch=fit_ms / group_used, alone_ms=alone.get('fit'), saturated_ms_per_batch=sat,
+                         cu_ms_per_batch=sat * N_CU if sat else None, residues=V, evaluations_per_batch=nfev_step,
+                         residues_per_s=V / (tref * 1e-3), evaluations_per_s=nfev_step / (tref * 1e-3),
+                         peak=PEAK_FP64_TFLOPS, unit='TFLOP/s',
+                         note='rates over the saturated duration (32 batches, longest residues first, in one launch / 32): the time the chip needs per batch when '
+                              'it is full of fits; a lone launch lasts as long as its slowest residue (alone_ms)')
+                if fflop:
+                    e['work_per_launch'] = float(fflop)
+                    e['achieved'] = fflop / (tref * 1e-3) / 1e12
+                    e['frac'] = e['achieved'] / PEAK_FP64_TFLOPS
+                    e['work_note'] = 'executed float64 flop per launch from the PMC pass of the committed profile %s (deterministic data)' % prof_src
+                    if fit_ms:
+                        # the launch as it ran inside the timed region: merged over the group, residues in permuted order -- its
+                        # duration includes the tail in which only the last-started expensive residues are still running
+                        e['achieved_in_pipeline'] = fflop * group_used / (fit_ms * 1e-3) / 1e12
+                        e['frac_in_pipeline'] = e['achieved_in_pipeline'] / PEAK_FP64_TFLOPS
+                    e['work_note'] += stale_txt
+                else:
+                    e['achieved'] = e['frac'] = None
+                    e['work_note'] = 'no committed float64-instruction PMC pass: flop rate not stated'
+                if fit_ms and sat:
+                    # merged launch = bulk (the chip full of fits: saturated time per batch x batches) + tail (the last-started
+                    # expensive residues finishing while nothing takes the freed slots; the group's histograms run there)
+                    bulk = sat * group_used
+                    e['in_pipeline_bulk_ms'] = bulk
+                    e['in_pipeline_tail_ms'] = max(0.0, fit_ms - bulk)
+                    e['in_pipeline_tail_frac'] = max(0.0, fit_ms - bulk) / fit_ms
+                e['traffic'] = pe['hbm_bytes_corrected'] if pe else None
+                e['traffic_note'] = 'from the committed profile %s -- not measured in this run%s' % (prof_src, stale_txt) if pe else None
+                e['algorithmic_bytes'] = 24 * V * L + 1024 * V
+                kernels['k_order_search'] = e
+            # how close the two float64 kernels are to what their occupancy lets the vector pipe issue (both hold 2 waves per SIMD)
+            probe = fp64_issue_probe()
+            if probe and prof:
+                ceil2 = probe['instr_per_us_per_simd_by_waves'].get('2')
+                for kn, dur_ms in ((kname, alone.get('ct')), ('k_order_search', alone.get('fit_saturated_per_batch'))):
+                    pe = prof_entry(prof, kn)
+                    if not (pe and pe.get('fp64_wave_instructions') and dur_ms and ceil2 and kn in kernels):
+                        continue
+                    n64 = float(sum(pe['fp64_wave_instructions'].values()))
+                    rate = n64 / 1024.0 / (dur_ms * 1e3)
+                    kernels[kn]['fp64_issue'] = {
+                        'fp64_wave_instructions_per_launch': n64, 'duration_ms': dur_ms, 'waves_per_simd': 2,
+                        'fp64_instr_per_us_per_simd': rate, 'two_wave_ceiling': ceil2, 'frac_of_two_wave_ceiling': rate / ceil2,
+                        'note': 'float64 VALU wave-instructions (PMC) per SIMD and microsecond over the kernel alone / saturated, against what a '
+                                'SIMD holding two waves issues in the probe (%s): the other VALU instructions of the kernel are not '
+                                'counted, so the true figure is higher%s' % (probe['source'], stale_txt)}
+            # the kernel that occupies most of the chip per batch
+            off_step = {'k_ct_palmer'} if use_fft else set()
+            ranked = sorted(((v.get('cu_ms_per_batch') or 0.0, k) for k, v in kernels.items() if k not in off_step), reverse=True)
+            top = ranked[0][1] if ranked and ranked[0][0] > 0 else kname
+            tk = kernels[top]
+            roofline = {'kernel': top, 'bound': tk['bound'], 'achieved': tk.get('achieved'), 'peak': tk['peak'], 'unit': tk['unit'],
+                        'frac': tk.get('frac'), 'traffic': tk.get('traffic'), 'traffic_note': tk.get('traffic_note'),
+                        'selection': 'largest cu_ms_per_batch among the kernels of a step: ' + ', '.join('%s %.0f' % (k, c) for c, k in ranked),
+                        'kernel_ms': tk.get('saturated_ms_per_batch') or tk.get('in_pipeline_ms') or tk.get('alone_ms'),
+                        'direct_equivalent': {'note': 'for comparison only, NOT a roofline: the reference formulation (8 flop, 24 B streamed per triple) '
+                                                      'credited to the duration of the kernel that computes C(t)',
+                                              'kernel': kname, 'kernel_ms': ct_ms, 'TFLOPs_equiv': 8.0 * triples / (ct_ms * 1e-3) / 1e12,
+                                              'streaming_equiv_GBps': 24.0 * triples / (ct_ms * 1e-3) / 1e9}}
+            # what the whole chip does per step: executed float64 work of every kernel of a batch over the step time (the
+            # per-kernel `frac` of an overlapped pipeline is diluted by sharing: two C(t) launches, the pack, the histogram and the
+            # chunk statistics run at the same time -- per-step schedule: the fits of three batches as well --, so a launch's own
+            # duration says little about the chip)
+            prof_all, _ = committed_profile()
+            step_flop = sum(float(v.get('fp64_flop_per_launch') or 0.0) * (2 if k.startswith('k_transpose') else 1) for k, v in prof_all.items()
+                            if not k.startswith('k_fft_init'))
+            roofline['traffic_stale'] = stale
+            roofline['library_build_id'] = build_id
+            roofline['profile_build_id'] = PROFILE_BUILD_ID if prof else None
+            step_bytes = sum(float(v.get('hbm_bytes_corrected') or 0.0) * (2 if k.startswith('k_transpose') else 1) for k, v in prof_all.items()
+                             if not k.startswith('k_fft_init')) if prof else 0.0
+            if step_bytes > 0:
+                compulsory = 12.0 * s['frames'] * V + 16.0 * L * V + 8.0 * V * 2592
+                roofline['hbm_bytes_per_step'] = {'pmc': step_bytes, 'compulsory': compulsory, 'ratio': step_bytes / compulsory,
+                                                  'GBps': step_bytes / (ms_per_step * 1e-3) / 1e9,
+                                                  'note': 'sum over the kernels of a batch of the committed PMC pass (2*FETCH_SIZE + WRITE_SIZE: requests the L2s send to the '
+                                                          'fabric, Infinity-Cache hits included) against vectors in once + C(t), dC(t), histogram out; not measured in this run. '
+                                                          'The pack writes the planes once and they are read by kernel 1 and kernel 2 (1.84 GB of it); k_ct_rfft32 re-reads its '
+                                                          'planes per pass and, at four workgroups per CU, 128 x 48 KB per XCD exceed its 4 MB L2: 0.9 GB of re-reads come from the '
+                                                          'Infinity Cache (DESIGN.md section 4)%s' % stale_txt}
+            roofline['fp64_issue_probe'] = probe
+            roofline['frac_alone'] = tk.get('frac_alone')
+            roofline['launches_of_this_kernel_in_flight'] = (tk.get('in_pipeline_ms') or 0.0) / ms_per_step if ms_per_step else None
+            step_flop32 = sum(float(v.get('fp32_flop_per_launch') or 0.0) for k, v in prof_all.items() if not k.startswith('k_fft_init') and not k.startswith('k_ct32_init'))
+            roofline['chip'] = None if not (cfg == 3 and V == 512 and step_flop > 0) else {
+                'fp64_flop_per_step': step_flop, 'fp32_flop_per_step': step_flop32,
+                'TFLOPs_fp64': step_flop / (ms_per_step * 1e-3) / 1e12, 'TFLOPs_fp32': step_flop32 / (ms_per_step * 1e-3) / 1e12,
+                'frac': (step_flop / PEAK_FP64_TFLOPS + step_flop32 / PEAK_FP32_TFLOPS) / 1e12 / (ms_per_step * 1e-3),
+                'note': 'executed float64 and float32 flop of all kernels of a batch (committed PMC pass) over ms_per_step, each against its vector '
+                        'peak: the share of the step during which the vector pipes would be busy at their peak rates' + stale_txt, 'stale': stale}
         res = {
             'metric': 'frame-vector-lag triples/s, C(t) + fit + R1/R2/NOE pipeline',
             'value': value, 'unit': 'triples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': ms_per_step, 'timed_region_samples_ms_per_step': [x / args.steps * 1e3 for x in samples],
-            'timed_region_note': 'the timed region (exactly %d steps between two synchronisations, fill and drain inside) was run %d times; '
+            'timed_region_note': 'the timed region (exactly %d steps between two synchronisations, fill and drain inside) was run %d time(s); '
                                  'value and ms_per_step are the median' % (args.steps, len(samples)),
             'value_with_h2d': None if with_h2d is None else triples_total / with_h2d,
             'with_h2d': None if with_h2d is None else {
@@ -973,7 +1061,7 @@ def main():
                              'same shard; ms_per_step_random_dispatch is the same timed region (once) with the fixed pseudo-random order of rounds 3-4',
             'ms_per_step_steady': None if steady is None else steady * 1e3,
             'steady_note': 'one run of %d steps, fill and drain amortised; not the headline' % args.steady_steps,
-            'spinup': {'seconds': spin_s, 'steps': spin_steps, 'note': 'untimed steps of the same pipeline before the warm-up steps (clock ramp of a fresh box)'},
+            'spinup': {'seconds': spin_s, 'steps': spin_steps, 'note': 'untimed steps of the same pipeline after the warm-up steps, right before the timed region (clock ramp of a fresh box)'},
             'latency_ms': latency, 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
             'dtype': ('f32 transforms + f64 mean terms and chunk statistics (C(t): the reference\'s own type); f64 (histogram, fit, J(w), R1/R2/NOE)' if use_f32 else
                       'f64 (C(t) by FFT on f32 inputs; histogram, fit, J(w), R1/R2/NOE)' if use_fft else
@@ -1006,10 +1094,18 @@ def main():
             'setup': {'synth_s': gen_s},
             **({'INVALID': 'fits skipped (--dev-skip-fits)'} if args.dev_skip_fits else {}),
         }
-        res['cpu_baseline'] = cpu_res            # measured before the GPU was initialised (rank 0, N = 1)
-        res['checksums'] = checksums
-        if world == 1 and not args.no_cli_wall:
-            res['cli_wall_s'] = cli_wall(vecs_host, s, cfg, res['cpu_baseline'])
+        if args.full:
+            res['cpu_baseline'] = cpu_res            # measured before the GPU was initialised (rank 0, N = 1)
+            res['checksums'] = checksums
+            if world == 1 and not args.no_cli_wall:
+                res['cli_wall_s'] = cli_wall(vecs_host, s, cfg, res['cpu_baseline'])
+        else:                                        # a plain run measures none of these
+            for k in ('value_with_h2d', 'with_h2d', 'ms_per_step_random_dispatch', 'dispatch_note', 'ms_per_step_steady', 'steady_note',
+                      'latency_ms', 'roofline', 'kernels', 'stages_alone_ms'):
+                del res[k]
+        res['full'] = bool(args.full)
+        if dumped is not None:
+            res['dump_outputs'] = dumped
         print(json.dumps(res))
     # deterministic teardown while the HIP runtime is alive: streams, pinned mirrors and the context's work areas go
     # here, not in __del__ / static destructors at interpreter exit

@@ -15,6 +15,6 @@ for v in fit_fast:4 fit_fast:8 fit_tab:4 fit_tab:8 fit_maxilp:4 fit_trackers:4; 
 done
 for nv in 256 128 64; do
   echo "== strong shard $nv vectors" | tee -a $out/shard.log
-  timeout -k 10 200 python bench.py --vectors $nv --steps 20 --warmup 5 --no-cpu-baseline --no-cli-wall --no-kernel-profile --steady-steps 60 2>/dev/null \
+  timeout -k 10 200 python bench.py --full --vectors $nv --steps 20 --warmup 5 --no-cpu-baseline --no-cli-wall --no-kernel-profile --steady-steps 60 2>/dev/null \
     | python3 -c "import sys,json; j=json.loads(sys.stdin.read()); print(j['config']['vectors_per_gpu'], 'ms_per_step', j['ms_per_step'], j['timed_region_samples_ms_per_step'], 'steady', j['ms_per_step_steady'], 'fit merged ms', j['kernels']['k_order_search']['in_pipeline_ms'], 'ct ms', j['kernels']['k_ct_rfft']['in_pipeline_ms'])" | tee -a $out/shard.log
 done

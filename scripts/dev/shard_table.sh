@@ -1,7 +1,7 @@
 #!/bin/bash
 # Per-rank step times of the strong-scaling shards, one rank at a time on ONE GPU (bench.py --shard r/N): the slowest rank of
 # every N sets the pace of the N-GPU run.  usage (GPU box, repo root): bash scripts/dev/shard_table.sh
-short="--steps 20 --warmup 5 --no-cpu-baseline --no-kernel-profile --no-cli-wall --no-h2d-stream"
+short="--full --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-profile --no-cli-wall --no-h2d-stream"
 for N in 1 2 4 8; do
     for ((r = 0; r < N; ++r)); do
         timeout -k 10 200 python bench.py $short --shard $r/$N 2>/dev/null |

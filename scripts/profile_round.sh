@@ -14,11 +14,11 @@ cd /tmp
 export TMPDIR=/tmp
 # which library the figures belong to (spinrelax_amd/build.py:build_id, compiled into the library): stored in every JSON summary
 python3 -c "import sys; sys.path.insert(0, '$root'); from spinrelax_amd import _lib; print(_lib.load().sr_build_id().decode())" > $out/build_id.txt
-short="--no-cpu-baseline --no-kernel-profile --no-cli-wall --spinup-s 0 --repeats 1 --steady-steps 0"
+short="--full --no-cpu-baseline --no-kernel-profile --no-cli-wall --spinup-s 0 --repeats 1 --steady-steps 0"
 # (1) kernel statistics of the benchmark command the driver runs (the per-kernel alone / saturated launches after the
 #     timed region, the CPU baseline and the CLI chain are left out so that the averages are the in-pipeline durations)
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- \
-    python3 $root/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-profile --no-cli-wall > $out/stats.log 2>&1
+    python3 $root/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-profile --no-cli-wall > $out/stats.log 2>&1
 echo "stats done"
 # (1b) the same kernels ONE BATCH AT A TIME (--depth 1: nothing overlaps): every average is the kernel's duration alone on
 #      the chip -- the "alone" fractions can be recomputed from this file without bench.py
@@ -56,7 +56,7 @@ for pass in "palmer_FETCH:FETCH_SIZE" "palmer_WRITE:WRITE_SIZE" "palmer_VALU:SQ_
 done
 # (6) BASELINE cfg2's size (F + L = 1536 -> k_ct_fft<8>): statistics and HBM counters
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/cfg2_stats -- \
-    python3 $root/bench.py --workload cfg2 --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-profile --no-cli-wall > $out/cfg2_stats.log 2>&1 || echo "cfg2 stats FAILED"
+    python3 $root/bench.py --full --workload cfg2 --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-profile --no-cli-wall > $out/cfg2_stats.log 2>&1 || echo "cfg2 stats FAILED"
 for pass in "cfg2_FETCH:FETCH_SIZE" "cfg2_WRITE:WRITE_SIZE" "cfg2_FP64:SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64"; do
     name=${pass%%:*}; ctr=${pass#*:}
     timeout -k 10 300 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $out/$name -- \

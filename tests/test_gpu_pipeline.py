@@ -509,7 +509,7 @@ def test_bench_two_ranks_on_one_device(tmp_path):
     result all-gathers on their own stream, max-over-ranks timing) must reproduce the one-rank run of the same 64 vectors --
     the checksums of the gathered C(t), dC(t), histogram and R1/R2/NOE table are those of the single-process run, `value`
     counts the workload's triples once -- and the weak mode keeps every rank on its own 64 vectors."""
-    common = ['--steps', '4', '--warmup', '1', '--vectors', '64', '--no-cpu-baseline', '--no-cli-wall', '--no-kernel-profile', '--spinup-s', '0',
+    common = ['--full', '--steps', '4', '--warmup', '1', '--vectors', '64', '--no-cpu-baseline', '--no-cli-wall', '--no-kernel-profile', '--spinup-s', '0',
               '--steady-steps', '0', '--repeats', '2']
     two = ['--gpus', '2', '--backend', 'gloo', '--all-ranks-on-device0']
     one = _run_bench(['--gpus', '1'] + common)
@@ -530,11 +530,42 @@ def test_bench_two_ranks_on_one_device(tmp_path):
 def test_bench_cfg4_workload_flag():
     """`--workload cfg4` (BASELINE configs[3]: 100 000 frames x 2 048 vectors, what 8 GPUs share at 256 vectors each) on one
     device with a reduced vector count: the line names the workload, counts its triples and carries the result checksums."""
-    j = _run_bench(['--gpus', '1', '--workload', 'cfg4', '--vectors', '64', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-cli-wall',
+    j = _run_bench(['--full', '--gpus', '1', '--workload', 'cfg4', '--vectors', '64', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-cli-wall',
                     '--no-kernel-profile', '--spinup-s', '0', '--steady-steps', '0', '--repeats', '1'])
     assert 'cfg4' in j['config']['workload'] and j['config']['vectors_total'] == 64 and j['scaling'] == 'strong'
     assert j['config']['exact_triples_total'] == 24 * 64 * (2048 * 4096 - 2048 * 2049 // 2)
     assert j['checksums']['shapes']['Ct'] == [2048, 64] and j['fit']['unfitted'] == 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps once and reports the headline without the figures that need runs of
+    their own; --dump-outputs writes what its last timed step computed.  The same arguments with --full dump the same arrays
+    (seeded inputs), and C(t), dC(t), histogram and table are those the --full run's checksummed extra batch of the shard yields."""
+    import hashlib
+    flags = ['--gpus', '1', '--vectors', '64', '--steps', '3', '--warmup', '1', '--spinup-s', '0']
+    plain = _run_bench(flags + ['--dump-outputs', str(tmp_path / 'plain')])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'config', 'fit'):
+        assert k in plain, k
+    for k in ('roofline', 'kernels', 'latency_ms', 'ms_per_step_steady', 'with_h2d', 'checksums', 'cpu_baseline', 'cli_wall_s'):
+        assert k not in plain, k
+    assert plain['full'] is False and plain['steps'] == 3 and plain['timed_region_samples_ms_per_step'] == [plain['ms_per_step']]
+    assert abs(plain['value'] - plain['config']['exact_triples_total'] / (plain['ms_per_step'] * 1e-3)) <= 1e-6 * plain['value']
+    d = plain['dump_outputs']
+    assert d['vectors'] == 64 and d['sampled_vectors'] is None and d['bytes'] <= 64 * 10 ** 6
+    full = _run_bench(flags + ['--full', '--no-cpu-baseline', '--no-cli-wall', '--no-kernel-profile', '--no-h2d-stream', '--steady-steps', '0',
+                               '--dump-outputs', str(tmp_path / 'full')])
+    assert full['full'] is True and full['dump_outputs']['files'] == d['files']
+    names = [f[:-len('.npy')] for f in d['files']]
+    assert set(names) == {'Ct', 'dCt', 'hist', 'relax', 'S2', 'C', 'tau', 'K', 'best'}
+    for n in names:
+        a, b = np.load(tmp_path / 'plain' / (n + '.npy')), np.load(tmp_path / 'full' / (n + '.npy'))
+        assert a.dtype == np.float64 and np.all(np.isfinite(a)) and np.array_equal(a, b), n
+    for n in ('Ct', 'dCt', 'hist', 'relax'):
+        a = np.load(tmp_path / 'plain' / (n + '.npy'))
+        assert list(a.shape) == full['checksums']['shapes'][n], n
+        assert hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16] == full['checksums'][n], n
+    best = np.load(tmp_path / 'plain' / 'best.npy')
+    assert best.shape == (64,) and np.all(best >= 0)
 
 
 def test_bench_single_rank_under_torchrun_equals_plain_run():
@@ -570,7 +601,7 @@ def test_bench_json_contract():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '6', '--warmup', '1', '--cpu-sample-vectors', '1', '--spinup-s', '0.2', '--steady-steps', '20'],
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '6', '--warmup', '1', '--cpu-sample-vectors', '1', '--spinup-s', '0.2', '--steady-steps', '20'],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]

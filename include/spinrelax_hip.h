@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 9
+#define SR_ABI_VERSION 10
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -55,8 +55,10 @@ int          sr_sync(sr_ctx *);
  * 512-residue benchmark batch against 0.60 at 4 and 0.82 at 1; a lone launch lasts 6.9 ms at 2, 6.3 at 4, 24.7 at 1; results are
  * bit-identical only between runs with the same value), "fit_lds" = 1/0 keep
  * a residue's t, C(t), 1/sigma in LDS, "fit_geo" = 1/0 (default 1): when a residue's time axis is a uniform grid (t[l] = t[0] + l dt
- * to 8 ulp -- checked per residue on the device; any other axis always takes exp() per point) the fit kernels form exp(-t/tau) at
- * the points a thread owns by multiplication, exp() once per thread: within 1e-15 of exp() per point, 17 % less time per batch
+ * to 1.8e-15 relative -- checked per residue on the device; any other axis always takes exp() per point) the fit kernels form
+ * exp(-t/tau) at the points a thread owns by multiplication, exp() once per thread: a point j products past its thread's exp()
+ * (j < L / (64 fit_waves): up to 15 at L = 2048 and two waves) is within ((3 + 3 j) + 12 t/tau) u of exp(-t/tau), u = 2^-53 (exp()
+ * per point: (3 + 2 t/tau) u), 17 % less time per batch
  * with the chip full; 0 = exp() per point whatever the axis, "ct_fft" = formulation of kernel 1 where the chunk length allows: 3 (default) the
  * FLOAT32 real-input FFT for 4096 < F + L <= 8192 (the reference's own arithmetic type; C(t) to 4e-8) and the float64 complex
  * FFT below, 4 float32 transforms for every 1024 < F + L <= 8192, 2 the float64 real-input FFT for 4096 < F + L <= 8192 (C(t) to
@@ -242,6 +244,14 @@ int sr_counter(sr_ctx *, const char *name, uint64_t *value);
 int sr_expfit_resjac_f64(sr_ctx *, const double *t /*[nRes,L]*/, const double *C, const double *sigma,
                          const double *params /*[nRes,P]*/, int nRes, int L, int P,
                          double *resid /*[nRes,L]*/, double *jac /*[nRes,L,P] or NULL*/);
+/* Test-facing probe of the fit kernels' evaluations: for each residue, ONE evaluation at params x (nRes,P) of what the solver
+ * evaluates at an iterate, by the same device code (Residue::stage, eval_f with its point cache, eval_jac; sr_fit.hip) at the bounds
+ * the solver builds from tau_max, under the context's fit_waves / fit_lds / fit_geo.  Outputs (host pointers): geo (nRes) whether
+ * the uniform-grid products were taken; cost (nRes) 0.5 f.f, NaN when a residual is not finite; f (nRes,L) the residuals
+ * (model - C)/sigma; JtJ (nRes,P,P) and Jtf (nRes,P) of the Jacobian (jac_mode 0: scipy's 2-point forward differences, 1: analytic);
+ * dx (nRes,P) the forward-difference steps (x + h) - x. */
+int sr_expfit_probe_f64(sr_ctx *, const double *t, const double *C, const double *sigma, const double *x, int nRes, int L, int P,
+                        double tau_max, int jac_mode, int *geo, double *cost, double *f, double *JtJ, double *Jtf, double *dx);
 /* Batched bounded least-squares fit, one workgroup per residue, whole solve on the device
  * (replaces the scipy curve_fit call of conduct_curve_fitting, fitting_Ct_functions.py:322-324:
  * bounds 0 <= C,S2 <= 1, 0 <= tau <= tau_max).  p0 in / popt out (nRes,P); pcov (nRes,P,P) is the

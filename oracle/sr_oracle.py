@@ -187,6 +187,77 @@ def curvefit_exponential(t, *params):
     return S2 + np.sum(C[:, None] * np.exp(-1.0 * t[None, :] / tau[:, None]), axis=0)
 
 
+def fd_step_2point(x, lb, ub):
+    """The forward-difference step of curve_fit's Jacobian (least_squares jac='2-point' -> scipy 1.15.3
+    optimize/_numdiff.py:approx_derivative): h = _compute_absolute_step(None, x, f0, '2-point') = sqrt(eps) sign(x) max(1, |x|)
+    (sign(0) = +1), then _adjust_scheme_to_bounds(x, h, 1, '1-sided', lb, ub); the quotient divides by dx = (x + h) - x.
+    float64 throughout, as scipy computes it.  Returns (h, dx)."""
+    x = np.asarray(x, dtype=np.float64)
+    lb = np.broadcast_to(np.asarray(lb, dtype=np.float64), x.shape)
+    ub = np.broadcast_to(np.asarray(ub, dtype=np.float64), x.shape)
+    sign_x0 = (x >= 0).astype(np.float64) * 2 - 1
+    h = np.finfo(np.float64).eps ** 0.5 * sign_x0 * np.maximum(1.0, np.abs(x))
+    lower_dist, upper_dist = x - lb, ub - x
+    x1 = x + h
+    violated = (x1 < lb) | (x1 > ub)
+    fitting = np.abs(h) <= np.maximum(lower_dist, upper_dist)
+    h = np.where(violated & fitting, -h, h)
+    h = np.where(~fitting & (upper_dist >= lower_dist), upper_dist, h)
+    h = np.where(~fitting & (upper_dist < lower_dist), -lower_dist, h)
+    return h, (x + h) - x
+
+
+def expfit_residuals_ld(t, y, w, x):
+    """Residuals w (model(t; x) - y) of curve_fit's fun for the model of curvefit_exponential, evaluated in np.longdouble
+    (x86: 80-bit, eps 1.1e-19) from the float64 inputs.  w = 1/sigma as curve_fit forms it (float64).  Also returns the
+    exponentials exp(-t / tau_k), (K, L)."""
+    ld = np.longdouble
+    x = np.asarray(x, dtype=np.float64)
+    n = x.size
+    K = n // 2
+    C = x[:K].astype(ld)
+    tau = x[K:2 * K].astype(ld)
+    S2 = ld(x[-1]) if n % 2 == 1 else ld(1) - np.sum(C)
+    tt = np.asarray(t, dtype=np.float64).astype(ld)
+    with np.errstate(over='ignore', under='ignore', divide='ignore', invalid='ignore'):
+        e = np.exp(-tt[None, :] / tau[:, None])
+    model = S2 + np.sum(C[:, None] * e, axis=0)
+    return np.asarray(w, dtype=np.float64).astype(ld) * (model - np.asarray(y, dtype=np.float64).astype(ld)), e
+
+
+def expfit_eval_exact(t, y, w, x, lb, ub, jac_mode=0):
+    """High-precision counterpart of one evaluation of the device fit (sr_expfit_probe_f64) at float64 x: residuals f, cost
+    0.5 f.f, the Jacobian J (L, n) -- jac_mode 0: the EXACT forward quotient (f(x + dx_i e_i) - f(x)) / dx_i with scipy's dx
+    (fd_step_2point; x + dx_i e_i is the float64 point scipy evaluates), jac_mode 1: the analytic derivative -- and J^T J,
+    J^T f.  Everything after the float64 inputs in np.longdouble.  Returns a dict (f, e, J, fi, ei, JtJ, Jtf, cost, dx): fi / ei
+    the residuals / exponentials at x + dx_i e_i."""
+    ld = np.longdouble
+    x = np.asarray(x, dtype=np.float64)
+    n = x.size
+    K = n // 2
+    f0, e = expfit_residuals_ld(t, y, w, x)
+    h, dx = fd_step_2point(x, lb, ub)
+    J = np.empty((f0.size, n), dtype=ld)
+    fi = np.empty((n, f0.size), dtype=ld)
+    ei = [e] * n
+    if jac_mode == 0:
+        for i in range(n):
+            xi = x.copy()
+            xi[i] = x[i] + h[i]
+            fi[i], ei[i] = expfit_residuals_ld(t, y, w, xi)
+            J[:, i] = (fi[i] - f0) / ld(dx[i])
+    else:
+        wl = np.asarray(w, dtype=np.float64).astype(ld)
+        tt = np.asarray(t, dtype=np.float64).astype(ld)
+        for k in range(K):
+            J[:, k] = wl * (e[k] - (0 if n % 2 else 1))
+            J[:, K + k] = wl * ld(x[k]) * e[k] * tt / (ld(x[K + k]) * ld(x[K + k]))
+        if n % 2:
+            J[:, n - 1] = wl
+        fi[:] = f0
+    return dict(f=f0, e=e, J=J, fi=fi, ei=ei, JtJ=J.T @ J, Jtf=J.T @ f0, cost=ld(0.5) * np.sum(f0 * f0), dx=dx)
+
+
 def calc_chiSq(t, y, dy, S2, C, tau, zeta=1.0):
     """fitting_Ct_functions.py:266-276: mean(resid^2 / sigma) -- sigma, not sigma^2."""
     model = zeta * (S2 + np.sum(np.asarray(C)[:, None] * np.exp(-1.0 * t[None, :] / np.asarray(tau)[:, None]), axis=0))

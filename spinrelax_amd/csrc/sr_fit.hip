@@ -60,10 +60,14 @@ __device__ __forceinline__ double wsum(double v) { return sr_wave_sum_f64(v); }
 //                            every measure once the reductions below were out of the way (6.69 / 0.728 against 6.84 / 0.746).
 //   SR_FIT_REDUCE_MANY=1 (default) the 54 lane sums of a Jacobian by the register-halving reduction of sr_internal.h
 //                            (different association: the fits move in their last bits): 8.95 -> 6.85 / 0.832 -> 0.745
-//   Round 5, NOT bit-identical (within 1e-15 per exponential; every parity test re-run, per-trial tallies refreshed):
+//   Round 5, NOT bit-identical (every parity test re-run, per-trial tallies refreshed):
 //   exp(-t/tau) on a uniform time grid by multiplication along a thread's points (Residue::stage, eval_f, eval_jac; option
 //       fit_geo): one exp() per exponential and thread instead of one per point -- 2 instructions per exponential and point
-//       instead of 23: 0.709 -> 0.607 ms saturated, an evaluation of the slowest residue 22.6 -> 18.7 us;
+//       instead of 23: 0.709 -> 0.607 ms saturated, an evaluation of the slowest residue 22.6 -> 18.7 us.  The point l of a
+//       thread is j = l / (64 W) products past the thread's exp(): up to ceil(L / 64 W) - 1 of them (L = 2048: 7 at W = 4, 15 at
+//       W = 2, 31 at W = 1).  Error bound, asserted by tests/test_gpu_fit_eval.py on the residuals and on J^T J / J^T f against
+//       an 80-bit reference at every W (u = 2^-53): |e - exp(-t/tau)| <= ((3 + 3 j) + 12 t/tau) u e, against (3 + 2 t/tau) u e
+//       for exp() per point;
 //   W = 2 and 37 KB of LDS per residue (C(t), weights, one time per thread; the times themselves are only read by the
 //       exp()-per-point paths, from global memory) -> four workgroups per CU: 0.607 -> 0.397 ms saturated.
 // Tried and dropped (bit-identical): evaluating trial points with a fused model + Jacobian pass (an accepted step then needs
@@ -121,8 +125,9 @@ __device__ __forceinline__ double div_shared(double a, double b, double r)
 // exp() (ROCm 7.2 ocml, read off its ISA: argument reduction by ln2 hi/lo, degree-11 polynomial in Horner form, ldexp)
 // minus what a non-positive argument cannot need -- the overflow select -- and with one v_max_f64 on the quotient in
 // place of the underflow select (which doubles as the guard for huge / infinite / NaN quotients).  Same bits as
-// exp(a / b) (scripts/dev/fit_dump.py: every fit of the fixtures ends on identical parameters); 23 instructions instead
-// of 11 + 23.
+// exp(a / b): tests/test_gpu_fit_eval.py compares the residuals of this path with k_resjac's exp((-t) / tau) bit for bit, over
+// divisors with significands of all ones, subnormal and zero results, t = 0 and taus whose reciprocal overflows (Model::recips
+// caps it); 23 instructions instead of 11 + 23.
 extern __shared__ __align__(16) double fit_smem[];
 // Measured and dropped (round 4): a table-driven exp -- 2^(j/64) from a 64-entry LDS table, degree-4 polynomial on |t| <= ln2/128,
 // 5 float64 instructions fewer per exponential, below one ulp like this sequence but not the same bits: 0.743 -> 0.718 ms per
@@ -173,13 +178,17 @@ struct Model {
 #pragma unroll
         for (int k = 0; k < K; ++k) e[k] = exp((-1.0 * t) / x[K + k]);
     }
-    // the same with the divisors tau_k and rtau[k] = 1.0 / tau_k hoisted out of the loop over the data points (SGPRs)
+    // the same with the divisors tau_k and rtau[k] = 1.0 / tau_k hoisted out of the loop over the data points (SGPRs).  The
+    // reciprocal is capped at DBL_MAX: a tau below 2^-1024 (strictly_feasible's nextafter(0, ub) makes 2^-1074 of a tau on its
+    // lower bound) would give rtau = inf, and div_shared(-0, tau, inf) = NaN at t = 0, which exp_neg_quotient's clamp turns into
+    // exp() = 0 instead of exp(-0 / tau) = 1.  With the cap t = 0 gives the quotient +0 (exp = 1); any t > 0 still gives a NaN or
+    // huge quotient and 0, as exp(-t / tau) does there.  One v_min_f64 per tau and evaluation, outside the point loops.
     __device__ static __forceinline__ void recips(const double *x, double *tau_u, double *rtau)
     {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             tau_u[k] = uni(x[K + k]);
-            rtau[k] = uni(1.0 / x[K + k]);
+            rtau[k] = uni(fmin(1.0 / x[K + k], 0x1.fffffffffffffp+1023));
         }
     }
     __device__ static __forceinline__ void exps(const double *tau_u, const double *rtau, double t, double *e)
@@ -581,7 +590,8 @@ struct Residue {
         }
         tg = t; yg = y; wg = wbuf;
         // Uniform grid?  A thread owns the points tid, tid + NTH, tid + 2 NTH, ...; when t[tid + j NTH] = t[tid] + j (t[NTH] - t[0]) to
-        // rounding (8 ulp; dt * arange(L) is within 1.5), the exponentials of its points form a geometric sequence and the point
+        // rounding (1.8e-15 relative, 8 to 16 ulp, at every point j >= 1 of every thread; dt * arange(L) is within 1.5 ulp; tests/
+        // test_gpu_fit_eval.py: 9 ulp above a power of two is refused), the exponentials of its points form a geometric sequence and the point
         // loops multiply instead of evaluating exp() per point (eval_f / eval_jac).  Any other time axis -- the interface takes
         // arbitrary t -- keeps the exp() per point, and so does L <= NTH (one point per thread: nothing to multiply).
         int odd = 0;
@@ -644,8 +654,10 @@ struct PointCache {
     double f[fit_point_cache<N>() ? kCacheCap : 1];
 };
 
+// f_out: null at every solver call site (a literal nullptr: the stores are compiled out), or (L) doubles that receive the
+// per-point residuals (k_fit_probe, the test-facing view of these evaluations)
 template <int N, class R>
-__device__ __forceinline__ double eval_f(const R &T, const double *x, bool &finite, PointCache<N> &pc)
+__device__ __forceinline__ double eval_f(const R &T, const double *x, bool &finite, PointCache<N> &pc, double *f_out)
 {
     constexpr int K = N / 2;
     constexpr bool CACHE = fit_point_cache<N>();
@@ -656,8 +668,9 @@ __device__ __forceinline__ double eval_f(const R &T, const double *x, bool &fini
     double tau_u[K > 0 ? K : 1], rtau[K > 0 ? K : 1];
     M::recips(x, tau_u, rtau);
     // GEO (uniform time grid, Residue::stage): exp(-t/tau) at the thread's first point, then one multiplication by
-    // exp(-(t[NTH] - t[0])/tau) per further point -- the points of a thread are NTH grid steps apart.  Within 1e-15 of the
-    // exp() per point (<= 7 products), 2 instructions per exponential and point instead of 23.
+    // exp(-(t[NTH] - t[0])/tau) per further point -- the points of a thread are NTH grid steps apart.  Point l is j = l / NTH
+    // products past the exp() (up to ceil(L / NTH) - 1: 15 at L = 2048, W = 2); within ((3 + 3 j) + 12 t/tau) u of exp(-t/tau)
+    // (u = 2^-53; tests/test_gpu_fit_eval.py), 2 instructions per exponential and point instead of 23.
     auto run = [&](auto GEO) {
         double er[K > 0 ? K : 1], Rk[K > 0 ? K : 1];
         if (GEO) {
@@ -682,6 +695,7 @@ __device__ __forceinline__ double eval_f(const R &T, const double *x, bool &fini
                 f = T.ld_w(l) * (M::value(x, e) - T.ld_y(l));
             }
             if (!isfinite(f)) bad = 1.0; else acc = fma(f, f, acc);
+            if (f_out) f_out[l] = f;
             return f;
         };
         int l0 = tid;
@@ -711,10 +725,11 @@ __device__ __forceinline__ double eval_f(const R &T, const double *x, bool &fini
     return 0.5 * v[0];
 }
 
-// J^T J (packed) and J^T f at x (f is recomputed from the same expression eval_f uses: identical bits)
+// J^T J (packed) and J^T f at x (f is recomputed from the same expression eval_f uses: identical bits).  dx_out: null at every
+// solver call site (literal nullptr), or (N) doubles that receive the forward-difference steps (k_fit_probe)
 template <int N, class R>
 __device__ __forceinline__ void eval_jac(const R &T, const double *x, const double *lb, const double *ub, int mode, double *A,
-                                         double *g, const PointCache<N> &pc)
+                                         double *g, const PointCache<N> &pc, double *dx_out)
 {
     constexpr bool CACHE = fit_point_cache<N>();
     constexpr int K = N / 2;
@@ -738,6 +753,7 @@ __device__ __forceinline__ void eval_jac(const R &T, const double *x, const doub
         dx[i] = (x[i] + hi) - x[i];
         dx[i] = uni(dx[i]);
         rdx[i] = uni(1.0 / dx[i]);
+        if (dx_out && tid == 0) dx_out[i] = dx[i];
     }
     double tau_u[K > 0 ? K : 1], rtau[K > 0 ? K : 1], tauh_u[K > 0 ? K : 1], rtau_h[K > 0 ? K : 1];
     M::recips(x, tau_u, rtau);
@@ -943,13 +959,13 @@ __device__ __forceinline__ void trf_solve(const R &T, const double *p0, const So
         strictly_feasible<N>(x, lb, ub, 1e-10);
         bool finite;
         PointCache<N> pcache;
-        cost = eval_f<N>(T, x, finite, pcache);
+        cost = eval_f<N>(T, x, finite, pcache, nullptr);
         nfev = 1;
         if (!finite) {
             status = -3;          // "Residuals are not finite in the initial point"
         } else {
             have_fit = true;
-            eval_jac<N>(T, x, lb, ub, P.jac_mode, A, g, pcache);
+            eval_jac<N>(T, x, lb, ub, P.jac_mode, A, g, pcache, nullptr);
             SR_NJEV_INC();
             const int max_nfev = P.max_nfev > 0 ? P.max_nfev : 100 * N;
             double v[N], dv[N];
@@ -1034,7 +1050,7 @@ __device__ __forceinline__ void trf_solve(const R &T, const double *p0, const So
                         predicted = bc[N]; step_h_norm = bc[N + 1]; step_norm = bc[N + 2];
                     }
                     bool finite2;
-                    cost_new = eval_f<N>(T, xn, finite2, pcache);
+                    cost_new = eval_f<N>(T, xn, finite2, pcache, nullptr);
                     nfev += 1;
                     if (!finite2) {
                         Delta = 0.25 * step_h_norm;
@@ -1063,7 +1079,7 @@ __device__ __forceinline__ void trf_solve(const R &T, const double *p0, const So
 #pragma unroll
                     for (int i = 0; i < N; ++i) x[i] = uni(xn[i]);
                     cost = cost_new;
-                    eval_jac<N>(T, x, lb, ub, P.jac_mode, A, g, pcache);
+                    eval_jac<N>(T, x, lb, ub, P.jac_mode, A, g, pcache, nullptr);
                     SR_NJEV_INC();
                 }
             }
@@ -1468,6 +1484,106 @@ __global__ __launch_bounds__(256) void k_resjac(const double *__restrict__ t, co
     }
 }
 
+// ---- evaluation probe (test-facing) -----------------------------------------------------------------
+// One evaluation of what trf_solve evaluates at its initial point, for a given x and without the solve: Residue::stage (with the
+// context's fit_geo), eval_f with the point cache, eval_jac(jac_mode) from that cache, at the bounds trf_solve builds from tau_max.
+// Same template code and the same calls; eval_f / eval_jac take the extra output pointers that every solver call site passes as a
+// literal nullptr (k_trf and k_order_search compile to the code they had without them).
+struct ProbeArgs {
+    const double *t, *y, *sigma, *x;  // (nRes, L), (nRes, L), (nRes, L) or null, (nRes, N)
+    double tau_max;
+    int nRes, L, jac_mode, geo;
+    double *fws;                      // (nRes, L) weights when the residue is not staged in LDS
+    int *geo_out;                     // (nRes) Residue::geo
+    double *cost, *f, *A, *g, *dx;    // (nRes), (nRes, L), (nRes, N, N), (nRes, N), (nRes, N)
+};
+
+// The probe's residue is a type of its own: eval_f / eval_jac and their lambdas are instantiated for it separately, so the
+// solver's instances keep their only call sites (a second caller of the same instance changes the inliner's decisions in them).
+template <int W, bool LDS>
+struct ProbeResidue : Residue<W, LDS> {};
+
+template <int N, int W, bool LDS>
+__global__ __launch_bounds__(W * 64) void k_fit_probe(ProbeArgs a)
+{
+    constexpr int K = N / 2;
+    const int res = blockIdx.x;
+    const int tid = threadIdx.x;
+    ProbeResidue<W, LDS> T;
+    T.L = a.L;
+    T.tid = tid;
+    const double *sg_res = a.sigma ? a.sigma + (int64_t)res * a.L : nullptr;
+    T.stage(a.t + (int64_t)res * a.L, a.y + (int64_t)res * a.L, sg_res, LDS ? nullptr : a.fws + (int64_t)res * a.L, a.geo);
+    double x[N], lb[N], ub[N], g[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        x[i] = a.x[(int64_t)res * N + i];
+        lb[i] = 0.0;
+        ub[i] = (i >= K && i < 2 * K) ? a.tau_max : 1.0;
+    }
+    bool finite;
+    PointCache<N> pcache;
+    const double cost = eval_f<N>(T, x, finite, pcache, a.f + (int64_t)res * a.L);
+    eval_jac<N>(T, x, lb, ub, a.jac_mode, T.matA(), g, pcache, a.dx + (int64_t)res * N);
+    if (tid == 0) {
+        const double *A = T.matA();
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) a.A[((int64_t)res * N + i) * N + j] = A[tri(i, j)];
+            a.g[(int64_t)res * N + i] = g[i];
+        }
+        a.cost[res] = finite ? cost : NAN;
+        a.geo_out[res] = T.geo;
+    }
+}
+
+template <int N, int W>
+int launch_probe_w(sr_ctx *ctx, const ProbeArgs &a)
+{
+    const size_t lds_small = fit_lds_doubles(W, 0) * sizeof(double);
+    const size_t lds_full = fit_lds_doubles(W, a.L) * sizeof(double);
+    if (ctx->fit_lds && lds_full <= sr_lds_limit(ctx)) {
+        if (lds_full > 64 * 1024)
+            SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fit_probe<N, W, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full));
+        hipLaunchKernelGGL((k_fit_probe<N, W, true>), dim3((unsigned)a.nRes), dim3(W * 64), lds_full, ctx->stream, a);
+    } else {
+        hipLaunchKernelGGL((k_fit_probe<N, W, false>), dim3((unsigned)a.nRes), dim3(W * 64), lds_small, ctx->stream, a);
+    }
+    SR_HIP(hipGetLastError());
+    return 0;
+}
+
+template <int N>
+int launch_probe(sr_ctx *ctx, const ProbeArgs &a)
+{
+    switch (ctx->fit_waves) {
+        case 1: return launch_probe_w<N, 1>(ctx, a);
+        case 2: return launch_probe_w<N, 2>(ctx, a);
+        default: return launch_probe_w<N, 4>(ctx, a);
+    }
+}
+
+int dispatch_probe(sr_ctx *ctx, int P, const ProbeArgs &a)
+{
+    switch (P) {
+        case 2: return launch_probe<2>(ctx, a);
+        case 3: return launch_probe<3>(ctx, a);
+        case 4: return launch_probe<4>(ctx, a);
+        case 5: return launch_probe<5>(ctx, a);
+        case 6: return launch_probe<6>(ctx, a);
+        case 7: return launch_probe<7>(ctx, a);
+        case 8: return launch_probe<8>(ctx, a);
+        case 9: return launch_probe<9>(ctx, a);
+        case 10: return launch_probe<10>(ctx, a);
+        case 11: return launch_probe<11>(ctx, a);
+        default:
+            sr_set_error("sr_expfit_probe_f64: P=%d parameters not supported (2..%d)", P, kNmax);
+            return -3;
+    }
+}
+
 template <int N, int W>
 int launch_trf_w(sr_ctx *ctx, const FitArgs &a)
 {
@@ -1675,6 +1791,41 @@ int sr_expfit_lm_f64(sr_ctx *ctx, const double *t, const double *C, const double
     SR_HIP(hipMemcpyAsync(chisq, chi_d, (size_t)nRes * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SR_HIP(hipMemcpyAsync(status, iout, (size_t)nRes * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     SR_HIP(hipMemcpyAsync(n_iter, iout + nRes, (size_t)nRes * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int sr_expfit_probe_f64(sr_ctx *ctx, const double *t, const double *C, const double *sigma, const double *x, int nRes, int L,
+                        int P, double tau_max, int jac_mode, int *geo, double *cost, double *f, double *JtJ, double *Jtf,
+                        double *dx)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(t && C && x && geo && cost && f && JtJ && Jtf && dx, -2, "sr_expfit_probe_f64: null pointer");
+    SR_REQUIRE(nRes >= 1 && L >= 1 && P >= 2 && P <= kNmax, -3, "sr_expfit_probe_f64: bad sizes nRes=%d L=%d P=%d", nRes, L, P);
+    SR_REQUIRE(jac_mode == 0 || jac_mode == 1, -3, "sr_expfit_probe_f64: jac_mode must be 0 or 1");
+    const size_t nL = (size_t)nRes * L, nP = (size_t)nRes * P;
+    double *in = (double *)sr_workspace(ctx, SR_WS_IN0, (3 * nL + nP) * sizeof(double));
+    double *out = (double *)sr_workspace(ctx, SR_WS_OUT0, (nRes + nL + nP * P + 2 * nP) * sizeof(double));
+    int *iout = (int *)sr_workspace(ctx, SR_WS_OUT1, (size_t)nRes * sizeof(int));
+    double *fws = (double *)sr_workspace(ctx, SR_WS_FIT, nL * sizeof(double));
+    if (!in || !out || !iout || !fws) return -5;
+    double *t_d = in, *y_d = in + nL, *s_d = in + 2 * nL, *x_d = in + 3 * nL;
+    SR_HIP(hipMemcpyAsync(t_d, t, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SR_HIP(hipMemcpyAsync(y_d, C, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (sigma) SR_HIP(hipMemcpyAsync(s_d, sigma, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SR_HIP(hipMemcpyAsync(x_d, x, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ProbeArgs a;
+    a.t = t_d; a.y = y_d; a.sigma = sigma ? s_d : nullptr; a.x = x_d;
+    a.tau_max = tau_max; a.nRes = nRes; a.L = L; a.jac_mode = jac_mode; a.geo = ctx->fit_geo; a.fws = fws;
+    a.cost = out; a.f = out + nRes; a.A = a.f + nL; a.g = a.A + nP * P; a.dx = a.g + nP; a.geo_out = iout;
+    const int rc = dispatch_probe(ctx, P, a);
+    if (rc) return rc;
+    SR_HIP(hipMemcpyAsync(cost, a.cost, (size_t)nRes * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipMemcpyAsync(f, a.f, nL * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipMemcpyAsync(JtJ, a.A, nP * P * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipMemcpyAsync(Jtf, a.g, nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipMemcpyAsync(dx, a.dx, nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipMemcpyAsync(geo, iout, (size_t)nRes * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     SR_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -343,6 +343,23 @@ class Context:
               'sr_expfit_resjac_f64')
         return resid, jac
 
+    def expfit_probe(self, t, y, sigma, x, tau_max, jac_mode=0):
+        """One evaluation of the fit kernels at x (nRes, P) (sr_expfit_probe_f64): the solver's own model / Jacobian code under the
+        current fit_waves / fit_lds / fit_geo.  Returns a dict: geo (nRes), cost (nRes), f (nRes, L), JtJ (nRes, P, P), Jtf (nRes, P),
+        dx (nRes, P)."""
+        y = _f64(np.atleast_2d(y))
+        nRes, L = y.shape
+        t = _f64(np.broadcast_to(np.atleast_2d(t), (nRes, L)))
+        s = None if sigma is None else _f64(np.broadcast_to(np.atleast_2d(sigma), (nRes, L)))
+        x = _f64(np.atleast_2d(x))
+        P = x.shape[1]
+        out = dict(geo=np.empty(nRes, dtype=np.int32), cost=np.empty(nRes), f=np.empty((nRes, L)), JtJ=np.empty((nRes, P, P)),
+                   Jtf=np.empty((nRes, P)), dx=np.empty((nRes, P)))
+        check(self.lib.sr_expfit_probe_f64(self.h, _ptr(t), _ptr(y), _ptr(s), _ptr(x), nRes, L, P, float(tau_max), int(jac_mode),
+                                           _ptr(out['geo']), _ptr(out['cost']), _ptr(out['f']), _ptr(out['JtJ']), _ptr(out['Jtf']),
+                                           _ptr(out['dx'])), 'sr_expfit_probe_f64')
+        return out
+
     def expfit(self, t, y, sigma, p0, tau_max, max_nfev=0, analytic_jac=False):
         """Batched bounded fit (scipy curve_fit/TRF semantics).  Returns popt, pcov, chisq, status, nfev."""
         y = _f64(np.atleast_2d(y))

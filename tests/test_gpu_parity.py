@@ -588,20 +588,44 @@ def test_fit_uniform_grid_products_and_the_fallback(ctx):
     minimum to what ftol = xtol = 1e-8 leave of it -- chi^2 to the 1e-6 tier of test_device_fit_vs_reference_trials (measured
     1e-7: the reference's own chi^2 moves as much under a one-ulp change of its input), parameters to 1e-5 of their scale; (2) an axis that is NOT a uniform grid (one time moved by 1e-9
     of itself; a quadratic axis) takes exp() per point whatever the option says: bit-identical results with fit_geo = 1 and 0;
-    (3) L <= 256 (cfg1: one point per thread) is the exp() path by construction: bit-identical as well."""
+    (3) L <= 256 (cfg1: one point per thread) is the exp() path by construction: bit-identical as well.
+    (4) the over-parameterised orders (7, 9 parameters), where one ulp of input moves the reference itself by more than any tier:
+    with either form every trial succeeds or fails as the reference does (unless the reference itself flips under a one-ulp change
+    of its input, <tag>_fit_sens.npz), and every chi^2 meets the 1e-4 tier of test_device_fit_vs_reference_trials or lies inside the
+    reference's own range of outcomes by that test's rule."""
     for tag in ('cfg2', 'cfg3s'):
         g = golden('%s_fit.npz' % tag)
+        sens = golden('%s_fit_sens.npz' % tag)
         t, y, dy = g['t'], g['y'], g['dy']
         tau_max = t[0, -1] * 10
         for j, nP in enumerate(g['listDoG']):
-            if nP > 5:
-                continue
             p0 = g['trial_p0'][:, j, :nP]
             out = {}
             for geo in (1, 0):
                 ctx.set_option('fit_geo', geo)
                 out[geo] = ctx.expfit(t, y, dy, p0, tau_max)
             ctx.set_option('fit_geo', 1)
+            if nP > 5:
+                tier = 1e-4
+                for geo in (1, 0):
+                    chi, status = out[geo][2], out[geo][3]
+                    n_tier = n_spread = 0
+                    for i in range(y.shape[0]):
+                        ref_ok = bool(g['trial_quality'][i, j, 0])
+                        assert (status[i] > 0) == ref_ok or bool(sens['trial_ok_flip'][i, j]), (tag, nP, geo, i, status[i])
+                        if not ref_ok or status[i] <= 0:
+                            continue
+                        rel = abs(chi[i] / g['trial_chi'][i, j] - 1)
+                        spread = float(sens['trial_chi_spread'][i, j])
+                        lo, hi = float(sens['trial_chi_lo'][i, j]), float(sens['trial_chi_hi'][i, j])
+                        inside = lo * (1 - tier) - 0.5 * (hi - lo) <= chi[i] <= hi * (1 + tier) + 0.5 * (hi - lo)
+                        assert rel <= tier or (spread > 0.1 * tier and (inside or rel <= 3.0 * spread)), \
+                            (tag, nP, geo, i, rel, spread, chi[i], lo, hi)
+                        n_tier += rel <= tier
+                        n_spread += rel > tier
+                    print('\n[fit_geo %s, %d parameters, geo=%d] within the tier %d, inside the reference\'s spread %d'
+                          % (tag, nP, geo, n_tier, n_spread))
+                continue
             ok = (out[1][3] > 0) & (out[0][3] > 0)
             assert np.array_equal(out[1][3] > 0, out[0][3] > 0) and ok.sum() >= 0.75 * len(ok)
             chi_rel = np.max(np.abs(out[1][2][ok] / out[0][2][ok] - 1.0))

@@ -257,3 +257,39 @@ def test_oracle_per_frame_rotation_equals_reference():
     Ct, dCt = o.calculate_Ct_Palmer(v4.astype(np.float64))
     np.testing.assert_array_equal(Ct, g['Ct64'])
     np.testing.assert_array_equal(dCt, g['dCt64'])
+
+
+def test_fit_eval_reference_step_rule_and_quotient():
+    """The host reference of the fit-evaluation tests (tests/test_gpu_fit_eval.py): fd_step_2point is scipy's own step rule
+    (optimize/_numdiff.py: _compute_absolute_step + _adjust_scheme_to_bounds '1-sided'), bit for bit, for x inside, on and within a
+    step of the bounds; expfit_eval_exact's 80-bit forward quotient of a cfg2 fixture residue agrees with scipy's float64
+    approx_derivative to the forward-difference noise of float64 (rounding of f over dx), and its analytic Jacobian with the model."""
+    from scipy.optimize import _numdiff
+    rng = np.random.default_rng(11)
+    tau_max = 51200.0
+    lb, ub = np.zeros(5), np.array([1.0, 1.0, tau_max, tau_max, 1.0])
+    xs = [rng.uniform(lb, ub) for _ in range(50)]
+    xs += [np.array([0.0, 1.0, tau_max, 1e-300, 0.0]), np.array([1 - 1e-9, 1e-9, tau_max * (1 - 1e-12), 5e-324, 1.0]),
+           np.array([0.5, 0.5, 1.0, 0.999999999, 1 - 2e-8])]
+    for x in xs:
+        h0 = _numdiff._compute_absolute_step(None, x, np.zeros(3), '2-point')
+        h_ref, _ = _numdiff._adjust_scheme_to_bounds(x, h0, 1, '1-sided', lb, ub)
+        h, dx = o.fd_step_2point(x, lb, ub)
+        assert np.array_equal(h, h_ref), (x, h, h_ref)
+        assert np.array_equal(dx, (x + h_ref) - x)
+    g = golden('cfg2_fit.npz')
+    t, y, dy = g['t'][0], g['y'][0], g['dy'][0]
+    x = g['trial_popt'][0, 2, :5]
+    lb5, ub5 = np.zeros(5), np.array([1.0, 1.0, t[-1] * 10, t[-1] * 10, 1.0])
+    ex = o.expfit_eval_exact(t, y, 1.0 / dy, x, lb5, ub5, 0)
+
+    def fun(p):
+        return (o.curvefit_exponential(t, *p) - y) / dy
+    J64 = _numdiff.approx_derivative(fun, x, method='2-point', bounds=(lb5, ub5))
+    J = np.asarray(ex['J'], dtype=np.float64)
+    noise = 8 * np.finfo(float).eps * np.max(np.abs(fun(x)) + np.abs(y / dy)) / np.abs(ex['dx'])
+    assert np.all(np.abs(J64 - J) <= noise[None, :] + 1e-12 * np.abs(J)), np.max(np.abs(J64 - J) / noise[None, :])
+    an = o.expfit_eval_exact(t, y, 1.0 / dy, x, lb5, ub5, 1)
+    assert np.max(np.abs(np.asarray(an['f'], dtype=np.float64) - fun(x))) < 1e-14 * np.max(np.abs(y / dy))   # f cancels: absolute
+    e = np.exp(-t / x[2])
+    assert relerr(np.asarray(an['J'][:, 2], dtype=np.float64), x[0] * e * t / x[2] ** 2 / dy) < 1e-12

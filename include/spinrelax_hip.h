@@ -134,9 +134,19 @@ int sr_pack_soa_rot_f32_dev(sr_ctx *, const float *vecs, int64_t N, int64_t Vtot
  *           C(t) to ~4e-8, the class of the direct kernel and of the reference's own float32); shorter chunks: float64
  *           transforms (~1e-15).  sr_set_option("ct_fft", 2) selects float64 transforms everywhere, 0 disables the
  *           formulation;
- *           otherwise: direct shifted products, float32 dot products and short float32 partial sums folded into
+ *           chunks beyond what the direct kernel can stage in LDS (about 13400 frames), up to sr_ct_max_frames_per_chunk() =
+ *           262144 frames per chunk: the same decomposition with
+ *           BLOCKED transforms (sr_ct_long.hip): blocks of 4096 samples, float32 forward transforms to a work area in device
+ *           memory, cross-spectra per block offset and the inverse transforms in float64 (C(t) to 1e-7).  The series of a
+ *           launch go in tiles whose spectra fit sr_set_option("ct_long_ws_mb", MiB) (default 256; results do not depend on it);
+ *           sr_set_option("ct_long_min_frames", F0) (5462 .. 262144, default 16384) also gives them the chunks of F0 frames
+ *           and more that the direct kernel could stage (F + L > 8192); by default the direct kernel keeps those.  Longer
+ *           chunks are refused (-4);
+ *           otherwise (short chunks, ct_fft = 0 or 1 beyond the transform lengths): direct shifted products, float32 dot products and short float32 partial sums folded into
  *           float64 (accurate to ~1e-8);
  * mode 1: direct shifted products, every product and sum in float64 (validation path).
+ * The direct kernels stage a whole chunk in LDS (12 bytes per frame): mode 1 and ct_fft = 0 / 1 refuse chunks beyond about
+ * 13400 frames (-4).
  * psum (optional, may be NULL): (nV, R, Lp) float64 raw sums  sum_j (u.u')^2, Lp = sr_ct_psum_stride(F). */
 int64_t sr_ct_psum_stride(int64_t F);
 int64_t sr_ct_max_frames_per_chunk(sr_ctx *);

@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libspinrelax_hip.so')
-SOURCES = ['sr_core.hip', 'sr_ct.hip', 'sr_ct32.hip', 'sr_vechist.hip', 'sr_fit.hip', 'sr_relax.hip', 'sr_dq.hip', 'sr_traj.hip', 'sr_vectors.hip', 'sr_textio.hip']
+SOURCES = ['sr_core.hip', 'sr_ct.hip', 'sr_ct32.hip', 'sr_ct_long.hip', 'sr_vechist.hip', 'sr_fit.hip', 'sr_relax.hip', 'sr_dq.hip', 'sr_traj.hip', 'sr_vectors.hip', 'sr_textio.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']
 # sr_ct.hip: the SLP vectoriser packs the FMAs of the C(t) inner loop into v_pk_fma_f32, whose operand pairs then
@@ -18,6 +18,7 @@ EXTRA = {'sr_ct.hip': ['-fno-slp-vectorize'],
          # sr_ct32.hip: the same for the float32 transforms (packed complex arithmetic by the vectoriser costs a v_mov per
          # operand pair and 270 B of scratch at 128 VGPRs; without it 56 B)
          'sr_ct32.hip': ['-fno-slp-vectorize'],
+         'sr_ct_long.hip': ['-fno-slp-vectorize'],
          # sr_fit.hip: explicit fma() only, see the note at the top of the file
          'sr_fit.hip': ['-ffp-contract=off']}
 if os.environ.get('SR_FIT_DEV_FAST'):          # development: only the order-search variants the benchmark uses
@@ -30,7 +31,7 @@ def build_id():
     of a profiling run (bench.py compares the two)."""
     import hashlib
     h = hashlib.sha256()
-    for name in sorted(SOURCES) + ['sr_internal.h']:
+    for name in sorted(SOURCES) + ['sr_internal.h', 'sr_ct32_fft.h']:
         with open(os.path.join(CSRC, name), 'rb') as fp:
             h.update(name.encode() + b'\0' + fp.read())
     with open(os.path.join(HERE, '..', 'include', 'spinrelax_hip.h'), 'rb') as fp:
@@ -55,7 +56,7 @@ def _same_flags(stamp, sig):
 
 
 def build(force=False, verbose=True):
-    hdrs = [os.path.join(CSRC, 'sr_internal.h'), os.path.join(HERE, '..', 'include', 'spinrelax_hip.h')]
+    hdrs = [os.path.join(CSRC, 'sr_internal.h'), os.path.join(CSRC, 'sr_ct32_fft.h'), os.path.join(HERE, '..', 'include', 'spinrelax_hip.h')]
     objs = []
     bid = build_id()
     idfile = os.path.join(CSRC, '.build_id')

@@ -93,6 +93,8 @@ sr_ctx *sr_create(int device)
     ctx->fit_geo = 1;
     ctx->ct_fft = 3;
     ctx->ct_traceless = 0;
+    ctx->ct_long_ws_mb = SR_CT_LONG_WS_MB;
+    ctx->ct_long_min_frames = SR_CT_LONG_MIN_FRAMES;
     ctx->fft_table_ready = 0;
     ctx->fft32_table_ready = 0;
     if (hipGetDeviceProperties(&ctx->prop, device) != hipSuccess) {
@@ -122,6 +124,7 @@ void sr_destroy(sr_ctx *ctx)
         if (ctx->slot[i]) (void)hipFree(ctx->slot[i]);
     (void)hipEventDestroy(ctx->ev0);
     (void)hipEventDestroy(ctx->ev1);
+    if (ctx->ctlong_ev) (void)hipEventDestroy(ctx->ctlong_ev);
     for (int i = 0; i < 2; ++i)
         if (ctx->stage[i]) {
             (void)hipHostFree(ctx->stage[i]);
@@ -147,6 +150,17 @@ int sr_set_option(sr_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "ct_wg_per_cu")) {
         SR_REQUIRE(value >= 0 && value <= 8, -3, "sr_set_option: ct_wg_per_cu must be 0 .. 8");
         ctx->ct_wg_per_cu = value;
+        return 0;
+    }
+    if (!strcmp(name, "ct_long_ws_mb")) {
+        SR_REQUIRE(value >= 1 && value <= 65536, -3, "sr_set_option: ct_long_ws_mb must be 1 .. 65536 (MiB)");
+        ctx->ct_long_ws_mb = value;
+        return 0;
+    }
+    if (!strcmp(name, "ct_long_min_frames")) {
+        SR_REQUIRE(value >= 5462 && value <= SR_CT_LONG_MAX_FRAMES, -3, "sr_set_option: ct_long_min_frames must be 5462 .. %d",
+                   SR_CT_LONG_MAX_FRAMES);
+        ctx->ct_long_min_frames = value;
         return 0;
     }
     if (!strcmp(name, "ct_traceless")) {

@@ -1453,12 +1453,18 @@ int sr_transpose_f64_dev(sr_ctx *ctx, const double *in, int64_t rows, int64_t co
 
 int64_t sr_ct_psum_stride(int64_t F) { return sr_round_up(F / 2 + 1 + kLagBlock, 8); }
 
-int64_t sr_ct_max_frames_per_chunk(sr_ctx *ctx)
+// the direct kernel stages a whole series in LDS: 12 bytes per frame
+static int64_t ct_direct_max_frames(const sr_ctx *ctx)
 {
-    if (!ctx) return -1;
     const int64_t lds = (int64_t)sr_lds_limit(ctx);
     int64_t F = lds / 12 - kPad - 64;
     return F > 0 ? F : 0;
+}
+
+int64_t sr_ct_max_frames_per_chunk(sr_ctx *ctx)
+{
+    if (!ctx) return -1;
+    return SR_CT_LONG_MAX_FRAMES;        // the blocked transforms of the default dispatch (sr_ct_long.hip)
 }
 
 int sr_pack_soa_f32_dev(sr_ctx *ctx, const float *vecs, int64_t N, int64_t Vtot, int64_t v0, int64_t nV,
@@ -1511,14 +1517,21 @@ int sr_ct_palmer_sums_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64
     SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1, -3, "sr_ct_palmer_sums_f32_dev: bad shape R=%lld F=%lld nV=%lld", (long long)R,
                (long long)F, (long long)nV);
     SR_REQUIRE(mode == 0 || mode == 1, -3, "sr_ct_palmer_sums_f32_dev: mode must be 0 or 1");
+    SR_REQUIRE(F <= SR_CT_LONG_MAX_FRAMES, -4, "sr_ct_palmer_sums_f32_dev: F=%lld frames per chunk; max F is %lld", (long long)F,
+               (long long)SR_CT_LONG_MAX_FRAMES);
+    const int64_t L = F / 2;
+    // chunks that do not fit one in-LDS transform: blocked transforms (sr_ct_long.hip) in the default dispatch -- every chunk the
+    // direct kernel cannot stage, and the shorter ones from ct_long_min_frames on (default: none -- which of the two is faster
+    // for 5462 <= F <= 13397 has not been measured, so the direct kernel keeps the range it had)
     const int64_t Fp = ct_Fp(F);
     const size_t lds_bytes = (size_t)Fp * 3 * sizeof(float);
-    SR_REQUIRE(lds_bytes <= sr_lds_limit(ctx), -4,
-               "sr_ct_palmer_sums_f32_dev: F=%lld frames per chunk need %zu B of LDS (> %zu); max F is %lld",
-               (long long)F, lds_bytes, sr_lds_limit(ctx),
-               (long long)sr_ct_max_frames_per_chunk(ctx));
+    const bool fits_direct = lds_bytes <= sr_lds_limit(ctx);
+    const bool blocked = mode == 0 && ctx->ct_fft >= 2 && F + L > 8192 && (F >= ctx->ct_long_min_frames || !fits_direct);
+    SR_REQUIRE(blocked || fits_direct, -4,
+               "sr_ct_palmer_sums_f32_dev: F=%lld frames per chunk need %zu B of LDS (> %zu) in the direct kernel (mode 1 or ct_fft < 2), "
+               "whose max F is %lld; the default dispatch takes up to %lld",
+               (long long)F, lds_bytes, sr_lds_limit(ctx), (long long)ct_direct_max_frames(ctx), (long long)SR_CT_LONG_MAX_FRAMES);
     SR_REQUIRE(R * nV < (int64_t)1 << 30, -3, "sr_ct_palmer_sums_f32_dev: too many series");
-    const int64_t L = F / 2;
     const int64_t Lp = sr_ct_psum_stride(F);
     if (chunk_start_host) {
         for (int64_t r = 0; r < R; ++r)
@@ -1542,6 +1555,7 @@ int sr_ct_palmer_sums_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64
     const int nb = mode == 0 ? (int)((L + 1) / kLagBlock) : 0;
     const int64_t series = R * nV;
     int rc;
+    if (blocked) return sr_launch_ct_long(ctx, soa, Npad, cs_dev, psum, (int)R, (int)F, (int)L, (int)Lp, series);
     // FFT formulation: chunk + lags must fit a 2048 / 4096 / 8192-point transform (shorter chunks are cheap anyway)
     const int64_t need = F + L;
     if (mode == 0 && ctx->ct_fft && need > 1024 && need <= 8192) {

@@ -7,7 +7,7 @@
 #include <cstring>
 #include "../../include/spinrelax_hip.h"
 
-#define SR_NSLOTS 15
+#define SR_NSLOTS 17
 
 struct sr_ctx {
     int device;
@@ -28,8 +28,14 @@ struct sr_ctx {
                         // 1 = complex float64 FFT formulation (k_ct_fft) everywhere, 0 = always the direct kernel
     int ct_wg_per_cu;   // k_ct_rfft32: at most this many workgroups per CU (0 = as many as fit: 4 for M = 6144); see sr_ct32.hip
     int ct_traceless;   // 1: k_ct_rfft<12> in its traceless five-signal form (faster alone, slower inside the pipeline: default 0)
+    int ct_long_ws_mb;  // blocked C(t) (sr_ct_long.hip): the series of a launch go in tiles whose block spectra fit this many MiB
+    int ct_long_min_frames;   // blocked C(t): chunks of at least this many frames take it (shorter ones that do not fit one transform:
+                        // the direct kernel); see SR_CT_LONG_MIN_FRAMES
     int fft_table_ready;
     int fft32_table_ready;
+    int ctlong_table_ready;
+    hipEvent_t ctlong_ev;   // behind the last kernel of the latest blocked C(t) call: the next call, on whatever stream, waits for it
+    int ctlong_ev_set;      // before it touches the work area
     // strided host -> device copies of bond vectors (sr_vectors.hip): two pinned staging buffers, and what went through them
     void *stage[2];
     hipEvent_t stage_ev[2];
@@ -37,7 +43,7 @@ struct sr_ctx {
     unsigned long long h2d_bytes, h2d_calls;
 };
 
-enum { SR_K_CT1 = 0, SR_K_CT4, SR_K_VECHIST, SR_K_DQ, SR_K_MISC };
+enum { SR_K_CT1 = 0, SR_K_CT4, SR_K_VECHIST, SR_K_DQ, SR_K_MISC, SR_K_CTL_CROSS, SR_K_CTL_INV };
 
 enum {
     SR_WS_VECS = 0,     // staged host vectors (frame-major)
@@ -48,7 +54,9 @@ enum {
     SR_WS_MISC,
     SR_WS_FIT,          // residual work space of the fit kernel (when the caller passes none)
     SR_WS_FFT,          // twiddle table of the FFT formulation of kernel 1
-    SR_WS_FFT32         // tables of its float32 form (sr_ct32.hip)
+    SR_WS_FFT32,        // tables of its float32 form (sr_ct32.hip)
+    SR_WS_CTLONG,       // blocked C(t) (sr_ct_long.hip): chunk constants, block spectra and cross-spectra of one tile of series
+    SR_WS_CTLONG_TAB    // twiddles of its float64 inverse transform
 };
 
 void sr_set_error(const char *fmt, ...);
@@ -91,6 +99,18 @@ static inline int64_t sr_round_up(int64_t x, int64_t m) { return (x + m - 1) / m
 // sr_ct32.hip: the float32 real-input FFT form of kernel 1 (raw lag sums per chunk, like k_ct_rfft); the chunk starts may be null
 int sr_launch_ct_rfft32(sr_ctx *ctx, const float *soa, int64_t Npad, const int64_t *cs_host, const int64_t *cs_dev, double *psum,
                         int R, int F, int L, int Lp, int64_t series);
+
+// the device tables of the float32 transforms (Ct32Tab[4], sr_ct32_fft.h), created on first use; NULL (error set) on failure
+const void *sr_ct32_tables(sr_ctx *ctx);
+
+// sr_ct_long.hip: the blocked form of kernel 1 for chunks that do not fit one in-LDS transform (F + L > 8192), up to
+// SR_CT_LONG_MAX_FRAMES frames per chunk; same raw lag sums
+#define SR_CT_LONG_MAX_FRAMES 262144
+#define SR_CT_LONG_MIN_FRAMES 16384     /* default of "ct_long_min_frames": above the direct kernel's LDS limit, i.e. the direct kernel keeps
+                                           every chunk it can stage (no timing of the two against each other exists yet) */
+#define SR_CT_LONG_WS_MB 256
+int sr_launch_ct_long(sr_ctx *ctx, const float *soa, int64_t Npad, const int64_t *cs_dev, double *psum, int R, int F, int L, int Lp,
+                      int64_t series);
 
 #ifdef __HIPCC__
 // ---- wave-level float64 sum on the VALU only (DPP + readlane), no LDS round trips -----------------

@@ -336,10 +336,14 @@ int sr_jomega_f64(sr_ctx *, const double *x, const double *y, double *out, int64
  *   model        0 direct transform (J_direct_transform, spectral_densities.py:2024-2033)
  *                1 rigid sphere, D[0] = Diso (J_combine_isotropic_exp_decayN, :2038-2050)
  *                2 symmetric top, D[0] = Dpar, D[1] = Dperp (J_combine_symmtop_exp_decayN, :2057-2077)
+ *                3 fully anisotropic (rhombic) ellipsoid, D = {Dx, Dy, Dz}: the principal values in any order, along the x, y, z
+ *                  axes of the frame the vectors are given in (Woessner 1962; Ghose, Fushman & Cowburn 2001).  Five rates
+ *                  4Dx+Dy+Dz, Dx+4Dy+Dz, Dx+Dy+4Dz, 6Diso +- 6R and five amplitudes per vector; no counterpart in the
+ *                  reference, whose helpers for this model (:1908-1932) do not work.  Needs vectors like model 2.
  *   omega        (E,5): [0, wX, wH-wX, wH, wH+wX] in 1/time-unit
  *   f_DD (E), f_CSA (E,nRes), time_fact (E), gamma_ratio (E) = gamma_H/gamma_X
  *   S2 (nRes), C/tau (nRes,Kmax) with nComps (nRes) valid entries -- already zeta-scaled
- *   binvecs (B,3) unit vectors shared by every residue (bin centres) or (nRes,3) when B == 0
+ *   binvecs (B,3) unit vectors shared by every residue (bin centres) or (nRes,3) when B == 0 (models 2 and 3)
  *   weights (nRes,B) or NULL (uniform); a DEVICE pointer when weights_on_device != 0 (the histogram
  *                kernel 2 left in HBM), otherwise a host pointer
  *   noe_mode     0: NOE from the per-vector R1 (old API, :1706/:1722)
@@ -359,7 +363,7 @@ int sr_jomega_relax_f64(sr_ctx *, int model, const double *D, int E, const doubl
                         int B, const double *binvecs, const double *weights, int weights_on_device, int noe_mode,
                         double *out, double *Jout, double *stats);
 /* Device-pointer form for a pipeline that never leaves the GPU: every array argument is a DEVICE pointer (D stays a
- * host array of 1 or 2 numbers), nComps[i] must be within 0..Kmax (not checked), S2 and C are multiplied by zeta on
+ * host array of 1, 2 or 3 numbers), nComps[i] must be within 0..Kmax (not checked), S2 and C are multiplied by zeta on
  * load (the reference scales the fitted model by zeta first, calculate-relaxations-from-Ct.py:747-750; pass 1.0 for
  * already-scaled input); asynchronous on the context's stream. */
 int sr_jomega_relax_f64_dev(sr_ctx *, int model, const double *D, int E, const double *omega, const double *f_DD,
@@ -387,7 +391,8 @@ int sr_rscsa_search_f64(sr_ctx *, int E, int nRes, const double *stats, const in
                         double *csa, double *values, double *errors, double *fopt, int *nfev);
 
 /* Per-residue CSA refinement of the legacy single-field mode `--opt new`: replaces the loop of fmin_powell calls over
- * optfunc_R1R2NOE_new (calculate-relaxations-from-Ct.py:210-258, 935-1000), axisymmetric diffusion + vector histogram only.
+ * optfunc_R1R2NOE_new (calculate-relaxations-from-Ct.py:210-258, 935-1000), axisymmetric diffusion + vector histogram only (no ellipsoid:
+ * the legacy modes stay as the reference has them).
  * One workgroup per residue runs scipy's one-variable Powell search (as sr_rscsa_search_f64); every objective call evaluates
  * R1, R2 and the old-API NOE over the B histogram bins with the arithmetic of sr_jomega_relax_f64 (noe_mode 0), casts value and
  * sigma to float32 like the reference's datablock and returns mean_k (model_k - exp_k)^2 / (sigma_exp_k^2 + sigma_model_k^2).

@@ -121,9 +121,18 @@ def main():
         elif len(tmp) == 2:
             aniso = tmp[1]
             diff_type = 'symmtop'
+        elif len(tmp) == 3:
+            # the triple the reference's workflow advertises and then never evaluates: three values always take the
+            # ellipsoid path, rhombicity 0 included
+            aniso, rhomb = tmp[1], tmp[2]
+            diff_type = 'ellipsoid'
         else:
-            print("= = = ERROR: fully anisotropic diffusion is not implemented (neither in the reference).", file=sys.stderr)
+            print("= = = ERROR: -D takes one, two or three values: Diso [Daniso [Drhomb]].", file=sys.stderr)
             sys.exit(1)
+    if diff_type == 'ellipsoid' and args.opt is not None:
+        print("= = = ERROR: the legacy --opt modes know the symmetric top only; optimise a fully anisotropic tensor with "
+              "calculate-relaxations-multi-field.py --opt Diso,Daniso,Drhomb.", file=sys.stderr)
+        sys.exit(1)
 
     vecXH, vecXHweights, resNH = None, None, None
     bHaveDy = False
@@ -134,11 +143,16 @@ def main():
         print("= = = Using a spherical rotational diffusion model.")
         relax_obj.set_rotdif_model('rigid_sphere_D', Diso)
     else:
-        Dperp = 3. * Diso / (2 + aniso)
-        Dpar = aniso * Dperp
-        print("= = = Calculated anisotropy to be: ", aniso)
-        print("= = = With Dpar, Dperp: %g, %g %s^-1" % (Dpar, Dperp, args.time_unit))
-        relax_obj.set_rotdif_model('rigid_symmtop_D', Dpar, Dperp)
+        if diff_type == 'ellipsoid':
+            relax_obj.set_rotdif_model('rigid_ellipsoid_Dref', Diso, aniso, rhomb)
+            print("= = = Using a fully anisotropic rotational diffusion model: anisotropy %g, rhombicity %g" % (aniso, rhomb))
+            print("= = = With Dx, Dy, Dz: %g, %g, %g %s^-1" % (tuple(relax_obj.rotdifModel.D) + (args.time_unit,)))
+        else:
+            Dperp = 3. * Diso / (2 + aniso)
+            Dpar = aniso * Dperp
+            print("= = = Calculated anisotropy to be: ", aniso)
+            print("= = = With Dpar, Dperp: %g, %g %s^-1" % (Dpar, Dperp, args.time_unit))
+            relax_obj.set_rotdif_model('rigid_symmtop_D', Dpar, Dperp)
         if args.vecfn is not None:
             print("= = = Using average vectors. Reading X-H vectors from %s ..." % args.vecfn)
             resNH, vecXH = gs.load_xys(args.vecfn)
@@ -182,7 +196,7 @@ def main():
         sys.exit(1)
     num_vecs = autoCorrs.nModels
     sim_resid = [int(k) for k in autoCorrs.model.keys()]
-    if diff_type == 'symmtop':
+    if diff_type in ('symmtop', 'ellipsoid'):
         sanity_check_two_list(sim_resid, resNH, "resid from fitted_Ct -versus- vectors as defined in anisotropy")
 
     # CSA input (calculate-relaxations-from-Ct.py:702-743): a number, or a file with one value per residue

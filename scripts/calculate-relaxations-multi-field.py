@@ -2,7 +2,7 @@
 """
 Drop-in for the reference's calculate-relaxations-multi-field.py (run-all.bash:537-543): predicts every given
 experiment (R1 / R2 / NOE at arbitrary fields) from the fitted C(t) parameters, the vector distribution and the
-global diffusion tensor, optionally optimising Diso, Daniso, zeta, CSA (global) and/or rsCSA (per residue), and
+global diffusion tensor, optionally optimising Diso, Daniso, Drhomb, zeta, CSA (global) and/or rsCSA (per residue), and
 writes `<o>_<15N1H>_<MHz>MHz_<Type>.xvg` per experiment and `<o>_CSA_opt.dat`.  All experiments, residues and
 histogram bins are evaluated in one batched GPU launch per objective call; the rsCSA step uses the closed-form
 CSA dependence (spinrelax_amd/spin_relaxation.py).
@@ -22,24 +22,37 @@ from spinrelax_amd import spectral_densities as sd          # noqa: E402
 from spinrelax_amd import dist as srdist                    # noqa: E402
 
 
-def parse_rotdif_params(D=None, tau=None, aniso=None):
-    """calculate-relaxations-multi-field.py:13-37."""
+def parse_rotdif_params(D=None, tau=None, aniso=None, rhomb=None):
+    """calculate-relaxations-multi-field.py:13-37, plus the fully anisotropic tensor the reference only announces:
+    --rhomb beside --aniso, or three values "Dx Dy Dz" in -D (two values are "Dpar Dperp" as in the reference)."""
+    if rhomb is not None and aniso is None:
+        print("= = ERROR: --rhomb needs --aniso.", file=sys.stderr)
+        sys.exit(1)
     if D is None:
         if tau is None:
             print("= = ERROR: No global tumbling parameters given!", file=sys.stderr)
             sys.exit(1)
         Diso = 1.0 / (6 * tau)
+        if rhomb is not None:
+            return sd.globalRotationalDiffusion_Ellipsoid(D=[Diso, aniso, rhomb])
         if aniso is None or aniso == 1.0:
             return sd.globalRotationalDiffusion_Isotropic(D=Diso)
         return sd.globalRotationalDiffusion_Axisymmetric(D=[Diso, aniso])
     tmp = [float(x) for x in regexp_split('[, ]', D) if len(x) > 0]
     if len(tmp) == 1:
+        if rhomb is not None:
+            return sd.globalRotationalDiffusion_Ellipsoid(D=[tmp[0], aniso, rhomb])
         if aniso is None:
             return sd.globalRotationalDiffusion_Isotropic(D=tmp[0])
         return sd.globalRotationalDiffusion_Axisymmetric(D=[tmp[0], aniso])
+    if rhomb is not None:
+        print("= = ERROR: --rhomb goes with -D Diso --aniso A; a -D of several values already names the whole tensor.", file=sys.stderr)
+        sys.exit(1)
     if len(tmp) == 2:
         return sd.globalRotationalDiffusion_Axisymmetric(D=tmp, bConvert=True)
-    print("WARNING: fully anisotropic global rotdif not implemented.", file=sys.stderr)
+    if len(tmp) == 3:
+        return sd.globalRotationalDiffusion_Ellipsoid(D=tmp, bConvert=True)
+    print("= = ERROR: -D takes one, two or three values.", file=sys.stderr)
     sys.exit(1)
 
 
@@ -53,7 +66,9 @@ def main():
     p.add_argument('--distfn', type=str, dest='distfn', default=None, help='Vector orientation distribution (.npz histogram).')
     p.add_argument('--tau', type=float, dest='tau', default=None, help='Isotropic relaxation time constant.')
     p.add_argument('--aniso', type=float, dest='aniso', default=None, help='Diffusion anisotropy.')
-    p.add_argument('-D', '--DTensor', type=str, dest='D', default=None, help='Diso, or "Dpar Dperp".')
+    p.add_argument('--rhomb', type=float, dest='rhomb', default=None,
+                   help='Diffusion rhombicity 3(Dy-Dx)/(2Dz-Dx-Dy), beside --aniso: the fully anisotropic tensor.')
+    p.add_argument('-D', '--DTensor', type=str, dest='D', default=None, help='Diso, "Dpar Dperp", or "Dx Dy Dz".')
     p.add_argument('--zeta', type=float, default=0.890023, help='Zero-point vibration scaling.')
     p.add_argument('--csa', type=str, default=None, help='CSA value or per-residue CSA file.')
     p.add_argument('--opt', '--fit', type=str, dest='listOptParams', default=None,
@@ -69,7 +84,7 @@ def main():
     if localCtModel.nModels == 0:
         print("= = = ERROR: The fitted-Ct file %s was read, but did not yield any usable parameters!" % args.in_Ct_fn)
         sys.exit(1)
-    globalRotDif = parse_rotdif_params(args.D, args.tau, args.aniso)
+    globalRotDif = parse_rotdif_params(args.D, args.tau, args.aniso, args.rhomb)
     if args.distfn is not None:
         globalRotDif.import_frame_vectors(args.distfn)
     elif args.refPDBFile is not None:

@@ -16,6 +16,12 @@
 // G[j][w] = S2*Jomega(D_j, w) + sum_k C_k*Jomega(D_j + 1/tau_k, w) independent of the bin, so a bin
 // costs 15 FMAs.  Weighted mean and weighted sigma over the bins use two passes (mean first), like
 // numpy.average followed by average((x-mean)^2).
+//
+// Fully anisotropic (rhombic) tensor, model 3 (Woessner 1962; Ghose, Fushman & Cowburn 2001): five rates
+// d_j and five amplitudes A_j(x, y, z), so the table is G[5][5] and a bin costs its five A_j plus 25 FMAs.  The bin loop
+// is the same code for both tensors, instantiated per coefficient functor (SymmTopCoef / EllipsoidCoef): no run-time
+// branch on the model inside it.  The reference has no working form of this model (its helpers at
+// spectral_densities.py:1908-1932 are dimensionally inconsistent), so it is built to the physics, not to those lines.
 #include "sr_internal.h"
 
 namespace {
@@ -26,7 +32,7 @@ constexpr int kNC = 2;       // covariances: (a1,b1), (a2,b2)
 
 struct RelaxArgs {
     int model, E, nRes, Kmax, B, noe_mode;
-    double D0, D1;
+    double D0, D1, D2;    // sphere: Diso; symmetric top: Dpar, Dperp; ellipsoid: Dx, Dy, Dz
     double zeta;          // S2 and C are multiplied by this on load (1.0: already scaled by the caller)
     const double *omega, *f_DD, *f_CSA, *time_fact, *gamma_ratio;
     const double *S2, *C, *tau;
@@ -54,6 +60,61 @@ __device__ __forceinline__ void quantities(const double *J, double fDD, double f
     q[11] = tf * J1;
     q[12] = tf * (0.5 * fDD * (4 * J0 + J2 + 3 * J1 + 6 * J4 + 6 * J3));
     q[13] = tf * (1.0 / 6.0 * (4 * J0 + 3 * J1));
+}
+
+// Amplitudes A_j of one unit vector in the principal-axis frame of the diffusion tensor.  NT: number of (A_j, d_j) terms.
+struct SymmTopCoef {
+    static constexpr int NT = 3;
+    bool prolate;      // unique axis z (Dpar > Dperp), else x
+    __device__ __forceinline__ SymmTopCoef(double Dpar, double Dperp, double = 0.0) : prolate(Dpar > Dperp) {}
+    __device__ __forceinline__ void operator()(const double *v, double *A) const
+    {
+        const double z = prolate ? v[2] : v[0];
+        const double z2 = z * z, w1 = 1 - z2;
+        A[0] = 3.0 * (z2 * w1); A[1] = 0.75 * (w1 * w1); A[2] = 0.25 * ((3 * z2 - 1) * (3 * z2 - 1));
+    }
+};
+
+// R^2 = Diso^2 - L^2 with L^2 = (DxDy + DxDz + DyDz)/3, written as the sum of squared differences it is equal to: the same
+// number without the cancellation of two nearly equal squares when the tensor is close to a sphere.
+__device__ __forceinline__ double ellipsoid_R(double Dx, double Dy, double Dz)
+{
+    const double a = Dx - Dy, b = Dx - Dz, c = Dy - Dz;
+    return sqrt((a * a + b * b + c * c) * (1.0 / 18.0));
+}
+
+struct EllipsoidCoef {
+    static constexpr int NT = 5;
+    double cx, cy, cz;     // delta_i / 12, delta_i = (D_i - Diso) / R; all zero for the sphere (R == 0)
+    __device__ __forceinline__ EllipsoidCoef(double Dx, double Dy, double Dz)
+    {
+        const double Diso = (Dx + Dy + Dz) * (1.0 / 3.0);
+        const double R = ellipsoid_R(Dx, Dy, Dz);
+        const double s = R > 0.0 ? 1.0 / (12.0 * R) : 0.0;
+        cx = (Dx - Diso) * s; cy = (Dy - Diso) * s; cz = (Dz - Diso) * s;
+    }
+    __device__ __forceinline__ void operator()(const double *v, double *A) const
+    {
+        const double x2 = v[0] * v[0], y2 = v[1] * v[1], z2 = v[2] * v[2];
+        const double yz = y2 * z2, xz = x2 * z2, xy = x2 * y2;
+        const double x4 = x2 * x2, y4 = y2 * y2, z4 = z2 * z2;
+        const double dd = 0.25 * (3.0 * (x4 + y4 + z4) - 1.0);
+        const double e = cx * (3.0 * x4 + 6.0 * yz - 1.0) + cy * (3.0 * y4 + 6.0 * xz - 1.0) + cz * (3.0 * z4 + 6.0 * xy - 1.0);
+        A[0] = 3.0 * yz; A[1] = 3.0 * xz; A[2] = 3.0 * xy; A[3] = dd - e; A[4] = dd + e;
+    }
+};
+
+// J(w) = sum_j A_j G[j][w], summed left to right
+template <int NT>
+__device__ __forceinline__ void combine_J(const double *A, const double (*G)[5], double *J)
+{
+#pragma unroll
+    for (int w = 0; w < 5; ++w) {
+        double j = A[0] * G[0][w];
+#pragma unroll
+        for (int t = 1; t < NT; ++t) j += A[t] * G[t][w];
+        J[w] = j;
+    }
 }
 
 template <int CNT>
@@ -100,10 +161,26 @@ __device__ __forceinline__ void fill_G(int model, double D0, double D1, double S
     }
 }
 
+// the same table for the ellipsoid: five rates d_j (threads 0..24 fill it)
+__device__ __forceinline__ void fill_G_ellipsoid(double Dx, double Dy, double Dz, double S2, double zeta, const double *C,
+                                                 const double *tau, int K, const double *om, double (*G)[5], int tid)
+{
+    if (tid < 25) {
+        const int j = tid / 5, w = tid - j * 5;
+        const double sum = Dx + Dy + Dz, R6 = 6.0 * ellipsoid_R(Dx, Dy, Dz);
+        const double DJ = j == 0 ? sum + 3 * Dx : (j == 1 ? sum + 3 * Dy : (j == 2 ? sum + 3 * Dz : (j == 3 ? 2 * sum + R6 : 2 * sum - R6)));
+        double g = S2 * jomega(DJ, om[w]);
+        for (int k = 0; k < K; ++k) { const double ck = zeta * C[k]; g += ck * jomega(DJ + 1. / tau[k], om[w]); }
+        G[j][w] = g;
+    }
+}
+
 // Weighted mean and variance over the B histogram bins (numpy.average / weighted_average_stdev: two passes) of the kNQ quantities
 // of `quantities()` at one (residue, experiment): J(bin, w) = sum_j A_j(bin) G[j][w].  Shared, inlined, by k_relax and by the
 // per-residue CSA search of the legacy `--opt new` mode, whose objective must reproduce k_relax's numbers exactly.
-__device__ __forceinline__ void relax_bins(const double (*G)[5], double fDD, double fCSA, double tf, double gr, bool prolate, int B,
+// Coef: SymmTopCoef or EllipsoidCoef, the amplitudes of a bin's vector.
+template <class Coef>
+__device__ __forceinline__ void relax_bins(const double (*G)[5], double fDD, double fCSA, double tf, double gr, const Coef &coef, int B,
                                            const double *binvecs, const double *wgt, double *red, int tid, double *mean, double *var)
 {
     double wsum;
@@ -113,11 +190,9 @@ __device__ __forceinline__ void relax_bins(const double (*G)[5], double fDD, dou
         for (int b = tid; b < B; b += 256) {
             const double w_ = wgt ? wgt[b] : 1.0;
             const double *v = binvecs + (int64_t)b * 3;
-            const double z = prolate ? v[2] : v[0];
-            const double z2 = z * z, w1 = 1 - z2;
-            const double A0 = 3.0 * (z2 * w1), A1 = 0.75 * (w1 * w1), A2 = 0.25 * ((3 * z2 - 1) * (3 * z2 - 1));
-            double J[5], q[kNQ];
-            for (int w = 0; w < 5; ++w) J[w] = A0 * G[0][w] + A1 * G[1][w] + A2 * G[2][w];
+            double A[Coef::NT], J[5], q[kNQ];
+            coef(v, A);
+            combine_J<Coef::NT>(A, G, J);
             quantities(J, fDD, fCSA, tf, gr, q);
             for (int k = 0; k < kNQ; ++k) s[k] += w_ * q[k];
             s[kNQ] += w_;
@@ -132,11 +207,9 @@ __device__ __forceinline__ void relax_bins(const double (*G)[5], double fDD, dou
         for (int b = tid; b < B; b += 256) {
             const double w_ = wgt ? wgt[b] : 1.0;
             const double *v = binvecs + (int64_t)b * 3;
-            const double z = prolate ? v[2] : v[0];
-            const double z2 = z * z, w1 = 1 - z2;
-            const double A0 = 3.0 * (z2 * w1), A1 = 0.75 * (w1 * w1), A2 = 0.25 * ((3 * z2 - 1) * (3 * z2 - 1));
-            double J[5], q[kNQ];
-            for (int w = 0; w < 5; ++w) J[w] = A0 * G[0][w] + A1 * G[1][w] + A2 * G[2][w];
+            double A[Coef::NT], J[5], q[kNQ];
+            coef(v, A);
+            combine_J<Coef::NT>(A, G, J);
             quantities(J, fDD, fCSA, tf, gr, q);
             for (int k = 0; k < kNQ; ++k) { const double d = q[k] - mean[k]; s[k] += w_ * (d * d); }
             s[kNQ] += w_ * ((q[10] - mean[10]) * (q[11] - mean[11]));
@@ -147,9 +220,12 @@ __device__ __forceinline__ void relax_bins(const double (*G)[5], double fDD, dou
     }
 }
 
+// Coef = SymmTopCoef serves models 0, 1 and 2; Coef = EllipsoidCoef serves model 3
+template <class Coef>
 __global__ __launch_bounds__(256) void k_relax(RelaxArgs a)
 {
-    __shared__ double G[3][5];
+    constexpr bool kEllipsoid = Coef::NT == 5;
+    __shared__ double G[Coef::NT][5];
     __shared__ double red[80];
     const int i = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
     const double *om = a.omega + e * 5;
@@ -158,24 +234,23 @@ __global__ __launch_bounds__(256) void k_relax(RelaxArgs a)
     const double *C = a.C + (int64_t)i * a.Kmax, *tau = a.tau + (int64_t)i * a.Kmax;
     const int K = a.nComps[i];
     const double zeta = a.zeta;
-    const bool prolate = a.D0 > a.D1;
+    const Coef coef(a.D0, a.D1, a.D2);
     double *out = a.out + ((int64_t)e * a.nRes + i) * 8;
     double *Jout = a.Jout ? a.Jout + ((int64_t)e * a.nRes + i) * 10 : nullptr;
     double *stats = a.stats ? a.stats + ((int64_t)e * a.nRes + i) * 12 : nullptr;
 
-    fill_G(a.model, a.D0, a.D1, S2, zeta, C, tau, K, om, G, tid);
+    if constexpr (kEllipsoid) fill_G_ellipsoid(a.D0, a.D1, a.D2, S2, zeta, C, tau, K, om, G, tid);
+    else fill_G(a.model, a.D0, a.D1, S2, zeta, C, tau, K, om, G, tid);
     __syncthreads();
 
-    if (a.model != 2 || a.B == 0) {
+    if (a.model < 2 || a.B == 0) {
         // one J per residue: no distribution, sigma = 0
         if (tid == 0) {
             double J[5], q[kNQ];
-            if (a.model == 2) {
-                const double *v = a.binvecs + (int64_t)i * 3;
-                const double z = prolate ? v[2] : v[0];
-                const double z2 = z * z, w1 = 1 - z2;
-                const double A0 = 3.0 * (z2 * w1), A1 = 0.75 * (w1 * w1), A2 = 0.25 * ((3 * z2 - 1) * (3 * z2 - 1));
-                for (int w = 0; w < 5; ++w) J[w] = A0 * G[0][w] + A1 * G[1][w] + A2 * G[2][w];
+            if (a.model >= 2) {
+                double A[Coef::NT];
+                coef(a.binvecs + (int64_t)i * 3, A);
+                combine_J<Coef::NT>(A, G, J);
             } else {
                 for (int w = 0; w < 5; ++w) J[w] = G[0][w];
             }
@@ -192,7 +267,7 @@ __global__ __launch_bounds__(256) void k_relax(RelaxArgs a)
 
     const double *wgt = a.weights ? a.weights + (int64_t)i * a.B : nullptr;
     double mean[kNQ], var[kNQ + kNC];
-    relax_bins(G, fDD, fCSA, tf, gr, prolate, a.B, a.binvecs, wgt, red, tid, mean, var);
+    relax_bins(G, fDD, fCSA, tf, gr, coef, a.B, a.binvecs, wgt, red, tid, mean, var);
     if (tid == 0) {
         out[0] = mean[0]; out[1] = sqrt(var[0]);
         out[2] = mean[1]; out[3] = sqrt(var[1]);
@@ -220,6 +295,13 @@ __global__ __launch_bounds__(256) void k_jomega(const double *__restrict__ x, co
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = jomega(x[i], y[i]);
+}
+
+void launch_relax(sr_ctx *ctx, const RelaxArgs &a)
+{
+    const dim3 grid((unsigned)a.nRes, (unsigned)a.E);
+    if (a.model == 3) hipLaunchKernelGGL(k_relax<EllipsoidCoef>, grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(k_relax<SymmTopCoef>, grid, dim3(256), 0, ctx->stream, a);
 }
 
 template <typename T>
@@ -526,7 +608,7 @@ struct LegacyObjective {
     double *red;
     const double *wgt;
     const double *ex;             // this residue's (3, 2)
-    bool prolate;
+    SymmTopCoef coef;             // the legacy modes know the symmetric top only
     int tid, calls;
     bool stop;
 
@@ -540,7 +622,7 @@ struct LegacyObjective {
             fcsa = ((2.0 / 15.0) * (csa * csa)) * a.g2;          // get_f_CSA: 2.0/15.0 * csa**2.0 * (gamma B0)**2
         }
         double mean[kNQ], var[kNQ + kNC];
-        relax_bins(G, a.fDD, fcsa, a.tf, a.gr, prolate, a.B, a.binvecs, wgt, red, tid, mean, var);
+        relax_bins(G, a.fDD, fcsa, a.tf, a.gr, coef, a.B, a.binvecs, wgt, red, tid, mean, var);
         double acc = 0.0;
         {
 #pragma clang fp contract(off)
@@ -565,7 +647,7 @@ __global__ __launch_bounds__(256) void k_legacy_csa_search(LegacyArgs a)
     const int i = blockIdx.x, tid = threadIdx.x;
     fill_G(2, a.D0, a.D1, a.S2[i], 1.0, a.C + (int64_t)i * a.Kmax, a.tau + (int64_t)i * a.Kmax, a.nComps[i], a.omega, G, tid);
     __syncthreads();
-    LegacyObjective f{a, G, red, a.weights + (int64_t)i * a.B, a.expt + (int64_t)i * 6, a.D0 > a.D1, tid, 0, false};
+    LegacyObjective f{a, G, red, a.weights + (int64_t)i * a.B, a.expt + (int64_t)i * 6, SymmTopCoef(a.D0, a.D1), tid, 0, false};
     double x, fval;
     powell_min_1d(f, a.csa0[i], a.step, a.xtol, a.ftol, a.maxiter, a.maxfun, x, fval);
     if (tid == 0) {
@@ -603,20 +685,20 @@ int sr_jomega_relax_f64(sr_ctx *ctx, int model, const double *D, int E, const do
                         double *Jout, double *stats)
 {
     SR_CHECK_CTX(ctx);
-    SR_REQUIRE(model >= 0 && model <= 2, -3, "sr_jomega_relax_f64: model must be 0, 1 or 2");
+    SR_REQUIRE(model >= 0 && model <= 3, -3, "sr_jomega_relax_f64: model must be 0, 1, 2 or 3");
     SR_REQUIRE(E >= 1 && nRes >= 1 && Kmax >= 1 && Kmax <= kMaxK && B >= 0, -3, "sr_jomega_relax_f64: bad sizes");
     SR_REQUIRE(E <= 65535, -3, "sr_jomega_relax_f64: too many experiments");
     SR_REQUIRE(omega && f_DD && f_CSA && time_fact && gamma_ratio && S2 && C && tau && nComps && out, -2,
                "sr_jomega_relax_f64: null pointer");
     SR_REQUIRE(model == 0 || D, -2, "sr_jomega_relax_f64: D required");
-    SR_REQUIRE(model != 2 || binvecs, -2, "sr_jomega_relax_f64: symmetric top needs vectors");
+    SR_REQUIRE(model < 2 || binvecs, -2, "sr_jomega_relax_f64: symmetric top and ellipsoid need vectors");
     SR_REQUIRE(noe_mode == 0 || noe_mode == 1, -3, "sr_jomega_relax_f64: noe_mode must be 0 or 1");
     for (int i = 0; i < nRes; ++i)
         SR_REQUIRE(nComps[i] >= 0 && nComps[i] <= Kmax, -3, "sr_jomega_relax_f64: nComps[%d]=%d out of range", i, nComps[i]);
     // pack every input into one staging buffer
     const size_t nE = (size_t)E, nR = (size_t)nRes;
     const size_t cnt = nE * 5 + nE + nE * nR + nE + nE + nR + 2 * nR * Kmax +
-                       (model == 2 ? (B > 0 ? (size_t)B * 3 : nR * 3) : 0) +
+                       (model >= 2 ? (B > 0 ? (size_t)B * 3 : nR * 3) : 0) +
                        ((B > 0 && weights && !weights_on_device) ? nR * B : 0);
     double *stage = (double *)sr_workspace(ctx, SR_WS_IN0, cnt * sizeof(double));
     int *ncomp_d = (int *)sr_workspace(ctx, SR_WS_IN1, nR * sizeof(int));
@@ -625,9 +707,10 @@ int sr_jomega_relax_f64(sr_ctx *ctx, int model, const double *D, int E, const do
     double *st_d = stats ? (double *)sr_workspace(ctx, SR_WS_OUT2, nE * nR * 12 * sizeof(double)) : nullptr;
     if (!stage || !ncomp_d || !out_d || (Jout && !J_d) || (stats && !st_d)) return -5;
     RelaxArgs a;
-    a.model = model; a.E = E; a.nRes = nRes; a.Kmax = Kmax; a.B = (model == 2) ? B : 0; a.noe_mode = noe_mode;
+    a.model = model; a.E = E; a.nRes = nRes; a.Kmax = Kmax; a.B = (model >= 2) ? B : 0; a.noe_mode = noe_mode;
     a.D0 = D ? D[0] : 0.0;
-    a.D1 = (D && model == 2) ? D[1] : 0.0;
+    a.D1 = (D && model >= 2) ? D[1] : 0.0;
+    a.D2 = (D && model == 3) ? D[2] : 0.0;
     a.zeta = 1.0;
     double *p = stage;
     auto put = [&](const double *src, size_t n) -> const double * {
@@ -647,8 +730,8 @@ int sr_jomega_relax_f64(sr_ctx *ctx, int model, const double *D, int E, const do
     a.tau = put(tau, nR * Kmax);
     a.binvecs = nullptr;
     a.weights = nullptr;
-    if (model == 2) a.binvecs = put(binvecs, B > 0 ? (size_t)B * 3 : nR * 3);
-    if (model == 2 && B > 0 && weights) a.weights = weights_on_device ? weights : put(weights, nR * B);
+    if (model >= 2) a.binvecs = put(binvecs, B > 0 ? (size_t)B * 3 : nR * 3);
+    if (model >= 2 && B > 0 && weights) a.weights = weights_on_device ? weights : put(weights, nR * B);
     SR_REQUIRE(a.omega && a.f_DD && a.f_CSA && a.time_fact && a.gamma_ratio && a.S2 && a.C && a.tau, -6,
                "sr_jomega_relax_f64: host to device copy failed");
     SR_HIP(hipMemcpyAsync(ncomp_d, nComps, nR * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -656,7 +739,7 @@ int sr_jomega_relax_f64(sr_ctx *ctx, int model, const double *D, int E, const do
     a.out = out_d;
     a.Jout = J_d;
     a.stats = st_d;
-    hipLaunchKernelGGL(k_relax, dim3((unsigned)nRes, (unsigned)E), dim3(256), 0, ctx->stream, a);
+    launch_relax(ctx, a);
     SR_HIP(hipGetLastError());
     SR_HIP(hipMemcpyAsync(out, out_d, nE * nR * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (Jout) SR_HIP(hipMemcpyAsync(Jout, J_d, nE * nR * 10 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -672,24 +755,25 @@ int sr_jomega_relax_f64_dev(sr_ctx *ctx, int model, const double *D, int E, cons
                             double *stats)
 {
     SR_CHECK_CTX(ctx);
-    SR_REQUIRE(model >= 0 && model <= 2, -3, "sr_jomega_relax_f64_dev: model must be 0, 1 or 2");
+    SR_REQUIRE(model >= 0 && model <= 3, -3, "sr_jomega_relax_f64_dev: model must be 0, 1, 2 or 3");
     SR_REQUIRE(E >= 1 && E <= 65535 && nRes >= 1 && Kmax >= 1 && Kmax <= kMaxK && B >= 0, -3, "sr_jomega_relax_f64_dev: bad sizes");
     SR_REQUIRE(omega && f_DD && f_CSA && time_fact && gamma_ratio && S2 && C && tau && nComps && out, -2,
                "sr_jomega_relax_f64_dev: null pointer");
     SR_REQUIRE(model == 0 || D, -2, "sr_jomega_relax_f64_dev: D required");
-    SR_REQUIRE(model != 2 || binvecs, -2, "sr_jomega_relax_f64_dev: symmetric top needs vectors");
+    SR_REQUIRE(model < 2 || binvecs, -2, "sr_jomega_relax_f64_dev: symmetric top and ellipsoid need vectors");
     SR_REQUIRE(noe_mode == 0 || noe_mode == 1, -3, "sr_jomega_relax_f64_dev: noe_mode must be 0 or 1");
     RelaxArgs a;
-    a.model = model; a.E = E; a.nRes = nRes; a.Kmax = Kmax; a.B = (model == 2) ? B : 0; a.noe_mode = noe_mode;
+    a.model = model; a.E = E; a.nRes = nRes; a.Kmax = Kmax; a.B = (model >= 2) ? B : 0; a.noe_mode = noe_mode;
     a.D0 = D ? D[0] : 0.0;
-    a.D1 = (D && model == 2) ? D[1] : 0.0;
+    a.D1 = (D && model >= 2) ? D[1] : 0.0;
+    a.D2 = (D && model == 3) ? D[2] : 0.0;
     a.zeta = zeta;
     a.omega = omega; a.f_DD = f_DD; a.f_CSA = f_CSA; a.time_fact = time_fact; a.gamma_ratio = gamma_ratio;
     a.S2 = S2; a.C = C; a.tau = tau; a.nComps = nComps;
-    a.binvecs = model == 2 ? binvecs : nullptr;
-    a.weights = (model == 2 && B > 0) ? weights : nullptr;
+    a.binvecs = model >= 2 ? binvecs : nullptr;
+    a.weights = (model >= 2 && B > 0) ? weights : nullptr;
     a.out = out; a.Jout = Jout; a.stats = stats;
-    hipLaunchKernelGGL(k_relax, dim3((unsigned)nRes, (unsigned)E), dim3(256), 0, ctx->stream, a);
+    launch_relax(ctx, a);
     SR_HIP(hipGetLastError());
     return 0;
 }

@@ -449,7 +449,10 @@ class Context:
 
     def relax_dev(self, model, D, E, omega_ptr, fDD_ptr, fCSA_ptr, tf_ptr, gr_ptr, nRes, Kmax, zeta, S2_ptr, C_ptr, tau_ptr,
                   K_ptr, B, binvecs_ptr, weights_ptr, noe_mode, out_ptr, Jout_ptr=None, stats_ptr=None):
+        """Context.relax on device pointers (sr_jomega_relax_f64_dev); model and D as there, model 3 = [Dx, Dy, Dz]"""
         Dh = _f64(np.atleast_1d(D))
+        if model == 3 and Dh.size != 3:
+            raise ValueError('ellipsoid model needs D = [Dx, Dy, Dz]')
         check(self.lib.sr_jomega_relax_f64_dev(self.h, model, _ptr(Dh), E, omega_ptr, fDD_ptr, fCSA_ptr, tf_ptr, gr_ptr, nRes,
                                                Kmax, float(zeta), S2_ptr, C_ptr, tau_ptr, K_ptr, B, binvecs_ptr, weights_ptr,
                                                noe_mode, out_ptr, Jout_ptr, stats_ptr), 'sr_jomega_relax_f64_dev')
@@ -468,8 +471,9 @@ class Context:
 
     def relax(self, model, D, omega, f_DD, f_CSA, time_fact, gamma_ratio, S2, C, tau, nComps,
               binvecs=None, weights=None, resvecs=None, noe_mode=0, want_J=False, weights_dev_ptr=None, want_stats=False):
-        """model 0 direct / 1 sphere (D=[Diso]) / 2 symmetric top (D=[Dpar, Dperp]).
-        Symmetric top: either `binvecs` (B,3) shared by all residues with optional `weights` (nRes,B), or
+        """model 0 direct / 1 sphere (D=[Diso]) / 2 symmetric top (D=[Dpar, Dperp]) / 3 rhombic ellipsoid (D=[Dx, Dy, Dz],
+        the principal values along the x, y, z axes of the frame the vectors are in).
+        Symmetric top and ellipsoid: either `binvecs` (B,3) shared by all residues with optional `weights` (nRes,B), or
         `resvecs` (nRes,3), one vector per residue.  Returns out (E, nRes, 4, 2) = [R1,R2,NOE,rho] x
         [mean, sigma] and J (E, nRes, 5, 2) or None."""
         omega = _f64(np.atleast_2d(omega))
@@ -488,7 +492,9 @@ class Context:
         B = 0
         bv = None
         w = None
-        if model == 2:
+        if model == 3 and (Dd is None or Dd.size != 3):
+            raise ValueError('ellipsoid model needs D = [Dx, Dy, Dz]')
+        if model in (2, 3):
             if binvecs is not None:
                 bv = _f64(binvecs)
                 B = bv.shape[0]
@@ -501,7 +507,7 @@ class Context:
                 if bv.shape != (nRes, 3):
                     raise ValueError('resvecs must be (nRes, 3)')
             else:
-                raise ValueError('symmetric-top model needs binvecs or resvecs')
+                raise ValueError('symmetric-top and ellipsoid models need binvecs or resvecs')
         out = np.empty((E, nRes, 4, 2))
         J = np.empty((E, nRes, 5, 2)) if want_J else None
         stats = np.empty((E, nRes, 12)) if want_stats else None

@@ -216,6 +216,10 @@ def run(optMode, relax_obj, Diso, matched, expblock_unused, nRefinementCycles, r
         param_names, param_scaling, param_units, print_xy, sim_resid_all, CSAvaluesArray, S2_list):
     """The mode switch of :853-1002.  Returns (optHeader, CSAvaluesArray, S2_list)."""
     sim_ind, fsim_resid, fS2, fconsts, ftaus, fvecXH, fw, fCSAs, expblock = matched
+    if relax_obj.rotdifModel.name == 'rigid_ellipsoid':
+        print("= = = ERROR: the legacy --opt modes know the symmetric top only, not the fully anisotropic tensor; "
+              "calculate-relaxations-multi-field.py optimises Diso, Daniso and Drhomb.", file=sys.stderr)
+        sys.exit(1)
     fnum = len(fS2)
     Diso_init = Diso
     if optMode == 'new':

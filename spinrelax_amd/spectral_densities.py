@@ -56,7 +56,9 @@ class gyromag:
 class diffusionModel:
     """The subset of spectral_densities.py:1450-1558 the hot path uses: 'direct_transform',
     'rigid_sphere_D' (D = Diso), 'rigid_sphere_T', 'rigid_symmtop_D' (D = [Dpar, Dperp]),
-    'rigid_symmtop_Dref' (Diso, aniso)."""
+    'rigid_symmtop_Dref' (Diso, aniso), and the fully anisotropic 'rigid_ellipsoid_D' (Dx, Dy, Dz) /
+    'rigid_ellipsoid_Dref' (Diso, aniso, rhomb): name 'rigid_ellipsoid', D = [Dx, Dy, Dz] along the axes of the
+    principal-axis frame.  The reference's branch for these uses undefined names; this one follows DESIGN.md."""
 
     def __init__(self, model, timeUnit, *args):
         self.timeUnit = timeUnit
@@ -77,6 +79,12 @@ class diffusionModel:
         elif model == 'rigid_symmtop_D':
             self.name = 'rigid_symmtop'
             self.D = np.array([args[0], args[1]], dtype=float)
+        elif model == 'rigid_ellipsoid_Dref':
+            self.name = 'rigid_ellipsoid'
+            self.D = np.array(_nph.ellipsoid_from_iso(args[0], args[1], args[2]), dtype=float)
+        elif model == 'rigid_ellipsoid_D':
+            self.name = 'rigid_ellipsoid'
+            self.D = np.array([args[0], args[1], args[2]], dtype=float)
         else:
             print("= = ERROR: rotational diffusion model %s is not supported by the GPU path." % model, file=sys.stderr)
             sys.exit(1)
@@ -95,6 +103,9 @@ class diffusionModel:
             tmp = self.D[0] / self.D[1]
             Dperp = 3.0 * Diso / (2.0 + tmp)
             self.D = np.array([tmp * Dperp, Dperp])
+        elif self.name == 'rigid_ellipsoid':
+            # all three principal values by one factor: anisotropy and rhombicity stay as they are
+            self.D = self.D * (Diso / np.mean(self.D))
 
 
 class relaxationModel:
@@ -204,6 +215,24 @@ def A_coefficients_symmtop(v, bProlate=True):
     return _nph.A_coefficients_symmtop(v, bProlate)
 
 
+# Fully anisotropic tensor (Woessner 1962): same names as the reference's helpers (spectral_densities.py:1908-1932), not
+# their arithmetic, which is dimensionally inconsistent -- see _hostmath.py and DESIGN.md.
+def D_coefficients_ellipsoid(D):
+    return _nph.D_coefficients_ellipsoid(D)
+
+
+def A_coefficients_ellipsoid(v, D):
+    return _nph.A_coefficients_ellipsoid(v, D)
+
+
+def J_combine_ellipsoid_exp_decayN(om, v, D, S2, consts, taus):
+    return _nph.J_combine_ellipsoid_exp_decayN(om, v, D, S2, consts, taus)
+
+
+ellipsoid_from_iso = _nph.ellipsoid_from_iso
+iso_from_ellipsoid = _nph.iso_from_ellipsoid
+
+
 # ---------------------------------------------------------------------------------------------------
 # batched R1/R2/NOE/rho (calculate-relaxations-from-Ct.py:82-191)
 # ---------------------------------------------------------------------------------------------------
@@ -227,6 +256,8 @@ def _model_args(RObj):
         return 1, [RObj.rotdifModel.D]
     if name == 'rigid_symmtop':
         return 2, [RObj.rotdifModel.D[0], RObj.rotdifModel.D[1]]
+    if name == 'rigid_ellipsoid':
+        return 3, [RObj.rotdifModel.D[0], RObj.rotdifModel.D[1], RObj.rotdifModel.D[2]]
     print("= = ERROR: Unknown rotdifModel in the relaxation object used in calculations!", file=sys.stderr)
     return None, None
 
@@ -241,7 +272,7 @@ def _run(RObj, nSites, S2, consts, taus, vecXH, weights, CSAvaluesArray, want_J,
     fcsa = RObj.get_f_CSA(np.asarray(CSAvaluesArray, dtype=float))
     kw = {}
     dist = False
-    if model == 2:
+    if model in (2, 3):
         vecXH = np.asarray(vecXH, dtype=float)
         if vecXH.ndim > 2:
             dist = True
@@ -321,5 +352,6 @@ def read_vector_distribution_from_file(fileName):
 # spinRelaxationExperiments) lives in spin_relaxation.py; re-exported here under the reference's module name
 from .spin_relaxation import (angularFrequencies, gyromagMultiCSA, globalRotationalDiffusion_Base,      # noqa: E402,F401
                               globalRotationalDiffusion_Isotropic, globalRotationalDiffusion_Axisymmetric,
+                              globalRotationalDiffusion_Ellipsoid,
                               spinRelaxationBase, spinRelaxationR1, spinRelaxationR2, spinRelaxationNOE,
                               spinRelaxationExperiments)

@@ -174,16 +174,27 @@ class globalRotationalDiffusion_Isotropic(globalRotationalDiffusion_Base):
     def set_Daniso(self, Daniso):
         return
 
+    def get_Drhomb(self):
+        return 0.0
+
+    def set_Drhomb(self, rhomb):
+        return
+
     def kernel_model(self):
         return 1, [self.D]
 
 
 class globalRotationalDiffusion_Axisymmetric(globalRotationalDiffusion_Base):
-    """spectral_densities.py:463-603; stored as (Diso, Daniso); bConvert: D given as (Dpar, Dperp)."""
+    """spectral_densities.py:463-603; stored as (Diso, Daniso); bConvert: D given as (Dpar, Dperp).
+    The object also carries a rhombicity, 0 unless set (set_Drhomb): at 0 it is the reference's symmetric top and takes
+    the symmetric-top kernel, unchanged; otherwise it evaluates as the ellipsoid of hm.ellipsoid_from_iso."""
 
     def __init__(self, D=None, bConvert=False, tau=None, aniso=None):
         globalRotationalDiffusion_Base.__init__(self)
         self.name = 'axisymmetric'
+        self.rhomb = 0.0
+        self.bEllipsoid = False
+        self.uniqueZ = None        # None: the unique axis follows the anisotropy (z for Daniso >= 1, else x)
         if D is not None:
             if bConvert:
                 self.D = np.array([(2.0 * D[1] + D[0]) / 3.0, D[0] / D[1]], dtype=float)
@@ -205,13 +216,42 @@ class globalRotationalDiffusion_Axisymmetric(globalRotationalDiffusion_Base):
     def get_Daniso(self):
         return self.D[1]
 
+    def set_Drhomb(self, rhomb):
+        self.rhomb = float(rhomb)
+
+    def get_Drhomb(self):
+        return self.rhomb
+
     def transform_D(self):
         tmp = 3.0 * self.D[0] / (2.0 + self.D[1])
         return self.D[1] * tmp, tmp
 
     def kernel_model(self):
+        if self.bEllipsoid or self.rhomb != 0.0:
+            return 3, list(hm.ellipsoid_from_iso(self.D[0], self.D[1], self.rhomb, self.uniqueZ))
         Dpar, Dperp = self.transform_D()
         return 2, [Dpar, Dperp]
+
+
+class globalRotationalDiffusion_Ellipsoid(globalRotationalDiffusion_Axisymmetric):
+    """Fully anisotropic tensor, built from three values: (Diso, Daniso, Drhomb), or with bConvert the principal values
+    (Dx, Dy, Dz) along the axes of the frame the vectors are in.  Always evaluated by the ellipsoid kernel (model 3), at
+    rhombicity 0 too.  Stored as (Diso, Daniso) + rhombicity like its parent, so Diso / Daniso / Drhomb can be optimised;
+    no counterpart in the reference."""
+
+    def __init__(self, D, bConvert=False):
+        if len(D) != 3:
+            _BAIL("globalRotationalDiffusion_Ellipsoid", "needs three values: Diso, Daniso, Drhomb (or Dx, Dy, Dz with bConvert)")
+        uniqueZ = None
+        if bConvert:
+            # any tensor: the unique axis found here stays fixed, whatever an optimiser does to the anisotropy
+            D0, D1, D2, uniqueZ = hm.iso_from_ellipsoid(D, with_axis=True)
+            D = (D0, D1, D2)
+        globalRotationalDiffusion_Axisymmetric.__init__(self, D=[D[0], D[1]])
+        self.name = 'ellipsoid'
+        self.rhomb = float(D[2])
+        self.bEllipsoid = True
+        self.uniqueZ = uniqueZ
 
 
 class spinRelaxationBase:
@@ -309,10 +349,10 @@ _TYPES = {'R1': spinRelaxationR1, 'R2': spinRelaxationR2, 'NOE': spinRelaxationN
 
 class spinRelaxationExperiments:
     """spectral_densities.py:909-1447."""
-    listAllowedOptimisationVariables = ['Diso', 'Daniso', 'CSA', 'zeta', 'rsCSA']
-    dictStepSizes = {'Diso': 1e-5, 'Daniso': 0.1, 'zeta': 0.1, 'CSA': 1e-5, 'rsCSA': 1e-5}
-    dictExportScaling = {'Diso': 1.0, 'Daniso': 1.0, 'zeta': 1.0, 'CSA': 1e6, 'rsCSA': 1e6}
-    dictExportUnits = {'Diso': 'ps^-1', 'Daniso': 'a.u.', 'zeta': 'a.u.', 'CSA': 'ppm', 'rsCSA': 'ppm'}
+    listAllowedOptimisationVariables = ['Diso', 'Daniso', 'Drhomb', 'CSA', 'zeta', 'rsCSA']
+    dictStepSizes = {'Diso': 1e-5, 'Daniso': 0.1, 'Drhomb': 0.1, 'zeta': 0.1, 'CSA': 1e-5, 'rsCSA': 1e-5}
+    dictExportScaling = {'Diso': 1.0, 'Daniso': 1.0, 'Drhomb': 1.0, 'zeta': 1.0, 'CSA': 1e6, 'rsCSA': 1e6}
+    dictExportUnits = {'Diso': 'ps^-1', 'Daniso': 'a.u.', 'Drhomb': 'a.u.', 'zeta': 'a.u.', 'CSA': 'ppm', 'rsCSA': 'ppm'}
 
     def __init__(self, globalRotDif=None, localCtModels=None, ctx=None):
         self.numExpts = 0
@@ -437,6 +477,12 @@ class spinRelaxationExperiments:
     def get_global_Daniso(self):
         return self.globalRotDif.get_Daniso()
 
+    def set_global_Drhomb(self, rhomb):
+        self.globalRotDif.set_Drhomb(rhomb)
+
+    def get_global_Drhomb(self):
+        return self.globalRotDif.get_Drhomb()
+
     def set_global_zeta(self, zeta):
         self.localCtModels.set_zeta(zeta)
 
@@ -451,11 +497,11 @@ class spinRelaxationExperiments:
         return self.spinrelax[0].angFreq.gA.get_csa(ind)
 
     def _getter(self, name):
-        return {'Diso': self.get_global_Diso, 'Daniso': self.get_global_Daniso, 'zeta': self.get_global_zeta,
+        return {'Diso': self.get_global_Diso, 'Daniso': self.get_global_Daniso, 'Drhomb': self.get_global_Drhomb, 'zeta': self.get_global_zeta,
                 'CSA': self.get_first_csa}[name]
 
     def _setter(self, name):
-        return {'Diso': self.set_global_Diso, 'Daniso': self.set_global_Daniso, 'zeta': self.set_global_zeta,
+        return {'Diso': self.set_global_Diso, 'Daniso': self.set_global_Daniso, 'Drhomb': self.set_global_Drhomb, 'zeta': self.set_global_zeta,
                 'CSA': self.set_all_csa}[name]
 
     # ---- evaluation: ONE batched GPU launch for all experiments ----
@@ -473,9 +519,9 @@ class spinRelaxationExperiments:
         gr = np.array([sp.angFreq.gB.gamma / sp.angFreq.gA.gamma for sp in self.spinrelax])
         model, D = self.globalRotDif.kernel_model()
         kw = {}
-        if model == 2:
+        if model in (2, 3):
             if not self.globalRotDif.bVecs:
-                _BAIL("eval_all", "the axisymmetric model needs a vector distribution (--distfn)")
+                _BAIL("eval_all", "the axisymmetric and ellipsoid models need a vector distribution (--distfn)")
             kw = dict(binvecs=self.globalRotDif.binvecs, weights=self.globalRotDif.vecWeights)
         return (model, D, om, fdd, fcsa, tf, gr, zeta * S2, zeta * C, tau, K), kw
 
@@ -702,6 +748,8 @@ class spinRelaxationExperiments:
         for x in spinRelaxationExperiments.listAllowedOptimisationVariables:
             if x == 'rsCSA':
                 continue
+            if x == 'Drhomb' and x not in self.listUpdateVariables and self.globalRotDif.kernel_model()[0] != 3:
+                continue          # the reference's header, unchanged, wherever the rhombicity plays no part
             v = self._getter(x)()
             s1 = 'Optimised' if x in self.listUpdateVariables else 'Fixed'
             if x == 'CSA' and type(v) is np.ndarray:

@@ -4,7 +4,9 @@
     # device code object of sr_fit.hip at any revision (the flags of spinrelax_amd/build.py, device only):
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -ffp-contract=off --offload-device-only \
         -c spinrelax_amd/csrc/sr_fit.hip -o a.co
-    scripts/dev/isa_diff.py a.co b.co 'k_trf|k_order_search|search_order'
+    # where hipcc wraps the code object in an offload bundle (llvm-objdump: "not recognized as a valid object file"):
+    /opt/rocm/llvm/bin/clang-offload-bundler --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=a.co --output=a.elf
+    scripts/dev/isa_diff.py a.elf b.elf 'k_trf|k_order_search|search_order'      # or a.co b.co where they are plain code objects
 
 Disassembles both with llvm-objdump -d, cuts the listing at every function symbol, drops addresses and encodings, writes branch
 targets as symbol + offset instead of a word offset and masks the offsets of pc-relative addresses (a function that only moved
@@ -31,8 +33,8 @@ def functions(co):
             continue
         code, _, comment = line.partition('//')
         ins = re.sub(r'<[^>]*>', '<>', code.strip())
-        if not ins:
-            continue
+        if not ins or ins == '...':        # '...': objdump's mark for the zero padding behind the last function of the section -- it
+            continue                       # moves to another function when the functions change places, and it is no instruction
         # s_branch / s_cbranch_* <signed word offset>: the offset is replaced by the target as objdump names it, symbol + byte
         # offset (the same symbol: "+0x..."), so a function that only moved -- or whose branches lead into code placed elsewhere
         # in the object -- compares equal, while a branch to another place in the function does not

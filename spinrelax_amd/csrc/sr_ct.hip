@@ -779,13 +779,7 @@ __global__ __launch_bounds__(256) void k_ct_fft(CtFftArgs a)
 template <int N1, bool HALF>
 int launch_ct_fft_h(sr_ctx *ctx, const CtFftArgs &a, int64_t series)
 {
-    const size_t lds = (size_t)fft_lds_slots(256 * N1) * sizeof(cplx);
-    if (lds > 64 * 1024)
-        SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ct_fft<N1, HALF>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_ct_fft<N1, HALF>), dim3((unsigned)series), dim3(256), lds, ctx->stream, a);
-    SR_HIP(hipGetLastError());
-    return 0;
+    return sr_launch(ctx, k_ct_fft<N1, HALF>, dim3((unsigned)series), dim3(256), (size_t)fft_lds_slots(256 * N1) * sizeof(cplx), a);
 }
 template <int N1>
 int launch_ct_fft(sr_ctx *ctx, const CtFftArgs &a, int64_t series)
@@ -1312,13 +1306,7 @@ constexpr size_t rfft_lds_bytes()
 template <int N1, bool HALF, bool TR>
 int launch_ct_rfft_h(sr_ctx *ctx, const CtRfftArgs &a, int64_t series)
 {
-    const size_t lds = rfft_lds_bytes<N1, HALF, TR>();
-    if (lds > 64 * 1024)
-        SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ct_rfft<N1, HALF, TR>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_ct_rfft<N1, HALF, TR>), dim3((unsigned)series), dim3(256), lds, ctx->stream, a);
-    SR_HIP(hipGetLastError());
-    return 0;
+    return sr_launch(ctx, k_ct_rfft<N1, HALF, TR>, dim3((unsigned)series), dim3(256), rfft_lds_bytes<N1, HALF, TR>(), a);
 }
 // With L = F/2 the two transform lengths are tied to the chunk length: M = 6144 serves 4096 < 1.5 F <= 6144, i.e. F <= 4096
 // (at most 8 of the 12 input blocks are non-zero: HALF), M = 8192 serves 4096 < F <= 5461 (more than half: not HALF).
@@ -1429,11 +1417,7 @@ __global__ __launch_bounds__(256) void k_transpose_f64(const double *__restrict_
 template <int W>
 int launch_ct(sr_ctx *ctx, const CtArgs &a, int64_t nblocks, size_t lds_bytes)
 {
-    if (int rc = sr_grant_lds(ctx, W == 1 ? SR_K_CT1 : SR_K_CT4, reinterpret_cast<const void *>(&k_ct_palmer<W>), lds_bytes))
-        return rc;
-    hipLaunchKernelGGL(k_ct_palmer<W>, dim3((unsigned)nblocks), dim3(W * 64), lds_bytes, ctx->stream, a);
-    SR_HIP(hipGetLastError());
-    return 0;
+    return sr_launch(ctx, k_ct_palmer<W>, dim3((unsigned)nblocks), dim3(W * 64), lds_bytes, a);
 }
 
 }  // namespace

@@ -453,9 +453,7 @@ int launch_ct_rfft32_h(sr_ctx *ctx, const Ct32Args &a, int64_t series)
     constexpr size_t Fmax = N1 == 4 ? 1365 : (N1 == 8 ? 2730 : (N1 == 12 ? 4096 : 5461));
     static_assert((size_t)f32_img_slots(N1) * sizeof(c32) >= (Fmax + 3) * 4, "k_ct_rfft32: E does not fit the image");
     static_assert((size_t)f32_img_slots(N1) * sizeof(c32) >= (Fmax / 2 + 2) * 8, "k_ct_rfft32: Tt does not fit the image");
-    hipLaunchKernelGGL((k_ct_rfft32<N1, FULL>), dim3((unsigned)series), dim3(256), lds, ctx->stream, a);
-    SR_HIP(hipGetLastError());
-    return 0;
+    return sr_launch(ctx, k_ct_rfft32<N1, FULL>, dim3((unsigned)series), dim3(256), lds, a);
 }
 
 }  // namespace

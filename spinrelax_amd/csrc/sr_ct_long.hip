@@ -492,18 +492,13 @@ int sr_launch_ct_long(sr_ctx *ctx, const float *soa, int64_t Npad, const int64_t
     SR_HIP(hipGetLastError());
     const size_t lds_cross = (size_t)(nd + 1) * kKTile * sizeof(double2) + (size_t)nb * kKTile * sizeof(c32);
     const size_t lds_inv = (size_t)kH * sizeof(double2);
-    if (int rc = sr_grant_lds(ctx, SR_K_CTL_CROSS, reinterpret_cast<const void *>(&k_ctl_cross), lds_cross)) return rc;
-    if (int rc = sr_grant_lds(ctx, SR_K_CTL_INV, reinterpret_cast<const void *>(&k_ctl_inverse), lds_inv)) return rc;
     static_assert(ctl_spectra_lds_bytes() <= 64 * 1024, "k_ctl_spectra: the image is meant to fit the default LDS grant");
     for (int64_t s0 = 0; s0 < series; s0 += tile) {
         const unsigned ns = (unsigned)(series - s0 < tile ? series - s0 : tile);
         a.s0 = (int)s0;
-        hipLaunchKernelGGL(k_ctl_spectra, dim3((unsigned)nb, ns), dim3(256), ctl_spectra_lds_bytes(), ctx->stream, a);
-        SR_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_ctl_cross, dim3((kH + kKTile) / kKTile, ns), dim3(256), lds_cross, ctx->stream, a);
-        SR_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_ctl_inverse, dim3((unsigned)nd, ns), dim3(256), lds_inv, ctx->stream, a);
-        SR_HIP(hipGetLastError());
+        if (int rc = sr_launch(ctx, k_ctl_spectra, dim3((unsigned)nb, ns), dim3(256), ctl_spectra_lds_bytes(), a)) return rc;
+        if (int rc = sr_launch(ctx, k_ctl_cross, dim3((kH + kKTile) / kKTile, ns), dim3(256), lds_cross, a)) return rc;
+        if (int rc = sr_launch(ctx, k_ctl_inverse, dim3((unsigned)nd, ns), dim3(256), lds_inv, a)) return rc;
     }
     SR_HIP(hipEventRecord(ctx->ctlong_ev, ctx->stream));
     ctx->ctlong_ev_set = 1;

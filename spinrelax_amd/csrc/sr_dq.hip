@@ -177,15 +177,14 @@ int sr_dq_moments_f64(sr_ctx *ctx, const double *q, int64_t N, const int32_t *la
     SR_REQUIRE(q && lags && out, -2, "sr_dq_moments_f64: null pointer");
     SR_REQUIRE(N >= 2 && nlags >= 1 && nchunk >= 1, -3, "sr_dq_moments_f64: bad sizes");
     const size_t nout = (size_t)nlags * nchunk * 7;
-    double *q_d = (double *)sr_workspace(ctx, SR_WS_VECS, (size_t)N * 4 * sizeof(double));
-    double *out_d = (double *)sr_workspace(ctx, SR_WS_OUT0, nout * sizeof(double));
-    if (!q_d || !out_d) return -5;
-    SR_HIP(hipMemcpyAsync(q_d, q, (size_t)N * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    sr_stage st(ctx);
+    const double *q_d = st.open(SR_WS_VECS, (size_t)N * 4 * sizeof(double)).put(q, (size_t)N * 4);
+    double *out_d = st.take<double>(SR_WS_OUT0, nout);
+    if (st.rc) return st.rc;
     int rc = sr_dq_moments_f64_dev(ctx, q_d, N, lags, nlags, nchunk, out_d);
     if (rc) return rc;
-    SR_HIP(hipMemcpyAsync(out, out_d, nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(out, out_d, nout);
+    return st.finish();
 }
 
 int sr_dq_moments_f32(sr_ctx *ctx, const float *q, int64_t N, const int32_t *lags, int nlags, int nchunk, double *out)
@@ -194,15 +193,14 @@ int sr_dq_moments_f32(sr_ctx *ctx, const float *q, int64_t N, const int32_t *lag
     SR_REQUIRE(q && lags && out, -2, "sr_dq_moments_f32: null pointer");
     SR_REQUIRE(N >= 2 && nlags >= 1 && nchunk >= 1, -3, "sr_dq_moments_f32: bad sizes");
     const size_t nout = (size_t)nlags * nchunk * 7;
-    float *q_d = (float *)sr_workspace(ctx, SR_WS_VECS, (size_t)N * 4 * sizeof(float));
-    double *out_d = (double *)sr_workspace(ctx, SR_WS_OUT0, nout * sizeof(double));
-    if (!q_d || !out_d) return -5;
-    SR_HIP(hipMemcpyAsync(q_d, q, (size_t)N * 4 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    sr_stage st(ctx);
+    const float *q_d = st.open(SR_WS_VECS, (size_t)N * 4 * sizeof(float)).put(q, (size_t)N * 4);
+    double *out_d = st.take<double>(SR_WS_OUT0, nout);
+    if (st.rc) return st.rc;
     int rc = sr_dq_moments_f32_dev(ctx, q_d, N, lags, nlags, nchunk, out_d);
     if (rc) return rc;
-    SR_HIP(hipMemcpyAsync(out, out_d, nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(out, out_d, nout);
+    return st.finish();
 }
 
 }  // extern "C"

@@ -1423,33 +1423,6 @@ __global__ __launch_bounds__(W * 64, NMAX <= 5 ? SR_FIT_WAVES_EU_LOW : SR_FIT_WA
     }
 }
 
-template <int NMAX, int W>
-int launch_search_w(sr_ctx *ctx, const SearchArgs &a)
-{
-    const size_t lds_small = fit_lds_doubles(W, 0) * sizeof(double);
-    const size_t lds_full = fit_lds_doubles(W, a.L) * sizeof(double);
-    if (ctx->fit_lds && lds_full <= sr_lds_limit(ctx)) {
-        if (lds_full > 64 * 1024)
-            SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_order_search<NMAX, W, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full));
-        hipLaunchKernelGGL((k_order_search<NMAX, W, true>), dim3((unsigned)a.nRes), dim3(W * 64), lds_full, ctx->stream, a);
-    } else {
-        hipLaunchKernelGGL((k_order_search<NMAX, W, false>), dim3((unsigned)a.nRes), dim3(W * 64), lds_small, ctx->stream, a);
-    }
-    SR_HIP(hipGetLastError());
-    return 0;
-}
-
-template <int NMAX>
-int launch_search(sr_ctx *ctx, const SearchArgs &a)
-{
-    switch (ctx->fit_waves) {
-        case 1: return launch_search_w<NMAX, 1>(ctx, a);
-        case 2: return launch_search_w<NMAX, 2>(ctx, a);
-        default: return launch_search_w<NMAX, 4>(ctx, a);
-    }
-}
-
 // residual + analytic Jacobian for arbitrary parameter sets
 __global__ __launch_bounds__(256) void k_resjac(const double *__restrict__ t, const double *__restrict__ y,
                                                 const double *__restrict__ sigma, const double *__restrict__ params,
@@ -1538,97 +1511,53 @@ __global__ __launch_bounds__(W * 64) void k_fit_probe(ProbeArgs a)
     }
 }
 
-template <int N, int W>
-int launch_probe_w(sr_ctx *ctx, const ProbeArgs &a)
+// ---- the one launch ladder of the three fit kernel templates ----------------------------------------
+// A function template cannot be a template argument: one tag per kernel hands out its instances.
+struct TrfKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_trf<N, W, LDS>; } };
+struct ProbeKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_fit_probe<N, W, LDS>; } };
+struct SearchKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_order_search<N, W, LDS>; } };
+
+// stage_lds: t, y and 1/sigma of a residue go to LDS when they fit (k_order_search and k_fit_probe pass the option "fit_lds",
+// k_trf stages whenever the residue fits)
+template <class K, int N, int W, class A>
+int launch_fit_w(sr_ctx *ctx, bool stage_lds, const A &a)
 {
-    const size_t lds_small = fit_lds_doubles(W, 0) * sizeof(double);
+    const dim3 grid((unsigned)a.nRes), block(W * 64);
     const size_t lds_full = fit_lds_doubles(W, a.L) * sizeof(double);
-    if (ctx->fit_lds && lds_full <= sr_lds_limit(ctx)) {
-        if (lds_full > 64 * 1024)
-            SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fit_probe<N, W, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full));
-        hipLaunchKernelGGL((k_fit_probe<N, W, true>), dim3((unsigned)a.nRes), dim3(W * 64), lds_full, ctx->stream, a);
-    } else {
-        hipLaunchKernelGGL((k_fit_probe<N, W, false>), dim3((unsigned)a.nRes), dim3(W * 64), lds_small, ctx->stream, a);
-    }
-    SR_HIP(hipGetLastError());
-    return 0;
-}
-
-template <int N>
-int launch_probe(sr_ctx *ctx, const ProbeArgs &a)
-{
-    switch (ctx->fit_waves) {
-        case 1: return launch_probe_w<N, 1>(ctx, a);
-        case 2: return launch_probe_w<N, 2>(ctx, a);
-        default: return launch_probe_w<N, 4>(ctx, a);
-    }
-}
-
-int dispatch_probe(sr_ctx *ctx, int P, const ProbeArgs &a)
-{
-    switch (P) {
-        case 2: return launch_probe<2>(ctx, a);
-        case 3: return launch_probe<3>(ctx, a);
-        case 4: return launch_probe<4>(ctx, a);
-        case 5: return launch_probe<5>(ctx, a);
-        case 6: return launch_probe<6>(ctx, a);
-        case 7: return launch_probe<7>(ctx, a);
-        case 8: return launch_probe<8>(ctx, a);
-        case 9: return launch_probe<9>(ctx, a);
-        case 10: return launch_probe<10>(ctx, a);
-        case 11: return launch_probe<11>(ctx, a);
-        default:
-            sr_set_error("sr_expfit_probe_f64: P=%d parameters not supported (2..%d)", P, kNmax);
-            return -3;
-    }
-}
-
-template <int N, int W>
-int launch_trf_w(sr_ctx *ctx, const FitArgs &a)
-{
-    const size_t lds_small = fit_lds_doubles(W, 0) * sizeof(double);
-    const size_t lds_full = fit_lds_doubles(W, a.L) * sizeof(double);
-    if (lds_full <= sr_lds_limit(ctx)) {
-        if (lds_full > 64 * 1024)
-            SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trf<N, W, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full));
-        hipLaunchKernelGGL((k_trf<N, W, true>), dim3((unsigned)a.nRes), dim3(W * 64), lds_full, ctx->stream, a);
-    } else {
-        hipLaunchKernelGGL((k_trf<N, W, false>), dim3((unsigned)a.nRes), dim3(W * 64), lds_small, ctx->stream, a);
-    }
-    SR_HIP(hipGetLastError());
-    return 0;
+    if (stage_lds && lds_full <= sr_lds_limit(ctx)) return sr_launch(ctx, K::template fn<N, W, true>(), grid, block, lds_full, a);
+    return sr_launch(ctx, K::template fn<N, W, false>(), grid, block, fit_lds_doubles(W, 0) * sizeof(double), a);
 }
 
 // The single-order solver uses the same number of waves per residue as the model-order search (sr_set_option
 // "fit_waves"): the workgroup sums are combined wave by wave, so only equal wave counts give bit-identical fits --
 // which is what lets the host-driven search (one sr_expfit_lm_f64 call per order) reproduce the one-launch search exactly.
-template <int N>
-int launch_trf(sr_ctx *ctx, const FitArgs &a)
+template <class K, int N, class A>
+int launch_fit(sr_ctx *ctx, bool stage_lds, const A &a)
 {
     switch (ctx->fit_waves) {
-        case 1: return launch_trf_w<N, 1>(ctx, a);
-        case 2: return launch_trf_w<N, 2>(ctx, a);
-        default: return launch_trf_w<N, 4>(ctx, a);
+        case 1: return launch_fit_w<K, N, 1>(ctx, stage_lds, a);
+        case 2: return launch_fit_w<K, N, 2>(ctx, stage_lds, a);
+        default: return launch_fit_w<K, N, 4>(ctx, stage_lds, a);
     }
 }
 
-int dispatch_trf(sr_ctx *ctx, int P, const FitArgs &a)
+// k_trf and k_fit_probe exist for every P = 2 .. kNmax (k_order_search: for the largest order only, see its entry point)
+template <class K, class A>
+int dispatch_fit(sr_ctx *ctx, const char *who, int P, bool stage_lds, const A &a)
 {
     switch (P) {
-        case 2: return launch_trf<2>(ctx, a);
-        case 3: return launch_trf<3>(ctx, a);
-        case 4: return launch_trf<4>(ctx, a);
-        case 5: return launch_trf<5>(ctx, a);
-        case 6: return launch_trf<6>(ctx, a);
-        case 7: return launch_trf<7>(ctx, a);
-        case 8: return launch_trf<8>(ctx, a);
-        case 9: return launch_trf<9>(ctx, a);
-        case 10: return launch_trf<10>(ctx, a);
-        case 11: return launch_trf<11>(ctx, a);
+        case 2: return launch_fit<K, 2>(ctx, stage_lds, a);
+        case 3: return launch_fit<K, 3>(ctx, stage_lds, a);
+        case 4: return launch_fit<K, 4>(ctx, stage_lds, a);
+        case 5: return launch_fit<K, 5>(ctx, stage_lds, a);
+        case 6: return launch_fit<K, 6>(ctx, stage_lds, a);
+        case 7: return launch_fit<K, 7>(ctx, stage_lds, a);
+        case 8: return launch_fit<K, 8>(ctx, stage_lds, a);
+        case 9: return launch_fit<K, 9>(ctx, stage_lds, a);
+        case 10: return launch_fit<K, 10>(ctx, stage_lds, a);
+        case 11: return launch_fit<K, 11>(ctx, stage_lds, a);
         default:
-            sr_set_error("sr_expfit_lm_f64: P=%d parameters not supported (2..%d)", P, kNmax);
+            sr_set_error("%s: P=%d parameters not supported (2..%d)", who, P, kNmax);
             return -3;
     }
 }
@@ -1652,7 +1581,7 @@ int sr_expfit_lm_f64_dev(sr_ctx *ctx, const double *t, const double *C, const do
     a.ftol = a.xtol = a.gtol = 1e-8;
     a.popt = popt; a.pcov = pcov; a.chisq = chisq; a.status = status; a.nfev = n_iter; a.fws = fws; a.geo = ctx->fit_geo;
     if (max_iter < 0) { a.max_nfev = -max_iter; a.jac_mode = 1; }     // negative: analytic Jacobian variant
-    return dispatch_trf(ctx, P, a);
+    return dispatch_fit<TrfKernel>(ctx, "sr_expfit_lm_f64", P, true, a);
 }
 
 int sr_expfit_order_search_f64_dev(sr_ctx *ctx, const double *t, const double *C, const double *sigma, int nRes, int L,
@@ -1707,11 +1636,11 @@ int sr_expfit_order_search_batched_f64_dev(sr_ctx *ctx, const double *t, int t_r
     a.sel_S2 = sel_S2; a.sel_C = sel_C; a.sel_tau = sel_tau; a.sel_chi = sel_chi; a.sel_K = sel_K; a.fws = fws;
 #ifdef SR_FIT_DEV_FAST
     SR_REQUIRE(pmax <= 9, -3, "development build: orders up to 9 only");
-    return launch_search<9>(ctx, a);
+    return launch_fit<SearchKernel, 9>(ctx, ctx->fit_lds != 0, a);
 #else
-    if (pmax <= 5) return launch_search<5>(ctx, a);
-    if (pmax <= 9) return launch_search<9>(ctx, a);
-    return launch_search<11>(ctx, a);
+    if (pmax <= 5) return launch_fit<SearchKernel, 5>(ctx, ctx->fit_lds != 0, a);
+    if (pmax <= 9) return launch_fit<SearchKernel, 9>(ctx, ctx->fit_lds != 0, a);
+    return launch_fit<SearchKernel, 11>(ctx, ctx->fit_lds != 0, a);
 #endif
 }
 
@@ -1733,36 +1662,32 @@ int sr_expfit_order_search_f64(sr_ctx *ctx, const double *t, const double *C, co
     }
     const size_t nL = (size_t)nRes * L, nR = (size_t)nRes, nO = (size_t)nOrders, kmax = (size_t)(pmax / 2);
     const size_t ntau = (size_t)tau_guess_rows * sumK;
-    double *in = (double *)sr_workspace(ctx, SR_WS_IN0, (3 * nL + ntau) * sizeof(double));
-    const size_t nd = 2 * nO * nR * pmax + nO * nR + nR * (2 + 2 * kmax);
-    double *out = (double *)sr_workspace(ctx, SR_WS_OUT0, nd * sizeof(double));
-    int *iout = (int *)sr_workspace(ctx, SR_WS_OUT1, (2 * nO * nR + 2 * nR) * sizeof(int));
-    if (!in || !out || !iout) return -5;
-    double *t_d = in, *y_d = in + nL, *s_d = in + 2 * nL, *tg_d = in + 3 * nL;
-    SR_HIP(hipMemcpyAsync(t_d, t, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SR_HIP(hipMemcpyAsync(y_d, C, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (sigma) SR_HIP(hipMemcpyAsync(s_d, sigma, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SR_HIP(hipMemcpyAsync(tg_d, tau_guess, ntau * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    double *popt_d = out, *dP_d = popt_d + nO * nR * pmax, *chi_d = dP_d + nO * nR * pmax, *sS2_d = chi_d + nO * nR;
-    double *sC_d = sS2_d + nR, *st_d = sC_d + nR * kmax, *schi_d = st_d + nR * kmax;
-    int *status_d = iout, *nfev_d = iout + nO * nR, *best_d = nfev_d + nO * nR, *sK_d = best_d + nR;
-    int rc = sr_expfit_order_search_f64_dev(ctx, t_d, y_d, sigma ? s_d : nullptr, nRes, L, orders, nOrders, tg_d, tau_guess_rows,
+    sr_stage st(ctx);
+    st.open(SR_WS_IN0, (3 * nL + ntau) * sizeof(double));
+    const double *t_d = st.put(t, nL), *y_d = st.put(C, nL), *s_d = st.put(sigma, nL), *tg_d = st.put(tau_guess, ntau);
+    st.open(SR_WS_OUT0, (2 * nO * nR * pmax + nO * nR + nR * (2 + 2 * kmax)) * sizeof(double));
+    double *popt_d = st.take<double>(nO * nR * pmax), *dP_d = st.take<double>(nO * nR * pmax), *chi_d = st.take<double>(nO * nR);
+    double *sS2_d = st.take<double>(nR), *sC_d = st.take<double>(nR * kmax), *st_d = st.take<double>(nR * kmax);
+    double *schi_d = st.take<double>(nR);
+    st.open(SR_WS_OUT1, (2 * nO * nR + 2 * nR) * sizeof(int));
+    int *status_d = st.take<int>(nO * nR), *nfev_d = st.take<int>(nO * nR), *best_d = st.take<int>(nR), *sK_d = st.take<int>(nR);
+    if (st.rc) return st.rc;
+    int rc = sr_expfit_order_search_f64_dev(ctx, t_d, y_d, s_d, nRes, L, orders, nOrders, tg_d, tau_guess_rows,
                                             tau_max, chi_threshold, nullptr, popt_d, dP_d, chi_d, status_d, nfev_d, best_d,
                                             sS2_d, sC_d, st_d, schi_d, sK_d);
     if (rc) return rc;
-    SR_HIP(hipMemcpyAsync(popt, popt_d, nO * nR * pmax * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(dP, dP_d, nO * nR * pmax * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(chisq, chi_d, nO * nR * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(sel_S2, sS2_d, nR * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(sel_C, sC_d, nR * kmax * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(sel_tau, st_d, nR * kmax * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(sel_chi, schi_d, nR * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(status, status_d, nO * nR * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(nfev, nfev_d, nO * nR * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(best, best_d, nR * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(sel_K, sK_d, nR * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(popt, popt_d, nO * nR * pmax);
+    st.fetch(dP, dP_d, nO * nR * pmax);
+    st.fetch(chisq, chi_d, nO * nR);
+    st.fetch(sel_S2, sS2_d, nR);
+    st.fetch(sel_C, sC_d, nR * kmax);
+    st.fetch(sel_tau, st_d, nR * kmax);
+    st.fetch(sel_chi, schi_d, nR);
+    st.fetch(status, status_d, nO * nR);
+    st.fetch(nfev, nfev_d, nO * nR);
+    st.fetch(best, best_d, nR);
+    st.fetch(sel_K, sK_d, nR);
+    return st.finish();
 }
 
 int sr_expfit_lm_f64(sr_ctx *ctx, const double *t, const double *C, const double *sigma, int nRes, int L, int P,
@@ -1772,27 +1697,24 @@ int sr_expfit_lm_f64(sr_ctx *ctx, const double *t, const double *C, const double
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(t && C && p0 && popt && pcov && chisq && status && n_iter, -2, "sr_expfit_lm_f64: null pointer");
     SR_REQUIRE(nRes >= 1 && L >= 1 && P >= 2 && P <= kNmax, -3, "sr_expfit_lm_f64: bad sizes nRes=%d L=%d P=%d", nRes, L, P);
-    const size_t nL = (size_t)nRes * L, nP = (size_t)nRes * P;
-    double *in = (double *)sr_workspace(ctx, SR_WS_IN0, (3 * nL + nP) * sizeof(double));
-    double *out = (double *)sr_workspace(ctx, SR_WS_OUT0, (nP + nP * P + nRes) * sizeof(double));
-    int *iout = (int *)sr_workspace(ctx, SR_WS_OUT1, (size_t)nRes * 2 * sizeof(int));
-    if (!in || !out || !iout) return -5;
-    double *t_d = in, *y_d = in + nL, *s_d = in + 2 * nL, *p0_d = in + 3 * nL;
-    SR_HIP(hipMemcpyAsync(t_d, t, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SR_HIP(hipMemcpyAsync(y_d, C, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (sigma) SR_HIP(hipMemcpyAsync(s_d, sigma, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SR_HIP(hipMemcpyAsync(p0_d, p0, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    double *popt_d = out, *pcov_d = out + nP, *chi_d = pcov_d + nP * P;
-    int rc = sr_expfit_lm_f64_dev(ctx, t_d, y_d, sigma ? s_d : nullptr, nRes, L, P, p0_d, tau_max, max_iter, nullptr, nullptr, popt_d, pcov_d,
-                                  chi_d, iout, iout + nRes);
+    const size_t nL = (size_t)nRes * L, nP = (size_t)nRes * P, nR = (size_t)nRes;
+    sr_stage st(ctx);
+    st.open(SR_WS_IN0, (3 * nL + nP) * sizeof(double));
+    const double *t_d = st.put(t, nL), *y_d = st.put(C, nL), *s_d = st.put(sigma, nL), *p0_d = st.put(p0, nP);
+    st.open(SR_WS_OUT0, (nP + nP * P + nR) * sizeof(double));
+    double *popt_d = st.take<double>(nP), *pcov_d = st.take<double>(nP * P), *chi_d = st.take<double>(nR);
+    st.open(SR_WS_OUT1, 2 * nR * sizeof(int));
+    int *status_d = st.take<int>(nR), *nfev_d = st.take<int>(nR);
+    if (st.rc) return st.rc;
+    int rc = sr_expfit_lm_f64_dev(ctx, t_d, y_d, s_d, nRes, L, P, p0_d, tau_max, max_iter, nullptr, nullptr, popt_d, pcov_d, chi_d,
+                                  status_d, nfev_d);
     if (rc) return rc;
-    SR_HIP(hipMemcpyAsync(popt, popt_d, nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(pcov, pcov_d, nP * P * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(chisq, chi_d, (size_t)nRes * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(status, iout, (size_t)nRes * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(n_iter, iout + nRes, (size_t)nRes * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(popt, popt_d, nP);
+    st.fetch(pcov, pcov_d, nP * P);
+    st.fetch(chisq, chi_d, nR);
+    st.fetch(status, status_d, nR);
+    st.fetch(n_iter, nfev_d, nR);
+    return st.finish();
 }
 
 int sr_expfit_probe_f64(sr_ctx *ctx, const double *t, const double *C, const double *sigma, const double *x, int nRes, int L,
@@ -1803,31 +1725,27 @@ int sr_expfit_probe_f64(sr_ctx *ctx, const double *t, const double *C, const dou
     SR_REQUIRE(t && C && x && geo && cost && f && JtJ && Jtf && dx, -2, "sr_expfit_probe_f64: null pointer");
     SR_REQUIRE(nRes >= 1 && L >= 1 && P >= 2 && P <= kNmax, -3, "sr_expfit_probe_f64: bad sizes nRes=%d L=%d P=%d", nRes, L, P);
     SR_REQUIRE(jac_mode == 0 || jac_mode == 1, -3, "sr_expfit_probe_f64: jac_mode must be 0 or 1");
-    const size_t nL = (size_t)nRes * L, nP = (size_t)nRes * P;
-    double *in = (double *)sr_workspace(ctx, SR_WS_IN0, (3 * nL + nP) * sizeof(double));
-    double *out = (double *)sr_workspace(ctx, SR_WS_OUT0, (nRes + nL + nP * P + 2 * nP) * sizeof(double));
-    int *iout = (int *)sr_workspace(ctx, SR_WS_OUT1, (size_t)nRes * sizeof(int));
-    double *fws = (double *)sr_workspace(ctx, SR_WS_FIT, nL * sizeof(double));
-    if (!in || !out || !iout || !fws) return -5;
-    double *t_d = in, *y_d = in + nL, *s_d = in + 2 * nL, *x_d = in + 3 * nL;
-    SR_HIP(hipMemcpyAsync(t_d, t, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SR_HIP(hipMemcpyAsync(y_d, C, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (sigma) SR_HIP(hipMemcpyAsync(s_d, sigma, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SR_HIP(hipMemcpyAsync(x_d, x, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const size_t nL = (size_t)nRes * L, nP = (size_t)nRes * P, nR = (size_t)nRes;
+    sr_stage st(ctx);
     ProbeArgs a;
-    a.t = t_d; a.y = y_d; a.sigma = sigma ? s_d : nullptr; a.x = x_d;
-    a.tau_max = tau_max; a.nRes = nRes; a.L = L; a.jac_mode = jac_mode; a.geo = ctx->fit_geo; a.fws = fws;
-    a.cost = out; a.f = out + nRes; a.A = a.f + nL; a.g = a.A + nP * P; a.dx = a.g + nP; a.geo_out = iout;
-    const int rc = dispatch_probe(ctx, P, a);
+    st.open(SR_WS_IN0, (3 * nL + nP) * sizeof(double));
+    a.t = st.put(t, nL); a.y = st.put(C, nL); a.sigma = st.put(sigma, nL); a.x = st.put(x, nP);
+    st.open(SR_WS_OUT0, (nR + nL + nP * P + 2 * nP) * sizeof(double));
+    a.cost = st.take<double>(nR); a.f = st.take<double>(nL); a.A = st.take<double>(nP * P);
+    a.g = st.take<double>(nP); a.dx = st.take<double>(nP);
+    a.geo_out = st.take<int>(SR_WS_OUT1, nR);
+    a.fws = st.take<double>(SR_WS_FIT, nL);
+    if (st.rc) return st.rc;
+    a.tau_max = tau_max; a.nRes = nRes; a.L = L; a.jac_mode = jac_mode; a.geo = ctx->fit_geo;
+    const int rc = dispatch_fit<ProbeKernel>(ctx, "sr_expfit_probe_f64", P, ctx->fit_lds != 0, a);
     if (rc) return rc;
-    SR_HIP(hipMemcpyAsync(cost, a.cost, (size_t)nRes * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(f, a.f, nL * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(JtJ, a.A, nP * P * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(Jtf, a.g, nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(dx, a.dx, nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(geo, iout, (size_t)nRes * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(cost, a.cost, nR);
+    st.fetch(f, a.f, nL);
+    st.fetch(JtJ, a.A, nP * P);
+    st.fetch(Jtf, a.g, nP);
+    st.fetch(dx, a.dx, nP);
+    st.fetch(geo, a.geo_out, nR);
+    return st.finish();
 }
 
 int sr_expfit_resjac_f64(sr_ctx *ctx, const double *t, const double *C, const double *sigma, const double *params,
@@ -1837,22 +1755,17 @@ int sr_expfit_resjac_f64(sr_ctx *ctx, const double *t, const double *C, const do
     SR_REQUIRE(t && C && params && resid, -2, "sr_expfit_resjac_f64: null pointer");
     SR_REQUIRE(nRes >= 1 && L >= 1 && P >= 1 && P <= 64, -3, "sr_expfit_resjac_f64: bad sizes");
     const size_t nL = (size_t)nRes * L, nP = (size_t)nRes * P;
-    double *in = (double *)sr_workspace(ctx, SR_WS_IN0, (3 * nL + nP) * sizeof(double));
-    double *r_d = (double *)sr_workspace(ctx, SR_WS_OUT0, nL * sizeof(double));
-    double *j_d = jac ? (double *)sr_workspace(ctx, SR_WS_OUT1, nL * P * sizeof(double)) : nullptr;
-    if (!in || !r_d || (jac && !j_d)) return -5;
-    double *t_d = in, *y_d = in + nL, *s_d = in + 2 * nL, *p_d = in + 3 * nL;
-    SR_HIP(hipMemcpyAsync(t_d, t, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SR_HIP(hipMemcpyAsync(y_d, C, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (sigma) SR_HIP(hipMemcpyAsync(s_d, sigma, nL * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SR_HIP(hipMemcpyAsync(p_d, params, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_resjac, dim3((unsigned)nRes), dim3(256), 0, ctx->stream, t_d, y_d, sigma ? s_d : nullptr, p_d, L, P,
-                       r_d, j_d);
+    sr_stage st(ctx);
+    st.open(SR_WS_IN0, (3 * nL + nP) * sizeof(double));
+    const double *t_d = st.put(t, nL), *y_d = st.put(C, nL), *s_d = st.put(sigma, nL), *p_d = st.put(params, nP);
+    double *r_d = st.take<double>(SR_WS_OUT0, nL);
+    double *j_d = jac ? st.take<double>(SR_WS_OUT1, nL * P) : nullptr;
+    if (st.rc) return st.rc;
+    hipLaunchKernelGGL(k_resjac, dim3((unsigned)nRes), dim3(256), 0, ctx->stream, t_d, y_d, s_d, p_d, L, P, r_d, j_d);
     SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(resid, r_d, nL * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (jac) SR_HIP(hipMemcpyAsync(jac, j_d, nL * P * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(resid, r_d, nL);
+    st.fetch(jac, j_d, nL * P);
+    return st.finish();
 }
 
 }  // extern "C"

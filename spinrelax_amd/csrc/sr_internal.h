@@ -43,8 +43,6 @@ struct sr_ctx {
     unsigned long long h2d_bytes, h2d_calls;
 };
 
-enum { SR_K_CT1 = 0, SR_K_CT4, SR_K_VECHIST, SR_K_DQ, SR_K_MISC, SR_K_CTL_CROSS, SR_K_CTL_INV };
-
 enum {
     SR_WS_VECS = 0,     // staged host vectors (frame-major)
     SR_WS_SOA,          // packed planes
@@ -89,10 +87,11 @@ static inline size_t sr_lds_limit(const sr_ctx *ctx)
     return a > b ? a : b;
 }
 
-// allow `func` to be launched with `bytes` of dynamic LDS on this context's device.  hipFuncSetAttribute is a per-DEVICE
-// function attribute: the largest size granted so far is remembered per (device, kernel family) for the whole PROCESS
-// (monotonic, under a mutex; sr_core.hip), so two contexts on one device can never lower each other's grant.
-int sr_grant_lds(sr_ctx *ctx, int kid, const void *func, size_t bytes);
+// allow the kernel `func` to be launched with `bytes` (> 64 KiB) of dynamic LDS on this context's device.  That permission
+// is a per-DEVICE attribute of ONE function: the largest size granted so far is remembered per (device, function pointer) for
+// the whole PROCESS (monotonic, under a lock; sr_core.hip), so two contexts on one device can never lower each other's grant,
+// and every instance of a kernel template has its own.  The only caller is sr_launch below.
+int sr_grant_lds(sr_ctx *ctx, const void *func, size_t bytes);
 
 static inline int64_t sr_round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -111,6 +110,78 @@ const void *sr_ct32_tables(sr_ctx *ctx);
 #define SR_CT_LONG_WS_MB 256
 int sr_launch_ct_long(sr_ctx *ctx, const float *soa, int64_t Npad, const int64_t *cs_dev, double *psum, int R, int F, int L, int Lp,
                       int64_t series);
+
+#ifdef __HIPCC__
+// ---- the one way to launch a kernel that takes dynamic LDS ------------------------------------------
+// grants `lds` first when it is above the 64 KiB every kernel may have, launches on ctx->stream, returns the launch's status
+template <class... KArgs, class... Args>
+inline int sr_launch(sr_ctx *ctx, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, Args &&...args)
+{
+    if (lds > 64 * 1024)
+        if (int rc = sr_grant_lds(ctx, reinterpret_cast<const void *>(kernel), lds)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args...);
+    SR_HIP(hipGetLastError());
+    return 0;
+}
+#endif
+
+// ---- staging of the host-pointer entry points -------------------------------------------------------
+// A bump allocator over one workspace slot at a time, with copies in stream order on ctx->stream: open() names the slot and
+// its size, take() carves (aligned to the element type), put() carves and copies host -> device, fetch() copies device -> host,
+// finish() waits for the stream.  The FIRST failure is kept -- the code and sr_set_error text that sr_workspace / SR_HIP give
+// -- and turns every later call into a no-op that returns null: an entry point tests `rc` once before it launches, and
+// returns finish().  A null host pointer is an optional array that is absent: put() returns null for it, fetch() skips it.
+struct sr_stage {
+    sr_ctx *ctx;
+    char *p = nullptr, *end = nullptr;
+    int rc = 0;
+
+    explicit sr_stage(sr_ctx *c) : ctx(c) {}
+    sr_stage &open(int slot, size_t bytes)
+    {
+        if (rc) return *this;
+        p = (char *)sr_workspace(ctx, slot, bytes);
+        end = p + bytes;
+        if (!p) rc = -5;
+        return *this;
+    }
+    template <class T>
+    T *take(size_t n)
+    {
+        char *q = p + (size_t)(-(uintptr_t)p & (alignof(T) - 1));
+        if (rc) return nullptr;
+        if (!p || n * sizeof(T) > (size_t)(end - q)) return (T *)fail(hipErrorInvalidValue, "sr_stage::take past the end of the slot");
+        p = q + n * sizeof(T);
+        return (T *)q;
+    }
+    template <class T>
+    T *take(int slot, size_t n) { return open(slot, n * sizeof(T)).template take<T>(n); }     // an array with a slot of its own
+    template <class T>
+    T *put(const T *host, size_t n)
+    {
+        T *d = host ? take<T>(n) : nullptr;
+        if (d) fail(hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(host to device)");
+        return rc ? nullptr : d;
+    }
+    template <class T>
+    void fetch(T *host, const T *dev, size_t n)
+    {
+        if (host && !rc) fail(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(device to host)");
+    }
+    int finish()
+    {
+        if (!rc) fail(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        return rc;
+    }
+    void *fail(hipError_t e, const char *what)
+    {
+        if (e != hipSuccess && !rc) {
+            sr_set_error("%s: %s -> %s", __FILE__, what, hipGetErrorString(e));
+            rc = -100 - (int)e;
+        }
+        return nullptr;
+    }
+};
 
 #ifdef __HIPCC__
 // ---- wave-level float64 sum on the VALU only (DPP + readlane), no LDS round trips -----------------

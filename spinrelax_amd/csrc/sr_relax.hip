@@ -304,17 +304,6 @@ void launch_relax(sr_ctx *ctx, const RelaxArgs &a)
     else hipLaunchKernelGGL(k_relax<SymmTopCoef>, grid, dim3(256), 0, ctx->stream, a);
 }
 
-template <typename T>
-T *upload(sr_ctx *ctx, int slot, const T *host, size_t count, int *rc)
-{
-    T *d = (T *)sr_workspace(ctx, slot, count * sizeof(T));
-    if (!d) { *rc = -5; return nullptr; }
-    hipError_t e = hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { sr_set_error("upload: %s", hipGetErrorString(e)); *rc = -100 - (int)e; return nullptr; }
-    return d;
-}
-
-
 // ---- residue-specific CSA search (new class API) -------------------------------------------------------------------
 // spectral_densities.py:1371-1382 + 1430-1447: for every residue, fmin_powell over ONE variable (its CSA) of the
 // mean of (value - target)^2 / (sigma_value^2 + sigma_target^2) over the experiments that cover the residue.  With
@@ -666,16 +655,15 @@ int sr_jomega_f64(sr_ctx *ctx, const double *x, const double *y, double *out, in
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(x && y && out && n >= 0, -2, "sr_jomega_f64: bad arguments");
     if (n == 0) return 0;
-    int rc = 0;
-    double *dx = upload(ctx, SR_WS_IN0, x, (size_t)n, &rc);
-    double *dy = upload(ctx, SR_WS_IN1, y, (size_t)n, &rc);
-    double *dout = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)n * sizeof(double));
-    if (rc || !dx || !dy || !dout) return rc ? rc : -5;
+    sr_stage st(ctx);
+    const double *dx = st.open(SR_WS_IN0, (size_t)n * sizeof(double)).put(x, (size_t)n);
+    const double *dy = st.open(SR_WS_IN1, (size_t)n * sizeof(double)).put(y, (size_t)n);
+    double *dout = st.take<double>(SR_WS_OUT0, (size_t)n);
+    if (st.rc) return st.rc;
     hipLaunchKernelGGL(k_jomega, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dx, dy, dout, n);
     SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(out, dout, (size_t)n);
+    return st.finish();
 }
 
 int sr_jomega_relax_f64(sr_ctx *ctx, int model, const double *D, int E, const double *omega, const double *f_DD,
@@ -685,67 +673,33 @@ int sr_jomega_relax_f64(sr_ctx *ctx, int model, const double *D, int E, const do
                         double *Jout, double *stats)
 {
     SR_CHECK_CTX(ctx);
-    SR_REQUIRE(model >= 0 && model <= 3, -3, "sr_jomega_relax_f64: model must be 0, 1, 2 or 3");
+    // what sizes the staging or is read here; sr_jomega_relax_f64_dev checks the rest
     SR_REQUIRE(E >= 1 && nRes >= 1 && Kmax >= 1 && Kmax <= kMaxK && B >= 0, -3, "sr_jomega_relax_f64: bad sizes");
     SR_REQUIRE(E <= 65535, -3, "sr_jomega_relax_f64: too many experiments");
-    SR_REQUIRE(omega && f_DD && f_CSA && time_fact && gamma_ratio && S2 && C && tau && nComps && out, -2,
-               "sr_jomega_relax_f64: null pointer");
-    SR_REQUIRE(model == 0 || D, -2, "sr_jomega_relax_f64: D required");
-    SR_REQUIRE(model < 2 || binvecs, -2, "sr_jomega_relax_f64: symmetric top and ellipsoid need vectors");
-    SR_REQUIRE(noe_mode == 0 || noe_mode == 1, -3, "sr_jomega_relax_f64: noe_mode must be 0 or 1");
+    SR_REQUIRE(nComps, -2, "sr_jomega_relax_f64: null pointer");
     for (int i = 0; i < nRes; ++i)
         SR_REQUIRE(nComps[i] >= 0 && nComps[i] <= Kmax, -3, "sr_jomega_relax_f64: nComps[%d]=%d out of range", i, nComps[i]);
-    // pack every input into one staging buffer
-    const size_t nE = (size_t)E, nR = (size_t)nRes;
-    const size_t cnt = nE * 5 + nE + nE * nR + nE + nE + nR + 2 * nR * Kmax +
-                       (model >= 2 ? (B > 0 ? (size_t)B * 3 : nR * 3) : 0) +
-                       ((B > 0 && weights && !weights_on_device) ? nR * B : 0);
-    double *stage = (double *)sr_workspace(ctx, SR_WS_IN0, cnt * sizeof(double));
-    int *ncomp_d = (int *)sr_workspace(ctx, SR_WS_IN1, nR * sizeof(int));
-    double *out_d = (double *)sr_workspace(ctx, SR_WS_OUT0, nE * nR * 8 * sizeof(double));
-    double *J_d = Jout ? (double *)sr_workspace(ctx, SR_WS_OUT1, nE * nR * 10 * sizeof(double)) : nullptr;
-    double *st_d = stats ? (double *)sr_workspace(ctx, SR_WS_OUT2, nE * nR * 12 * sizeof(double)) : nullptr;
-    if (!stage || !ncomp_d || !out_d || (Jout && !J_d) || (stats && !st_d)) return -5;
-    RelaxArgs a;
-    a.model = model; a.E = E; a.nRes = nRes; a.Kmax = Kmax; a.B = (model >= 2) ? B : 0; a.noe_mode = noe_mode;
-    a.D0 = D ? D[0] : 0.0;
-    a.D1 = (D && model >= 2) ? D[1] : 0.0;
-    a.D2 = (D && model == 3) ? D[2] : 0.0;
-    a.zeta = 1.0;
-    double *p = stage;
-    auto put = [&](const double *src, size_t n) -> const double * {
-        hipError_t e = hipMemcpyAsync(p, src, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return nullptr;
-        const double *r = p;
-        p += n;
-        return r;
-    };
-    a.omega = put(omega, nE * 5);
-    a.f_DD = put(f_DD, nE);
-    a.f_CSA = put(f_CSA, nE * nR);
-    a.time_fact = put(time_fact, nE);
-    a.gamma_ratio = put(gamma_ratio, nE);
-    a.S2 = put(S2, nR);
-    a.C = put(C, nR * Kmax);
-    a.tau = put(tau, nR * Kmax);
-    a.binvecs = nullptr;
-    a.weights = nullptr;
-    if (model >= 2) a.binvecs = put(binvecs, B > 0 ? (size_t)B * 3 : nR * 3);
-    if (model >= 2 && B > 0 && weights) a.weights = weights_on_device ? weights : put(weights, nR * B);
-    SR_REQUIRE(a.omega && a.f_DD && a.f_CSA && a.time_fact && a.gamma_ratio && a.S2 && a.C && a.tau, -6,
-               "sr_jomega_relax_f64: host to device copy failed");
-    SR_HIP(hipMemcpyAsync(ncomp_d, nComps, nR * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    a.nComps = ncomp_d;
-    a.out = out_d;
-    a.Jout = J_d;
-    a.stats = st_d;
-    launch_relax(ctx, a);
-    SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(out, out_d, nE * nR * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (Jout) SR_HIP(hipMemcpyAsync(Jout, J_d, nE * nR * 10 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (stats) SR_HIP(hipMemcpyAsync(stats, st_d, nE * nR * 12 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    const size_t nE = (size_t)E, nR = (size_t)nRes, nvec = model >= 2 ? (B > 0 ? (size_t)B * 3 : nR * 3) : 0;
+    const bool host_w = B > 0 && weights && !weights_on_device;
+    sr_stage st(ctx);
+    st.open(SR_WS_IN0, (nE * 5 + nE + nE * nR + nE + nE + nR + 2 * nR * Kmax + nvec + (host_w ? nR * B : 0)) * sizeof(double));
+    const double *omega_d = st.put(omega, nE * 5), *fDD_d = st.put(f_DD, nE), *fCSA_d = st.put(f_CSA, nE * nR);
+    const double *tf_d = st.put(time_fact, nE), *gr_d = st.put(gamma_ratio, nE);
+    const double *S2_d = st.put(S2, nR), *C_d = st.put(C, nR * Kmax), *tau_d = st.put(tau, nR * Kmax);
+    const double *vec_d = nvec ? st.put(binvecs, nvec) : nullptr;
+    const double *w_d = host_w && model >= 2 ? st.put(weights, nR * B) : weights;
+    const int *ncomp_d = st.open(SR_WS_IN1, nR * sizeof(int)).put(nComps, nR);
+    double *out_d = out ? st.take<double>(SR_WS_OUT0, nE * nR * 8) : nullptr;
+    double *J_d = Jout ? st.take<double>(SR_WS_OUT1, nE * nR * 10) : nullptr;
+    double *st_d = stats ? st.take<double>(SR_WS_OUT2, nE * nR * 12) : nullptr;
+    if (st.rc) return st.rc;
+    const int rc = sr_jomega_relax_f64_dev(ctx, model, D, E, omega_d, fDD_d, fCSA_d, tf_d, gr_d, nRes, Kmax, 1.0, S2_d, C_d, tau_d, ncomp_d,
+                                           B, vec_d, w_d, noe_mode, out_d, J_d, st_d);
+    if (rc) return rc;
+    st.fetch(out, out_d, nE * nR * 8);
+    st.fetch(Jout, J_d, nE * nR * 10);
+    st.fetch(stats, st_d, nE * nR * 12);
+    return st.finish();
 }
 
 int sr_jomega_relax_f64_dev(sr_ctx *ctx, int model, const double *D, int E, const double *omega, const double *f_DD,
@@ -790,47 +744,34 @@ int sr_rscsa_search_f64(sr_ctx *ctx, int E, int nRes, const double *stats, const
     for (int e = 0; e < E; ++e)
         SR_REQUIRE(column[e] >= 0 && column[e] <= 2, -3, "sr_rscsa_search_f64: column[%d]=%d is not 0 (R1), 1 (R2) or 2 (NOE)", e, column[e]);
     const size_t nE = (size_t)E, nR = (size_t)nRes, EN = nE * nR;
-    const size_t nd_in = EN * 12 + 3 * nE + 2 * EN + nR;
-    double *din = (double *)sr_workspace(ctx, SR_WS_IN0, nd_in * sizeof(double));
-    int *iin = (int *)sr_workspace(ctx, SR_WS_IN1, nE * sizeof(int) + EN);
-    double *dout = (double *)sr_workspace(ctx, SR_WS_OUT0, (2 * EN + 2 * nR) * sizeof(double) + nR * sizeof(int));
-    if (!din || !iin || !dout) return -5;
-    double *p = din;
-    auto put = [&](const double *src, size_t n) -> const double * {
-        hipError_t e = hipMemcpyAsync(p, src, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return nullptr;
-        const double *r = p;
-        p += n;
-        return r;
-    };
+    sr_stage st(ctx);
     RscsaArgs a;
     a.E = E; a.n = nRes; a.has_err = has_err ? 1 : 0; a.maxfun = 1000; a.maxiter = 1000;
     a.step = step; a.xtol = xtol; a.ftol = ftol;
-    a.stats = put(stats, EN * 12);
-    a.pref = put(csa_prefactor, nE);
-    a.cnoe = put(noe_factor, nE);
-    a.fdd = put(f_DD, nE);
-    a.y = put(target, EN);
-    a.dy = put(dtarget, EN);
-    a.csa0 = put(csa0, nR);
-    SR_REQUIRE(a.stats && a.pref && a.cnoe && a.fdd && a.y && a.dy && a.csa0, -6, "sr_rscsa_search_f64: host to device copy failed");
-    SR_HIP(hipMemcpyAsync(iin, column, nE * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    unsigned char *cov_d = (unsigned char *)(iin + nE);
-    SR_HIP(hipMemcpyAsync(cov_d, cover, EN, hipMemcpyHostToDevice, ctx->stream));
-    a.col = iin;
-    a.cover = cov_d;
-    a.val = dout; a.err = dout + EN; a.csa = dout + 2 * EN; a.fopt = a.csa + nR;
-    a.nfev = (int *)(a.fopt + nR);
-    SR_HIP(hipMemsetAsync(dout, 0, 2 * EN * sizeof(double), ctx->stream));
+    st.open(SR_WS_IN0, (EN * 12 + 3 * nE + 2 * EN + nR) * sizeof(double));
+    a.stats = st.put(stats, EN * 12);
+    a.pref = st.put(csa_prefactor, nE);
+    a.cnoe = st.put(noe_factor, nE);
+    a.fdd = st.put(f_DD, nE);
+    a.y = st.put(target, EN);
+    a.dy = st.put(dtarget, EN);
+    a.csa0 = st.put(csa0, nR);
+    st.open(SR_WS_IN1, nE * sizeof(int) + EN);
+    a.col = st.put(column, nE);
+    a.cover = st.put(cover, EN);
+    st.open(SR_WS_OUT0, (2 * EN + 2 * nR) * sizeof(double) + nR * sizeof(int));
+    a.val = st.take<double>(EN); a.err = st.take<double>(EN); a.csa = st.take<double>(nR); a.fopt = st.take<double>(nR);
+    a.nfev = st.take<int>(nR);
+    if (st.rc) return st.rc;
+    SR_HIP(hipMemsetAsync(a.val, 0, 2 * EN * sizeof(double), ctx->stream));
     hipLaunchKernelGGL(k_rscsa_search, dim3((unsigned)((nRes + 63) / 64)), dim3(64), 0, ctx->stream, a);
     SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(values, a.val, EN * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(errors, a.err, EN * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(csa, a.csa, nR * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(fopt, a.fopt, nR * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(nfev, a.nfev, nR * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(values, a.val, EN);
+    st.fetch(errors, a.err, EN);
+    st.fetch(csa, a.csa, nR);
+    st.fetch(fopt, a.fopt, nR);
+    st.fetch(nfev, a.nfev, nR);
+    return st.finish();
 }
 
 int sr_legacy_csa_search_f64(sr_ctx *ctx, const double *D, const double *omega, double f_DD, double gammaB0_sq, double time_fact,
@@ -847,43 +788,30 @@ int sr_legacy_csa_search_f64(sr_ctx *ctx, const double *D, const double *omega, 
     for (int i = 0; i < nRes; ++i)
         SR_REQUIRE(nComps[i] >= 0 && nComps[i] <= Kmax, -3, "sr_legacy_csa_search_f64: nComps[%d]=%d out of range", i, nComps[i]);
     const size_t nR = (size_t)nRes;
-    const size_t cnt = 5 + nR + 2 * nR * Kmax + (size_t)B * 3 + nR * B + nR * 6 + nR;
-    double *stage = (double *)sr_workspace(ctx, SR_WS_IN0, cnt * sizeof(double));
-    int *ncomp_d = (int *)sr_workspace(ctx, SR_WS_IN1, nR * sizeof(int));
-    double *dout = (double *)sr_workspace(ctx, SR_WS_OUT0, 2 * nR * sizeof(double) + nR * sizeof(int));
-    if (!stage || !ncomp_d || !dout) return -5;
-    double *p = stage;
-    auto put = [&](const double *src, size_t n) -> const double * {
-        hipError_t e = hipMemcpyAsync(p, src, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return nullptr;
-        const double *r = p;
-        p += n;
-        return r;
-    };
+    sr_stage st(ctx);
     LegacyArgs a;
     a.nRes = nRes; a.Kmax = Kmax; a.B = B; a.maxiter = maxiter; a.maxfun = maxfun;
     a.D0 = D[0]; a.D1 = D[1]; a.fDD = f_DD; a.g2 = gammaB0_sq; a.tf = time_fact; a.gr = gamma_ratio;
     a.step = step; a.xtol = xtol; a.ftol = ftol;
-    a.omega = put(omega, 5);
-    a.S2 = put(S2, nR);
-    a.C = put(C, nR * Kmax);
-    a.tau = put(tau, nR * Kmax);
-    a.binvecs = put(binvecs, (size_t)B * 3);
-    a.weights = put(weights, nR * B);
-    a.expt = put(expt, nR * 6);
-    a.csa0 = put(csa0, nR);
-    SR_REQUIRE(a.omega && a.S2 && a.C && a.tau && a.binvecs && a.weights && a.expt && a.csa0, -6,
-               "sr_legacy_csa_search_f64: host to device copy failed");
-    SR_HIP(hipMemcpyAsync(ncomp_d, nComps, nR * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    a.nComps = ncomp_d;
-    a.csa = dout; a.fopt = dout + nR; a.nfev = (int *)(dout + 2 * nR);
+    st.open(SR_WS_IN0, (5 + nR + 2 * nR * Kmax + (size_t)B * 3 + nR * B + nR * 6 + nR) * sizeof(double));
+    a.omega = st.put(omega, 5);
+    a.S2 = st.put(S2, nR);
+    a.C = st.put(C, nR * Kmax);
+    a.tau = st.put(tau, nR * Kmax);
+    a.binvecs = st.put(binvecs, (size_t)B * 3);
+    a.weights = st.put(weights, nR * B);
+    a.expt = st.put(expt, nR * 6);
+    a.csa0 = st.put(csa0, nR);
+    a.nComps = st.open(SR_WS_IN1, nR * sizeof(int)).put(nComps, nR);
+    st.open(SR_WS_OUT0, 2 * nR * sizeof(double) + nR * sizeof(int));
+    a.csa = st.take<double>(nR); a.fopt = st.take<double>(nR); a.nfev = st.take<int>(nR);
+    if (st.rc) return st.rc;
     hipLaunchKernelGGL(k_legacy_csa_search, dim3((unsigned)nRes), dim3(256), 0, ctx->stream, a);
     SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(csa, a.csa, nR * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(fopt, a.fopt, nR * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(nfev, a.nfev, nR * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(csa, a.csa, nR);
+    st.fetch(fopt, a.fopt, nR);
+    st.fetch(nfev, a.nfev, nR);
+    return st.finish();
 }
 
 }  // extern "C"

@@ -232,21 +232,19 @@ int sr_xh_vectors_f32(sr_ctx *ctx, const float *xyz, int64_t nFrames, int64_t nA
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(xyz && idxX && idxH, -2, "sr_xh_vectors_f32: null pointer");
     SR_REQUIRE(nFrames >= 1 && nAtoms >= 1 && nV >= 1, -3, "sr_xh_vectors_f32: bad sizes");
-    const size_t in_bytes = (size_t)nFrames * nAtoms * 3 * sizeof(float);
-    const size_t vb = (size_t)nFrames * nV * 3 * sizeof(float);
-    float *xyz_d = (float *)sr_workspace(ctx, SR_WS_VECS, in_bytes);
-    float *lab_d = vec_lab ? (float *)sr_workspace(ctx, SR_WS_OUT0, vb) : nullptr;
-    float *fit_d = vec_fit ? (float *)sr_workspace(ctx, SR_WS_OUT1, vb) : nullptr;
-    double *q_d = quat ? (double *)sr_workspace(ctx, SR_WS_OUT2, (size_t)nFrames * 4 * sizeof(double)) : nullptr;
-    if (!xyz_d || (vec_lab && !lab_d) || (vec_fit && !fit_d) || (quat && !q_d)) return -5;
-    SR_HIP(hipMemcpyAsync(xyz_d, xyz, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const size_t nin = (size_t)nFrames * nAtoms * 3, nvec = (size_t)nFrames * nV * 3, nq = (size_t)nFrames * 4;
+    sr_stage st(ctx);
+    const float *xyz_d = st.open(SR_WS_VECS, nin * sizeof(float)).put(xyz, nin);
+    float *lab_d = vec_lab ? st.take<float>(SR_WS_OUT0, nvec) : nullptr;
+    float *fit_d = vec_fit ? st.take<float>(SR_WS_OUT1, nvec) : nullptr;
+    double *q_d = quat ? st.take<double>(SR_WS_OUT2, nq) : nullptr;
+    if (st.rc) return st.rc;
     int rc = sr_xh_vectors_f32_dev(ctx, xyz_d, nFrames, nAtoms, idxX, idxH, nV, fit_idx, nFit, ref_xyz, lab_d, fit_d, q_d);
     if (rc) return rc;
-    if (vec_lab) SR_HIP(hipMemcpyAsync(vec_lab, lab_d, vb, hipMemcpyDeviceToHost, ctx->stream));
-    if (vec_fit) SR_HIP(hipMemcpyAsync(vec_fit, fit_d, vb, hipMemcpyDeviceToHost, ctx->stream));
-    if (quat) SR_HIP(hipMemcpyAsync(quat, q_d, (size_t)nFrames * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(vec_lab, lab_d, nvec);
+    st.fetch(vec_fit, fit_d, nvec);
+    st.fetch(quat, q_d, nq);
+    return st.finish();
 }
 
 }  // extern "C"

@@ -492,9 +492,8 @@ int sr_rotate_hist_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t 
     a.edges = edges_d; a.hist_u32 = h32; a.partials = partials;
     const size_t lds = (size_t)ne * sizeof(double) + (size_t)((nbins + 3) & ~3) * sizeof(unsigned int) +
                        (kRangesPerWG * (kMaxRange / 32) + 4) * sizeof(unsigned int) + (size_t)kListCap * sizeof(unsigned short);
-    if (int rc = sr_grant_lds(ctx, SR_K_VECHIST, reinterpret_cast<const void *>(&k_vechist), lds)) return rc;
-    hipLaunchKernelGGL(k_vechist, dim3((unsigned)((a.nranges + kRangesPerWG - 1) / kRangesPerWG), (unsigned)nV), dim3(256), lds, ctx->stream, a);
-    SR_HIP(hipGetLastError());
+    if (int rc = sr_launch(ctx, k_vechist, dim3((unsigned)((a.nranges + kRangesPerWG - 1) / kRangesPerWG), (unsigned)nV), dim3(256), lds, a))
+        return rc;
     hipLaunchKernelGGL(k_vechist_finalize, dim3((unsigned)nV), dim3(256), 0, ctx->stream, h32, partials, nV, nbins,
                        a.nranges, a.nB, a.m, rot, hist, vecsum, outer);
     SR_HIP(hipGetLastError());
@@ -522,21 +521,19 @@ int sr_rotate_vectors_f32(sr_ctx *ctx, const float *vecs, int64_t N, int64_t Vto
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(vecs && out, -2, "sr_rotate_vectors_f32: null pointer");
     SR_REQUIRE(N > 0 && Vtot > 0 && nV > 0 && v0 >= 0 && v0 + nV <= Vtot, -3, "sr_rotate_vectors_f32: bad shape");
-    const size_t in_bytes = (size_t)N * Vtot * 3 * sizeof(float);
-    const size_t out_bytes = (size_t)N * nV * 3 * sizeof(double);
-    float *dvecs = (float *)sr_workspace(ctx, SR_WS_VECS, in_bytes);
-    double *dout = (double *)sr_workspace(ctx, SR_WS_OUT0, out_bytes);
-    if (!dvecs || !dout) return -5;
+    const size_t nin = (size_t)N * Vtot * 3, nout = (size_t)N * nV * 3;
+    sr_stage st(ctx);
+    const float *dvecs = st.open(SR_WS_VECS, nin * sizeof(float)).put(vecs, nin);
+    double *dout = st.take<double>(SR_WS_OUT0, nout);
+    if (st.rc) return st.rc;
     double qn[4] = {1, 0, 0, 0};
     if (q) normalise_q(q, qn);
-    SR_HIP(hipMemcpyAsync(dvecs, vecs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     const int64_t tot = N * nV;
     hipLaunchKernelGGL(k_rotate_vectors, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, dvecs, N, Vtot, v0,
                        nV, q ? 1 : 0, qn[0], qn[1], qn[2], qn[3], (const double *)nullptr, dout);
     SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(out, dout, nout);
+    return st.finish();
 }
 
 int sr_rotate_vectors_perframe_f32(sr_ctx *ctx, const float *vecs, int64_t N, int64_t Vtot, int64_t v0, int64_t nV,
@@ -545,21 +542,18 @@ int sr_rotate_vectors_perframe_f32(sr_ctx *ctx, const float *vecs, int64_t N, in
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(vecs && out && quat, -2, "sr_rotate_vectors_perframe_f32: null pointer");
     SR_REQUIRE(N > 0 && Vtot > 0 && nV > 0 && v0 >= 0 && v0 + nV <= Vtot, -3, "sr_rotate_vectors_perframe_f32: bad shape");
-    const size_t in_bytes = (size_t)N * Vtot * 3 * sizeof(float);
-    const size_t out_bytes = (size_t)N * nV * 3 * sizeof(double);
-    float *dvecs = (float *)sr_workspace(ctx, SR_WS_VECS, in_bytes);
-    double *dout = (double *)sr_workspace(ctx, SR_WS_OUT0, out_bytes);
-    double *dq = (double *)sr_workspace(ctx, SR_WS_IN0, (size_t)N * 4 * sizeof(double));
-    if (!dvecs || !dout || !dq) return -5;
-    SR_HIP(hipMemcpyAsync(dvecs, vecs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    SR_HIP(hipMemcpyAsync(dq, quat, (size_t)N * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const size_t nin = (size_t)N * Vtot * 3, nout = (size_t)N * nV * 3;
+    sr_stage st(ctx);
+    const float *dvecs = st.open(SR_WS_VECS, nin * sizeof(float)).put(vecs, nin);
+    const double *dq = st.open(SR_WS_IN0, (size_t)N * 4 * sizeof(double)).put(quat, (size_t)N * 4);
+    double *dout = st.take<double>(SR_WS_OUT0, nout);
+    if (st.rc) return st.rc;
     const int64_t tot = N * nV;
     hipLaunchKernelGGL(k_rotate_vectors, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, dvecs, N, Vtot, v0,
-                       nV, 1, 1.0, 0.0, 0.0, 0.0, (const double *)dq, dout);
+                       nV, 1, 1.0, 0.0, 0.0, 0.0, dq, dout);
     SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    st.fetch(out, dout, nout);
+    return st.finish();
 }
 
 }  // extern "C"

@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 10
+#define SR_ABI_VERSION 11
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -59,10 +59,12 @@ int          sr_sync(sr_ctx *);
  * exp(-t/tau) at the points a thread owns by multiplication, exp() once per thread: a point j products past its thread's exp()
  * (j < L / (64 fit_waves): up to 15 at L = 2048 and two waves) is within ((3 + 3 j) + 12 t/tau) u of exp(-t/tau), u = 2^-53 (exp()
  * per point: (3 + 2 t/tau) u), 17 % less time per batch
- * with the chip full; 0 = exp() per point whatever the axis, "ct_fft" = formulation of kernel 1 where the chunk length allows: 3 (default) the
+ * with the chip full; 0 = exp() per point whatever the axis, "ct_fft" = formulation of kernel 1 for the chunks that fit one transform
+ * in LDS, 1024 < F + L <= 8192: 3 (default) the
  * FLOAT32 real-input FFT for 4096 < F + L <= 8192 (the reference's own arithmetic type; C(t) to 4e-8) and the float64 complex
- * FFT below, 4 float32 transforms for every 1024 < F + L <= 8192, 2 the float64 real-input FFT for 4096 < F + L <= 8192 (C(t) to
- * 1e-15), 1 the float64 complex FFT everywhere, 0 always direct;
+ * FFT below, 4 float32 transforms at every such length, 2 the float64 real-input FFT for 4096 < F + L <= 8192 (C(t) to
+ * 1e-15) and the complex one below, 1 the float64 complex FFT at every such length, 0 always direct; 2 and more also admit the
+ * blocked transforms for longer chunks (sr_ct_formulation() below is the rule itself);
  * "ct_traceless" = 1/0 (default 0): the real-input FFT kernel for F <= 4096 transforms the five traceless components of
  * u (x) u and takes the trace term from a scan of |u|^2 - 1 (one transform fewer; series that are not unit vectors fall back
  * to six inside the kernel) -- 4 % faster alone, 3 % slower per step inside the pipeline, same results to 1e-13. */
@@ -149,6 +151,23 @@ int sr_pack_soa_rot_f32_dev(sr_ctx *, const float *vecs, int64_t N, int64_t Vtot
  * 13400 frames (-4).
  * psum (optional, may be NULL): (nV, R, Lp) float64 raw sums  sum_j (u.u')^2, Lp = sr_ct_psum_stride(F). */
 int64_t sr_ct_psum_stride(int64_t F);
+/* Which formulation mode 0 / 1 runs for chunks of F frames under the options "ct_fft" and "ct_long_min_frames" when a workgroup may
+ * have lds_limit bytes of LDS (sr_device_info: 163840 on gfx950) -- the dispatch of sr_ct_palmer_sums_f32_dev itself, as a host
+ * function that needs no context and no GPU (like sr_ct_psum_stride).  With need = F + F/2, the length one transform must hold, and
+ * "fits" = the direct kernel can stage the chunk in lds_limit: mode 1 is direct; in mode 0 chunks with need > 8192 are blocked
+ * when ct_fft >= 2 and (F >= ct_long_min_frames or they do not fit); of the rest, ct_fft = 0, need <= 1024 and need > 8192 are direct,
+ * ct_fft = 4 and (ct_fft = 3, need > 4096) float32 transforms, (ct_fft = 2, need > 4096) real-input float64 transforms, everything
+ * else complex float64 transforms.  Whatever is left with the direct kernel and does not fit is refused (-4 from the entry points),
+ * as are arguments outside their ranges. */
+enum {
+    SR_CT_REFUSED = 0,
+    SR_CT_DIRECT = 1,      /* shifted products (k_ct_palmer) */
+    SR_CT_FFT64 = 2,       /* complex float64 transforms (k_ct_fft) */
+    SR_CT_RFFT64 = 3,      /* real-input float64 transforms (k_ct_rfft) */
+    SR_CT_RFFT32 = 4,      /* real-input float32 transforms (k_ct_rfft32) */
+    SR_CT_BLOCKED = 5      /* blocked float32 transforms through device memory (sr_ct_long.hip) */
+};
+int sr_ct_formulation(int ct_fft, int64_t ct_long_min_frames, int mode, int64_t F, int64_t lds_limit);
 int64_t sr_ct_max_frames_per_chunk(sr_ctx *);
 /* the two halves of sr_ct_palmer_f32_dev as separate launches: raw sums per (vector, chunk, lag) into caller memory
  * (psum: (nV, R, Lp) float64, required here), then mean / std over the chunks (calculate-Ct-from-traj.py:226-228).

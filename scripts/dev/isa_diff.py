@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: compare two gfx950 code objects of one source file function by function.
+"""Developer tool: compare the gfx950 code objects of two revisions function by function.
 
     # device code object of sr_fit.hip at any revision (the flags of spinrelax_amd/build.py, device only):
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -ffp-contract=off --offload-device-only \
@@ -7,11 +7,15 @@
     # where hipcc wraps the code object in an offload bundle (llvm-objdump: "not recognized as a valid object file"):
     /opt/rocm/llvm/bin/clang-offload-bundler --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=a.co --output=a.elf
     scripts/dev/isa_diff.py a.elf b.elf 'k_trf|k_order_search|search_order'      # or a.co b.co where they are plain code objects
+    # a side may be several code objects, joined with commas: code that moved between sources, e.g. the parent's sr_ct.hip
+    # against the files it was split into (add -fno-slp-vectorize, as build.py does for them)
+    scripts/dev/isa_diff.py old/sr_ct.elf sr_pack.elf,sr_ct.elf,sr_ct_direct.elf,sr_ct_fft64.elf,sr_ct_rfft64.elf
 
-Disassembles both with llvm-objdump -d, cuts the listing at every function symbol, drops addresses and encodings, writes branch
+Disassembles them with llvm-objdump -d, cuts the listing at every function symbol, drops addresses and encodings, writes branch
 targets as symbol + offset instead of a word offset and masks the offsets of pc-relative addresses (a function that only moved
 inside the object is not a change) and prints, per function whose demangled name matches the pattern, "same" or the number of
-differing instruction lines; functions present in only one object are listed as such.  Exit status 1 if any differ."""
+differing instruction lines; functions present on only one side are listed as such.  The function maps of one side's objects
+are merged; a name that two of them define is an error (which of the two would be compared?).  Exit status 1 if any differ."""
 import re
 import subprocess
 import sys
@@ -53,8 +57,19 @@ def functions(co):
     return out
 
 
+def side(arg):
+    out = {}
+    for co in arg.split(','):
+        f = functions(co)
+        dup = sorted(set(out) & set(f))
+        if dup:
+            sys.exit('%s: %s is defined in another object of this side too' % (co, dup[0]))
+        out.update(f)
+    return out
+
+
 def main():
-    a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    a, b = side(sys.argv[1]), side(sys.argv[2])
     pat = re.compile(sys.argv[3] if len(sys.argv) > 3 else '.')
     bad = 0
     for name in sorted(set(a) | set(b)):

@@ -54,6 +54,7 @@ SIGNATURES = {
     'sr_pack_soa_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64]),
     'sr_pack_soa_rot_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64]),
     'sr_ct_psum_stride': (c_int64, [c_int64]),
+    'sr_ct_formulation': (c_int, [c_int, c_int64, c_int, c_int64, c_int64]),       # (ct_fft, ct_long_min_frames, mode, F, lds_limit)
     'sr_ct_max_frames_per_chunk': (c_int64, [c_void_p]),
     'sr_ct_palmer_sums_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p]),
     'sr_ct_finalize_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
@@ -136,7 +137,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 10
+ABI_VERSION = 11
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -9,20 +9,26 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libspinrelax_hip.so')
-SOURCES = ['sr_core.hip', 'sr_ct.hip', 'sr_ct32.hip', 'sr_ct_long.hip', 'sr_vechist.hip', 'sr_fit.hip', 'sr_relax.hip', 'sr_dq.hip', 'sr_traj.hip', 'sr_vectors.hip', 'sr_textio.hip']
+SOURCES = ['sr_core.hip', 'sr_pack.hip', 'sr_ct.hip', 'sr_ct_direct.hip', 'sr_ct_fft64.hip', 'sr_ct_rfft64.hip', 'sr_ct32.hip', 'sr_ct_long.hip',
+           'sr_vechist.hip', 'sr_fit.hip', 'sr_relax.hip', 'sr_dq.hip', 'sr_traj.hip', 'sr_vectors.hip', 'sr_textio.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']
-# sr_ct.hip: the SLP vectoriser packs the FMAs of the C(t) inner loop into v_pk_fma_f32, whose operand pairs then
-# need ~1 v_mov per FMA (rocprofv3: 4.8e9 VALU instructions for 2.5e9 FMAs); plain v_fma_f32 issues at the same rate.
-EXTRA = {'sr_ct.hip': ['-fno-slp-vectorize'],
-         # sr_ct32.hip: the same for the float32 transforms (packed complex arithmetic by the vectoriser costs a v_mov per
-         # operand pair and 270 B of scratch at 128 VGPRs; without it 56 B)
-         'sr_ct32.hip': ['-fno-slp-vectorize'],
-         'sr_ct_long.hip': ['-fno-slp-vectorize'],
+# Kernels 0 and 1, no SLP vectoriser.  sr_ct_direct.hip: it packs the FMAs of the C(t) inner loop into v_pk_fma_f32, whose operand
+# pairs then need ~1 v_mov per FMA (rocprofv3: 4.8e9 VALU instructions for 2.5e9 FMAs); plain v_fma_f32 issues at the same rate.
+# sr_ct32.hip, sr_ct_long.hip: packed complex arithmetic by the vectoriser costs a v_mov per operand pair and 270 B of scratch at
+# 128 VGPRs; without it 56 B.  The others were one file with the direct kernel and are compiled as they always were.
+EXTRA = {'sr_pack.hip': ['-fno-slp-vectorize'], 'sr_ct.hip': ['-fno-slp-vectorize'], 'sr_ct_direct.hip': ['-fno-slp-vectorize'],
+         'sr_ct_fft64.hip': ['-fno-slp-vectorize'], 'sr_ct_rfft64.hip': ['-fno-slp-vectorize'],
+         'sr_ct32.hip': ['-fno-slp-vectorize'], 'sr_ct_long.hip': ['-fno-slp-vectorize'],
          # sr_fit.hip: explicit fma() only, see the note at the top of the file
          'sr_fit.hip': ['-ffp-contract=off']}
 if os.environ.get('SR_FIT_DEV_FAST'):          # development: only the order-search variants the benchmark uses
     EXTRA['sr_fit.hip'] = EXTRA['sr_fit.hip'] + ['-DSR_FIT_DEV_FAST']
+
+
+def headers():
+    """every header of csrc/, sorted: all of them go into the build id and into the staleness check"""
+    return sorted(n for n in os.listdir(CSRC) if n.endswith('.h'))
 
 
 def build_id():
@@ -31,7 +37,7 @@ def build_id():
     of a profiling run (bench.py compares the two)."""
     import hashlib
     h = hashlib.sha256()
-    for name in sorted(SOURCES) + ['sr_internal.h', 'sr_ct32_fft.h']:
+    for name in sorted(SOURCES) + headers():
         with open(os.path.join(CSRC, name), 'rb') as fp:
             h.update(name.encode() + b'\0' + fp.read())
     with open(os.path.join(HERE, '..', 'include', 'spinrelax_hip.h'), 'rb') as fp:
@@ -56,7 +62,7 @@ def _same_flags(stamp, sig):
 
 
 def build(force=False, verbose=True):
-    hdrs = [os.path.join(CSRC, 'sr_internal.h'), os.path.join(CSRC, 'sr_ct32_fft.h'), os.path.join(HERE, '..', 'include', 'spinrelax_hip.h')]
+    hdrs = [os.path.join(CSRC, n) for n in headers()] + [os.path.join(HERE, '..', 'include', 'spinrelax_hip.h')]
     objs = []
     bid = build_id()
     idfile = os.path.join(CSRC, '.build_id')

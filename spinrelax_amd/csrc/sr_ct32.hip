@@ -2,7 +2,7 @@
 // autocorrelation with FLOAT32 transforms (k_ct_rfft32): production for 4096 < F + L <= 8192, option for 1024 < F + L <= 4096.
 //
 // Reference semantics: calculate_Ct_Palmer, calculate-Ct-from-traj.py:200-238 -- which computes in float32
-// (`Ct = np.zeros(..., dtype=vecs.dtype)`, :219; the shifted products :222-228).  The float64 kernels of sr_ct.hip
+// (`Ct = np.zeros(..., dtype=vecs.dtype)`, :219; the shifted products :222-228).  The float64 kernels of sr_ct_fft64.hip
 // (k_ct_rfft, k_ct_fft) are wider than the reference; this one matches its type and is what the pipeline runs.
 //
 // Why a float32 transform needs care, and what is done about it.  S[d] = sum_j (u_j.u_{j+d})^2 is a sum of ordinary
@@ -29,7 +29,7 @@
 //
 // Structure: one 256-thread workgroup per (chunk, vector) series, real-input transforms of half length H = N1 * 256
 // (N1 = 12: M = 6144, F <= 4096;  N1 = 16: M = 8192, F <= 5461), three steps N1 x 16 x 16 in registers with two LDS
-// exchanges, spectrum by frequency pairs -- the layout of k_ct_rfft (sr_ct.hip), every index mapping the same.  A complex
+// exchanges, spectrum by frequency pairs -- the layout of k_ct_rfft (sr_ct_fft64.hip), every index mapping the same.  A complex
 // float is 8 bytes: the transform image is 26 KB (N1 = 12) and a thread's 12 + 16 points fit 128 VGPRs -- FOUR waves per SIMD
 // and four workgroups per CU where the float64 kernel has two and two.
 #include "sr_internal.h"
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
     // input blocks (of 512 frames) that can hold frames: F + L <= M with L = F/2, i.e. F <= 1365 / 2730 / 4096 / 5461 for N1 = 4 / 8 / 12 / 16
     constexpr int NZ = N1 == 4 ? 3 : (N1 == 8 ? 6 : (N1 == 12 ? 8 : 16));
     constexpr int IPT = N1 == 4 ? 3 : (N1 == 8 ? 6 : (N1 == 12 ? 8 : 11));     // scan: half-series elements per thread (256 IPT >= ceil(F/2))
-    c32 *tw1 = lds + f32_img_slots(N1) + 256;                      // 4 x 256 step-1 twiddle bases: w_H^(j tid), j = 1, 2, 4, 8
+    c32 *tw1 = lds + rfft_img_slots(N1) + 256;                      // 4 x 256 step-1 twiddle bases: w_H^(j tid), j = 1, 2, 4, 8
     c32 *tw3 = tw1 + 1024;                                         // 256 x w_M^t: the spectrum step's twiddle of thread (k1, k2a) at k1 + N1 k2a
     float *aux = reinterpret_cast<float *>(tw3 + 256);             // [0 .. 32): wave partial sums; [32 .. 49): m_c, w_c m_c, weight of eps;
                                                                    // [50]: P[H/2] (thread 0's self-paired frequency); [52 .. 54): K (double)
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
     }
     {
         const int j = ((tid0 & 15) * (tid0 >> 4)) & 255;
-        lds[f32_img_slots(N1) + tid0] = c32{a.tab->w2[2 * j], a.tab->w2[2 * j + 1]};
+        lds[rfft_img_slots(N1) + tid0] = c32{a.tab->w2[2 * j], a.tab->w2[2 * j + 1]};
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) tw1[256 * jj + tid0] = c32{a.tab->w1[jj][2 * tid0], a.tab->w1[jj][2 * tid0 + 1]};
         tw3[tid0] = c32{a.tab->w3[2 * tid0], a.tab->w3[2 * tid0 + 1]};
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
 #pragma unroll 1
     for (int c = 0; c < nsig; ++c) {
         asm volatile("" ::: "memory");
-        const int tid = opaquei(tid0);
+        const int tid = opaque(tid0);
         const int k1 = (tid >> 4) & 15, k2a = tid & 15;
         const bool act = k1 < N1;
         const int pt = k1 != 0 ? (N1 - k1) * 16 + (15 - k2a) : (k2a != 0 ? 16 - k2a : 0);
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
             // S = Z[k] + conj Z[H-k], D = Z[k] - conj Z[H-k], T = w_M^k D:  4 |A[k]|^2 = |S - i T|^2, 4 |A[H-k]|^2 = |S + i T|^2
 #pragma unroll
             for (int q = 0; q < 8; q += 2) {
-                const c32 zk0 = w[bitrevf<4>(q)], zm0 = b[15 - q], zk1 = w[bitrevf<4>(q + 1)], zm1 = b[14 - q];
+                const c32 zk0 = w[bitrev<4>(q)], zm0 = b[15 - q], zk1 = w[bitrev<4>(q + 1)], zm1 = b[14 - q];
                 const c32 S0 = add_conj(zk0, zm0), S1 = add_conj(zk1, zm1);
                 c32 T0 = sub_conj(zk0, zm0), T1 = sub_conj(zk1, zm1);
                 cmulf2(T0, mulf_w32_rt(wb, q), T1, mulf_w32_rt(wb, q + 1));
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
                 W2[q + 1] = pk_fma(splat(wgt), pk_fma(A1, A1, B1 * B1), W2[q + 1]);
             }
             if (off0) {                                            // k = H/2 (k2b = 8) mirrors onto itself
-                const c32 zk = w[bitrevf<4>(8)];
+                const c32 zk = w[bitrev<4>(8)];
                 const c32 D = {0.0f, 2.0f * zk.y};
                 const c32 T = cmulf(D, mulf_w32_rt(wb, 8));
                 const float pr = 2.0f * zk.x + T.y, pi = -T.x;
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
 #endif
 
     // ---- back: Y[k] = (P[k] + P[H-k]) + i (P[k] - P[H-k]) conj(w_M^k), through the same transform (see k_ct_rfft) ----
-    const int tid = opaquei(tid0);
+    const int tid = opaque(tid0);
     const int k1 = (tid >> 4) & 15, k2a = tid & 15;
     const bool act = k1 < N1;
     const int pt = k1 != 0 ? (N1 - k1) * 16 + (15 - k2a) : (k2a != 0 ? 16 - k2a : 0);
@@ -410,7 +410,7 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
         const double inv = 1.0 / (double)M, sixth = 1.0 / 6.0;
 #pragma unroll
         for (int p = 0; p < 16; ++p) {
-            const int m = k1 + N1 * (k2a + 16 * bitrevf<4>(p));
+            const int m = k1 + N1 * (k2a + 16 * bitrev<4>(p));
             const int le = 2 * m, lod = 2 * m - 1;
             if (le >= 1 && le <= L) out[le] = fma((double)w[p].x, inv, Tt[le]) * sixth;
             if (lod >= 1 && lod <= L) out[lod] = fma((double)w[p].y, inv, Tt[lod]) * sixth;
@@ -435,7 +435,7 @@ template <int N1>
 constexpr size_t f32_lds_bytes()
 {
     // transform image + the 16 x 16 step-2 twiddles + the 4 x 256 step-1 bases + the 256 spectrum twiddles + reduction scratch
-    return (size_t)(f32_img_slots(N1) + 256 + 1024 + 256) * sizeof(c32) + 64 * sizeof(float);
+    return (size_t)(rfft_img_slots(N1) + 256 + 1024 + 256) * sizeof(c32) + 64 * sizeof(float);
 }
 
 template <int N1, bool FULL>
@@ -451,8 +451,8 @@ int launch_ct_rfft32_h(sr_ctx *ctx, const Ct32Args &a, int64_t series)
     }
     // the scan's tables share the image: F floats, then L + 1 doubles
     constexpr size_t Fmax = N1 == 4 ? 1365 : (N1 == 8 ? 2730 : (N1 == 12 ? 4096 : 5461));
-    static_assert((size_t)f32_img_slots(N1) * sizeof(c32) >= (Fmax + 3) * 4, "k_ct_rfft32: E does not fit the image");
-    static_assert((size_t)f32_img_slots(N1) * sizeof(c32) >= (Fmax / 2 + 2) * 8, "k_ct_rfft32: Tt does not fit the image");
+    static_assert((size_t)rfft_img_slots(N1) * sizeof(c32) >= (Fmax + 3) * 4, "k_ct_rfft32: E does not fit the image");
+    static_assert((size_t)rfft_img_slots(N1) * sizeof(c32) >= (Fmax / 2 + 2) * 8, "k_ct_rfft32: Tt does not fit the image");
     return sr_launch(ctx, k_ct_rfft32<N1, FULL>, dim3((unsigned)series), dim3(256), lds, a);
 }
 
@@ -475,33 +475,33 @@ const void *sr_ct32_tables(sr_ctx *ctx)
 // Called by sr_ct_palmer_sums_f32_dev (sr_ct.hip): ct_fft = 3 (default) for 4096 < F + L <= 8192, ct_fft = 4 for every 1024 < F + L <= 8192.
 // (Why the shorter chunks keep float64 transforms by default: at cfg2's size the launch is 80 us either way, and the drop-in chain THROUGH
 // ITS TEXT FILES -- _Ctint.dat keeps 8 digits -- reproduces the reference's printed digits only with float64 C(t); with float32 C(t) one
-// of 16 cfg2 residues lands 1.1e-6 from the reference's through-files table, tests/test_gpu_cli.py.)  chunk starts: cs_host (may be
-// null: chunk r starts at r F) is what decides the aligned fast path, cs_dev is what the kernel reads.
-int sr_launch_ct_rfft32(sr_ctx *ctx, const float *soa, int64_t Npad, const int64_t *cs_host, const int64_t *cs_dev, double *psum,
-                        int R, int F, int L, int Lp, int64_t series)
+// of 16 cfg2 residues lands 1.1e-6 from the reference's through-files table, tests/test_gpu_cli.py.)  Of the chunk starts, the host copy is
+// what decides the aligned fast path, the device copy is what the kernel reads.
+int sr_launch_ct_rfft32(sr_ctx *ctx, const sr_ct_job &j)
 {
     const Ct32Tab *tab = (const Ct32Tab *)sr_ct32_tables(ctx);
     if (!tab) return -5;
+    const int F = j.F;
     Ct32Args a;
-    a.soa = soa; a.Npad = Npad; a.chunk_start = cs_dev; a.psum = psum;
-    a.R = R; a.F = F; a.L = L; a.Lp = Lp;
-    bool aligned = (Npad & 1) == 0 && (F & 1) == 0 && (((uintptr_t)soa) & 7) == 0;
-    if (cs_host)
-        for (int r = 0; r < R; ++r) aligned = aligned && (cs_host[r] & 1) == 0;
-    const int need = F + L;
+    a.soa = j.soa; a.Npad = j.Npad; a.chunk_start = j.cs_dev; a.psum = j.psum;
+    a.R = j.R; a.F = F; a.L = j.L; a.Lp = j.Lp;
+    bool aligned = (j.Npad & 1) == 0 && (F & 1) == 0 && (((uintptr_t)j.soa) & 7) == 0;
+    if (j.cs_host)
+        for (int r = 0; r < j.R; ++r) aligned = aligned && (j.cs_host[r] & 1) == 0;
+    const int need = F + j.L;
     SR_REQUIRE(need > 1024 && need <= 8192, -3, "k_ct_rfft32: F=%d outside the transform lengths", F);
     if (need <= 2048) {
         a.tab = tab + f32_tab_set(4);
-        return launch_ct_rfft32_h<4, false>(ctx, a, series);
+        return launch_ct_rfft32_h<4, false>(ctx, a, j.series);
     }
     if (need <= 4096) {
         a.tab = tab + f32_tab_set(8);
-        return launch_ct_rfft32_h<8, false>(ctx, a, series);
+        return launch_ct_rfft32_h<8, false>(ctx, a, j.series);
     }
     if (need <= 6144) {
         a.tab = tab + f32_tab_set(12);
-        return aligned && F == 4096 ? launch_ct_rfft32_h<12, true>(ctx, a, series) : launch_ct_rfft32_h<12, false>(ctx, a, series);
+        return aligned && F == 4096 ? launch_ct_rfft32_h<12, true>(ctx, a, j.series) : launch_ct_rfft32_h<12, false>(ctx, a, j.series);
     }
     a.tab = tab + f32_tab_set(16);
-    return launch_ct_rfft32_h<16, false>(ctx, a, series);
+    return launch_ct_rfft32_h<16, false>(ctx, a, j.series);
 }

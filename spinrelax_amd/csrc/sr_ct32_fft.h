@@ -1,8 +1,9 @@
 // sr_ct32_fft.h -- device functions of the float32 transforms of kernel 1, shared by sr_ct32.hip (k_ct_rfft32: one transform per
 // series) and sr_ct_long.hip (the blocked form for long chunks): packed complex arithmetic, the in-register butterflies, the
-// workgroup transform of half length 256 N1, its tables, wave scans, and the one definition of the transforms' inputs.
+// workgroup transform of half length 256 N1, its tables, and the one definition of the transforms' inputs.  Index maps, image
+// size and wave scans: sr_fft_common.h.
 #pragma once
-#include "sr_internal.h"
+#include "sr_fft_common.h"
 
 namespace {
 
@@ -148,14 +149,6 @@ SR_PK c32 mulf_w24(c32 d)
     else return mul_const<fbits(c[E]), fbits(s[E])>(d);
 }
 
-template <int LOGN>
-__host__ __device__ constexpr int bitrevf(int p)
-{
-    int r = 0;
-    for (int b = 0; b < LOGN; ++b) r |= ((p >> b) & 1) << (LOGN - 1 - b);
-    return r;
-}
-
 template <int LOGN, int S, int BLK, int J>
 struct FftStageF {
     __device__ static __forceinline__ void run(c32 *v)
@@ -181,10 +174,8 @@ __device__ __forceinline__ void fftf_reg(c32 *v)
 }
 
 template <int N1>
-struct FStage1 {                                           // N1 = 4, 8, 16
-    static constexpr int LOG = N1 == 4 ? 2 : (N1 == 8 ? 3 : 4);
-    __host__ __device__ static constexpr int k1(int p) { return bitrevf<LOG>(p); }
-    __device__ static __forceinline__ void run(c32 *v) { fftf_reg<LOG>(v); }
+struct FStage1 : Stage1Map<N1> {                           // N1 = 4, 8, 16
+    __device__ static __forceinline__ void run(c32 *v) { fftf_reg<Stage1Map<N1>::LOG>(v); }
 };
 template <int B>
 __device__ __forceinline__ void dft3f_col12(c32 *v, c32 (*y)[4])
@@ -200,8 +191,7 @@ __device__ __forceinline__ void dft3f_col12(c32 *v, c32 (*y)[4])
     if constexpr (B + 1 < 4) dft3f_col12<B + 1>(v, y);
 }
 template <>
-struct FStage1<12> {                                       // n1 = 4 a + b, k1 = ka + 3 kb
-    __host__ __device__ static constexpr int k1(int p) { return (p >> 2) + 3 * bitrevf<2>(p & 3); }
+struct FStage1<12> : Stage1Map<12> {
     __device__ static __forceinline__ void run(c32 *v)
     {
         c32 y[3][4];
@@ -215,17 +205,12 @@ struct FStage1<12> {                                       // n1 = 4 a + b, k1 =
     }
 };
 
-// Hide a value's provenance from the optimiser (see sr_ct.hip: thread-invariant twiddles and addresses would otherwise be
-// computed once per kernel, parked in registers the loop does not have, and spilled).
+// Hide a value's provenance from the optimiser (see k_ct_rfft, sr_ct_fft64.hip: thread-invariant twiddles would otherwise be
+// computed once per kernel, parked in registers the loop does not have, and spilled).  The thread index: opaque(), sr_fft_common.h.
 __device__ __forceinline__ c32 opaquef(c32 z)
 {
     asm volatile("" : "+v"(z));
     return z;
-}
-__device__ __forceinline__ int opaquei(int t)
-{
-    asm volatile("" : "+v"(t));
-    return t;
 }
 
 // v[p] *= base^k(p), base = w_H^tid.  The thread reads base^1, base^2, base^4, base^8 from four float32 tables (each entry
@@ -313,8 +298,6 @@ struct Ct32Args {
     int R, F, L, Lp;
 };
 
-__host__ __device__ constexpr int f32_img_slots(int N1) { return 256 * N1 + 256 + 16; }     // as rfft_lds_slots (sr_ct.hip)
-
 #ifdef SR_CT32_STAMPS           // development: s_memtime stamps around the phases of a pass, summed per wave, left behind lag L of the
 #define SR_STAMP(I) { const long long t_ = __builtin_amdgcn_s_memtime(); stamp_acc[I] += t_ - stamp_t; stamp_t = t_; }   // series' sums
 #else
@@ -363,15 +346,15 @@ __device__ __forceinline__ void rfft32_workgroup(c32 *v, c32 *w, c32 *lds, const
 #endif
         fftf_reg<4>(u);
         {
-            const c32 *tw = lds + f32_img_slots(N1) + lo;         // w_256^(lo k2a) at [k2a*16 + lo], filled at kernel start
+            const c32 *tw = lds + rfft_img_slots(N1) + lo;         // w_256^(lo k2a) at [k2a*16 + lo], filled at kernel start
 #pragma unroll
-            for (int p = 1; p < 15; p += 2) cmulf2(u[p], tw[16 * bitrevf<4>(p)], u[p + 1], tw[16 * bitrevf<4>(p + 1)]);
-            u[15] = cmulf(u[15], tw[16 * bitrevf<4>(15)]);
+            for (int p = 1; p < 15; p += 2) cmulf2(u[p], tw[16 * bitrev<4>(p)], u[p + 1], tw[16 * bitrev<4>(p + 1)]);
+            u[15] = cmulf(u[15], tw[16 * bitrev<4>(15)]);
         }
         // in place (see k_ct_rfft): the cells this thread has read are the ones it writes
         c32 *bw = lds + 272 * k1 + lo;
 #pragma unroll
-        for (int p = 0; p < 16; ++p) bw[17 * bitrevf<4>(p)] = u[p];
+        for (int p = 0; p < 16; ++p) bw[17 * bitrev<4>(p)] = u[p];
         SR_STAMP(3)
     }
     // row tid was written by the thread's own 16-lane group, and the LDS operations of one wave complete in order: only the
@@ -393,47 +376,13 @@ __device__ __forceinline__ void rfft32_workgroup(c32 *v, c32 *w, c32 *lds, const
             c32 *bo = lds + 17 * tid;
 #pragma unroll
             for (int p = 0; p < 16; ++p)
-                if (bitrevf<4>(p) >= 8) bo[bitrevf<4>(p)] = w[p];
+                if (bitrev<4>(p) >= 8) bo[bitrev<4>(p)] = w[p];
             if (tid == 0) bo[16] = w[0];
         }
     }
 }
 
 constexpr float kUnitTolF = 5e-7f;
-
-// inclusive float64 prefix scan over the 64 lanes of a wave: row_shr 1, 2, 4, 8 inside the rows of 16 lanes, then
-// row_bcast15 / row_bcast31; lanes without a source add 0
-__device__ __forceinline__ double wave_scan_f64(double v)
-{
-    union U { double d; int i[2]; };
-#define SR_SCAN_STEP(CTRL, RM)                                                                   \
-    {                                                                                            \
-        U a_, b_;                                                                                \
-        a_.d = v;                                                                                \
-        b_.i[0] = __builtin_amdgcn_update_dpp(0, a_.i[0], CTRL, RM, 0xF, false);                 \
-        b_.i[1] = __builtin_amdgcn_update_dpp(0, a_.i[1], CTRL, RM, 0xF, false);                 \
-        v += b_.d;                                                                               \
-    }
-    SR_SCAN_STEP(0x111, 0xF) SR_SCAN_STEP(0x112, 0xF) SR_SCAN_STEP(0x114, 0xF) SR_SCAN_STEP(0x118, 0xF)
-    SR_SCAN_STEP(0x142, 0xA) SR_SCAN_STEP(0x143, 0xC)
-#undef SR_SCAN_STEP
-    return v;
-}
-// wave totals of float values with the same sequence (lane 63 ends up with the sum)
-__device__ __forceinline__ float wave_total_f32(float v)
-{
-#define SR_TOT_STEP(CTRL, RM) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, RM, 0xF, false));
-    SR_TOT_STEP(0x111, 0xF) SR_TOT_STEP(0x112, 0xF) SR_TOT_STEP(0x114, 0xF) SR_TOT_STEP(0x118, 0xF) SR_TOT_STEP(0x142, 0xA) SR_TOT_STEP(0x143, 0xC)
-#undef SR_TOT_STEP
-    return v;
-}
-__device__ __forceinline__ float wave_max_f32(float v)       // v >= 0: 0 is neutral
-{
-#define SR_MAX_STEP(CTRL, RM) v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, RM, 0xF, false)));
-    SR_MAX_STEP(0x111, 0xF) SR_MAX_STEP(0x112, 0xF) SR_MAX_STEP(0x114, 0xF) SR_MAX_STEP(0x118, 0xF) SR_MAX_STEP(0x142, 0xA) SR_MAX_STEP(0x143, 0xC)
-#undef SR_MAX_STEP
-    return v;
-}
 
 // planes of signal c (0 = x, 1 = y, 2 = z): c = 1, 2: x y;  3: x z;  4: y z;  5 (|u|^2): x y, then z
 __device__ __forceinline__ int f32_plane_a(int c) { return c == 4 ? 1 : 0; }

@@ -215,14 +215,14 @@ __device__ __forceinline__ void ctl_load(c32 *dst, const float *plane, int Fb, b
     }
 }
 
-constexpr size_t ctl_spectra_lds_bytes() { return (size_t)(f32_img_slots(16) + 256 + 1024 + 256) * sizeof(c32); }
+constexpr size_t ctl_spectra_lds_bytes() { return (size_t)(rfft_img_slots(16) + 256 + 1024 + 256) * sizeof(c32); }
 
 __global__ __launch_bounds__(256, 3) void k_ctl_spectra(CtlArgs a)
 {
     extern __shared__ __align__(16) unsigned char ctl_smem[];
     c32 *lds = reinterpret_cast<c32 *>(ctl_smem);
     constexpr int N1 = 16, NZ = 8;                                 // a block fills the first NZ of the N1 inputs of a thread
-    c32 *tw1 = lds + f32_img_slots(N1) + 256;
+    c32 *tw1 = lds + rfft_img_slots(N1) + 256;
     c32 *tw3 = tw1 + 1024;
     const int tid0 = threadIdx.x, blk = blockIdx.x, sl = blockIdx.y, s = a.s0 + sl;
     const int v = s / a.R, r = s - v * a.R;
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256, 3) void k_ctl_spectra(CtlArgs a)
     const bool even = ((start | a.Npad | (int64_t)Fb) & 1) == 0;   // frames 2m, 2m + 1 of every plane share an aligned 8 bytes
     {
         const int j = ((tid0 & 15) * (tid0 >> 4)) & 255;
-        lds[f32_img_slots(N1) + tid0] = c32{a.tab->w2[2 * j], a.tab->w2[2 * j + 1]};
+        lds[rfft_img_slots(N1) + tid0] = c32{a.tab->w2[2 * j], a.tab->w2[2 * j + 1]};
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) tw1[256 * jj + tid0] = c32{a.tab->w1[jj][2 * tid0], a.tab->w1[jj][2 * tid0 + 1]};
         tw3[tid0] = c32{a.tab->w3[2 * tid0], a.tab->w3[2 * tid0 + 1]};
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256, 3) void k_ctl_spectra(CtlArgs a)
 #pragma unroll 1
     for (int c = 0; c < nsig; ++c) {
         asm volatile("" ::: "memory");
-        const int tid = opaquei(tid0);
+        const int tid = opaque(tid0);
         const float mc = uniform_f(cc->m[c]);
         c32 sig[N1];
         {
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256, 3) void k_ctl_spectra(CtlArgs a)
         c32 *out = a.spec + ((int64_t)(sl * 6 + c) * a.nb + blk) * kSpecLen + tid;
 #pragma unroll
         for (int q = 0; q < 8; q += 2) {
-            const c32 zk0 = w[bitrevf<4>(q)], zm0 = b[15 - q], zk1 = w[bitrevf<4>(q + 1)], zm1 = b[14 - q];
+            const c32 zk0 = w[bitrev<4>(q)], zm0 = b[15 - q], zk1 = w[bitrev<4>(q + 1)], zm1 = b[14 - q];
             const c32 S0 = add_conj(zk0, zm0), S1 = add_conj(zk1, zm1);
             c32 T0 = sub_conj(zk0, zm0), T1 = sub_conj(zk1, zm1);
             cmulf2(T0, mulf_w32_rt(wb, q), T1, mulf_w32_rt(wb, q + 1));
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256, 3) void k_ctl_spectra(CtlArgs a)
             out[2048 + 256 * (q + 1)] = c32{A1.y, -B1.y};
         }
         if (off0) {                                                // k = H/2 (k2b = 8) mirrors onto itself
-            const c32 zk = w[bitrevf<4>(8)];
+            const c32 zk = w[bitrev<4>(8)];
             const c32 D = {0.0f, 2.0f * zk.y};
             const c32 T = cmulf(D, mulf_w32_rt(wb, 8));
             out[4096] = c32{2.0f * zk.x + T.y, -T.x};
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256) void k_ctl_inverse(CtlArgs a)
         const int n0 = (int)(__builtin_bitreverse32((unsigned)tid) >> 24);
 #pragma unroll
         for (int p = 0; p < 16; p += 2) {
-            const int n = 256 * bitrevf<4>(p) + n0;
+            const int n = 256 * bitrev<4>(p) + n0;
             lag[2 * n] = u[p].x;
             lag[2 * n + 1] = u[p].y;
         }
@@ -450,10 +450,11 @@ int64_t sr_ct_long_bytes_per_series(int64_t F)
     return 6 * nb * kSpecLen * (int64_t)sizeof(c32) + nd * kSpecLen * (int64_t)sizeof(double2);
 }
 
-// Called by sr_ct_palmer_sums_f32_dev (sr_ct.hip) for F + L > 8192 in the default dispatch.
-int sr_launch_ct_long(sr_ctx *ctx, const float *soa, int64_t Npad, const int64_t *cs_dev, double *psum, int R, int F, int L, int Lp,
-                      int64_t series)
+// Called by sr_ct_palmer_sums_f32_dev (sr_ct.hip) for the chunks its dispatch gives the blocked form (F + L > 8192).
+int sr_launch_ct_long(sr_ctx *ctx, const sr_ct_job &j)
 {
+    const int F = j.F, L = j.L;
+    const int64_t series = j.series;
     SR_REQUIRE(F + L > 8192 && F <= SR_CT_LONG_MAX_FRAMES, -3, "blocked C(t): F=%d outside its range", F);
     const Ct32Tab *tab32 = (const Ct32Tab *)sr_ct32_tables(ctx);
     if (!tab32) return -5;
@@ -481,11 +482,11 @@ int sr_launch_ct_long(sr_ctx *ctx, const float *soa, int64_t Npad, const int64_t
     if (ctx->ctlong_ev_set) SR_HIP(hipStreamWaitEvent(ctx->stream, ctx->ctlong_ev, 0));
 
     CtlArgs a;
-    a.soa = soa; a.Npad = Npad; a.chunk_start = cs_dev; a.psum = psum; a.tab = tab32 + f32_tab_set(16); a.itab = itab;
+    a.soa = j.soa; a.Npad = j.Npad; a.chunk_start = j.cs_dev; a.psum = j.psum; a.tab = tab32 + f32_tab_set(16); a.itab = itab;
     a.consts = reinterpret_cast<CtlConst *>(ws);
     a.spec = reinterpret_cast<c32 *>(ws + const_bytes);
     a.Q = reinterpret_cast<double2 *>(ws + const_bytes + (size_t)tile * 6 * nb * kSpecLen * sizeof(c32));
-    a.R = R; a.F = F; a.L = L; a.Lp = Lp; a.nb = nb; a.nd = nd; a.s0 = 0;
+    a.R = j.R; a.F = F; a.L = L; a.Lp = j.Lp; a.nb = nb; a.nd = nd; a.s0 = 0;
     hipLaunchKernelGGL(k_ctl_consts, dim3((unsigned)series), dim3(256), 0, ctx->stream, a);
     SR_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_ctl_scan, dim3((unsigned)series), dim3(256), 0, ctx->stream, a);

@@ -22,15 +22,13 @@ struct sr_ctx {
     int fit_geo;        // 1 (default): on a uniform time grid the fit kernels form exp(-t/tau) of a thread's points by multiplication
                         // (sr_fit.hip, Residue::stage); 0: exp() per point whatever the grid
     int fit_lds;        // 1: stage t, y, 1/sigma of a residue in LDS when it fits; 0: read them from global memory
-    int ct_fft;         // kernel 1 when the chunk length allows: 3 (default) = float32 real-input FFT (k_ct_rfft32) for 4096 < F + L <=
-                        // 8192, the float64 complex FFT below; 4 = float32 transforms for every 1024 < F + L <= 8192;
-                        // 2 = the float64 real-input FFT (k_ct_rfft) for 4096 < F + L <= 8192;
-                        // 1 = complex float64 FFT formulation (k_ct_fft) everywhere, 0 = always the direct kernel
+    int ct_fft;         // formulation of kernel 1, 0 .. 4 (default 3): one input of sr_ct_formulation(), whose rule is written out at
+                        // the top of sr_ct.hip
     int ct_wg_per_cu;   // k_ct_rfft32: at most this many workgroups per CU (0 = as many as fit: 4 for M = 6144); see sr_ct32.hip
     int ct_traceless;   // 1: k_ct_rfft<12> in its traceless five-signal form (faster alone, slower inside the pipeline: default 0)
     int ct_long_ws_mb;  // blocked C(t) (sr_ct_long.hip): the series of a launch go in tiles whose block spectra fit this many MiB
-    int ct_long_min_frames;   // blocked C(t): chunks of at least this many frames take it (shorter ones that do not fit one transform:
-                        // the direct kernel); see SR_CT_LONG_MIN_FRAMES
+    int ct_long_min_frames;   // blocked C(t): beyond one transform (F + L > 8192), chunks of at least this many frames take it, and the
+                        // shorter ones that the direct kernel cannot stage; default SR_CT_LONG_MIN_FRAMES
     int fft_table_ready;
     int fft32_table_ready;
     int ctlong_table_ready;
@@ -95,21 +93,42 @@ int sr_grant_lds(sr_ctx *ctx, const void *func, size_t bytes);
 
 static inline int64_t sr_round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-// sr_ct32.hip: the float32 real-input FFT form of kernel 1 (raw lag sums per chunk, like k_ct_rfft); the chunk starts may be null
-int sr_launch_ct_rfft32(sr_ctx *ctx, const float *soa, int64_t Npad, const int64_t *cs_host, const int64_t *cs_dev, double *psum,
-                        int R, int F, int L, int Lp, int64_t series);
+// ---- kernel 1: the formulations behind sr_ct_palmer_sums_f32_dev (sr_ct.hip chooses, see its header) ------------------------
+constexpr int kLagBlock = 128;          // lags per wave pass of the direct kernel, which writes whole blocks: the slack of sr_ct_psum_stride
+
+// what every launcher below gets: R chunks of F frames of nV vectors, raw lag sums out
+struct sr_ct_job {
+    const float *soa;                   // packed planes, Npad floats each
+    int64_t Npad;
+    const int64_t *cs_host, *cs_dev;    // chunk starts, the same R values on the host and on the device; both null: chunk r starts at r F
+    double *psum;                       // (nV, R, Lp)
+    int R, F, L, Lp;
+    int64_t series;                     // R nV
+};
+
+// sr_ct_direct.hip: shifted products (k_ct_palmer); mode as in sr_ct_palmer_sums_f32_dev.  The series is staged in LDS, so the
+// caller checks sr_ct_direct_lds_bytes(F) against sr_lds_limit() first; the longest F that a limit admits is for messages.
+int sr_launch_ct_direct(sr_ctx *ctx, const sr_ct_job &job, int mode);
+size_t sr_ct_direct_lds_bytes(int64_t F);
+int64_t sr_ct_direct_max_frames(size_t lds_limit);
+
+// sr_ct_fft64.hip: float64 transforms in LDS, complex (k_ct_fft: 1024 < F + L <= 8192) and real-input (k_ct_rfft: 4096 < F + L <= 8192)
+int sr_launch_ct_fft64(sr_ctx *ctx, const sr_ct_job &job);
+int sr_launch_ct_rfft64(sr_ctx *ctx, const sr_ct_job &job);
+
+// sr_ct32.hip: float32 real-input transforms in LDS (k_ct_rfft32: 1024 < F + L <= 8192)
+int sr_launch_ct_rfft32(sr_ctx *ctx, const sr_ct_job &job);
 
 // the device tables of the float32 transforms (Ct32Tab[4], sr_ct32_fft.h), created on first use; NULL (error set) on failure
 const void *sr_ct32_tables(sr_ctx *ctx);
 
-// sr_ct_long.hip: the blocked form of kernel 1 for chunks that do not fit one in-LDS transform (F + L > 8192), up to
-// SR_CT_LONG_MAX_FRAMES frames per chunk; same raw lag sums
+// sr_ct_long.hip: blocked float32 transforms for chunks that do not fit one in-LDS transform (F + L > 8192), up to
+// SR_CT_LONG_MAX_FRAMES frames per chunk
 #define SR_CT_LONG_MAX_FRAMES 262144
-#define SR_CT_LONG_MIN_FRAMES 16384     /* default of "ct_long_min_frames": above the direct kernel's LDS limit, i.e. the direct kernel keeps
-                                           every chunk it can stage (no timing of the two against each other exists yet) */
+#define SR_CT_LONG_MIN_FRAMES 16384     /* default of "ct_long_min_frames": above what the direct kernel can stage (about 13400 frames), i.e. the
+                                           direct kernel keeps every chunk it can stage (no timing of the two against each other exists yet) */
 #define SR_CT_LONG_WS_MB 256
-int sr_launch_ct_long(sr_ctx *ctx, const float *soa, int64_t Npad, const int64_t *cs_dev, double *psum, int R, int F, int L, int Lp,
-                      int64_t series);
+int sr_launch_ct_long(sr_ctx *ctx, const sr_ct_job &job);
 
 #ifdef __HIPCC__
 // ---- the one way to launch a kernel that takes dynamic LDS ------------------------------------------

@@ -39,6 +39,49 @@ def test_library_exports_every_declared_symbol():
     assert bound.sr_ct_psum_stride(4096) >= 2049                   # pure host helper, safe without a GPU
 
 
+def test_ct_formulation_dispatch_table():
+    """Which formulation of kernel 1 runs for (ct_fft, ct_long_min_frames, mode, F): sr_ct_formulation() is the dispatch that
+    sr_ct_palmer_sums_f32_dev switches on, a host function that needs no GPU.  Every formulation meets the accuracy bars of the GPU
+    tests, so only this table notices a chunk length that goes to another kernel.  The expected values are written out from the
+    rule (include/spinrelax_hip.h; L = F // 2, need = F + L), not recomputed: both sides of need = 1024 (F = 683 | 684), 2048
+    (1365 | 1366), 4096 (2731 | 2732; 2730 as well), 6144 (4096 | 4097) and 8192 (5461 | 5462), at the 160 KiB of LDS of gfx950."""
+    from spinrelax_amd import _lib
+    if not os.path.isfile(_lib.LIB_PATH):
+        from spinrelax_amd import build
+        build.build(verbose=False)
+    form = _lib.load().sr_ct_formulation
+    REFUSED, DIRECT, FFT64, RFFT64, RFFT32, BLOCKED = range(6)          # SR_CT_* of the header
+    LDS, MIN = 160 * 1024, 16384                                       # MIN: the default of "ct_long_min_frames"
+    #            ct_fft =  0       1      2       3       4
+    table = {682:  (DIRECT, DIRECT, DIRECT, DIRECT, DIRECT),            # need 1023
+             683:  (DIRECT, DIRECT, DIRECT, DIRECT, DIRECT),            # need 1024
+             684:  (DIRECT, FFT64, FFT64, FFT64, RFFT32),               # need 1026
+             1365: (DIRECT, FFT64, FFT64, FFT64, RFFT32),               # need 2047
+             1366: (DIRECT, FFT64, FFT64, FFT64, RFFT32),               # need 2049
+             2730: (DIRECT, FFT64, FFT64, FFT64, RFFT32),               # need 4095
+             2731: (DIRECT, FFT64, FFT64, FFT64, RFFT32),               # need 4096
+             2732: (DIRECT, FFT64, RFFT64, RFFT32, RFFT32),             # need 4098
+             4096: (DIRECT, FFT64, RFFT64, RFFT32, RFFT32),             # need 6144
+             4097: (DIRECT, FFT64, RFFT64, RFFT32, RFFT32),             # need 6145
+             5461: (DIRECT, FFT64, RFFT64, RFFT32, RFFT32),             # need 8191
+             5462: (DIRECT, DIRECT, DIRECT, DIRECT, DIRECT)}            # need 8193: fits the direct kernel, shorter than MIN
+    for F, row in table.items():
+        for ct_fft, want in enumerate(row):
+            assert form(ct_fft, MIN, 0, F, LDS) == want, (F, ct_fft)
+            assert form(ct_fft, MIN, 1, F, LDS) == DIRECT, (F, ct_fft)  # mode 1: the direct kernel whatever the option
+    # beyond one transform: 13000 frames fit the direct kernel's LDS (158592 B), 20000 do not (242304 B)
+    assert form(3, MIN, 0, 13000, LDS) == DIRECT
+    assert form(3, 5462, 0, 13000, LDS) == BLOCKED
+    assert form(3, MIN, 0, 20000, LDS) == BLOCKED
+    assert form(2, MIN, 0, 20000, LDS) == BLOCKED
+    assert form(0, MIN, 0, 20000, LDS) == REFUSED
+    assert form(1, MIN, 0, 20000, LDS) == REFUSED
+    assert form(3, MIN, 1, 20000, LDS) == REFUSED
+    assert form(3, 5462, 1, 13000, LDS) == DIRECT
+    assert form(3, MIN, 0, 262144, LDS) == BLOCKED and form(3, MIN, 0, 262145, LDS) == REFUSED       # sr_ct_max_frames_per_chunk
+    assert form(5, MIN, 0, 4096, LDS) == REFUSED and form(3, MIN, 2, 4096, LDS) == REFUSED and form(3, MIN, 0, 1, LDS) == REFUSED
+
+
 def test_build_id_and_flag_stamps(tmp_path, monkeypatch):
     """The library reports the id of the sources / flags it was built from (bench.py ties the committed PMC figures to it), and an
     object whose flags changed is rebuilt: a flag change re-labels sr_core.o, so it must not leave the other objects behind."""

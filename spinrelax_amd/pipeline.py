@@ -28,12 +28,25 @@ DevicePipeline    per batch: C(t) on two alternating main streams, the histogram
 GroupedPipeline   throughput over many batches: the C(t)-side kernels of a GROUP of batches back to back, then one merged
                   fit launch over the group's residues (below).  What bench.py times by default.
 
+How the module is put together.  _Pipeline holds what both schedules need: constants, streams and their CU masks, time
+axis, tau guesses, bin vectors, relaxation constants, quaternions, the plane ring and the stage_* methods; each schedule adds
+the buffers it runs on (DevicePipeline `depth` _Slots, GroupedPipeline two _Groups and a pool of raw-sum buffers) and frees
+them in its _free().  Three things exist once and are shared:
+
+  result_layout / _Results   the 12 result arrays of the search and the relaxation kernel: ONE layout table, the float64 and
+                             the int32 device buffer, their pinned mirrors, views and host copies for n residues (a _Slot
+                             uses n = V, a _Group n = g V)
+  _PlaneRing                 the plane buffers and the events that order the pack (auxiliary stream) against the C(t) and
+                             histogram launches that read a buffer
+  _Pipeline._launch_relax    the relaxation launch (isotropic or symmetric-top model)
+
 The runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): streams that share a queue serialise
 (two fit streams on one queue run their stragglers one after the other), so set GPU_MAX_HW_QUEUES >= streams in use before
 the first HIP call (bench.py does).  CU-masked streams (`reserve_cus`, `aux_cus`: parts of the chip set aside for the fits or
 for the bandwidth kernels) are kept as options of DevicePipeline; neither pays on MI355X.
 """
 import ctypes
+import os
 import weakref
 
 import numpy as np
@@ -43,8 +56,55 @@ from . import ct as hostct
 from . import fitting_Ct_functions as fitCt
 from . import _hostmath as hm
 from . import spectral_densities as sd
+from .hip import SpinRelaxHipError
 
 
+# ======================================================================================================================
+# Pure host functions (tests/test_pipeline_hostlogic.py)
+# ======================================================================================================================
+def result_layout(nO, Pmax, E):
+    """THE layout table of the result arrays: (float64 arrays, int32 arrays), each entry (name, axes before the residue
+    axis, axes behind it).  Every float64 / int32 result of the search and the relaxation kernel lives in ONE buffer each, in
+    this order, so that a batch (or a group) needs two copies to the host."""
+    Kmax = Pmax // 2
+    return ((('popt', (nO,), (Pmax,)), ('dP', (nO,), (Pmax,)), ('chisq', (nO,), ()), ('S2', (), ()), ('chi', (), ()),
+             ('C', (), (Kmax,)), ('tau', (), (Kmax,)), ('relax', (E,), (4, 2))),
+            (('status', (nO,), ()), ('nfev', (nO,), ()), ('best', (), ()), ('K', (), ())))
+
+
+def layout_cut(layout, n):
+    """one buffer of result_layout laid out for n residues: [(name, offset, shape, residue axis)] and the element count"""
+    out, o = [], 0
+    for name, lead, trail in layout:
+        sh = lead + (n,) + trail
+        out.append((name, o, sh, len(lead)))
+        o += int(np.prod(sh))
+    return out, o
+
+
+def dispatch_order(g, V, cost=None):
+    """order in which the workgroups of a merged launch take the g V residues (int32): a fixed pseudo-random permutation,
+    stably re-sorted longest first by `cost` (V predicted costs, the same for every batch) when there is one"""
+    n = g * V
+    p = np.random.RandomState(20240 + g).permutation(n).astype(np.int32) if g > 1 else np.arange(n, dtype=np.int32)
+    if cost is not None:
+        p = p[np.argsort(-np.asarray(cost)[p % V], kind='stable')]
+    return np.ascontiguousarray(p, dtype=np.int32)
+
+
+def group_sizes(group, nb, override=None):
+    """how a run of nb batches is cut into groups of at most `group`; `override` (development): the first sizes, explicitly"""
+    out, rem, want = [], nb, list(override or ())
+    while rem > 0:
+        g = min(int(want.pop(0)) if want else group, rem, group)
+        out.append(g)
+        rem -= g
+    return out
+
+
+# ======================================================================================================================
+# Buffers
+# ======================================================================================================================
 def _pinned_array(ctx, n, dtype):
     """numpy array over page-locked memory owned by the library (sr_host_alloc); returns (array, address)."""
     dtype = np.dtype(dtype)
@@ -54,13 +114,112 @@ def _pinned_array(ctx, n, dtype):
     return np.frombuffer(buf, dtype=dtype, count=n), addr
 
 
-class _Slot:
-    """Device buffers, pinned host mirrors and stream of one in-flight batch."""
+def _event(stream):
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    return ev
 
-    def __init__(self, ctx, dev, V, L, R, nbins, nO, Pmax, E, stream, need_fitwork, psum_len=0):
+
+def _stamp(events, i, stream):
+    """record the caller's timing event i, if there are any"""
+    if events is not None:
+        events[i].record(stream)
+
+
+class _Lease:
+    """one hand-out of a recycled host buffer: exposes the memory through the array interface, so that numpy arrays made
+    from it (np.asarray) and all their views hold a reference to THIS object; when the last of them is gone the lease is
+    collected and _Results._pooled_copy may reuse the buffer"""
+    __slots__ = ('__array_interface__', '_keep', '__weakref__')
+
+    def __init__(self, arr):
+        self._keep = arr
+        self.__array_interface__ = dict(arr.__array_interface__)
+
+
+class _Results:
+    """The result arrays of up to nmax residues: the float64 and the int32 device buffer, their pinned mirrors and the one
+    layout table.  The mirrors are owned by the library and filled with sr_memcpy_d2h_async on the launch's stream: torch
+    keeps no per-stream record of these copies, so the streams can be destroyed when the pipeline closes."""
+
+    def __init__(self, ctx, dev, nmax, nO, Pmax, E):
+        self._ctx = ctx
+        self.layout = result_layout(nO, Pmax, E)
+        nd, ni = self.counts(nmax)
+        self.dres = torch.empty((nd,), device=dev, dtype=torch.float64)
+        self.ires = torch.empty((ni,), device=dev, dtype=torch.int32)
+        self.h_dres, self._h_dres_addr = _pinned_array(ctx, nd, np.float64)
+        self.h_ires, self._h_ires_addr = _pinned_array(ctx, ni, np.int32)
+        self._views = {}
+        self._pools = ([], [])
+
+    def counts(self, n):
+        """elements of the two buffers that n residues fill"""
+        return tuple(layout_cut(l, n)[1] for l in self.layout)
+
+    def _cut(self, bufs, n):
+        return {name: (buf[o:o + int(np.prod(sh))].reshape(sh), axis)
+                for buf, l in zip(bufs, self.layout) for name, o, sh, axis in layout_cut(l, n)[0]}
+
+    def views(self, n):
+        """device views of the result buffers for a launch over n residues (cached: no allocation per launch)"""
+        if n not in self._views:
+            self._views[n] = {name: v for name, (v, _) in self._cut((self.dres, self.ires), n).items()}
+        return self._views[n]
+
+    def download(self, n):
+        """the two asynchronous copies into the pinned mirrors, on the context's current stream"""
+        nd, ni = self.counts(n)
+        self._ctx.memcpy_d2h_async(self._h_dres_addr, self.dres.data_ptr(), nd * 8)
+        self._ctx.memcpy_d2h_async(self._h_ires_addr, self.ires.data_ptr(), ni * 4)
+
+    def _pooled_copy(self, pool, mirror, n):
+        """the first n elements of a pinned mirror in pageable memory the caller may keep.  The buffers are recycled, with
+        explicit ownership: every hand-out goes through a fresh _Lease object that the returned array (and every view cut
+        from it) keeps alive as its base; a pool buffer is taken again only when the lease of its last hand-out is gone
+        (a dead weak reference) -- no interpreter-specific reference counts.  Results stay valid for as long as anybody holds
+        them, and a collect does not start with a 10 MB allocation and its page faults (1.5 ms when the allocator has just
+        seen another size).  Where leases die late (no reference counting) the pool simply is not reused."""
+        entry = None
+        for e in pool:
+            if e[1] is None or e[1]() is None:
+                entry = e
+                break
+        if entry is None:
+            entry = [np.empty(mirror.size, dtype=mirror.dtype), None]
+            if len(pool) < 4:
+                pool.append(entry)
+        buf = entry[0]
+        np.copyto(buf[:n], mirror[:n])     # 10 MB for a 20-batch group: 0.46 ms (a threaded copy was measured: no faster)
+        lease = _Lease(buf[:n])
+        entry[1] = weakref.ref(lease)
+        return np.asarray(lease)
+
+    def host(self, n, pooled=False):
+        """{name: (array, residue axis)} for n residues, COPIES of the pinned mirrors (valid after the launch's `done`): the
+        next launch overwrites the mirrors, the arrays handed to the caller stay what they were.  pooled: recycled buffers"""
+        mirrors = (self.h_dres, self.h_ires)
+        if pooled:
+            bufs = [self._pooled_copy(p, m, c) for p, m, c in zip(self._pools, mirrors, self.counts(n))]
+        else:
+            bufs = [m[:c].copy() for m, c in zip(mirrors, self.counts(n))]
+        return self._cut(bufs, n)
+
+    def release(self):
+        for name in ('_h_dres_addr', '_h_ires_addr'):
+            addr = getattr(self, name)
+            if addr:
+                self._ctx.host_free(addr)
+                setattr(self, name, None)
+        self.h_dres = self.h_ires = None
+
+
+class _Slot:
+    """Device buffers, results and stream of one in-flight batch."""
+
+    def __init__(self, ctx, dev, V, L, R, nbins, nO, Pmax, E, stream, psum_len):
         f64 = dict(device=dev, dtype=torch.float64)
-        i32 = dict(device=dev, dtype=torch.int32)
-        Kmax = Pmax // 2
+        self.V = V
         self.Ct = torch.empty((L, V), **f64)
         self.dCt = torch.empty((L, V), **f64)
         self.CtT = torch.empty((V, L), **f64)
@@ -68,27 +227,11 @@ class _Slot:
         self.hist = torch.empty((V, nbins), **f64)
         self.vecsum = torch.empty((V, 3), **f64)
         self.outer = torch.empty((R, V, 6), **f64)
-        self.psum = torch.empty((psum_len,), **f64) if psum_len else None     # raw C(t) sums of this batch
-        # every float64 / int32 result of the search in ONE buffer each, so that a batch needs two copies to the host
-        self._dlayout = (('popt', (nO, V, Pmax)), ('dP', (nO, V, Pmax)), ('chisq', (nO, V)), ('S2', (V,)), ('chi', (V,)),
-                         ('C', (V, Kmax)), ('tau', (V, Kmax)), ('relax', (E, V, 4, 2)))
-        self._ilayout = (('status', (nO, V)), ('nfev', (nO, V)), ('best', (V,)), ('K', (V,)))
-        nd = sum(int(np.prod(sh)) for _, sh in self._dlayout)
-        ni = sum(int(np.prod(sh)) for _, sh in self._ilayout)
-        self.dres = torch.empty((nd,), **f64)
-        self.ires = torch.empty((ni,), **i32)
-        for buf, layout in ((self.dres, self._dlayout), (self.ires, self._ilayout)):
-            o = 0
-            for name, sh in layout:
-                n = int(np.prod(sh))
-                setattr(self, name, buf[o:o + n].view(sh))
-                o += n
-        self.fitwork = torch.empty((V, L), **f64) if need_fitwork else None
-        # pinned mirrors owned by the library, filled with sr_memcpy_d2h_async on the batch's stream: torch keeps no
-        # per-stream record of these copies, so the streams can be destroyed when the pipeline closes
-        self._ctx = ctx
-        self.h_dres, self._h_dres_addr = _pinned_array(ctx, nd, np.float64)
-        self.h_ires, self._h_ires_addr = _pinned_array(ctx, ni, np.int32)
+        self.psum = torch.empty((psum_len,), **f64)     # raw C(t) sums of this batch
+        self.res = _Results(ctx, dev, V, nO, Pmax, E)
+        for name, view in self.res.views(V).items():    # slot.popt, slot.relax, slot.S2, ...
+            setattr(self, name, view)
+        self.fitwork = torch.empty((V, L), **f64)       # weight scratch for residues that are not LDS-resident (concurrent launches)
         self.stream = stream
         self.front_done = None
         self.hist_done = None
@@ -100,31 +243,162 @@ class _Slot:
         self.result = None
 
     def host_results(self):
-        """COPIES of the pinned mirrors (valid after `done`): the next batch on this slot overwrites the mirrors, the
-        arrays handed to the caller stay what they were."""
-        out = {}
-        for buf, layout in ((self.h_dres.copy(), self._dlayout), (self.h_ires.copy(), self._ilayout)):
-            o = 0
-            for name, sh in layout:
-                n = int(np.prod(sh))
-                out[name] = buf[o:o + n].reshape(sh)
-                o += n
-        return out
+        return {name: arr for name, (arr, _) in self.res.host(self.V).items()}
 
     def release(self):
-        for name in ('_h_dres_addr', '_h_ires_addr'):
-            addr = getattr(self, name, None)
-            if addr:
-                self._ctx.host_free(addr)
-                setattr(self, name, None)
-        self.h_dres = self.h_ires = None
+        self.res.release()
 
 
-class DevicePipeline:
+class _BatchView:
+    """What the stage functions need of one batch inside a group (views into the group's contiguous buffers)."""
+    __slots__ = ('Ct', 'dCt', 'CtT', 'dCtT', 'hist', 'vecsum', 'outer', 'psum', 'result', 'relax_out', 'index')
+
+
+class _Group:
+    """Device buffers, results and stream of a GROUP of up to G batches.  Inputs of the merged launches are
+    contiguous over the group's residues (batch j = rows j V .. (j + 1) V), results are laid out for the g batches a
+    launch really holds (the residue axis has length g V)."""
+
+    def __init__(self, ctx, dev, G, V, L, R, nbins, nO, Pmax, E, stream):
+        f64 = dict(device=dev, dtype=torch.float64)
+        self.G, self.V, self.L = G, V, L
+        GV = G * V
+        self._Ct = torch.empty((G, L, V), **f64)
+        self._dCt = torch.empty((G, L, V), **f64)
+        self.CtT = torch.empty((GV, L), **f64)
+        self.dCtT = torch.empty((GV, L), **f64)
+        self._hist = torch.empty((GV, nbins), **f64)
+        self.vecsum = torch.empty((GV, 3), **f64)
+        self.outer = torch.empty((G, R, V, 6), **f64)
+        self.fitwork = torch.empty((GV, L), **f64)
+        self.res = _Results(ctx, dev, GV, nO, Pmax, E)
+        # dispatch order of the merged launch: pinned host copy + device copy (refreshed per launch, stream-ordered before it)
+        self._ctx = ctx
+        self.h_order, self._h_order_addr = _pinned_array(ctx, GV, np.int32)
+        self.order_dev = torch.empty((GV,), device=dev, dtype=torch.int32)
+        self.stream = stream
+        self.g = 0                 # batches of the group in flight / last collected
+        self.first = 0             # index (in the run) of the group's first batch
+        self.done = None
+        self.guard = None
+        self.busy = False
+        self.batches = []
+        self.signal, self.epoch = None, 0      # late histograms: what the merged launch's last workgroup releases
+
+    # what a device-side consumer of a finished group reads (bench.py's all-gather): the g batches in flight
+    @property
+    def Ct(self):
+        return self._Ct[:self.g]
+
+    @property
+    def dCt(self):
+        return self._dCt[:self.g]
+
+    @property
+    def hist(self):
+        return self._hist[:self.g * self.V]
+
+    @property
+    def relax(self):
+        return self.res.views(self.g * self.V)['relax']
+
+    def batch(self, j):
+        V = self.V
+        b = _BatchView()
+        b.Ct, b.dCt = self._Ct[j], self._dCt[j]
+        b.CtT, b.dCtT = self.CtT[j * V:(j + 1) * V], self.dCtT[j * V:(j + 1) * V]
+        b.hist, b.vecsum, b.outer = self._hist[j * V:(j + 1) * V], self.vecsum[j * V:(j + 1) * V], self.outer[j]
+        b.psum = None
+        b.result = b.relax_out = None
+        b.index = j
+        return b
+
+    def host_results(self):
+        """per batch: COPIES of the pinned mirrors, split along the residue axis"""
+        g, V = self.g, self.V
+        whole = self.res.host(g * V, pooled=True)
+        return [{name: arr[j * V:(j + 1) * V] if axis == 0 else arr[:, j * V:(j + 1) * V] for name, (arr, axis) in whole.items()}
+                for j in range(g)]
+
+    def release(self):
+        self.res.release()
+        if self._h_order_addr:
+            self._ctx.host_free(self._h_order_addr)
+            self._h_order_addr = None
+        self.h_order = None
+
+
+class _PlaneRing:
+    """The plane buffers and who may touch them when.  Batch k lives in buffer k % NB: the pack writes it on the auxiliary
+    stream, the C(t) kernel and the histogram read it on theirs.  `packed`, `ct_done`, `hist_done` hold per buffer the
+    event of the last such launch; `ahead` says that the coming batch has been packed already."""
+
+    def __init__(self, pipe, bufs):
+        self.pipe, self.bufs, self.NB = pipe, bufs, len(bufs)
+        self.ahead = False
+        self.clear()
+
+    def clear(self):
+        self.packed, self.ct_done, self.hist_done = ([None] * self.NB for _ in range(3))
+
+    def buf(self, k):
+        return self.bufs[k % self.NB]
+
+    def _pack(self, vecs, k):
+        """on the auxiliary stream: wait for the readers of batch k - NB, pack batch k, record that it is there.  `vecs`: a
+        device tensor (frames, Vtot, 3), or a FEED -- an object with acquire(k, stream) -> object with data_ptr() / shape of
+        that batch's device array (the feed makes `stream` wait until the frames are there) and release(k, stream) (called
+        once the pack has been queued: the feed may refill the buffer when `stream` has passed that point).  bench.py's
+        PinnedFeed streams every batch from host memory."""
+        pipe, aux, b = self.pipe, self.pipe.aux, k % self.NB
+        for ev in (self.ct_done[b], self.hist_done[b]):
+            if ev is not None:
+                aux.wait_event(ev)
+        if hasattr(vecs, 'acquire'):
+            src = vecs.acquire(k, aux)
+            pipe.ctx.set_stream(aux.cuda_stream)          # the feed drives the context from its own stream
+            pipe.stage_pack(src, self.bufs[b])
+            vecs.release(k, aux)
+        else:
+            pipe.stage_pack(vecs, self.bufs[b])
+        self.packed[b] = _event(aux)
+
+    def pack_now(self, vecs, k):
+        """batch k, unless it was packed ahead (the first batch of a run was not)"""
+        if not self.ahead:
+            aux = self.pipe.aux
+            self.pipe.ctx.set_stream(aux.cuda_stream)
+            with torch.cuda.stream(aux):
+                self._pack(vecs, k)
+        self.ahead = False
+
+    def pack_ahead(self, vecs, k):
+        """batch k + 1 beside the C(t) launch of batch k; the caller has the context on the auxiliary stream"""
+        self._pack(vecs, k + 1)
+        self.ahead = True
+
+    def wait_packed(self, stream, k):
+        stream.wait_event(self.packed[k % self.NB])
+
+    def ct_done_with(self, k, stream):
+        """the C(t) kernel just queued on `stream` reads batch k's buffer; returns the event that marks its end"""
+        self.ct_done[k % self.NB] = ev = _event(stream)
+        return ev
+
+    def hist_done_with(self, k, stream):
+        self.hist_done[k % self.NB] = ev = _event(stream)
+        return ev
+
+
+# ======================================================================================================================
+# What both schedules need
+# ======================================================================================================================
+class _Pipeline:
     def __init__(self, ctx, device, frames, V, R, F, dt, q_rot=None, Diso=None, aniso=None, field_MHz=(600.133,),
                  zeta=0.890023, histBinX=72, listDoG=(2, 3, 5, 7, 9), csa=None, depth=1, stream=None, reserve_cus=0,
                  fits_on_reserved_only=False, chiSqThreshold=0.5, q_orient=None, hist_on_aux=True, v0=0, aux_cus=0, fit_priority=0, plane_buffers=3,
-                 pack_cus=0):
+                 pack_cus=0, batch_streams=0):
+        self._closed = False
         self.ctx = ctx
         self.dev = device
         self.frames, self.V, self.R, self.F, self.dt = frames, V, R, F, dt
@@ -144,7 +418,7 @@ class DevicePipeline:
         self.main = stream if stream is not None else torch.cuda.current_stream(device)
         self._owned_streams = []
         self._main_bits = None
-        resv_words = None
+        resv_words = None           # CU mask of the fit streams (None: the whole chip)
         self.reserve_cus = 0
         self.fit_priority = int(fit_priority)
         info = ctx.device_info()
@@ -175,21 +449,15 @@ class DevicePipeline:
             self._main_bits = (range(ncu - r), ncu)
             resv_words = self._mask_words(range(ncu - r), ncu)          # fits: same complement as the main stream
             aux_words = self._mask_words(range(ncu - r, ncu), ncu)
-        Pmax = max(self.listDoG)
-        E = len(self.fields)
-        need_fitwork = True      # per-batch weight scratch for residues that are not LDS-resident (concurrent launches)
-        self.slots = []
-        for i in range(self.depth):
-            st = self.main if self.depth == 1 else self._fit_stream(resv_words)
-            self.slots.append(_Slot(ctx, device, V, self.L, R, self.nbins, len(self.listDoG), Pmax, E, st, need_fitwork,
-                                    psum_len=V * R * ctx.psum_stride(F)))
+        # `batch_streams`: one stream per batch in flight for the latency half (DevicePipeline)
+        self.batch_streams = [self.main if self.depth == 1 else self._fit_stream(resv_words) for _ in range(batch_streams)]
         # planes: two buffers and an auxiliary stream when batches overlap -- the pack of batch k+1 and the histogram of
         # batch k (bandwidth / FP64 work) run beside the C(t) launch of batch k (FP32 issue bound) instead of in line with it
         self.soa = torch.empty((V, 3, self.Npad), device=device, dtype=torch.float32)
         # (three plane buffers: the pack of batch k+1 only needs the C(t) launch of batch k-2 to be done, so it is off the
         # critical path of two C(t) launches that overlap each other)
         self.NB = max(2, int(plane_buffers)) if self.depth > 1 else 1
-        self.soa_bufs = [self.soa] + [torch.empty_like(self.soa) for _ in range(self.NB - 1)]
+        self.ring = _PlaneRing(self, [self.soa] + [torch.empty_like(self.soa) for _ in range(self.NB - 1)])
         # `pack_cus`: the auxiliary stream (the pack kernel, per-batch histograms) confined to this many CUs while the compute
         # streams keep the whole chip.  The pack is HBM-bound and hardly issues (83 % of its waves' lifetime parked); spread
         # over all 256 CUs its waves sit beside every C(t) workgroup pair (16 + 2 x 248 VGPRs fill a SIMD exactly) and its
@@ -207,7 +475,6 @@ class DevicePipeline:
                 self.pack_cus = n
                 aux_words = self._mask_words(range(0, n), ncu)
         self.aux = (self._borrow(aux_words) if aux_words is not None else torch.cuda.Stream(device=device)) if self.depth > 1 else None
-        self._packed_ev = [None] * self.NB
         self.hist_on_aux = hist_on_aux
         # Consecutive C(t) launches alternate between two streams (one per plane buffer): the next grid's workgroups fill the
         # slots the previous grid's last, partially filled round leaves (a twelfth of a launch) and its launch latency
@@ -218,10 +485,6 @@ class DevicePipeline:
                 self.main_alt = self._masked_stream(*self._main_bits)
             else:
                 self.main_alt = torch.cuda.Stream(device=device, priority=getattr(self.main, 'priority', 0))
-        # the mean / std over the chunks and the transposes only feed this batch's fits: they run on the batch's own
-        # stream, so that the main stream issues the C(t) kernels back to back (4.50 -> 4.41 ms per step)
-        self.tail_on_slot_stream = True
-        self._ct_done_ev = [None] * self.NB
         t = hostct.calculate_dt(dt, F * dt)
         self.t_host = np.ascontiguousarray(np.broadcast_to(t, (V, self.L)))
         self.t_dev = torch.from_numpy(self.t_host).to(device)
@@ -238,7 +501,6 @@ class DevicePipeline:
             qc[:, 1:] *= -1.0
             self.quat_dev = torch.from_numpy(np.ascontiguousarray(hostct.vecnorm_NDarray(qc))).to(device)
         self.csa = csa
-        self._packed = False
         self.nfev_total = 0
         self.nfev_last = {}
         self.fit_best = None
@@ -256,7 +518,6 @@ class DevicePipeline:
             gr.append(RObj.gH.gamma / RObj.gX.gamma)
         self._relax_consts = (np.array(oms), np.array(fdd), np.array(fcsa), np.array(tf), np.array(gr))
         self._relax_dev = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device) for a in self._relax_consts]
-        torch.cuda.synchronize(device)
 
     # ---- streams ----
     @staticmethod
@@ -283,23 +544,20 @@ class DevicePipeline:
         return self._borrow(resv_words)
 
     def close(self):
-        """Deterministic teardown: wait for the device, drop every event / stream wrapper, free the pinned mirrors and
-        destroy the CU-masked streams.  The pipeline must not be used afterwards."""
-        if getattr(self, '_closed', False):
+        """Deterministic teardown: wait for the device, drop every event / stream wrapper, free what the schedule allocated
+        (_free: pinned mirrors, signals) and destroy the CU-masked streams.  The pipeline must not be used afterwards."""
+        if self._closed:
             return
         self._closed = True
         torch.cuda.synchronize(self.dev)
         self.ctx.device_sync()
         self.ctx.set_stream(0)
-        for s in self.slots:
-            s.front_done = s.hist_done = s.done = s.psum_free = s.guard = None
-            s.stream = None
-            s.release()
-        self._packed_ev = [None] * self.NB
-        self._ct_done_ev = [None] * self.NB
+        self._free()
+        self.ring.clear()
         self.main = None
         self.main_alt = None
         self.aux = None
+        self.batch_streams = []
         owned, self._owned_streams = self._owned_streams, []
         for h in owned:
             self.ctx.stream_destroy(h)
@@ -354,207 +612,37 @@ class DevicePipeline:
                                   self.tau_guess.data_ptr(), 1, self.tau_max, self.chi_thr,
                                   s.popt.data_ptr(), s.dP.data_ptr(), s.chisq.data_ptr(), s.status.data_ptr(), s.nfev.data_ptr(),
                                   s.best.data_ptr(), s.S2.data_ptr(), s.C.data_ptr(), s.tau.data_ptr(), s.chi.data_ptr(),
-                                  s.K.data_ptr(), work_ptr=None if s.fitwork is None else s.fitwork.data_ptr())
+                                  s.K.data_ptr(), work_ptr=s.fitwork.data_ptr())
+
+    def _launch_relax(self, n, S2_ptr, C_ptr, tau_ptr, K_ptr, hist_ptr, fcsa, out_ptr):
+        """R1/R2/NOE/rho of n residues from their selected models: isotropic tumbling, or the symmetric top with the
+        histogram over the bin vectors as weights"""
+        om, fdd, _, tf, gr = self._relax_dev
+        if self.aniso is None or self.aniso == 1.0:
+            model, D, nbins, binvecs_ptr, hist_ptr = 1, [self.Diso], 0, None, None
+        else:
+            model, D, nbins, binvecs_ptr = 2, list(hm.symmtop_from_iso(self.Diso, self.aniso)), self.nbins, self.binvecs_dev.data_ptr()
+        self.ctx.relax_dev(model, D, len(self.fields), om.data_ptr(), fdd.data_ptr(), fcsa.data_ptr(), tf.data_ptr(), gr.data_ptr(),
+                           n, max(self.listDoG) // 2, self.zeta, S2_ptr, C_ptr, tau_ptr, K_ptr,
+                           nbins, binvecs_ptr, hist_ptr, 0, out_ptr)
 
     def stage_relax(self, s=None):
         """R1/R2/NOE/rho from the selected models and the histogram, all operands resident in HBM."""
         s = s or self.slots[0]
-        om, fdd, fcsa, tf, gr = self._relax_dev
-        Kmax = max(self.listDoG) // 2
-        E = len(self.fields)
-        if self.aniso is None or self.aniso == 1.0:
-            self.ctx.relax_dev(1, [self.Diso], E, om.data_ptr(), fdd.data_ptr(), fcsa.data_ptr(), tf.data_ptr(), gr.data_ptr(),
-                               self.V, Kmax, self.zeta, s.S2.data_ptr(), s.C.data_ptr(), s.tau.data_ptr(), s.K.data_ptr(),
-                               0, None, None, 0, s.relax.data_ptr())
-        else:
-            Dpar, Dperp = hm.symmtop_from_iso(self.Diso, self.aniso)
-            self.ctx.relax_dev(2, [Dpar, Dperp], E, om.data_ptr(), fdd.data_ptr(), fcsa.data_ptr(), tf.data_ptr(), gr.data_ptr(),
-                               self.V, Kmax, self.zeta, s.S2.data_ptr(), s.C.data_ptr(), s.tau.data_ptr(), s.K.data_ptr(),
-                               self.nbins, self.binvecs_dev.data_ptr(), s.hist.data_ptr(), 0, s.relax.data_ptr())
+        self._launch_relax(self.V, s.S2.data_ptr(), s.C.data_ptr(), s.tau.data_ptr(), s.K.data_ptr(), s.hist.data_ptr(),
+                           self._relax_dev[2], s.relax.data_ptr())
 
     def stage_download(self, s=None):
         s = s or self.slots[0]
-        self.ctx.memcpy_d2h_async(s._h_dres_addr, s.dres.data_ptr(), s.dres.numel() * 8)
-        self.ctx.memcpy_d2h_async(s._h_ires_addr, s.ires.data_ptr(), s.ires.numel() * 4)
+        s.res.download(self.V)
 
-    # ---- batch-level API ----
-    def front(self, vecs, k, events=None, pack_next=None):
-        """Throughput half of batch k.  Serial form (depth 1): pack, C(t), histogram, transposes on the main stream.
-        Overlapped form: C(t) + transposes on the main stream; the histogram of batch k and the pack of batch k+1
-        (`pack_next`: its vectors) on the auxiliary stream, beside the C(t) launch, on alternating plane buffers.
-        events: [before the C(t) kernel, after it (before its finalize), before histogram, after histogram, (4, 5: see
-        back())]; the first two on the main stream."""
-        s = self.slots[k % self.depth]
-        if self.aux is None:
-            self.ctx.set_stream(self.main.cuda_stream)
-            with torch.cuda.stream(self.main):
-                self.stage_pack(vecs)
-                if events is not None:
-                    events[0].record(self.main)
-                self.stage_ct(s, mid_event=None if events is None else events[1])
-                if events is not None:
-                    events[2].record(self.main)
-                self.stage_hist(s)
-                if events is not None:
-                    events[3].record(self.main)
-                s.front_done = torch.cuda.Event()
-                s.front_done.record(self.main)
-                s.hist_done = s.front_done
-            return s
-        b = k % self.NB
-        buf = self.soa_bufs[b]
-        if not self._packed:
-            # first batch of a run: nothing was packed ahead
-            self.ctx.set_stream(self.aux.cuda_stream)
-            with torch.cuda.stream(self.aux):
-                if self._ct_done_ev[b] is not None:
-                    self.aux.wait_event(self._ct_done_ev[b])
-                self.stage_pack(vecs, buf)
-                self._packed_ev[b] = torch.cuda.Event()
-                self._packed_ev[b].record(self.aux)
-        self._packed = False
-        prev_done = s.done if s.busy else None       # the batch that used this slot `depth` batches ago, if still in flight
-        main = self.main_alt if (k % 2 == 1 and self.main_alt is not None and self.tail_on_slot_stream) else self.main
-        self.ctx.set_stream(main.cuda_stream)
-        with torch.cuda.stream(main):
-            main.wait_event(self._packed_ev[b])
-            if s.busy and s.psum_free is not None:
-                main.wait_event(s.psum_free)         # its raw sums are the only thing of that batch this kernel overwrites
-            if events is not None:
-                events[0].record(main)
-            self.stage_ct(s, buf, mid_event=None if events is None else events[1], finalize=not self.tail_on_slot_stream)
-            if not self.hist_on_aux:
-                if prev_done is not None:
-                    main.wait_event(prev_done)
-                if s.guard is not None:
-                    main.wait_event(s.guard)
-                if events is not None:
-                    events[2].record(main)
-                self.stage_hist(s, buf)
-                if events is not None:
-                    events[3].record(main)
-            self._ct_done_ev[b] = torch.cuda.Event()            # "the C(t) kernel is done with this plane buffer"
-            self._ct_done_ev[b].record(main)
-            s.front_done = torch.cuda.Event()
-            s.front_done.record(main)
-            s.hist_done = s.front_done
-        self.ctx.set_stream(self.aux.cuda_stream)
-        with torch.cuda.stream(self.aux):
-            # the pack of batch k+1 first: the next C(t) launch waits for nothing else, while the histogram below may have
-            # to wait for the batch that used this slot before (its relaxation kernel reads the slot's histogram)
-            if pack_next is not None:
-                nb = (k + 1) % self.NB
-                if self._ct_done_ev[nb] is not None:
-                    self.aux.wait_event(self._ct_done_ev[nb])       # C(t) of batch k+1-NB has read that buffer (its histogram
-                                                                    # ran earlier on this stream)
-                self.stage_pack(pack_next, self.soa_bufs[nb])
-                self._packed_ev[nb] = torch.cuda.Event()
-                self._packed_ev[nb].record(self.aux)
-                self._packed = True
-            if self.hist_on_aux:
-                if prev_done is not None:
-                    self.aux.wait_event(prev_done)
-                if s.guard is not None:
-                    self.aux.wait_event(s.guard)
-                if events is not None:
-                    events[2].record(self.aux)
-                self.stage_hist(s, buf)                 # ordered behind the pack of this buffer on the same stream
-                if events is not None:
-                    events[3].record(self.aux)
-                s.hist_done = torch.cuda.Event()
-                s.hist_done.record(self.aux)
-        self.ctx.set_stream(self.main.cuda_stream)
-        return s
-
-    def back(self, k, events=None):
-        """Latency half of batch k on the slot's own stream: model-order search, relaxation, copies to pinned memory.
-        events (optional): [4] and [5] are recorded around the search kernel on the slot's stream."""
-        s = self.slots[k % self.depth]
-        if s.stream is not self.main:
-            s.stream.wait_event(s.front_done)
-            s.stream.wait_event(s.hist_done)
-            if s.guard is not None:
-                s.stream.wait_event(s.guard)         # a device-side reader of the previous batch's C(t) / table / histogram
-                s.guard = None
-        self.ctx.set_stream(s.stream.cuda_stream)
-        with torch.cuda.stream(s.stream):
-            if self.aux is not None and self.tail_on_slot_stream:
-                self.stage_ct_finalize(s)
-                s.psum_free = torch.cuda.Event()
-                s.psum_free.record(s.stream)
-            if events is not None and len(events) > 5:
-                events[4].record(s.stream)
-            self.stage_fit(s)
-            if events is not None and len(events) > 5:
-                events[5].record(s.stream)
-            self.stage_relax(s)
-            self.stage_download(s)
-            s.done = torch.cuda.Event()
-            s.done.record(s.stream)
-        s.busy = True
-        self.ctx.set_stream(self.main.cuda_stream)
-        return s
-
-    def collect(self, s):
-        """Wait for a batch and return its results (copies: they stay valid when the slot is reused)."""
-        s.done.synchronize()
-        s.busy = False
-        r = s.host_results()
-        s.result = r
-        s.relax_out = r['relax']
+    def _count(self, r):
+        """book-keeping of one collected batch"""
         self.relax_out = r['relax']
         self.fit_best = r['best']
         tried = r['status'] != -100
         self.nfev_total += int(r['nfev'][tried].sum())
         self.nfev_last = {nP: r['nfev'][j][tried[j]] for j, nP in enumerate(self.listDoG)}
-        return r
-
-    def run(self, vecs, nb, events=None, on_finished=None, on_enqueued=None):
-        """nb batches, up to `depth` in flight.  on_finished(slot) is called on the host for every finished batch, in order
-        (results collected).  on_enqueued(slot) is called right after a batch's last launch: a consumer that works on the
-        device (e.g. the all-gather of the results) queues itself behind slot.done there and returns an event, which the
-        pipeline waits for before it overwrites that slot's result buffers.  (With batches overlapping, the throughput half
-        of batch k + depth is already queued when on_finished(slot) runs for batch k: the host copies -- slot.result, and
-        C(t) / dC(t) in HBM -- are still batch k's, the slot's histogram in HBM may already be the next batch's.)"""
-        D = self.depth
-        for k in range(nb):
-            s = self.slots[k % D]
-            run_ahead = self.aux is not None and self.tail_on_slot_stream
-            if s.busy and not run_ahead:
-                self.collect(s)
-                if on_finished is not None:
-                    on_finished(s)
-            # Overlapped form: the throughput half of batch k is queued BEFORE the host waits for the batch that used the
-            # slot `depth` batches ago -- C(t) only overwrites that batch's raw sums (free once its chunk statistics ran),
-            # the histogram waits for it on the device -- so the main stream always has its next launch queued.
-            self.front(vecs, k, None if events is None else events[k], pack_next=vecs if k + 1 < nb else None)
-            if s.busy:
-                self.collect(s)
-                if on_finished is not None:
-                    on_finished(s)
-            self.back(k, None if events is None else events[k])
-            if on_enqueued is not None:
-                s.guard = on_enqueued(s)
-        for k in range(max(0, nb - D), nb):
-            s = self.slots[k % D]
-            if s.busy:
-                self.collect(s)
-                if on_finished is not None:
-                    on_finished(s)
-        self.ctx.set_stream(self.main.cuda_stream)
-
-    def prime(self, vecs):
-        """Set-up: push one batch through every slot so that code objects are loaded, the slots' device and pinned
-        buffers are resident and every stream has seen a launch before the first batch that counts."""
-        self.run(vecs, self.depth)
-        torch.cuda.synchronize(self.dev)
-        self.nfev_total = 0
-
-    def step(self, vecs):
-        """One batch from vectors to R1/R2/NOE; returns the (E, V, 4, 2) table."""
-        self.front(vecs, 0)
-        s = self.back(0)
-        return self.collect(s)['relax']
 
     def selected_params(self, s=None):
         """S2, C, tau (sorted by tau), number of components and chi^2 of the selected models of a collected batch."""
@@ -577,166 +665,167 @@ class DevicePipeline:
 
 
 # ======================================================================================================================
+# Per-batch schedule
+# ======================================================================================================================
+class DevicePipeline(_Pipeline):
+    def __init__(self, ctx, device, frames, V, R, F, dt, **kw):
+        super().__init__(ctx, device, frames, V, R, F, dt, batch_streams=max(1, int(kw.get('depth', 1))), **kw)
+        self.slots = [_Slot(ctx, device, V, self.L, R, self.nbins, len(self.listDoG), max(self.listDoG), len(self.fields),
+                            st, V * R * ctx.psum_stride(F)) for st in self.batch_streams]
+        torch.cuda.synchronize(device)
+
+    def _free(self):
+        for s in self.slots:
+            s.front_done = s.hist_done = s.done = s.psum_free = s.guard = None
+            s.stream = None
+            s.release()
+
+    # ---- batch-level API ----
+    def front(self, vecs, k, events=None, pack_next=None):
+        """Throughput half of batch k.  Serial form (depth 1): pack, C(t), histogram, transposes on the main stream.
+        Overlapped form: C(t) on one of the two main streams; the histogram of batch k and the pack of batch k+1
+        (`pack_next`: its vectors) on the auxiliary stream, beside the C(t) launch, on the plane ring.
+        events: [before the C(t) kernel, after it (before its finalize), before histogram, after histogram, (4, 5: see
+        back())]; the first two on the main stream."""
+        s = self.slots[k % self.depth]
+        if self.aux is None:
+            self.ctx.set_stream(self.main.cuda_stream)
+            with torch.cuda.stream(self.main):
+                self.stage_pack(vecs)
+                _stamp(events, 0, self.main)
+                self.stage_ct(s, mid_event=None if events is None else events[1])
+                _stamp(events, 2, self.main)
+                self.stage_hist(s)
+                _stamp(events, 3, self.main)
+                s.front_done = _event(self.main)
+                s.hist_done = s.front_done
+            return s
+        ring = self.ring
+        buf = ring.buf(k)
+        ring.pack_now(vecs, k)
+        prev_done = s.done if s.busy else None       # the batch that used this slot `depth` batches ago, if still in flight
+        main = self.main_alt if (k % 2 == 1 and self.main_alt is not None) else self.main
+        # the histogram may have to wait for the batch that used this slot before (its relaxation kernel reads the slot's
+        # histogram); it runs behind the pack of its buffer, on the auxiliary stream or (hist_on_aux off) behind the C(t) kernel
+        hist_stream = self.aux if self.hist_on_aux else main
+
+        def hist():
+            if prev_done is not None:
+                hist_stream.wait_event(prev_done)
+            if s.guard is not None:
+                hist_stream.wait_event(s.guard)
+            _stamp(events, 2, hist_stream)
+            self.stage_hist(s, buf)
+            _stamp(events, 3, hist_stream)
+        self.ctx.set_stream(main.cuda_stream)
+        with torch.cuda.stream(main):
+            ring.wait_packed(main, k)
+            if s.busy and s.psum_free is not None:
+                main.wait_event(s.psum_free)         # its raw sums are the only thing of that batch this kernel overwrites
+            _stamp(events, 0, main)
+            self.stage_ct(s, buf, mid_event=None if events is None else events[1], finalize=False)
+            if not self.hist_on_aux:
+                hist()
+            ring.ct_done_with(k, main)
+            s.front_done = _event(main)
+            s.hist_done = s.front_done
+        self.ctx.set_stream(self.aux.cuda_stream)
+        with torch.cuda.stream(self.aux):
+            # the pack of batch k+1 first: the next C(t) launch waits for nothing else
+            if pack_next is not None:
+                ring.pack_ahead(pack_next, k)
+            if self.hist_on_aux:
+                hist()
+                s.hist_done = _event(self.aux)
+        self.ctx.set_stream(self.main.cuda_stream)
+        return s
+
+    def back(self, k, events=None):
+        """Latency half of batch k on the slot's own stream: chunk statistics (overlapped form), model-order search,
+        relaxation, copies to pinned memory.  events (optional): [4] and [5] are recorded around the search kernel."""
+        s = self.slots[k % self.depth]
+        events45 = events if events is not None and len(events) > 5 else None
+        if s.stream is not self.main:
+            s.stream.wait_event(s.front_done)
+            s.stream.wait_event(s.hist_done)
+            if s.guard is not None:
+                s.stream.wait_event(s.guard)         # a device-side reader of the previous batch's C(t) / table / histogram
+                s.guard = None
+        self.ctx.set_stream(s.stream.cuda_stream)
+        with torch.cuda.stream(s.stream):
+            if self.aux is not None:
+                # the mean / std over the chunks only feed this batch's fits: they run on the batch's own stream, so that
+                # the main streams issue the C(t) kernels back to back (4.50 -> 4.41 ms per step)
+                self.stage_ct_finalize(s)
+                s.psum_free = _event(s.stream)
+            _stamp(events45, 4, s.stream)
+            self.stage_fit(s)
+            _stamp(events45, 5, s.stream)
+            self.stage_relax(s)
+            self.stage_download(s)
+            s.done = _event(s.stream)
+        s.busy = True
+        self.ctx.set_stream(self.main.cuda_stream)
+        return s
+
+    def collect(self, s):
+        """Wait for a batch and return its results (copies: they stay valid when the slot is reused)."""
+        s.done.synchronize()
+        s.busy = False
+        r = s.host_results()
+        s.result = r
+        s.relax_out = r['relax']
+        self._count(r)
+        return r
+
+    def run(self, vecs, nb, events=None, on_finished=None, on_enqueued=None):
+        """nb batches, up to `depth` in flight.  on_finished(slot) is called on the host for every finished batch, in order
+        (results collected).  on_enqueued(slot) is called right after a batch's last launch: a consumer that works on the
+        device (e.g. the all-gather of the results) queues itself behind slot.done there and returns an event, which the
+        pipeline waits for before it overwrites that slot's result buffers.  (With batches overlapping, the throughput half
+        of batch k + depth is already queued when on_finished(slot) runs for batch k: the host copies -- slot.result, and
+        C(t) / dC(t) in HBM -- are still batch k's, the slot's histogram in HBM may already be the next batch's.)"""
+        D = self.depth
+
+        def finish(s):
+            if s.busy:
+                self.collect(s)
+                if on_finished is not None:
+                    on_finished(s)
+        for k in range(nb):
+            s = self.slots[k % D]
+            if self.aux is None:
+                finish(s)
+            # Overlapped form: the throughput half of batch k is queued BEFORE the host waits for the batch that used the
+            # slot `depth` batches ago -- C(t) only overwrites that batch's raw sums (free once its chunk statistics ran),
+            # the histogram waits for it on the device -- so the main stream always has its next launch queued.
+            self.front(vecs, k, None if events is None else events[k], pack_next=vecs if k + 1 < nb else None)
+            finish(s)
+            self.back(k, None if events is None else events[k])
+            if on_enqueued is not None:
+                s.guard = on_enqueued(s)
+        for k in range(max(0, nb - D), nb):
+            finish(self.slots[k % D])
+        self.ctx.set_stream(self.main.cuda_stream)
+
+    def prime(self, vecs):
+        """Set-up: push one batch through every slot so that code objects are loaded, the slots' device and pinned
+        buffers are resident and every stream has seen a launch before the first batch that counts."""
+        self.run(vecs, self.depth)
+        torch.cuda.synchronize(self.dev)
+        self.nfev_total = 0
+
+    def step(self, vecs):
+        """One batch from vectors to R1/R2/NOE; returns the (E, V, 4, 2) table."""
+        self.front(vecs, 0)
+        s = self.back(0)
+        return self.collect(s)['relax']
+
+
+# ======================================================================================================================
 # Grouped schedule: throughput halves of G batches back to back, then ONE merged launch for their latency halves
 # ======================================================================================================================
-class _Lease:
-    """one hand-out of a recycled host buffer: exposes the memory through the array interface, so that numpy arrays made
-    from it (np.asarray) and all their views hold a reference to THIS object; when the last of them is gone the lease is
-    collected and _Group._host_copy may reuse the buffer"""
-    __slots__ = ('__array_interface__', '_keep', '__weakref__')
-
-    def __init__(self, arr):
-        self._keep = arr
-        self.__array_interface__ = dict(arr.__array_interface__)
-
-
-class _BatchView:
-    """What the stage functions need of one batch inside a group (views into the group's contiguous buffers)."""
-    __slots__ = ('Ct', 'dCt', 'CtT', 'dCtT', 'hist', 'vecsum', 'outer', 'psum', 'result', 'relax_out', 'index')
-
-
-class _Group:
-    """Device buffers, pinned mirrors and stream of a GROUP of up to G batches.  Inputs of the merged launches are
-    contiguous over the group's residues (batch j = rows j V .. (j + 1) V), results are laid out for the g batches a
-    launch really holds (the residue axis has length g V)."""
-
-    def __init__(self, ctx, dev, G, V, L, R, nbins, nO, Pmax, E, stream):
-        f64 = dict(device=dev, dtype=torch.float64)
-        i32 = dict(device=dev, dtype=torch.int32)
-        self.G, self.V, self.L = G, V, L
-        self._shape = (nO, Pmax, Pmax // 2, E)
-        GV = G * V
-        self._Ct = torch.empty((G, L, V), **f64)
-        self._dCt = torch.empty((G, L, V), **f64)
-        self.CtT = torch.empty((GV, L), **f64)
-        self.dCtT = torch.empty((GV, L), **f64)
-        self._hist = torch.empty((GV, nbins), **f64)
-        self.vecsum = torch.empty((GV, 3), **f64)
-        self.outer = torch.empty((G, R, V, 6), **f64)
-        self.fitwork = torch.empty((GV, L), **f64)
-        nd, ni = self._sizes(G)
-        self.dres = torch.empty((nd,), **f64)
-        self.ires = torch.empty((ni,), **i32)
-        self._ctx = ctx
-        self.h_dres, self._h_dres_addr = _pinned_array(ctx, nd, np.float64)
-        self.h_ires, self._h_ires_addr = _pinned_array(ctx, ni, np.int32)
-        # dispatch order of the merged launch: pinned host copy + device copy (refreshed per launch, stream-ordered before it)
-        self.h_order, self._h_order_addr = _pinned_array(ctx, GV, np.int32)
-        self.order_dev = torch.empty((GV,), **i32)
-        self.stream = stream
-        self.g = 0                 # batches of the group in flight / last collected
-        self.first = 0             # index (in the run) of the group's first batch
-        self.done = None
-        self.guard = None
-        self.busy = False
-        self.batches = []
-        self._views = {}
-        self._dpool, self._ipool = [], []
-
-    def _layouts(self, g):
-        nO, Pmax, Kmax, E = self._shape
-        n = g * self.V
-        return ((('popt', (nO, n, Pmax), 1), ('dP', (nO, n, Pmax), 1), ('chisq', (nO, n), 1), ('S2', (n,), 0), ('chi', (n,), 0),
-                 ('C', (n, Kmax), 0), ('tau', (n, Kmax), 0), ('relax', (E, n, 4, 2), 1)),
-                (('status', (nO, n), 1), ('nfev', (nO, n), 1), ('best', (n,), 0), ('K', (n,), 0)))
-
-    def _sizes(self, g):
-        dl, il = self._layouts(g)
-        return sum(int(np.prod(sh)) for _, sh, _ in dl), sum(int(np.prod(sh)) for _, sh, _ in il)
-
-    def views(self, g):
-        """device views of the result buffers for a launch over g batches"""
-        if g not in self._views:
-            out = {}
-            for buf, layout in zip((self.dres, self.ires), self._layouts(g)):
-                o = 0
-                for name, sh, _ in layout:
-                    n = int(np.prod(sh))
-                    out[name] = buf[o:o + n].view(sh)
-                    o += n
-            self._views[g] = out
-        return self._views[g]
-
-    # what a device-side consumer of a finished group reads (bench.py's all-gather): the g batches in flight
-    @property
-    def Ct(self):
-        return self._Ct[:self.g]
-
-    @property
-    def dCt(self):
-        return self._dCt[:self.g]
-
-    @property
-    def hist(self):
-        return self._hist[:self.g * self.V]
-
-    @property
-    def relax(self):
-        return self.views(self.g)['relax']
-
-    def batch(self, j):
-        V = self.V
-        b = _BatchView()
-        b.Ct, b.dCt = self._Ct[j], self._dCt[j]
-        b.CtT, b.dCtT = self.CtT[j * V:(j + 1) * V], self.dCtT[j * V:(j + 1) * V]
-        b.hist, b.vecsum, b.outer = self._hist[j * V:(j + 1) * V], self.vecsum[j * V:(j + 1) * V], self.outer[j]
-        b.psum = None
-        b.result = b.relax_out = None
-        b.index = j
-        return b
-
-    def _host_copy(self, pool, mirror, n):
-        """the first n elements of a pinned mirror in pageable memory the caller may keep.  The buffers are recycled, with
-        explicit ownership: every hand-out goes through a fresh _Lease object that the returned array (and every view cut
-        from it) keeps alive as its base; a pool buffer is taken again only when the lease of its last hand-out is gone
-        (a dead weak reference) -- no interpreter-specific reference counts.  Results stay valid for as long as anybody holds
-        them, and a collect does not start with a 10 MB allocation and its page faults (1.5 ms when the allocator has just
-        seen another size).  Where leases die late (no reference counting) the pool simply is not reused."""
-        entry = None
-        for e in pool:
-            if e[1] is None or e[1]() is None:
-                entry = e
-                break
-        if entry is None:
-            entry = [np.empty(mirror.size, dtype=mirror.dtype), None]
-            if len(pool) < 4:
-                pool.append(entry)
-        buf = entry[0]
-        np.copyto(buf[:n], mirror[:n])     # 10 MB for a 20-batch group: 0.46 ms (a threaded copy was measured: no faster)
-        lease = _Lease(buf[:n])
-        entry[1] = weakref.ref(lease)
-        return np.asarray(lease)
-
-    def host_results(self):
-        """per batch: COPIES of the pinned mirrors, split along the residue axis"""
-        g, V = self.g, self.V
-        nd, ni = self._sizes(g)
-        whole = {}
-        for buf, layout in zip((self._host_copy(self._dpool, self.h_dres, nd), self._host_copy(self._ipool, self.h_ires, ni)),
-                               self._layouts(g)):
-            o = 0
-            for name, sh, axis in layout:
-                n = int(np.prod(sh))
-                whole[name] = (buf[o:o + n].reshape(sh), axis)
-                o += n
-        out = []
-        for j in range(g):
-            r = {}
-            for name, (arr, axis) in whole.items():
-                r[name] = arr[j * V:(j + 1) * V] if axis == 0 else arr[:, j * V:(j + 1) * V]
-            out.append(r)
-        return out
-
-    def release(self):
-        for name in ('_h_dres_addr', '_h_ires_addr', '_h_order_addr'):
-            addr = getattr(self, name, None)
-            if addr:
-                self._ctx.host_free(addr)
-                setattr(self, name, None)
-        self.h_dres = self.h_ires = self.h_order = None
-
-
-class GroupedPipeline(DevicePipeline):
+class GroupedPipeline(_Pipeline):
     """The same stages as DevicePipeline, scheduled for throughput over MANY batches (trajectory shards):
 
       phase 1   pack, C(t), histogram, chunk statistics of `group` batches back to back (two C(t) streams, the bandwidth
@@ -779,8 +868,8 @@ class GroupedPipeline(DevicePipeline):
 
     def __init__(self, ctx, device, frames, V, R, F, dt, group=32, overlap=True, psum_buffers=3, late_hist=False, **kw):
         kw = dict(kw)
-        kw.setdefault('pack_cus', 128)                    # the pack stream on half of the CUs (DevicePipeline.__init__)
-        kw['depth'] = max(2, int(psum_buffers))          # the base class's slots: only their raw-sum buffers are used (a rotating pool)
+        kw.setdefault('pack_cus', 128)                    # the pack stream on half of the CUs (_Pipeline.__init__)
+        kw['depth'] = max(2, int(psum_buffers))           # raw-sum buffers in rotation (reported as the schedule's depth)
         self.late_hist = bool(late_hist)
         self.late_hist_note = None
         if self.late_hist:
@@ -806,27 +895,31 @@ class GroupedPipeline(DevicePipeline):
         super().__init__(ctx, device, frames, V, R, F, dt, **kw)
         self.group = max(1, int(group))
         self.overlap = bool(overlap)
+        self.sizes_override = None     # development: explicit group sizes (group_sizes)
         self.permute = True            # False: dispatch the merged launch's residues in natural order
         self.dispatch = 'history'      # 'history': longest first by the evaluation counts of the last collected batch; 'random'
         self._cost = None              # (V,) evaluations per residue (all orders) of the most recent collected batch
         self._cost_version = 0
         self.dev_skip_fits = False     # development only
-        import os as _os
-        self.dev_skip_hist = bool(_os.environ.get('SR_DEV_SKIP_HIST'))      # development only: marginal cost of the histogram in phase 1
-        self.pool = self.slots
-        self.NP = len(self.pool)
+        self.dev_skip_hist = bool(os.environ.get('SR_DEV_SKIP_HIST'))      # development only: marginal cost of the histogram in phase 1
+        # the raw C(t) sums of the batches whose chunk statistics have not run yet: a rotating pool, and per entry the event
+        # "the statistics have read it"
+        self.NP = self.depth
+        self.psums = [torch.empty((V * R * ctx.psum_stride(F),), device=device, dtype=torch.float64) for _ in range(self.NP)]
         self._psum_free = [None] * self.NP
         self.tail = torch.cuda.Stream(device=device)
-        Pmax = max(self.listDoG)
-        E = len(self.fields)
-        self.groups = [_Group(ctx, device, self.group, V, self.L, R, self.nbins, len(self.listDoG), Pmax, E,
+        self.groups = [_Group(ctx, device, self.group, V, self.L, R, self.nbins, len(self.listDoG), max(self.listDoG), len(self.fields),
                               torch.cuda.Stream(device=device)) for _ in range(2)]
+        self.slots = self.groups                          # what a caller iterates over to set up per-slot consumers
         self.hist_stream = torch.cuda.Stream(device=device) if self.late_hist else None      # (confined to 64 / 128 / 192 CUs: slower, 2.40-2.76 ms per step)
         self._late = []
-        self._hist_done_ev = [None] * self.NB           # late histograms: "the histogram that read this plane buffer has run"
-        from .hip import SpinRelaxHipError
-        for grp in self.groups:                           # every group has both attributes whatever the allocation does
-            grp.signal, grp.epoch = None, 0
+        self._perm = {}
+        self._fcsa = {}
+        self._on_part = None
+        self._last_fin = None
+        self._last_hist = None
+        self._prev_done = None
+        self._nbatch = 0
         try:
             for grp in self.groups:
                 grp.signal = ctx.signal_alloc()
@@ -837,65 +930,36 @@ class GroupedPipeline(DevicePipeline):
                     ctx.signal_free(grp.signal)
                 grp.signal = None
             if self.late_hist:
-                for grp in self.groups:               # pinned mirrors and streams of the group buffers
-                    grp.stream = None
-                    grp.release()
-                self.slots = self.pool
-                super().close()
+                self.close()
                 raise SpinRelaxHipError('late_hist needs sr_signal_alloc (hipStreamWaitValue32 on signal memory); construct the '
                                         'pipeline with late_hist=False on this device')
-        # gate_next: hold the next group's C(t) launches back (same signal) until the merged launch begins to drain.  Measured, off:
-        # 2.13 against 2.115 ms per step in steady state (queued behind a launch that fills the chip they hardly get a slot before
-        # that moment anyway), and no help to unequal splits of a 20-batch run (16 + 4, 14 + 6, ...: 49-51 ms like one group of
-        # 20) -- when the last workgroup starts, the 512 resident ones are the long-lived ones and free their slots over
-        # milliseconds, so C(t) grids released at that moment run at a fraction of their speed (4 launches: 9 ms).
-        self.gate_next = False
-        self._prev_signal = None
-        self.slots = self.groups                          # what a caller iterates over to set up per-slot consumers
-        self._perm = {}
-        self._fcsa = {}
-        self._on_part = None
-        self._last_fin = None
-        self._last_hist = None
-        self._prev_done = None
-        self._nbatch = 0
         torch.cuda.synchronize(device)
 
+    def _free(self):
+        for grp in self.groups:
+            grp.done = grp.guard = None
+            grp.stream = None
+            grp.batches = []
+            if grp.signal:
+                self.ctx.signal_free(grp.signal)
+                grp.signal = None
+            grp.release()
+        self.hist_stream = None
+        self.tail = None
+        self._late = []
+        self._psum_free = [None] * self.NP
+        self._last_fin = self._last_hist = self._prev_done = None
+
     def group_sizes(self, nb):
-        """how a run of nb batches is cut into groups (at most `group` each).  `sizes_override` (development): explicit list."""
-        ov = getattr(self, 'sizes_override', None)
-        if ov:
-            out, rem = [], nb
-            for g in ov:
-                if rem <= 0:
-                    break
-                g = min(int(g), rem, self.group)
-                out.append(g)
-                rem -= g
-            while rem > 0:
-                g = min(self.group, rem)
-                out.append(g)
-                rem -= g
-            return out
-        out, rem = [], nb
-        while rem > 0:
-            g = min(self.group, rem)
-            out.append(g)
-            rem -= g
-        return out
+        return group_sizes(self.group, nb, self.sizes_override)
 
     def _dispatch_order(self, g):
-        """order in which the workgroups of a merged launch take the g V residues (host int32 array): a fixed pseudo-random
-        permutation, stably re-sorted longest first by the predicted cost when there is a history (see the class comment)"""
+        """dispatch_order for a launch over g batches, cached per history (see the class comment)"""
         hist = self.dispatch == 'history' and self._cost is not None
         key = (g, self._cost_version if hist else -1)
         if key not in self._perm:
-            n = g * self.V
-            p = np.random.RandomState(20240 + g).permutation(n).astype(np.int32) if g > 1 else np.arange(n, dtype=np.int32)
-            if hist:
-                p = p[np.argsort(-self._cost[p % self.V], kind='stable')]
             self._perm = {k: v for k, v in self._perm.items() if k[1] == -1}       # older histories are dead
-            self._perm[key] = np.ascontiguousarray(p, dtype=np.int32)
+            self._perm[key] = dispatch_order(g, self.V, self._cost if hist else None)
         return self._perm[key]
 
     def _fcsa_for(self, g):
@@ -903,97 +967,52 @@ class GroupedPipeline(DevicePipeline):
             self._fcsa[g] = self._relax_dev[2].repeat(1, g).contiguous() if self._relax_dev[2].dim() == 2 else self._relax_dev[2].repeat(g).contiguous()
         return self._fcsa[g]
 
-    def _pack_from(self, vecs, kk, buf):
-        """pack batch kk's vectors into plane buffer `buf` on the auxiliary stream.  `vecs`: a device tensor (frames, Vtot, 3), or a
-        FEED -- an object with acquire(kk, stream) -> object with data_ptr() / shape of that batch's device array (the feed makes
-        `stream` wait until the frames are there) and release(kk, stream) (called once the pack has been queued: the feed may
-        refill the buffer when `stream` has passed that point).  bench.py's PinnedFeed streams every batch from host memory."""
-        if hasattr(vecs, 'acquire'):
-            src = vecs.acquire(kk, self.aux)
-            self.ctx.set_stream(self.aux.cuda_stream)          # the feed drives the context from its own stream
-            self.stage_pack(src, buf)
-            vecs.release(kk, self.aux)
-        else:
-            self.stage_pack(vecs, buf)
-
     def _front_grouped(self, vecs, kk, grp, j, events, pack_next):
         bv = grp.batches[j]
-        b = kk % self.NB
-        buf = self.soa_bufs[b]
+        ring = self.ring
+        buf = ring.buf(kk)
         pi = kk % self.NP
-        bv.psum = self.pool[pi].psum
-        if not self._packed:
-            self.ctx.set_stream(self.aux.cuda_stream)
-            with torch.cuda.stream(self.aux):
-                if self._ct_done_ev[b] is not None:
-                    self.aux.wait_event(self._ct_done_ev[b])
-                if self._hist_done_ev[b] is not None:
-                    self.aux.wait_event(self._hist_done_ev[b])
-                self._pack_from(vecs, kk, buf)
-                self._packed_ev[b] = torch.cuda.Event()
-                self._packed_ev[b].record(self.aux)
-        self._packed = False
+        bv.psum = self.psums[pi]
+        ring.pack_now(vecs, kk)
         main = self.main_alt if (kk % 2 == 1 and self.main_alt is not None) else self.main
         self.ctx.set_stream(main.cuda_stream)
         with torch.cuda.stream(main):
-            main.wait_event(self._packed_ev[b])
+            ring.wait_packed(main, kk)
             if self._psum_free[pi] is not None:
                 main.wait_event(self._psum_free[pi])      # the chunk statistics of batch kk - NP have read these raw sums
             if j < 2 and not self.overlap and self._prev_done is not None:
                 main.wait_event(self._prev_done)          # strict phases: the previous group's merged launch has finished (both C(t) streams)
-            elif j < 2 and self.gate_next and self._prev_signal is not None:
-                self.ctx.stream_wait_signal(*self._prev_signal)
-
-            if events is not None:
-                events[0].record(main)
+            _stamp(events, 0, main)
             # (Offsetting the two C(t) streams by half a launch -- first launch of a run in two halves, the second stream waiting
             # for the first half -- was measured: the launches then alternate perfectly, 1.25 ms apart, and the group's C(t) phase
             # takes exactly as long as in lockstep: the phase is bound by the kernels' own time, not by coinciding tails.)
             self.ctx.ct_sums_dev(buf.data_ptr(), self.Npad, self.R, self.F, self.V, bv.psum.data_ptr())
-            if events is not None:
-                events[1].record(main)
-            ct_ev = torch.cuda.Event()
-            ct_ev.record(main)
-            self._ct_done_ev[b] = ct_ev
+            _stamp(events, 1, main)
+            ct_ev = ring.ct_done_with(kk, main)
         tail = self.tail          # (chunk statistics spread over 3 or 5 streams: measured, no difference)
         self.ctx.set_stream(tail.cuda_stream)
         with torch.cuda.stream(tail):
             tail.wait_event(ct_ev)
             if j == 0 and grp.guard is not None:
                 tail.wait_event(grp.guard)                # a device-side reader of the group's previous C(t)
-            self.ctx.ct_finalize_dev(bv.psum.data_ptr(), self.R, self.F, self.V, bv.Ct.data_ptr(), bv.dCt.data_ptr(),
-                                     bv.CtT.data_ptr(), bv.dCtT.data_ptr())
-            ev = torch.cuda.Event()
-            ev.record(tail)
-            self._psum_free[pi] = ev
-            self._last_fin = ev
+            self.stage_ct_finalize(bv)
+            self._psum_free[pi] = self._last_fin = ev = _event(tail)
             if self._on_part is not None:
                 self._on_part('ct', bv, ev)          # C(t), dC(t) of this batch are final once `ev` has passed
         self.ctx.set_stream(self.aux.cuda_stream)
         with torch.cuda.stream(self.aux):
             if pack_next is not None:
-                nb = (kk + 1) % self.NB
-                if self._ct_done_ev[nb] is not None:
-                    self.aux.wait_event(self._ct_done_ev[nb])
-                if self._hist_done_ev[nb] is not None:
-                    self.aux.wait_event(self._hist_done_ev[nb])
-                self._pack_from(pack_next, kk + 1, self.soa_bufs[nb])
-                self._packed_ev[nb] = torch.cuda.Event()
-                self._packed_ev[nb].record(self.aux)
-                self._packed = True
+                ring.pack_ahead(pack_next, kk)
             if j == 0 and grp.guard is not None:
                 self.aux.wait_event(grp.guard)
-            if events is not None and not self.late_hist:
-                events[2].record(self.aux)
             if self.late_hist:
-                self._late.append((bv, buf, b, events))
-            elif not self.dev_skip_hist:
-                self.stage_hist(bv, buf)
-            if events is not None and not self.late_hist:
-                events[3].record(self.aux)
-            ev = torch.cuda.Event()
-            ev.record(self.aux)
-            self._last_hist = ev
+                self._late.append((bv, buf, kk, events))
+            else:
+                _stamp(events, 2, self.aux)
+                if not self.dev_skip_hist:
+                    self.stage_hist(bv, buf)
+                _stamp(events, 3, self.aux)
+            self._last_hist = ev = _event(self.aux)
             if self._on_part is not None and not self.late_hist:
                 self._on_part('hist', bv, ev)
         self.ctx.set_stream(self.main.cuda_stream)
@@ -1002,10 +1021,11 @@ class GroupedPipeline(DevicePipeline):
         st = grp.stream
         st.wait_event(self._last_fin)        # the tail and auxiliary streams run in order: their last events cover the group
         st.wait_event(self._last_hist)
-        grp.guard_hist = grp.guard if self.late_hist else None
+        late_guard = grp.guard if self.late_hist else None
+        events45 = events if events is not None and len(events) > 5 else None
         grp.guard = None
-        v = grp.views(g)
         n = g * self.V
+        v = grp.res.views(n)
         self.ctx.set_stream(st.cuda_stream)
         with torch.cuda.stream(st):
             order_ptr = None
@@ -1014,8 +1034,7 @@ class GroupedPipeline(DevicePipeline):
                 grp.h_order[:n] = self._dispatch_order(g)
                 self.ctx.memcpy_h2d_async(grp.order_dev.data_ptr(), grp._h_order_addr, n * 4)
                 order_ptr = grp.order_dev.data_ptr()
-            if events is not None and len(events) > 5:
-                events[4].record(st)
+            _stamp(events45, 4, st)
             if not self.dev_skip_fits:
                 self.ctx.order_search_batched_dev(self.t_dev.data_ptr(), 1, grp.CtT.data_ptr(), grp.dCtT.data_ptr(), n, self.L, self.listDoG,
                                                   self.tau_guess.data_ptr(), 1, self.tau_max, self.chi_thr,
@@ -1025,12 +1044,10 @@ class GroupedPipeline(DevicePipeline):
                                                   work_ptr=grp.fitwork.data_ptr(),
                                                   dispatch_order_ptr=order_ptr,
                                                   tail_signal=grp.signal, tail_value=grp.epoch + 1 if grp.signal else 0)
-            if events is not None and len(events) > 5:
-                events[5].record(st)
+            _stamp(events45, 5, st)
             if grp.signal:
                 grp.epoch += 1
                 self.ctx.stream_write_signal(grp.signal, grp.epoch)
-                self._prev_signal = (grp.signal, grp.epoch)
             if self.late_hist:
                 # The group's histograms fill the TAIL of the merged launch.  Its last workgroup releases the signal when it
                 # starts (every residue has a CU by then; from here on slots only free up while the longest fits finish); the
@@ -1038,46 +1055,26 @@ class GroupedPipeline(DevicePipeline):
                 # when the launch is over (skipped fits, a launch that fits the chip at once).
                 hs = self.hist_stream
                 hs.wait_event(self._last_hist)            # every pack of the group has run (auxiliary stream, in order)
-                if grp.guard_hist is not None:
-                    hs.wait_event(grp.guard_hist)
-                    grp.guard_hist = None
+                if late_guard is not None:
+                    hs.wait_event(late_guard)
                 self.ctx.set_stream(hs.cuda_stream)
                 with torch.cuda.stream(hs):
                     self.ctx.stream_wait_signal(grp.signal, grp.epoch)
-                    for bv, buf, b, evs in self._late:
-                        if evs is not None:
-                            evs[2].record(hs)
+                    for bv, buf, kk, evs in self._late:
+                        _stamp(evs, 2, hs)
                         self.stage_hist(bv, buf)
-                        if evs is not None:
-                            evs[3].record(hs)
-                        ev = torch.cuda.Event()
-                        ev.record(hs)
-                        self._hist_done_ev[b] = ev
+                        _stamp(evs, 3, hs)
+                        ev = self.ring.hist_done_with(kk, hs)      # the pack that reuses this plane buffer waits for it
                         if self._on_part is not None:
                             self._on_part('hist', bv, ev)
-                    hev = torch.cuda.Event()
-                    hev.record(hs)
+                    hev = _event(hs)
                 self._late = []
                 self.ctx.set_stream(st.cuda_stream)
                 st.wait_event(hev)
-            om, fdd, _, tf, gr = self._relax_dev
-            fcsa = self._fcsa_for(g)
-            Kmax = max(self.listDoG) // 2
-            E = len(self.fields)
-            if self.aniso is None or self.aniso == 1.0:
-                self.ctx.relax_dev(1, [self.Diso], E, om.data_ptr(), fdd.data_ptr(), fcsa.data_ptr(), tf.data_ptr(), gr.data_ptr(),
-                                   n, Kmax, self.zeta, v['S2'].data_ptr(), v['C'].data_ptr(), v['tau'].data_ptr(), v['K'].data_ptr(),
-                                   0, None, None, 0, v['relax'].data_ptr())
-            else:
-                Dpar, Dperp = hm.symmtop_from_iso(self.Diso, self.aniso)
-                self.ctx.relax_dev(2, [Dpar, Dperp], E, om.data_ptr(), fdd.data_ptr(), fcsa.data_ptr(), tf.data_ptr(), gr.data_ptr(),
-                                   n, Kmax, self.zeta, v['S2'].data_ptr(), v['C'].data_ptr(), v['tau'].data_ptr(), v['K'].data_ptr(),
-                                   self.nbins, self.binvecs_dev.data_ptr(), grp._hist.data_ptr(), 0, v['relax'].data_ptr())
-            nd, ni = grp._sizes(g)
-            self.ctx.memcpy_d2h_async(grp._h_dres_addr, grp.dres.data_ptr(), nd * 8)
-            self.ctx.memcpy_d2h_async(grp._h_ires_addr, grp.ires.data_ptr(), ni * 4)
-            grp.done = torch.cuda.Event()
-            grp.done.record(st)
+            self._launch_relax(n, v['S2'].data_ptr(), v['C'].data_ptr(), v['tau'].data_ptr(), v['K'].data_ptr(), grp._hist.data_ptr(),
+                               self._fcsa_for(g), v['relax'].data_ptr())
+            grp.res.download(n)
+            grp.done = _event(st)
         self._prev_done = grp.done
         grp.busy = True
         self.ctx.set_stream(self.main.cuda_stream)
@@ -1090,11 +1087,7 @@ class GroupedPipeline(DevicePipeline):
             bv = grp.batches[j]
             bv.result = r
             bv.relax_out = r['relax']
-            self.relax_out = r['relax']
-            self.fit_best = r['best']
-            tried = r['status'] != -100
-            self.nfev_total += int(r['nfev'][tried].sum())
-            self.nfev_last = {nP: r['nfev'][i][tried[i]] for i, nP in enumerate(self.listDoG)}
+            self._count(r)
             if on_finished is not None:
                 on_finished(bv)
         if res:                                # the cost prediction of the following launches: evaluations per residue, last batch
@@ -1112,7 +1105,8 @@ class GroupedPipeline(DevicePipeline):
         (kind 'ct') or histogram ('hist') has been queued; `event` marks its completion -- a device-side consumer can move the
         bulky per-batch arrays while the group is still being computed and leave only the small table for on_enqueued (whose
         returned event must cover everything the consumer read of the group).  events[k] as in DevicePipeline.run; [4], [5] are
-        recorded around the merged launch on the entry of the group's FIRST batch."""
+        recorded around the merged launch on the entry of the group's FIRST batch.  `vecs`: a device tensor or a feed object
+        (_PlaneRing._pack)."""
         self._on_part = on_part
         k, gi = 0, self._nbatch
         pending = []
@@ -1150,24 +1144,3 @@ class GroupedPipeline(DevicePipeline):
     def step(self, vecs):
         self.run(vecs, 1)
         return self.relax_out
-
-    def close(self):
-        if getattr(self, '_closed', False):
-            return
-        torch.cuda.synchronize(self.dev)
-        self.ctx.device_sync()
-        for grp in self.groups:
-            grp.done = grp.guard = None
-            grp.stream = None
-            grp.batches = []
-            if getattr(grp, 'signal', None):
-                self.ctx.signal_free(grp.signal)
-                grp.signal = None
-            grp.release()
-        self.hist_stream = None
-        self._hist_done_ev = []
-        self._psum_free = [None] * self.NP
-        self._last_fin = self._last_hist = self._prev_done = None
-        self.tail = None
-        self.slots = self.pool
-        super().close()

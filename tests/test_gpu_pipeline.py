@@ -22,14 +22,14 @@ def setup():
     return dict(torch=torch, synth=synth, ctx=ctx, dev=dev, s=s, vecs=vecs, dvecs=torch.from_numpy(vecs).to(dev))
 
 
-def _pipe(st, depth, aniso=True, reserve=0, only=False):
+def _pipe(st, depth, aniso=True, reserve=0, only=False, **opts):
     from spinrelax_amd.pipeline import DevicePipeline
     s, synth = st['s'], st['synth']
     V = st['vecs'].shape[1]
     return DevicePipeline(st['ctx'], st['dev'], s['frames'], V, s['R'], s['F'], s['dt'], q_rot=synth.Q_EXT if aniso else None,
                           Diso=synth.DISO, aniso=synth.DANI if aniso else None, field_MHz=(synth.FIELD_MHZ, 500.0),
                           zeta=synth.ZETA, depth=depth, stream=st['torch'].cuda.Stream(device=st['dev']), reserve_cus=reserve,
-                          fits_on_reserved_only=only)
+                          fits_on_reserved_only=only, **opts)
 
 
 @pytest.mark.parametrize('aniso', [True, False])
@@ -75,14 +75,22 @@ def test_pipeline_step_equals_staged_calls(setup, aniso):
     pipe.close()
 
 
-@pytest.mark.parametrize('depth,reserve,only', [(2, 0, False), (4, 16, False), (3, 32, True)])
-def test_pipeline_batches_in_flight_are_identical_and_ordered(setup, depth, reserve, only):
+@pytest.mark.parametrize('depth,reserve,only,opts', [
+    pytest.param(2, 0, False, {}, id='2-0-False'), pytest.param(4, 16, False, {}, id='4-16-False'), pytest.param(3, 32, True, {}, id='3-32-True'),
+    # the other ways through the plane ring: auxiliary stream on its own CUs, histogram behind the C(t) kernel, masked pack
+    # stream, two plane buffers
+    pytest.param(3, 0, False, dict(aux_cus=16), id='3-aux_cus'), pytest.param(2, 0, False, dict(hist_on_aux=False), id='2-hist_on_main'),
+    pytest.param(3, 0, False, dict(pack_cus=64), id='3-pack_cus'), pytest.param(3, 0, False, dict(plane_buffers=2), id='3-two_planes')])
+def test_pipeline_batches_in_flight_are_identical_and_ordered(setup, depth, reserve, only, opts):
     st = setup
     serial = _pipe(st, 1)
     want = serial.step(st['dvecs']).copy()
     want_best = serial.fit_best.copy()
     serial.close()
-    pipe = _pipe(st, depth, True, reserve, only)
+    pipe = _pipe(st, depth, True, reserve, only, **opts)
+    for name in ('aux_cus', 'pack_cus'):
+        assert getattr(pipe, name) == opts.get(name, 0)
+    assert pipe.NB == (2 if 'plane_buffers' in opts else 3) and (pipe.main_alt is None) == (opts.get('hist_on_aux') is False)
     assert pipe.reserve_cus == reserve
     seen = []
 
@@ -180,6 +188,76 @@ def test_grouped_schedule_without_signal_memory(setup, monkeypatch):
         for k in want:
             assert np.array_equal(r[k], want[k], equal_nan=True), k
     pipe.close()
+
+
+def _grouped(st, **kw):
+    from spinrelax_amd.pipeline import GroupedPipeline
+    s, synth = st['s'], st['synth']
+    return GroupedPipeline(st['ctx'], st['dev'], s['frames'], st['vecs'].shape[1], s['R'], s['F'], s['dt'], q_rot=synth.Q_EXT, Diso=synth.DISO,
+                           aniso=synth.DANI, field_MHz=(synth.FIELD_MHZ, 500.0), zeta=synth.ZETA,
+                           stream=st['torch'].cuda.Stream(device=st['dev']), **kw)
+
+
+def test_grouped_schedule_from_a_feed_object(setup):
+    """GroupedPipeline.run fed by an object instead of a tensor (what bench.py's PinnedFeed is): acquire(k, stream) hands out
+    batch k's device array, release(k, stream) is told when its pack has been queued -- each exactly once per batch, in batch
+    order, and every batch comes out as the serial pipeline gives it."""
+    st = setup
+    serial = _pipe(st, 1)
+    serial.step(st['dvecs'])
+    st['torch'].cuda.synchronize()
+    sl = serial.slots[0]
+    want = {k: v.copy() for k, v in sl.result.items()}
+    want_Ct, want_dCt, want_hist = sl.Ct.cpu().numpy(), sl.dCt.cpu().numpy(), sl.hist.cpu().numpy()
+    serial.close()
+
+    class Feed:
+        def __init__(self, tns):
+            self.tns, self.acquired, self.released = tns, [], []
+
+        def acquire(self, k, stream):
+            self.acquired.append(k)
+            return self.tns
+
+        def release(self, k, stream):
+            assert self.acquired[-1] == k                   # the pack of batch k has been queued, nothing else since
+            self.released.append(k)
+    feed = Feed(st['dvecs'])
+    pipe = _grouped(st, group=3)
+    seen = []
+    pipe.run(feed, 7, None, lambda b: seen.append(({k: v.copy() for k, v in b.result.items()}, b.Ct.cpu().numpy(), b.dCt.cpu().numpy(),
+                                                     b.hist.cpu().numpy())))
+    st['torch'].cuda.synchronize()
+    assert feed.acquired == list(range(7)) and feed.released == list(range(7))
+    assert len(seen) == 7
+    for r, Ct, dCt, hist in seen:
+        assert set(r) == set(want)
+        for k in want:
+            assert np.array_equal(r[k], want[k], equal_nan=True), k
+        assert np.array_equal(Ct, want_Ct) and np.array_equal(dCt, want_dCt) and np.array_equal(hist, want_hist)
+    pipe.close()
+
+
+def test_grouped_pipeline_owns_no_slot_and_closes_clean(setup):
+    """A GroupedPipeline allocates group buffers and raw-sum buffers, no per-batch slot; its `slots` ARE its groups; after its
+    close() the context serves a fresh serial pipeline as before."""
+    from spinrelax_amd.pipeline import _Slot
+    st = setup
+    serial = _pipe(st, 1)
+    want = serial.step(st['dvecs']).copy()
+    serial.close()
+    pipe = _grouped(st, group=2, psum_buffers=4)
+    assert pipe.slots is pipe.groups and len(pipe.groups) == 2 and pipe.depth == 4
+    V, s = st['vecs'].shape[1], st['s']
+    assert len(pipe.psums) == 4 and all(p.numel() == V * s['R'] * st['ctx'].psum_stride(s['F']) for p in pipe.psums)
+    pipe.close()
+
+    def holds_slot(x):
+        return isinstance(x, _Slot) or (isinstance(x, (list, tuple)) and any(holds_slot(y) for y in x))
+    assert not any(holds_slot(x) for x in vars(pipe).values())
+    again = _pipe(st, 1)
+    assert np.array_equal(again.step(st['dvecs']), want, equal_nan=True)
+    again.close()
 
 
 def test_batched_order_search_entry_point(setup):

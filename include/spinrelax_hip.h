@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 11
+#define SR_ABI_VERSION 12
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -67,7 +67,9 @@ int          sr_sync(sr_ctx *);
  * blocked transforms for longer chunks (sr_ct_formulation() below is the rule itself);
  * "ct_traceless" = 1/0 (default 0): the real-input FFT kernel for F <= 4096 transforms the five traceless components of
  * u (x) u and takes the trace term from a scan of |u|^2 - 1 (one transform fewer; series that are not unit vectors fall back
- * to six inside the kernel) -- 4 % faster alone, 3 % slower per step inside the pipeline, same results to 1e-13. */
+ * to six inside the kernel) -- 4 % faster alone, 3 % slower per step inside the pipeline, same results to 1e-13;
+ * "ired_ksplit" = S >= 1: the iRED matrix kernel splits every window's frames over S workgroups per tile pair; 0 (default): the
+ * rule of sr_ired_matrix_f32_dev below, a function of the shape alone.  M is bit-equal between runs with the same value. */
 int          sr_set_option(sr_ctx *, const char *name, int value);
 /* Streams that partition the chip.  The fits of fitting_Ct_functions.py:278-345 are a latency chain of small
  * launches; queued behind a C(t) launch that fills every CU they starve (queue priority does not pre-empt
@@ -265,6 +267,31 @@ int sr_ct_finalize_sums_f64(sr_ctx *, const double *sums_host, int64_t R, int64_
 int sr_vectors_hist_f32(sr_ctx *, sr_vectors *, int64_t N_hist, const double *q, const double *edges_phi, int nphi,
                         const double *edges_cos, int ncos, double *hist, double *vecsum, double *outer, int64_t block_len);
 int sr_counter(sr_ctx *, const char *name, uint64_t *value);
+
+/* ---- iRED: equal-time P2 cross-correlation matrix of the bond vectors ----------------------------------------------------
+ * The isotropic reorientational eigenmode dynamics analysis (Prompers & Brueschweiler, J. Am. Chem. Soc. 124, 4522 (2002);
+ * its windowed form for long trajectories: Gu, Li & Brueschweiler, J. Chem. Theory Comput. 10, 2599 (2014)) that the reference
+ * announces in calculate_S2_by_iRED / calculate_S2_by_wiRED (calculate-S2.py:158-191) and leaves as stubs that stop after the
+ * window length.  Built to the publications.  For window w = frames [win_start[w], win_start[w] + win_len[w]) of the planes:
+ *     M[w][i][j] = (1 / F_w) sum_t ( 1.5 (u_i(t) . u_j(t))^2 - 0.5 ),   F_w = win_len[w],  i, j < nV
+ * (nV, nV) float64 per window, exactly symmetric.  The literal definition: no unit-length assumption, a (0,0,0) vector (what
+ * vecnorm_NDarray makes of 0/0) contributes -0.5.  The eigen-decomposition and S2 = 1 - sum_{m > G} lambda_m |m>_i^2 are host work
+ * (spinrelax_amd/ired.py).
+ * (u_i.u_j)^2 = sum_{a<=b} w_ab (u_ia u_ib)(u_ja u_jb), w = 1, 1, 1, 2, 2, 2: a symmetric rank-k update over K = 6 F_w whose
+ * operands, products of two float32 values, are exact in float64 (the 2 is put on one side).  k_ired_matrix accumulates the 64 x 64
+ * tiles with tile row <= tile column on the float64 matrix pipe (v_mfma_f64_16x16x4_f64), operands formed in registers from float32
+ * x, y, z staged in LDS; a window's frames are shared by S workgroups per tile pair, whose partial tiles go to a context work area;
+ * k_ired_finish adds the S partials in fixed order, applies 1.5 / F_w and -0.5 and writes both triangles.  No atomics: equal input
+ * and equal S give bit-equal M.  S = "ired_ksplit" when set, else min(64, max(1, Fmax / 256), ceil(1024 / (W T (T + 1) / 2))) with
+ * T = ceil(nV / 64) and Fmax the longest window: about four workgroups per CU, at least 256 frames each.
+ * The window tables are HOST arrays of W entries, range-checked (0 <= start, 1 <= len, start + len <= Npad; the sr_vectors form:
+ * against the frames held) before anything is queued and consumed on return.  nV < 1, W < 1 and a window shorter than one frame
+ * are refused (-3).  M_dev: DEVICE, (W, nV, nV) float64. */
+int sr_ired_matrix_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t nV, const int64_t *win_start_host,
+                           const int64_t *win_len_host, int W, double *M_dev);
+/* kernel 0 (once per object; the planes that sr_vectors_ct_f32 / sr_vectors_hist_f32 left are reused) + the two kernels above;
+ * M_host: (W, nV, nV) float64 on the host.  Blocks until M is there. */
+int sr_vectors_ired_f32(sr_ctx *, sr_vectors *, const int64_t *win_start_host, const int64_t *win_len_host, int W, double *M_host);
 
 /* ---- kernel 3b: multi-exponential C(t) model --------------------------------------------
  * Model of curvefit_exponential (fitting_Ct_functions.py:419-427): params = [C_1..C_K, tau_1..tau_K

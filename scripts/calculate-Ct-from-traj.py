@@ -2,7 +2,7 @@
 """
 Drop-in for the reference's calculate-Ct-from-traj.py (run-all.bash:476-481): same flags, same output
 files (<o>_Ctext.dat, <o>_Ctint.dat, <o>_vecHistogram.npz | _vecPhiTheta.npz|.dat, <o>_avgvec.dat,
-<o>_S2.dat).  C(t), the rotation into the PAF, the spherical histogram, the mean vector and S2 are
+<o>_S2.dat; with the [extension] --iRED also <o>_iRED_S2.dat, <o>_iRED_eig.dat and, with --binary, <o>_iRED_matrix.npz).  C(t), the rotation into the PAF, the spherical histogram, the mean vector and S2 are
 computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
 Several GPUs: run under torchrun (`torchrun --nproc-per-node N scripts/calculate-Ct-from-traj.py ...`): rank r computes the
@@ -61,6 +61,14 @@ def build_parser():
                         'the fitted (body-frame) vectors are the lab-frame vectors rotated on the GPU by the inverse orientation '
                         'quaternion of every frame, instead of coming from a superposition.')
     p.add_argument('--exact', action='store_true', help='[extension] float64 validation mode of the C(t) kernel.')
+    p.add_argument('--iRED', dest='bDoIRED', action='store_true', default=False,
+                   help='[extension] iRED order parameters (Prompers & Brueschweiler 2002; Gu, Li & Brueschweiler 2014) from the P2 '
+                        'cross-correlation matrix of all lab-frame vectors: <o>_iRED_S2.dat, <o>_iRED_eig.dat; with --binary also '
+                        '<o>_iRED_matrix.npz.  Single process only.')
+    p.add_argument('--iRED_window', type=float, dest='ired_window', default=None,
+                   help='[extension] averaging window of --iRED in the units of the trajectory; windows tile every file from its first '
+                        'frame. Default: 5 tau when --tau is given, otherwise every file as a whole.')
+    p.add_argument('--iRED_modes', type=int, dest='ired_modes', default=5, help='[extension] number of global (tumbling) modes of --iRED.')
     return p
 
 
@@ -108,7 +116,7 @@ def load_mdtraj(args, frames_per_chunk_of):
     are computed and APPENDED to this rank's resident vectors (spinrelax_amd.hip.ResidentVectors) -- the host never holds
     more than one chunk of coordinates and no vectors at all.  A file's tail that does not fill a block of memory time is
     cut when the file ends (reformat_vecs_by_tau, :259-272).  frames_per_chunk_of(dt) -> frames per block or None.
-    Returns (resXH, lab vectors, fitted vectors, deltaT, total vectors V, first vector i0, frames kept)."""
+    Returns (resXH, lab vectors, fitted vectors, deltaT, total vectors V, first vector i0, frames kept, frames kept of each file)."""
     try:
         import mdtraj as md
     except ImportError:
@@ -135,6 +143,7 @@ def load_mdtraj(args, frames_per_chunk_of):
 
     ctx = hip.default_context()
     resXH, dt, lab, fit, V, i0, nloc = None, None, None, None, None, 0, 0
+    kept = []
     for i, fn in enumerate(args.infn):
         top = args.topfn[i] if len(args.topfn) > 1 else args.topfn[0]
         ref = md.load(top)
@@ -173,9 +182,10 @@ def load_mdtraj(args, frames_per_chunk_of):
         if nloc > 0 and keep != nfile:
             lab.truncate(file_start + keep)
             fit.truncate(file_start + keep)
+        kept.append(keep)
         print("= = = Molecule centered and fitted: %s, %i frames read, %i kept." % (fn, nfile, keep))
     frames = 0 if lab is None else lab.frames
-    return resXH, lab, fit, dt, V, i0, frames
+    return resXH, lab, fit, dt, V, i0, frames, kept
 
 
 def main():
@@ -196,6 +206,11 @@ def main():
         if len(q_rot) != 4 or not np.allclose(np.dot(q_rot, q_rot), 1):
             print("= = = ERROR: input rotation quaternion is malformed!", q_rot)
             sys.exit(23)
+    if args.bDoIRED and world > 1:
+        # the ranks hold ranges of vectors and the matrix needs every pair
+        print("= = = ERROR: --iRED needs all vectors on one GPU and does not run under torchrun with more than one rank; "
+              "run it as a single process.", file=sys.stderr)
+        sys.exit(1)
     if len(args.topfn) > 1 and len(args.topfn) != len(args.infn):
         print("= = ERROR: When giving multiple reference files, you must have one for each trajecfile file given!", file=sys.stderr)
         sys.exit(1)
@@ -234,12 +249,13 @@ def main():
         rv_fit, V, i0, N = hostct.upload_shard(vecXHfit, F)
         rv_lab = rv_fit if same or not args.bDoCt or repl else hostct.upload_shard(vecXH, F)[0]
         host_fit, host_lab = vecXHfit, vecXH
+        frames_per_file = [v.shape[0] if F is None else (v.shape[0] // F) * F for v in vecXH]      # what upload_shard kept
         del vecXH
     else:
         if args.qfile is not None:
             print("= = = ERROR: --qfile works on vector-file input (.npy/.npz), not on MDTraj input.", file=sys.stderr)
             sys.exit(1)
-        resXH, rv_lab, rv_fit, deltaT, V, i0, N = load_mdtraj(args, frames_per_chunk_of)
+        resXH, rv_lab, rv_fit, deltaT, V, i0, N, frames_per_file = load_mdtraj(args, frames_per_chunk_of)
         repl = False
         if srdist.replicate_sharding(V):
             print("= = = ERROR: %i ranks for %i vectors: trajectory input is sharded by vector; use at most %i ranks (vector-file "
@@ -275,6 +291,27 @@ def main():
         elif rv_fit is not rv_lab:
             Ct, dCt = hostct.calculate_Ct_resident(rv_fit, V, R, F, mode=mode)
         gs.print_sxylist(out_pref + '_Ctint.dat', resXH, dt, np.stack((Ct.T, dCt.T), axis=-1))
+    if args.bDoIRED:
+        # the lab-frame vectors as they are held (P2(u_i.u_j) at equal times does not change under a rotation of the frame):
+        # no superposition, no de-tumbling, no fit
+        from spinrelax_amd import ired
+        print("= = = Conducting iRED analysis of the %i vectors with %i global modes." % (V, args.ired_modes))
+        if V <= args.ired_modes:
+            print("= = = ERROR: iRED needs more vectors (%i) than global modes (%i)!" % (V, args.ired_modes), file=sys.stderr)
+            sys.exit(1)
+        try:
+            res = ired.calculate_iRED_resident(rv_lab, frames_per_file, deltaT, window=args.ired_window, tau=tau_memory,
+                                               n_global=args.ired_modes)
+        except ValueError as exc:
+            print("= = = ERROR: %s" % exc, file=sys.stderr)
+            sys.exit(1)
+        print("    ...%i windows of %i to %i frames." % (res['win_len'].size, res['win_len'].min(), res['win_len'].max()))
+        gs.print_xylist(out_pref + '_iRED_S2.dat', resXH, np.stack((res['S2'], res['dS2'])) * args.zeta, True)
+        gs.print_xylist(out_pref + '_iRED_eig.dat', np.arange(1, V + 1), res['eig'][np.newaxis, :], True)
+        if args.binary:
+            np.savez(out_pref + '_iRED_matrix.npz', M=res['M'], win_start=res['win_start'], win_len=res['win_len'],
+                     resid=np.array(resXH))
+        print("      ...complete.")
     if rv_lab is not None and rv_lab is not rv_fit:
         rv_lab.close()
 

@@ -128,6 +128,9 @@ SIGNATURES = {
     'sr_ct_finalize_sums_f64': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     'sr_vectors_hist_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p, c_int64]),
+    # (ctx, soa, Npad, nV, win_start, win_len, W, M_dev) / (ctx, vectors, win_start, win_len, W, M_host)
+    'sr_ired_matrix_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
+    'sr_vectors_ired_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'sr_counter': (c_int, [c_void_p, c_char_p, POINTER(ctypes.c_uint64)]),
     'sr_transpose_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'sr_jomega_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
@@ -137,7 +140,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 11
+ABI_VERSION = 12
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -171,6 +171,11 @@ int sr_set_option(sr_ctx *ctx, const char *name, int value)
         ctx->fit_geo = value;
         return 0;
     }
+    if (!strcmp(name, "ired_ksplit")) {
+        SR_REQUIRE(value >= 0 && value <= 1024, -3, "sr_set_option: ired_ksplit must be 0 (automatic) .. 1024");
+        ctx->ired_ksplit = value;
+        return 0;
+    }
     if (!strcmp(name, "fit_lds")) {
         SR_REQUIRE(value == 0 || value == 1, -3, "sr_set_option: fit_lds must be 0 or 1");
         ctx->fit_lds = value;

@@ -7,7 +7,7 @@
 #include <cstring>
 #include "../../include/spinrelax_hip.h"
 
-#define SR_NSLOTS 17
+#define SR_NSLOTS 18
 
 struct sr_ctx {
     int device;
@@ -29,6 +29,7 @@ struct sr_ctx {
     int ct_long_ws_mb;  // blocked C(t) (sr_ct_long.hip): the series of a launch go in tiles whose block spectra fit this many MiB
     int ct_long_min_frames;   // blocked C(t): beyond one transform (F + L > 8192), chunks of at least this many frames take it, and the
                         // shorter ones that the direct kernel cannot stage; default SR_CT_LONG_MIN_FRAMES
+    int ired_ksplit;    // iRED matrix (sr_ired.hip): workgroups that share a window's frames per tile pair; 0 (default) = sr_ired_ksplit()'s rule
     int fft_table_ready;
     int fft32_table_ready;
     int ctlong_table_ready;
@@ -52,7 +53,8 @@ enum {
     SR_WS_FFT,          // twiddle table of the FFT formulation of kernel 1
     SR_WS_FFT32,        // tables of its float32 form (sr_ct32.hip)
     SR_WS_CTLONG,       // blocked C(t) (sr_ct_long.hip): chunk constants, block spectra and cross-spectra of one tile of series
-    SR_WS_CTLONG_TAB    // twiddles of its float64 inverse transform
+    SR_WS_CTLONG_TAB,   // twiddles of its float64 inverse transform
+    SR_WS_IRED          // iRED matrix (sr_ired.hip): partial tiles of the frame split, (W, tile pairs, S, 64 x 64) float64
 };
 
 void sr_set_error(const char *fmt, ...);

@@ -7,7 +7,7 @@
 // the device: frames are APPENDED chunk by chunk (from host memory: a strided copy of the rank's columns through two pinned
 // staging buffers, 12 * frames * nV bytes over PCIe and not a byte more; from device memory: what the trajectory front end
 // sr_xh_vectors_f32_dev just produced), packed once into per-vector planes (kernel 0), and then read by kernel 1 and
-// kernel 2 as often as the caller asks.  The host-pointer entry points sr_ct_palmer_f32 / sr_rotate_hist_f32 are this
+// kernel 2 (and the iRED matrix kernel, sr_ired.hip) as often as the caller asks.  The host-pointer entry points sr_ct_palmer_f32 / sr_rotate_hist_f32 are this
 // object used once.
 #include "sr_internal.h"
 #include <cstdlib>
@@ -354,6 +354,26 @@ int sr_vectors_hist_f32(sr_ctx *ctx, sr_vectors *h, int64_t N_hist, const double
     SR_HIP(hipMemcpyAsync(hist, hist_d, (size_t)nV * nbins * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (vecsum) SR_HIP(hipMemcpyAsync(vecsum, vs_d, (size_t)nV * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (outer) SR_HIP(hipMemcpyAsync(outer, outer_d, (size_t)nB * nV * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int sr_vectors_ired_f32(sr_ctx *ctx, sr_vectors *h, const int64_t *win_start_host, const int64_t *win_len_host, int W, double *M)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(h && win_start_host && win_len_host && M, -2, "sr_vectors_ired_f32: null pointer");
+    SR_REQUIRE(W >= 1, -3, "sr_vectors_ired_f32: W=%d windows", W);
+    for (int w = 0; w < W; ++w)
+        SR_REQUIRE(win_len_host[w] >= 1 && win_start_host[w] >= 0 && win_start_host[w] <= h->N && win_len_host[w] <= h->N - win_start_host[w], -3,
+                   "sr_vectors_ired_f32: window %d = frames [%lld, %lld) is outside the %lld held", w, (long long)win_start_host[w],
+                   (long long)(win_start_host[w] + win_len_host[w]), (long long)h->N);
+    if (int rc = pack(ctx, h)) return rc;
+    const size_t n = (size_t)W * h->nV * h->nV;
+    double *M_d = (double *)sr_workspace(ctx, SR_WS_OUT0, n * sizeof(double));
+    if (!M_d) return -5;
+    int rc = sr_ired_matrix_f32_dev(ctx, h->soa, h->Npad, h->nV, win_start_host, win_len_host, W, M_d);
+    if (rc) return rc;
+    SR_HIP(hipMemcpyAsync(M, M_d, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SR_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -26,6 +26,14 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _windows(win_start, win_len):
+    ws = np.ascontiguousarray(np.atleast_1d(win_start), dtype=np.int64)
+    wl = np.ascontiguousarray(np.atleast_1d(win_len), dtype=np.int64)
+    if ws.ndim != 1 or ws.shape != wl.shape:
+        raise ValueError('win_start and win_len must be 1-D and of equal length')
+    return ws, wl
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = _lib.load()
@@ -165,6 +173,14 @@ class Context:
 
     def psum_stride(self, F):
         return int(self.lib.sr_ct_psum_stride(F))
+
+    # ---- iRED matrix (sr_ired.hip) ----
+    def ired_matrix_dev(self, soa_ptr, Npad, nV, win_start, win_len, M_ptr):
+        """M[w] = mean over frames [win_start[w], win_start[w] + win_len[w]) of P2(u_i . u_j) from packed planes, into the device
+        array M_ptr (W, nV, nV) float64 (sr_ired_matrix_f32_dev); asynchronous on the context's stream"""
+        ws, wl = _windows(win_start, win_len)
+        check(self.lib.sr_ired_matrix_f32_dev(self.h, soa_ptr, int(Npad), int(nV), _ptr(ws), _ptr(wl), ws.size, M_ptr),
+              'sr_ired_matrix_f32_dev')
 
     # ---- resident vectors (sr_vectors.hip) ----
     def vectors(self, nV, capacity=0):
@@ -651,6 +667,14 @@ class ResidentVectors:
         check(self.ctx.lib.sr_vectors_hist_f32(self.ctx.h, self.h, int(N), _ptr(qq), _ptr(ep), nphi, _ptr(ec), ncos, _ptr(hist),
                                                _ptr(vecsum), _ptr(outer), int(block_len or 0)), 'sr_vectors_hist_f32')
         return hist, vecsum, outer
+
+    def ired(self, win_start, win_len):
+        """iRED matrices of the resident vectors: M (W, nV, nV) float64, M[w][i][j] = mean over the frames
+        [win_start[w], win_start[w] + win_len[w]) of 1.5 (u_i . u_j)^2 - 0.5 (sr_vectors_ired_f32)"""
+        ws, wl = _windows(win_start, win_len)
+        M = np.empty((ws.size, self.nV, self.nV))
+        check(self.ctx.lib.sr_vectors_ired_f32(self.ctx.h, self.h, _ptr(ws), _ptr(wl), ws.size, _ptr(M)), 'sr_vectors_ired_f32')
+        return M
 
 
 def append_xyz(ctx, lab, fit, xyz, indexX, indexH, fit_indices=None, ref_xyz=None):

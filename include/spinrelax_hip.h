@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 12
+#define SR_ABI_VERSION 13
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -69,7 +69,9 @@ int          sr_sync(sr_ctx *);
  * u (x) u and takes the trace term from a scan of |u|^2 - 1 (one transform fewer; series that are not unit vectors fall back
  * to six inside the kernel) -- 4 % faster alone, 3 % slower per step inside the pipeline, same results to 1e-13;
  * "ired_ksplit" = S >= 1: the iRED matrix kernel splits every window's frames over S workgroups per tile pair; 0 (default): the
- * rule of sr_ired_matrix_f32_dev below, a function of the shape alone.  M is bit-equal between runs with the same value. */
+ * rule of sr_ired_matrix_f32_dev below, a function of the shape alone.  M is bit-equal between runs with the same value;
+ * "ired_ws_mb" = MiB (1 .. 65536, default 1024): sr_ired_mode_ct_f32_dev processes its windows in batches whose amplitudes fit this
+ * work area (a batch always holds at least one window); the results do not depend on it. */
 int          sr_set_option(sr_ctx *, const char *name, int value);
 /* Streams that partition the chip.  The fits of fitting_Ct_functions.py:278-345 are a latency chain of small
  * launches; queued behind a C(t) launch that fills every CU they starve (queue priority does not pre-empt
@@ -292,6 +294,29 @@ int sr_ired_matrix_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t nV,
 /* kernel 0 (once per object; the planes that sr_vectors_ct_f32 / sr_vectors_hist_f32 left are reused) + the two kernels above;
  * M_host: (W, nV, nV) float64 on the host.  Blocks until M is there. */
 int sr_vectors_ired_f32(sr_ctx *, sr_vectors *, const int64_t *win_start_host, const int64_t *win_len_host, int W, double *M_host);
+
+/* ---- iRED: time-correlation functions of the modes -------------------------------------------------------------------------
+ * The dynamics half of the analysis (same publications).  For window w and row m of its coefficient matrix coef[w] (K rows of nV
+ * weights e_mi, float64; the production caller passes the eigenvectors of M[w] as rows, the kernels take any matrix), with c over
+ * (xx, yy, zz, xy, xz, yz) and w_c = 1, 1, 1, 2, 2, 2:
+ *     A_mc(t) = sum_i e_mi u_ia(t) u_ib(t)
+ *     C_m(k)  = 1.5 / (F_w - k) sum_{tau = 0}^{F_w - k - 1} sum_c w_c A_mc(tau) A_mc(tau + k) - 0.5 sigma_m^2,   sigma_m = sum_i e_mi
+ *             = sum_ij e_mi e_mj < 1.5 (u_i(tau) . u_j(tau + k))^2 - 0.5 >_tau,      k = 0 .. n_lags - 1
+ * No unit-length assumption, like M; with eigenvectors as rows C_m(0) = lambda_m.
+ * k_ired_project forms the amplitudes as a GEMM over the vectors on the float64 matrix pipe (v_mfma_f64_16x16x4_f64; the operands
+ * u_a u_b are formed in registers from float32 x, y, z and are exact, the only rounding is the accumulation) into a context work
+ * area, 48 K F_w bytes per window; k_ired_mode_ct, one workgroup per (window, mode), takes the six amplitude series through the
+ * in-LDS float64 transforms of kernel 1's k_ct_fft (three packed pairs, weighted power spectrum, one transform back) with
+ * M = 2048 / 4096 / 6144 / 8192 points, the smallest M >= F_w + n_lags - 1.  The windows of a call go in batches whose amplitudes fit
+ * "ired_ws_mb".  No atomics and no split of a reduction: equal input gives bit-equal output, whatever the batches.
+ * The window tables are HOST arrays, range-checked like sr_ired_matrix_f32_dev's before anything is queued.  Refused with -3:
+ * K < 1, n_lags < 1, a window with n_lags > F_w; with -4: a window with F_w + n_lags - 1 > 8192 (blocked transforms for longer
+ * windows do not exist yet).  coef_dev: DEVICE, (W, K, nV) float64; Cm_dev: DEVICE, (W, K, n_lags) float64.  Asynchronous. */
+int sr_ired_mode_ct_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t nV, const int64_t *win_start_host,
+                            const int64_t *win_len_host, int W, const double *coef_dev, int K, int n_lags, double *Cm_dev);
+/* the same of resident vectors, coefficient matrices and result on the HOST.  Blocks until Cm is there. */
+int sr_vectors_ired_mode_ct_f32(sr_ctx *, sr_vectors *, const int64_t *win_start_host, const int64_t *win_len_host, int W,
+                                const double *coef_host, int K, int n_lags, double *Cm_host);
 
 /* ---- kernel 3b: multi-exponential C(t) model --------------------------------------------
  * Model of curvefit_exponential (fitting_Ct_functions.py:419-427): params = [C_1..C_K, tau_1..tau_K

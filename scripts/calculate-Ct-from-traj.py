@@ -2,7 +2,8 @@
 """
 Drop-in for the reference's calculate-Ct-from-traj.py (run-all.bash:476-481): same flags, same output
 files (<o>_Ctext.dat, <o>_Ctint.dat, <o>_vecHistogram.npz | _vecPhiTheta.npz|.dat, <o>_avgvec.dat,
-<o>_S2.dat; with the [extension] --iRED also <o>_iRED_S2.dat, <o>_iRED_eig.dat and, with --binary, <o>_iRED_matrix.npz).  C(t), the rotation into the PAF, the spherical histogram, the mean vector and S2 are
+<o>_S2.dat; with the [extension] --iRED also <o>_iRED_S2.dat, <o>_iRED_eig.dat and, with --binary, <o>_iRED_matrix.npz; with --iRED_Ct
+also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat).  C(t), the rotation into the PAF, the spherical histogram, the mean vector and S2 are
 computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
 Several GPUs: run under torchrun (`torchrun --nproc-per-node N scripts/calculate-Ct-from-traj.py ...`): rank r computes the
@@ -68,6 +69,11 @@ def build_parser():
     p.add_argument('--iRED_window', type=float, dest='ired_window', default=None,
                    help='[extension] averaging window of --iRED in the units of the trajectory; windows tile every file from its first '
                         'frame. Default: 5 tau when --tau is given, otherwise every file as a whole.')
+    p.add_argument('--iRED_Ct', dest='bDoIREDCt', action='store_true', default=False,
+                   help='[extension, needs --iRED] correlation functions of the iRED modes: <o>_iRED_Ctint.dat (per vector, the format of '
+                        '_Ctint.dat, lags 1 .. F_w/2), <o>_iRED_modeCt.dat (per mode rank, lag 0 included), <o>_iRED_tau.dat (rank, mean '
+                        'eigenvalue, correlation time); with --binary the .npz also holds Cm_w and the eigenvectors.  Windows of at '
+                        'most 5461 frames.')
     p.add_argument('--iRED_modes', type=int, dest='ired_modes', default=5, help='[extension] number of global (tumbling) modes of --iRED.')
     return p
 
@@ -206,6 +212,9 @@ def main():
         if len(q_rot) != 4 or not np.allclose(np.dot(q_rot, q_rot), 1):
             print("= = = ERROR: input rotation quaternion is malformed!", q_rot)
             sys.exit(23)
+    if args.bDoIREDCt and not args.bDoIRED:
+        print("= = = ERROR: --iRED_Ct extends --iRED and needs it; give both.", file=sys.stderr)
+        sys.exit(1)
     if args.bDoIRED and world > 1:
         # the ranks hold ranges of vectors and the matrix needs every pair
         print("= = = ERROR: --iRED needs all vectors on one GPU and does not run under torchrun with more than one rank; "
@@ -300,17 +309,30 @@ def main():
             print("= = = ERROR: iRED needs more vectors (%i) than global modes (%i)!" % (V, args.ired_modes), file=sys.stderr)
             sys.exit(1)
         try:
-            res = ired.calculate_iRED_resident(rv_lab, frames_per_file, deltaT, window=args.ired_window, tau=tau_memory,
-                                               n_global=args.ired_modes)
+            if args.bDoIREDCt:
+                res = ired.calculate_iRED_resident(rv_lab, frames_per_file, deltaT, window=args.ired_window, tau=tau_memory,
+                                                   n_global=args.ired_modes, mode_ct=True)
+            else:
+                res = ired.calculate_iRED_resident(rv_lab, frames_per_file, deltaT, window=args.ired_window, tau=tau_memory,
+                                                   n_global=args.ired_modes)
         except ValueError as exc:
             print("= = = ERROR: %s" % exc, file=sys.stderr)
             sys.exit(1)
         print("    ...%i windows of %i to %i frames." % (res['win_len'].size, res['win_len'].min(), res['win_len'].max()))
         gs.print_xylist(out_pref + '_iRED_S2.dat', resXH, np.stack((res['S2'], res['dS2'])) * args.zeta, True)
         gs.print_xylist(out_pref + '_iRED_eig.dat', np.arange(1, V + 1), res['eig'][np.newaxis, :], True)
+        if args.bDoIREDCt:
+            # lag k of the arrays is k frames: _Ctint.dat's layout (lags 1 .. F_w / 2, x = k dt) for the vectors, lag 0 too for the modes
+            lags = np.arange(res['Cm'].shape[1]) * float(deltaT)
+            gs.print_sxylist(out_pref + '_iRED_Ctint.dat', resXH, lags[1:], np.stack((res['Ct_vec'][1:].T, res['dCt_vec'][1:].T), axis=-1))
+            _, dCm = ired.ired_reduce(res['Cm_w'].reshape(res['Cm_w'].shape[0], -1))
+            gs.print_sxylist(out_pref + '_iRED_modeCt.dat', list(range(1, V + 1)), lags,
+                             np.stack((res['Cm'], dCm.reshape(res['Cm'].shape)), axis=-1))
+            gs.print_xylist(out_pref + '_iRED_tau.dat', np.arange(1, V + 1), np.stack((res['eig'], res['tau'])), True)
         if args.binary:
+            extra = dict(Cm_w=res['Cm_w'], modes_w=res['modes_w']) if args.bDoIREDCt else {}
             np.savez(out_pref + '_iRED_matrix.npz', M=res['M'], win_start=res['win_start'], win_len=res['win_len'],
-                     resid=np.array(resXH))
+                     resid=np.array(resXH), **extra)
         print("      ...complete.")
     if rv_lab is not None and rv_lab is not rv_fit:
         rv_lab.close()

@@ -131,6 +131,9 @@ SIGNATURES = {
     # (ctx, soa, Npad, nV, win_start, win_len, W, M_dev) / (ctx, vectors, win_start, win_len, W, M_host)
     'sr_ired_matrix_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     'sr_vectors_ired_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    # (ctx, soa, Npad, nV, win_start, win_len, W, coef_dev, K, n_lags, Cm_dev) / (ctx, vectors, win_start, win_len, W, coef_host, K, n_lags, Cm_host)
+    'sr_ired_mode_ct_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    'sr_vectors_ired_mode_ct_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     'sr_counter': (c_int, [c_void_p, c_char_p, POINTER(ctypes.c_uint64)]),
     'sr_transpose_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'sr_jomega_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
@@ -140,7 +143,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 12
+ABI_VERSION = 13
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -93,6 +93,7 @@ sr_ctx *sr_create(int device)
     ctx->ct_traceless = 0;
     ctx->ct_long_ws_mb = SR_CT_LONG_WS_MB;
     ctx->ct_long_min_frames = SR_CT_LONG_MIN_FRAMES;
+    ctx->ired_ws_mb = SR_IRED_WS_MB;
     ctx->fft_table_ready = 0;
     ctx->fft32_table_ready = 0;
     if (hipGetDeviceProperties(&ctx->prop, device) != hipSuccess) {
@@ -174,6 +175,11 @@ int sr_set_option(sr_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "ired_ksplit")) {
         SR_REQUIRE(value >= 0 && value <= 1024, -3, "sr_set_option: ired_ksplit must be 0 (automatic) .. 1024");
         ctx->ired_ksplit = value;
+        return 0;
+    }
+    if (!strcmp(name, "ired_ws_mb")) {
+        SR_REQUIRE(value >= 1 && value <= 65536, -3, "sr_set_option: ired_ws_mb must be 1 .. 65536 (MiB)");
+        ctx->ired_ws_mb = value;
         return 0;
     }
     if (!strcmp(name, "fit_lds")) {

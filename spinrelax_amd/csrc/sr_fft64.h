@@ -1,6 +1,7 @@
 // sr_fft64.h -- the float64 pieces that k_ct_fft (sr_ct_fft64.hip) and k_ct_rfft (sr_ct_rfft64.hip) share: complex arithmetic, the
 // in-register transforms (radix 2 up to 32 points; the step-1 transforms of each kernel, 24 = 3 x 8 and 12 = 3 x 4 among them),
-// and the layout of the context's twiddle table.  What is independent of the scalar type: sr_fft_common.h.
+// the layout of the context's twiddle table, and the complex workgroup transform of 256 N1 points (fft_workgroup) that k_ct_fft shares
+// with k_ired_mode_ct (sr_ired_modes.hip).  What is independent of the scalar type: sr_fft_common.h.
 #pragma once
 #include <cstddef>
 #include "sr_fft_common.h"
@@ -188,6 +189,96 @@ constexpr int kFftTabDoubles = sizeof(Ct64Tab) / sizeof(double);
 // the table as the flat array of complex entries that Ct64Tab lays out: t < 1280 the two k_ct_fft tables, then 2 x 3 x 256
 static_assert(offsetof(Ct64Tab, w6144) == 2 * 1024 * sizeof(double) && offsetof(Ct64Tab, rfft) == 2 * 1280 * sizeof(double) &&
               sizeof(Ct64Tab::Rfft) == 2 * 768 * sizeof(double) && kFftTabDoubles == 2 * (1280 + 2 * 768), "k_fft_init_table's indexing");
+
+// ---- the complex workgroup transform of M = 256 N1 points (k_ct_fft, sr_ct_fft64.hip; k_ired_mode_ct, sr_ired_modes.hip) ----
+// v[p] *= base^k(p), k(p) < N: base^k = A[k & 7] * B[k >> 3] with 8 + N/8 powers held in registers (a full table of N
+// powers would cost 4 N VGPRs next to the 4 N of the data)
+template <int N, class KOF>
+__device__ __forceinline__ void apply_twiddles(cplx *v, cplx base)
+{
+    constexpr int NA = N < 8 ? N : 8, NB = N / 8 > 0 ? N / 8 : 1;
+    cplx A[NA], B[NB];
+    A[0] = {1.0, 0.0};
+#pragma unroll
+    for (int k = 1; k < NA; ++k) A[k] = k == 1 ? base : cmul(A[k >> 1], A[k - (k >> 1)]);
+    B[0] = {1.0, 0.0};
+    if (NB > 1) {
+        B[1] = cmul(A[4], A[4]);
+#pragma unroll
+        for (int k = 2; k < NB; ++k) B[k] = cmul(B[k >> 1], B[k - (k >> 1)]);
+    }
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+        const int k = KOF::k1(p);
+        if (k == 0) continue;
+        const cplx t = (k >> 3) == 0 ? A[k & 7] : ((k & 7) == 0 ? B[k >> 3] : cmul(A[k & 7], B[k >> 3]));
+        v[p] = cmul(v[p], t);
+    }
+}
+
+// LDS slot of logical element a: one pad slot per 8 elements and eight per 256.  Every access pattern below splits into
+// a per-thread part and a compile-time part without carries between them, so each access is `base + immediate`.
+__host__ __device__ constexpr int fft_pad(int a) { return a + (a >> 3) + 8 * (a >> 8); }
+__host__ __device__ constexpr int fft_lds_slots(int M) { return M + (M >> 3) + 8 * (M >> 8); }
+
+// one full transform of the thread's N1 samples v[] (natural order, sample n = tid + 256 n1) -> the thread's
+// G = N1/8 groups of 8 spectrum values w[j][p] = X[g + 32 N1 rev3(p)], g = tid + 256 j.  Ends with a barrier.
+template <int N1>
+__device__ __forceinline__ void fft_workgroup(cplx *v, cplx (*w)[8], cplx *lds, const Ct64Tab *__restrict__ tab, int tid)
+{
+    constexpr int G = N1 / 8;
+    constexpr bool kPow2 = (N1 & (N1 - 1)) == 0;
+    // step 1: N1-point transforms over n1, twiddle w_M^(n2 k1), to LDS as element k1*256 + n2
+    Stage1<N1>::run(v);
+    {
+        const double *tw = kPow2 ? tab->w8192 + 2 * (8192 / (N1 * 256)) * tid : tab->w6144 + 2 * tid;      // w_M^tid
+        apply_twiddles<N1, Stage1<N1>>(v, cplx{tw[0], tw[1]});
+        cplx *b = lds + tid + (tid >> 3);
+#pragma unroll
+        for (int p = 0; p < N1; ++p) b[fft_pad(Stage1<N1>::k1(p) * 256)] = v[p];
+    }
+    __syncthreads();
+    // step 2: thread (k1, lo), active while k1 < N1: 32-point transforms over h (n2 = lo + 8 h), twiddle w_256^(lo k2a)
+    cplx u[32];
+    const int k1 = tid >> 3, lo = tid & 7;
+    const bool act = k1 < N1;
+    if (act) {
+        const cplx *b = lds + fft_pad(256) * k1 + lo;
+#pragma unroll
+        for (int h = 0; h < 32; ++h) u[h] = b[9 * h];
+        fft_reg<5>(u);
+        apply_twiddles<32, Stage1<32>>(u, cplx{tab->w8192[2 * (32 * lo)], tab->w8192[2 * (32 * lo) + 1]});
+    }
+    __syncthreads();
+    if (act) {
+        // element (k1 + N1 k2a)*8 + lo
+        if constexpr (kPow2) {
+            cplx *b = lds + 9 * k1 + lo;
+#pragma unroll
+            for (int p = 0; p < 32; ++p) b[fft_pad(8 * N1 * bitrev<5>(p))] = u[p];
+        } else {
+            // 8 N1 is not a power of two: the per-thread and the constant part of the slot can carry into each other
+            const int t = 8 * k1 + lo;
+#pragma unroll
+            for (int p = 0; p < 32; ++p) {
+                const int c = 8 * N1 * bitrev<5>(p);
+                lds[t + c + ((t + c) >> 3) + 8 * ((t + c) >> 8)] = u[p];
+            }
+        }
+    }
+    __syncthreads();
+    // step 3: thread q, groups g = q + 256 j: 8-point transforms over lo
+    {
+        const cplx *b = lds + 9 * tid + 8 * (tid >> 5);
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) w[j][e] = b[fft_pad(2048 * j) + e];
+            fft_reg<3>(w[j]);
+        }
+    }
+    __syncthreads();
+}
 
 }  // namespace
 

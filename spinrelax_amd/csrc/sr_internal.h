@@ -7,7 +7,7 @@
 #include <cstring>
 #include "../../include/spinrelax_hip.h"
 
-#define SR_NSLOTS 18
+#define SR_NSLOTS 19
 
 struct sr_ctx {
     int device;
@@ -30,6 +30,7 @@ struct sr_ctx {
     int ct_long_min_frames;   // blocked C(t): beyond one transform (F + L > 8192), chunks of at least this many frames take it, and the
                         // shorter ones that the direct kernel cannot stage; default SR_CT_LONG_MIN_FRAMES
     int ired_ksplit;    // iRED matrix (sr_ired.hip): workgroups that share a window's frames per tile pair; 0 (default) = sr_ired_ksplit()'s rule
+    int ired_ws_mb;     // iRED mode correlation functions (sr_ired_modes.hip): the windows of a call go in batches whose amplitudes fit this many MiB
     int fft_table_ready;
     int fft32_table_ready;
     int ctlong_table_ready;
@@ -54,7 +55,8 @@ enum {
     SR_WS_FFT32,        // tables of its float32 form (sr_ct32.hip)
     SR_WS_CTLONG,       // blocked C(t) (sr_ct_long.hip): chunk constants, block spectra and cross-spectra of one tile of series
     SR_WS_CTLONG_TAB,   // twiddles of its float64 inverse transform
-    SR_WS_IRED          // iRED matrix (sr_ired.hip): partial tiles of the frame split, (W, tile pairs, S, 64 x 64) float64
+    SR_WS_IRED,         // iRED matrix (sr_ired.hip): partial tiles of the frame split, (W, tile pairs, S, 64 x 64) float64
+    SR_WS_IRED_AMP      // iRED mode correlation functions (sr_ired_modes.hip): amplitudes of one batch of windows, (m, 6, F_w) float64 each
 };
 
 void sr_set_error(const char *fmt, ...);
@@ -117,6 +119,11 @@ int64_t sr_ct_direct_max_frames(size_t lds_limit);
 // sr_ct_fft64.hip: float64 transforms in LDS, complex (k_ct_fft: 1024 < F + L <= 8192) and real-input (k_ct_rfft: 4096 < F + L <= 8192)
 int sr_launch_ct_fft64(sr_ctx *ctx, const sr_ct_job &job);
 int sr_launch_ct_rfft64(sr_ctx *ctx, const sr_ct_job &job);
+
+// sr_ired_modes.hip
+#define SR_IRED_WS_MB 1024
+int sr_ired_mode_ct_check(const char *who, int64_t frames, int64_t nV, const int64_t *win_start_host, const int64_t *win_len_host, int W, int K,
+                          int n_lags);
 
 // sr_ct32.hip: float32 real-input transforms in LDS (k_ct_rfft32: 1024 < F + L <= 8192)
 int sr_launch_ct_rfft32(sr_ctx *ctx, const sr_ct_job &job);

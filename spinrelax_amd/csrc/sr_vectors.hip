@@ -7,7 +7,7 @@
 // the device: frames are APPENDED chunk by chunk (from host memory: a strided copy of the rank's columns through two pinned
 // staging buffers, 12 * frames * nV bytes over PCIe and not a byte more; from device memory: what the trajectory front end
 // sr_xh_vectors_f32_dev just produced), packed once into per-vector planes (kernel 0), and then read by kernel 1 and
-// kernel 2 (and the iRED matrix kernel, sr_ired.hip) as often as the caller asks.  The host-pointer entry points sr_ct_palmer_f32 / sr_rotate_hist_f32 are this
+// kernel 2 (and the iRED kernels, sr_ired.hip and sr_ired_modes.hip) as often as the caller asks.  The host-pointer entry points sr_ct_palmer_f32 / sr_rotate_hist_f32 are this
 // object used once.
 #include "sr_internal.h"
 #include <cstdlib>
@@ -374,6 +374,28 @@ int sr_vectors_ired_f32(sr_ctx *ctx, sr_vectors *h, const int64_t *win_start_hos
     int rc = sr_ired_matrix_f32_dev(ctx, h->soa, h->Npad, h->nV, win_start_host, win_len_host, W, M_d);
     if (rc) return rc;
     SR_HIP(hipMemcpyAsync(M, M_d, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int sr_vectors_ired_mode_ct_f32(sr_ctx *ctx, sr_vectors *h, const int64_t *win_start_host, const int64_t *win_len_host, int W,
+                                const double *coef_host, int K, int n_lags, double *Cm)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(h && win_start_host && win_len_host && coef_host && Cm, -2, "sr_vectors_ired_mode_ct_f32: null pointer");
+    if (int rc = sr_ired_mode_ct_check("sr_vectors_ired_mode_ct_f32", h->N, h->nV, win_start_host, win_len_host, W, K, n_lags)) return rc;
+    if (int rc = pack(ctx, h)) return rc;
+    const size_t nc = (size_t)W * K * h->nV, no = (size_t)W * K * n_lags;
+    double *coef_d = (double *)sr_workspace(ctx, SR_WS_IN0, nc * sizeof(double));
+    double *Cm_d = (double *)sr_workspace(ctx, SR_WS_OUT0, no * sizeof(double));
+    if (!coef_d || !Cm_d) return -5;
+    SR_HIP(hipMemcpyAsync(coef_d, coef_host, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    int rc = sr_ired_mode_ct_f32_dev(ctx, h->soa, h->Npad, h->nV, win_start_host, win_len_host, W, coef_d, K, n_lags, Cm_d);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);        // the upload reads the caller's array
+        return rc;
+    }
+    SR_HIP(hipMemcpyAsync(Cm, Cm_d, no * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SR_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -182,6 +182,15 @@ class Context:
         check(self.lib.sr_ired_matrix_f32_dev(self.h, soa_ptr, int(Npad), int(nV), _ptr(ws), _ptr(wl), ws.size, M_ptr),
               'sr_ired_matrix_f32_dev')
 
+    # ---- iRED mode correlation functions (sr_ired_modes.hip) ----
+    def ired_mode_ct_dev(self, soa_ptr, Npad, nV, win_start, win_len, coef_ptr, K, n_lags, Cm_ptr):
+        """C_m(k), k < n_lags, of the K rows of every window's coefficient matrix (device array coef_ptr (W, K, nV) float64) from
+        packed planes, into the device array Cm_ptr (W, K, n_lags) float64 (sr_ired_mode_ct_f32_dev); asynchronous on the
+        context's stream"""
+        ws, wl = _windows(win_start, win_len)
+        check(self.lib.sr_ired_mode_ct_f32_dev(self.h, soa_ptr, int(Npad), int(nV), _ptr(ws), _ptr(wl), ws.size, coef_ptr, int(K),
+                                               int(n_lags), Cm_ptr), 'sr_ired_mode_ct_f32_dev')
+
     # ---- resident vectors (sr_vectors.hip) ----
     def vectors(self, nV, capacity=0):
         """An empty ResidentVectors object for nV vectors (this rank's columns)."""
@@ -675,6 +684,20 @@ class ResidentVectors:
         M = np.empty((ws.size, self.nV, self.nV))
         check(self.ctx.lib.sr_vectors_ired_f32(self.ctx.h, self.h, _ptr(ws), _ptr(wl), ws.size, _ptr(M)), 'sr_vectors_ired_f32')
         return M
+
+    def ired_mode_ct(self, win_start, win_len, coef, n_lags):
+        """iRED mode correlation functions of the resident vectors: coef (W, K, nV) float64, row m of window w the weights e_mi
+        of one mode -> Cm (W, K, n_lags) float64,
+        Cm[w][m][k] = sum_ij e_mi e_mj < 1.5 (u_i(t) . u_j(t + k))^2 - 0.5 >_t over the window (sr_vectors_ired_mode_ct_f32)"""
+        ws, wl = _windows(win_start, win_len)
+        coef = _f64(coef)
+        if coef.ndim != 3 or coef.shape[0] != ws.size or coef.shape[2] != self.nV:
+            raise ValueError('coef must be (windows, modes, vectors) = (%d, K, %d)' % (ws.size, self.nV))
+        K, n_lags = coef.shape[1], int(n_lags)
+        Cm = np.empty((ws.size, K, max(n_lags, 0)))
+        check(self.ctx.lib.sr_vectors_ired_mode_ct_f32(self.ctx.h, self.h, _ptr(ws), _ptr(wl), ws.size, _ptr(coef), K, n_lags, _ptr(Cm)),
+              'sr_vectors_ired_mode_ct_f32')
+        return Cm
 
 
 def append_xyz(ctx, lab, fit, xyz, indexX, indexH, fit_indices=None, ref_xyz=None):

@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 13
+#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -317,6 +317,36 @@ int sr_ired_mode_ct_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t nV
 /* the same of resident vectors, coefficient matrices and result on the HOST.  Blocks until Cm is there. */
 int sr_vectors_ired_mode_ct_f32(sr_ctx *, sr_vectors *, const int64_t *win_start_host, const int64_t *win_len_host, int W,
                                 const double *coef_host, int K, int n_lags, double *Cm_host);
+
+/* ---- time-lagged P2 cross-correlation between pairs of vectors (sr_ct_cross.hip; beyond the reference) ---------------------------
+ * For pair p = (i, j) = (pair_i[p], pair_j[p]) on the Palmer chunk table of kernel 1 (R chunks of F frames, chunk_start_host as there):
+ *     S_ij[k] = sum_{t = 0}^{F - 1 - k} (u_i(t) . u_j(t + k))^2,      k = 0 .. L = F / 2,   per chunk
+ *     C_ij(k) = mean over the chunks of 1.5 S_ij[k] / (F - k) - 0.5   (k = 1 .. L),   dC = std over the chunks / (sqrt(R) - 1)
+ * -- what every cross-correlated relaxation rate computed from a trajectory starts from (the two C-H dipoles of a methylene group,
+ * N-H against CA-HA, a dipole against a CSA axis).  sym = 1: S is (S_ij + S_ji) / 2, the symmetric function relaxation theory uses
+ * (for i = j: the autocorrelation, to rounding); sym = 0: S_ij alone -- the later frame belongs to j; C_ji is the pair (j, i).
+ * Arithmetic and modes as the direct form of kernel 1 (mode 0: float32 dot products, short float32 partial sums folded into float64;
+ * mode 1: float64 throughout); no atomics, equal input gives bit-equal output.  Mean and dC come from kernel 1's own reduction over
+ * the chunks (the raw sums have its layout, pairs in the place of vectors), so R = 1 gives the dC it gives.
+ *   P0  (nP)     equal-time <P2(u_i . u_j)>: mean over the chunks of 1.5 S[0] / F - 0.5, the rigid-limit P2(cos theta_ij)
+ *   dP0 (nP)     its error over the chunks by the same formula as dC (optional, may be NULL)
+ *   Ct, dCt      (L, nP) float64, lags 1 .. L like kernel 1
+ * One workgroup stages both series of a (pair, chunk) in LDS, 24 bytes per frame: F up to sr_ct_cross_max_frames() (6624 with the
+ * 160 KiB of gfx950); a longer chunk is refused with -4 (there is no blocked form).  The pair tables are HOST arrays, consumed on
+ * return; an index outside [0, nV) is refused with -3.  Every refusal comes before anything is launched.
+ * _dev: packed planes in, P0 / dP0 / Ct / dCt DEVICE arrays, asynchronous behind the upload of the tables; psum_ws (optional, may be NULL):
+ * (nP, R, sr_ct_psum_stride(F)) float64 raw sums, S[0] in slot 0.  sr_vectors_: kernel 0 once per object, results on the HOST, blocking; _err_ is the same call
+ * with dP0 as well. */
+int64_t sr_ct_cross_max_frames(sr_ctx *);
+int sr_ct_cross_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                        const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode, double *psum_ws,
+                        double *P0, double *dP0, double *Ct, double *dCt);
+int sr_vectors_ct_cross_f32(sr_ctx *, sr_vectors *, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                            const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode,
+                            double *P0, double *Ct, double *dCt);
+int sr_vectors_ct_cross_err_f32(sr_ctx *, sr_vectors *, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode,
+                                double *P0, double *dP0, double *Ct, double *dCt);
 
 /* ---- kernel 3b: multi-exponential C(t) model --------------------------------------------
  * Model of curvefit_exponential (fitting_Ct_functions.py:419-427): params = [C_1..C_K, tau_1..tau_K

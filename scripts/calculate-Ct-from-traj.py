@@ -3,7 +3,8 @@
 Drop-in for the reference's calculate-Ct-from-traj.py (run-all.bash:476-481): same flags, same output
 files (<o>_Ctext.dat, <o>_Ctint.dat, <o>_vecHistogram.npz | _vecPhiTheta.npz|.dat, <o>_avgvec.dat,
 <o>_S2.dat; with the [extension] --iRED also <o>_iRED_S2.dat, <o>_iRED_eig.dat and, with --binary, <o>_iRED_matrix.npz; with --iRED_Ct
-also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat).  C(t), the rotation into the PAF, the spherical histogram, the mean vector and S2 are
+also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat; with the [extension] --crossCt --pairs FILE also <o>_crossCtint.dat
+and <o>_crossPairs.dat).  C(t), the rotation into the PAF, the spherical histogram, the mean vector and S2 are
 computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
 Several GPUs: run under torchrun (`torchrun --nproc-per-node N scripts/calculate-Ct-from-traj.py ...`): rank r computes the
@@ -75,6 +76,16 @@ def build_parser():
                         'eigenvalue, correlation time); with --binary the .npz also holds Cm_w and the eigenvectors.  Windows of at '
                         'most 5461 frames.')
     p.add_argument('--iRED_modes', type=int, dest='ired_modes', default=5, help='[extension] number of global (tumbling) modes of --iRED.')
+    p.add_argument('--crossCt', dest='bDoCrossCt', action='store_true', default=False,
+                   help='[extension, needs --pairs and --tau] time-lagged P2 cross-correlation functions <P2(u_i(t).u_j(t+k))> between pairs of '
+                        'the fitted vectors, chunked by --tau like --Ct: <o>_crossCtint.dat (the format of _Ctint.dat, one block per pair, '
+                        'labelled by the ordinal of the pair; calculate-fitted-Ct.py reads it) and <o>_crossPairs.dat (ordinal, i, j, their '
+                        'residue ids, the equal-time value P0 = <P2(u_i.u_j)> and its standard error over the chunks).  Dot products do '
+                        'not change under a rotation: --vecRot has no effect on these files.  Single process only.')
+    p.add_argument('--pairs', type=str, dest='pairs_fn', default=None,
+                   help='[extension] pair file of --crossCt: two integers per line, 0-based indices into the list of vectors; # starts a comment.')
+    p.add_argument('--asym', dest='bCrossAsym', action='store_true', default=False,
+                   help='[extension] --crossCt writes C_ij and C_ji of every pair as two blocks, one after the other, instead of their mean.')
     return p
 
 
@@ -195,7 +206,10 @@ def load_mdtraj(args, frames_per_chunk_of):
 
 
 def main():
-    args = build_parser().parse_args()
+    parser = build_parser()
+    args = parser.parse_args()
+    if args.bDoCrossCt and args.pairs_fn is None:
+        parser.error('--crossCt needs --pairs FILE')
     time_start = time.time()
     rank, world = srdist.start()
     if args.help_sel:
@@ -204,6 +218,14 @@ def main():
     tau_memory = args.tau
     if args.bDoCt and tau_memory is None:
         print("= = = Refusing to do C(t)-analysis without using a block averaging over memory_time tau!", file=sys.stderr)
+        sys.exit(1)
+    if args.bDoCrossCt and tau_memory is None:
+        print("= = = Refusing to do cross-correlation analysis without using a block averaging over memory_time tau!", file=sys.stderr)
+        sys.exit(1)
+    if args.bDoCrossCt and world > 1:
+        # the ranks hold ranges of vectors and a pair needs both of its vectors
+        print("= = = ERROR: --crossCt needs all vectors on one GPU and does not run under torchrun with more than one rank; "
+              "run it as a single process.", file=sys.stderr)
         sys.exit(1)
     bDoVecDistrib = args.bDoVecDistrib or args.bDoVecHist
     q_rot = None
@@ -336,6 +358,24 @@ def main():
         print("      ...complete.")
     if rv_lab is not None and rv_lab is not rv_fit:
         rv_lab.close()
+    if args.bDoCrossCt:
+        try:
+            pairs = hostct.read_pairs(args.pairs_fn, V)
+        except (OSError, ValueError) as exc:
+            print("= = = ERROR: %s" % exc, file=sys.stderr)
+            sys.exit(1)
+        if args.bCrossAsym:
+            pairs = np.stack((pairs, pairs[:, ::-1]), axis=1).reshape(-1, 2)      # (i, j) then (j, i)
+        print("= = = Conducting cross-correlation analysis of %i pairs of fitted vectors using Palmer's approach." % len(pairs))
+        P0, dP0, Cx, dCx = hostct.calculate_Ct_cross_resident(rv_fit, pairs, R, F, symmetric=not args.bCrossAsym, mode=1 if args.exact else 0,
+                                                              want_dP0=True)
+        ordinals = list(range(1, len(pairs) + 1))
+        gs.print_sxylist(out_pref + '_crossCtint.dat', ordinals, hostct.calculate_dt(deltaT, tau_memory), np.stack((Cx.T, dCx.T), axis=-1))
+        with open(out_pref + '_crossPairs.dat', 'w') as fp:
+            print("# pair i j resid_i resid_j P0 dP0", file=fp)
+            for n, (i, j) in enumerate(pairs):
+                print("%d %d %d %s %s %.8g %.8g" % (ordinals[n], i, j, resXH[i], resXH[j], P0[n], dP0[n]), file=fp)
+        print("      ...complete.")
 
     need_dist = args.bDoVecAverage or args.bDoS2 or (bDoVecDistrib and args.bDoVecHist)
     if need_dist:

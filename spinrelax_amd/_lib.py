@@ -134,6 +134,15 @@ SIGNATURES = {
     # (ctx, soa, Npad, nV, win_start, win_len, W, coef_dev, K, n_lags, Cm_dev) / (ctx, vectors, win_start, win_len, W, coef_host, K, n_lags, Cm_host)
     'sr_ired_mode_ct_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     'sr_vectors_ired_mode_ct_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    # (ctx, soa, Npad, nV, R, F, chunk_start, pair_i, pair_j, nP, sym, mode, psum_ws, P0_dev, dP0_dev, Ct_dev, dCt_dev) /
+    # (ctx, vectors, R, F, chunk_start, pair_i, pair_j, nP, sym, mode, P0_host, [dP0_host,] Ct_host, dCt_host)
+    'sr_ct_cross_max_frames': (c_int64, [c_void_p]),
+    'sr_ct_cross_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'sr_vectors_ct_cross_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p]),
+    'sr_vectors_ct_cross_err_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     'sr_counter': (c_int, [c_void_p, c_char_p, POINTER(ctypes.c_uint64)]),
     'sr_transpose_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'sr_jomega_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
@@ -143,7 +152,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13
+ABI_VERSION = 13      # unchanged by the sr_ct_cross entry points: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -1,0 +1,193 @@
+// sr_ct_cross.hip -- time-lagged P2 cross-correlation between pairs of bond vectors (k_ct_cross), an extension beyond the
+// reference, which only ever correlates a vector with itself:
+//     S_ij[k] = sum_{t=0}^{F-1-k} (u_i(t) . u_j(t+k))^2,   k = 0 .. L = F/2,   per (pair p = (i, j), chunk r)
+// on the Palmer chunk table of kernel 1.  Lags 1 .. L leave as raw sums in kernel 1's layout (pair, chunk, sr_ct_psum_stride(F)) --
+// pairs in the place of vectors -- so k_ct_finalize (sr_ct.hip) turns them into C(t) = mean over chunks of 1.5 S / (F - k) - 0.5 and
+// dC(t) unchanged.  Lag 0, the equal-time <P2(u_i . u_j)> (the rigid-limit P2(cos theta_ij)), sits in slot 0 of the same rows, which
+// the finalizer skips; k_ct_cross_p0 averages it over the chunks.
+//
+// Design:
+//   * one workgroup of 8 waves stages BOTH series of one (pair, chunk) in LDS in the layout of the direct kernel (sr_ct_shift.h):
+//     24 bytes per frame, 101 KB at F = 4096 -- one workgroup per CU, hence 8 waves and not the direct kernel's 4 (at 150 VGPRs a
+//     SIMD holds 3 waves, so a CU holds one such workgroup whatever F is: 8 waves per CU against the direct kernel's 12);
+//   * a wave owns a block of 128 lags and runs the direct kernel's lag-block loop on it, a from series i and b from series j for
+//     S_ij; in the symmetric form (sym = 1, what relaxation theory uses) the same wave runs the loop a second time with the series
+//     exchanged and writes (S_ij + S_ji) / 2: both directions of a lag are summed by one lane in a fixed order, so there are no
+//     atomics and the bits do not change from run to run.  For i = j the symmetric sum is the autocorrelation's, to rounding;
+//   * serpentine assignment of the lag blocks to the waves as in the direct kernel (at F = 4096: 16 blocks, two per wave, equal work);
+//   * lags that do not fill a block, and every lag in the validation mode (mode 1), take a float64 path in the same launch.
+// A chunk whose two series do not fit the LDS is refused (sr_ct_cross_max_frames); a blocked form is not built.
+#include "sr_ct_shift.h"
+
+namespace {
+
+constexpr int kCrossWaves = 8;
+
+struct CtCrossArgs {
+    const float *soa;
+    int64_t Npad;
+    const int64_t *chunk_start;   // device, may be null
+    const int32_t *pair_i, *pair_j;   // device
+    double *psum;                 // (nP, R, Lp)
+    int R, F, Fp, L, Lp, sym, mode;
+};
+
+__global__ __launch_bounds__(kCrossWaves * 64, 2) void k_ct_cross(CtCrossArgs a)
+{
+    extern __shared__ __align__(16) float lds[];
+    const int Fp = a.Fp, Hf = (Fp >> 3) * 12, F = a.F;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int p = blockIdx.x / a.R;
+    const int r = blockIdx.x - p * a.R;
+    float *si = lds, *sj = lds + 2 * Hf;
+
+    // ---- stage the two series ----
+    {
+        const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
+        const float *pi = a.soa + (int64_t)a.pair_i[p] * 3 * a.Npad + start;
+        const float *pj = a.soa + (int64_t)a.pair_j[p] * 3 * a.Npad + start;
+        ct_stage_series<kCrossWaves * 64>(si, pi, pi + a.Npad, pi + 2 * a.Npad, F, Fp, Hf, tid);
+        ct_stage_series<kCrossWaves * 64>(sj, pj, pj + a.Npad, pj + 2 * a.Npad, F, Fp, Hf, tid);
+    }
+    __syncthreads();
+
+    double *out = a.psum + ((int64_t)p * a.R + r) * a.Lp;
+    const int nb = (a.mode == 0) ? (a.L + 1) / kLagBlock : 0;
+    const double scale = a.sym ? 0.5 : 1.0;
+
+    // ---- fast path: full lag blocks (lag 0 included), serpentine assignment balances the (F - lag) work ----
+    int g, l16;
+    lane_to_strip(lane, g, l16);
+    for (int i = 0; i * kCrossWaves < nb; ++i) {
+        const int k = (i & 1) ? i * kCrossWaves + (kCrossWaves - 1 - wave) : i * kCrossWaves + wave;
+        if (k >= nb) continue;
+        const int dw = k * kLagBlock;
+        double acc64[kLagsPerLane];
+#pragma unroll
+        for (int d = 0; d < kLagsPerLane; ++d) acc64[d] = 0.0;
+        ct_shift_block(si, sj, Hf, F, dw, g, l16, acc64);                 // S_ij
+        if (a.sym) ct_shift_block(sj, si, Hf, F, dw, g, l16, acc64);      // + S_ji
+        ct_combine_strips(acc64, l16);
+        if (g == 0) {
+            double *o = out + dw + kLagsPerLane * l16;
+#pragma unroll
+            for (int d = 0; d < kLagsPerLane; ++d) o[d] = scale * acc64[d];
+        }
+    }
+
+    // ---- float64 path: remaining lags (and every lag in validation mode) ----
+    for (int d = nb * kLagBlock + wave; d <= a.L; d += kCrossWaves) {
+        double s = 0.0;
+        for (int t = lane; t + d < F; t += 64) {
+            const int pa = lds_pos(t, 0, Hf), pb = lds_pos(t + d, 0, Hf);
+            const double x = (double)si[pa] * (double)sj[pb] + (double)si[pa + 4] * (double)sj[pb + 4] +
+                             (double)si[pa + 8] * (double)sj[pb + 8];
+            s += x * x;
+            if (a.sym) {
+                const double y = (double)sj[pa] * (double)si[pb] + (double)sj[pa + 4] * (double)si[pb + 4] +
+                                 (double)sj[pa + 8] * (double)si[pb + 8];
+                s += y * y;
+            }
+        }
+        s = wave_sum_f64(s);
+        if (lane == 0) out[d] = scale * s;
+    }
+}
+
+// P0[p] = mean over the chunks of 1.5 S[p][r][0] / F - 0.5, summed in chunk order; dP0[p] (may be null) = their two-pass standard
+// deviation / (sqrt(R) - 1), the formula of k_ct_finalize
+__global__ __launch_bounds__(256) void k_ct_cross_p0(const double *__restrict__ psum, int R, int F, int Lp, int64_t nP, double *__restrict__ P0,
+                                                     double *__restrict__ dP0)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= nP) return;
+    const double *s = psum + p * R * Lp;
+    double m = 0.0;
+    for (int r = 0; r < R; ++r) m += 1.5 * (s[(int64_t)r * Lp] / (double)F) - 0.5;
+    m /= (double)R;
+    P0[p] = m;
+    if (!dP0) return;
+    double v = 0.0;
+    for (int r = 0; r < R; ++r) {
+        const double e = (1.5 * (s[(int64_t)r * Lp] / (double)F) - 0.5) - m;
+        v += e * e;
+    }
+    dP0[p] = sqrt(v / (double)R) / (sqrt((double)R) - 1.0);
+}
+
+size_t cross_lds_bytes(int64_t F) { return 2 * sr_ct_direct_lds_bytes(F); }
+
+int64_t cross_max_frames(size_t lds_limit)
+{
+    int64_t F = (int64_t)lds_limit / 24 - kPad;         // an upper bound: ct_Fp(F) >= F + kPad
+    while (F >= 2 && cross_lds_bytes(F) > lds_limit) --F;
+    return F >= 2 ? F : 0;
+}
+
+}  // namespace
+
+int sr_ct_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                      const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode)
+{
+    SR_REQUIRE(pair_i && pair_j, -2, "%s: null pointer", who);
+    SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1 && nP >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld nP=%lld", who, (long long)R, (long long)F,
+               (long long)nV, (long long)nP);
+    SR_REQUIRE((mode == 0 || mode == 1) && (sym == 0 || sym == 1), -3, "%s: mode and sym must be 0 or 1", who);
+    SR_REQUIRE(cross_lds_bytes(F) <= sr_lds_limit(ctx), -4,
+               "%s: the two series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (no blocked form for cross-correlations)",
+               who, (long long)F, cross_lds_bytes(F), sr_lds_limit(ctx), (long long)cross_max_frames(sr_lds_limit(ctx)));
+    SR_REQUIRE(R * nP < (int64_t)1 << 30, -3, "%s: too many series", who);
+    if (chunk_start_host) {
+        for (int64_t r = 0; r < R; ++r)
+            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= frames, -3, "%s: chunk %lld start %lld out of range", who,
+                       (long long)r, (long long)chunk_start_host[r]);
+    } else {
+        SR_REQUIRE(R * F <= frames, -3, "%s: R*F=%lld exceeds the %lld frames held", who, (long long)(R * F), (long long)frames);
+    }
+    for (int64_t p = 0; p < nP; ++p)
+        SR_REQUIRE(pair_i[p] >= 0 && pair_i[p] < nV && pair_j[p] >= 0 && pair_j[p] < nV, -3, "%s: pair %lld = (%d, %d) is outside the %lld vectors",
+                   who, (long long)p, (int)pair_i[p], (int)pair_j[p], (long long)nV);
+    return 0;
+}
+
+extern "C" {
+
+int64_t sr_ct_cross_max_frames(sr_ctx *ctx)
+{
+    if (!ctx) return -1;
+    return cross_max_frames(sr_lds_limit(ctx));
+}
+
+int sr_ct_cross_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                        const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode, double *psum_ws,
+                        double *P0, double *dP0, double *Ct, double *dCt)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(soa && P0 && Ct && dCt, -2, "sr_ct_cross_f32_dev: null pointer");
+    if (int rc = sr_ct_cross_check(ctx, "sr_ct_cross_f32_dev", Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode)) return rc;
+    const int64_t Lp = sr_ct_psum_stride(F);
+    double *psum = psum_ws;
+    if (!psum) {
+        psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(nP * R * Lp) * sizeof(double));
+        if (!psum) return -5;
+    }
+    // ---- stage the chunk starts and the pair table ----
+    sr_stage st(ctx);
+    st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 2 * (size_t)nP * sizeof(int32_t));
+    CtCrossArgs a;
+    a.chunk_start = st.put(chunk_start_host, (size_t)R);
+    a.pair_i = st.put(pair_i_host, (size_t)nP);
+    a.pair_j = st.put(pair_j_host, (size_t)nP);
+    if (int rc = st.finish()) return rc;            // small tables: the caller's arrays are free again when this returns
+    // ---- launch ----
+    a.soa = soa; a.Npad = Npad; a.psum = psum;
+    a.R = (int)R; a.F = (int)F; a.Fp = (int)(sr_ct_direct_lds_bytes(F) / 12); a.L = (int)(F / 2); a.Lp = (int)Lp; a.sym = sym; a.mode = mode;
+    if (int rc = sr_launch(ctx, k_ct_cross, dim3((unsigned)(nP * R)), dim3(kCrossWaves * 64), cross_lds_bytes(F), a)) return rc;
+    hipLaunchKernelGGL(k_ct_cross_p0, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, ctx->stream, psum, (int)R, (int)F, (int)Lp, nP, P0, dP0);
+    SR_HIP(hipGetLastError());
+    return sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt);
+}
+
+}  // extern "C"

@@ -120,6 +120,11 @@ int64_t sr_ct_direct_max_frames(size_t lds_limit);
 int sr_launch_ct_fft64(sr_ctx *ctx, const sr_ct_job &job);
 int sr_launch_ct_rfft64(sr_ctx *ctx, const sr_ct_job &job);
 
+// sr_ct_cross.hip: what both entry points of the pair cross-correlation refuse, before anything is queued: shapes, a chunk whose two
+// series do not fit the LDS (-4), chunk starts and pair indices outside the `frames` frames / nV vectors held (-3)
+int sr_ct_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                      const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode);
+
 // sr_ired_modes.hip
 #define SR_IRED_WS_MB 1024
 int sr_ired_mode_ct_check(const char *who, int64_t frames, int64_t nV, const int64_t *win_start_host, const int64_t *win_len_host, int W, int K,

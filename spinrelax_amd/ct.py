@@ -94,6 +94,73 @@ def calculate_Ct_from_files(vec_list, dt, tau, ctx=None, mode=0, v0=0, nV=None):
     return _ctx(ctx).ct_palmer(cat, R, F, v0=v0, nV=nV, chunk_start=starts, mode=mode)
 
 
+def read_pairs(path, nV):
+    """The pair file of --crossCt: one pair per line, two integers, indices into the list of nV vectors (0-based); blank lines and
+    everything behind a '#' are ignored.  Returns an (nP, 2) int32 array.  Pure parsing: a malformed line, an index outside
+    [0, nV) and a file without pairs raise ValueError, before any device call."""
+    pairs = []
+    with open(path) as fp:
+        for n, line in enumerate(fp, 1):
+            tok = line.split('#', 1)[0].split()
+            if not tok:
+                continue
+            try:
+                if len(tok) != 2:
+                    raise ValueError
+                i, j = int(tok[0]), int(tok[1])
+            except ValueError:
+                raise ValueError('%s line %d: expected two integers, got %r' % (path, n, line.rstrip('\n'))) from None
+            if not (0 <= i < nV and 0 <= j < nV):
+                raise ValueError('%s line %d: pair (%d, %d) is outside the %d vectors (indices are 0 .. %d)' % (path, n, i, j, nV, nV - 1))
+            pairs.append((i, j))
+    if not pairs:
+        raise ValueError('%s holds no pairs' % path)
+    return np.array(pairs, dtype=np.int32)
+
+
+def _check_pairs(pairs, nV):
+    """shape, type and range of a pair table, before any device call"""
+    return np.stack(hip.pair_columns(pairs, nV), axis=1)
+
+
+def calculate_Ct_cross(vecs, pairs, symmetric=True, ctx=None, mode=0):
+    """Time-lagged P2 cross-correlation functions between pairs of vectors, C_ij(k) = <P2(u_i(t) . u_j(t + k))>, an extension beyond
+    the reference.  vecs (nReplicates, nFrames, nVectors, 3) as calculate_Ct_Palmer takes them, pairs (nP, 2) indices into the vectors.
+    Returns P0 (nP), the equal-time value <P2(u_i . u_j)>, and Ct, dCt (nFrames // 2, nP) for the lags 1 .. nFrames // 2: mean over
+    the replicates and std / (sqrt(nReplicates) - 1) like C(t).  symmetric (the default): (C_ij + C_ji) / 2, the function relaxation
+    theory uses, equal to the autocorrelation for i = j; otherwise C_ij alone, the later frame taken from vector j."""
+    sh = np.shape(vecs)
+    if len(sh) != 4 or sh[3] != 3:
+        raise ValueError('vecs must be (replicates, frames, vectors, 3), got %s' % (sh,))
+    R, F, V = sh[0], sh[1], sh[2]
+    pairs = _check_pairs(pairs, V)
+    flat = np.ascontiguousarray(vecs, dtype=np.float32).reshape(R * F, V, 3)
+    with _ctx(ctx).vectors(V, R * F) as rv:
+        rv.append(flat)
+        return rv.ct_cross(R, F, pairs, sym=int(bool(symmetric)), mode=mode)
+
+
+def calculate_Ct_cross_from_files(vec_list, dt, tau, pairs, symmetric=True, ctx=None, mode=0):
+    """calculate_Ct_cross on the chunks reformat_vecs_by_tau would form from the files (concat_with_chunk_starts: the tail of every
+    file that does not fill a chunk of int(tau / dt) frames is skipped, exactly as for C(t))."""
+    F = int(tau / dt)
+    cat, starts, R = concat_with_chunk_starts(vec_list, F)
+    if R < 1:
+        raise ValueError('no trajectory holds a full block of memory time tau')
+    pairs = _check_pairs(pairs, cat.shape[1])
+    with _ctx(ctx).vectors(cat.shape[1], cat.shape[0]) as rv:
+        rv.append(cat)
+        return rv.ct_cross(R, F, pairs, chunk_start=starts, sym=int(bool(symmetric)), mode=mode)
+
+
+def calculate_Ct_cross_resident(rv, pairs, R, F, symmetric=True, mode=0, chunk_start=None, want_dP0=False):
+    """calculate_Ct_cross of resident vectors (regular chunks r * F unless chunk_start is given).  A pair needs both of its vectors on
+    one GPU: rv holds ALL vectors (a single process), not a rank's range.  want_dP0: (P0, dP0, Ct, dCt), dP0 the error of P0 over the
+    chunks, std / (sqrt(R) - 1) like dCt."""
+    pairs = _check_pairs(pairs, rv.nV)
+    return rv.ct_cross(R, F, pairs, chunk_start=chunk_start, sym=int(bool(symmetric)), mode=mode, want_dP0=want_dP0)
+
+
 def upload_shard(vec_list, frames_per_chunk=None, ctx=None):
     """The product path's single upload: this rank's vector range (srdist.my_range; everything in a single process) of the
     files' vectors, each file cut to whole chunks of frames_per_chunk frames when given (reformat_vecs_by_tau,

@@ -26,6 +26,17 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def pair_columns(pairs, nV=None):
+    """(nP, 2) vector indices -> the two contiguous int32 columns the C ABI takes; with nV, indices outside [0, nV) raise
+    ValueError here (otherwise the library refuses them)"""
+    pr = np.asarray(pairs)
+    if pr.ndim != 2 or pr.shape[1] != 2 or pr.shape[0] < 1 or not np.issubdtype(pr.dtype, np.integer):
+        raise ValueError('pairs must be an integer array of shape (nP, 2), nP >= 1')
+    if nV is not None and (pr.min() < 0 or pr.max() >= nV):
+        raise ValueError('pairs hold an index outside the %d vectors' % nV)
+    return np.ascontiguousarray(pr[:, 0], dtype=np.int32), np.ascontiguousarray(pr[:, 1], dtype=np.int32)
+
+
 def _windows(win_start, win_len):
     ws = np.ascontiguousarray(np.atleast_1d(win_start), dtype=np.int64)
     wl = np.ascontiguousarray(np.atleast_1d(win_len), dtype=np.int64)
@@ -173,6 +184,20 @@ class Context:
 
     def psum_stride(self, F):
         return int(self.lib.sr_ct_psum_stride(F))
+
+    # ---- pair cross-correlation functions (sr_ct_cross.hip) ----
+    def ct_cross_max_frames(self):
+        """longest chunk whose two series fit the LDS of a workgroup (sr_ct_cross_max_frames)"""
+        return int(self.lib.sr_ct_cross_max_frames(self.h))
+
+    def ct_cross_dev(self, soa_ptr, Npad, nV, R, F, pairs, P0_ptr, Ct_ptr, dCt_ptr, chunk_start=None, sym=1, mode=0, psum_ptr=None,
+                     dP0_ptr=None):
+        """P0 (nP) (and its error dP0 when dP0_ptr is given), C(t) and dC(t) (F//2, nP) of the pairs (nP, 2) from packed planes into
+        device arrays (sr_ct_cross_f32_dev); asynchronous on the context's stream"""
+        pi, pj = pair_columns(pairs)
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        check(self.lib.sr_ct_cross_f32_dev(self.h, soa_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
+                                           int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr), 'sr_ct_cross_f32_dev')
 
     # ---- iRED matrix (sr_ired.hip) ----
     def ired_matrix_dev(self, soa_ptr, Npad, nV, win_start, win_len, M_ptr):
@@ -652,6 +677,27 @@ class ResidentVectors:
         check(self.ctx.lib.sr_vectors_ct_f32(self.ctx.h, self.h, int(R), int(F), _ptr(cs), int(mode), _ptr(Ct), _ptr(dCt)),
               'sr_vectors_ct_f32')
         return Ct, dCt
+
+    def ct_cross(self, R, F, pairs, chunk_start=None, sym=1, mode=0, want_dP0=False):
+        """time-lagged P2 cross-correlation of the pairs (nP, 2) of resident vectors (sr_vectors_ct_cross_f32): P0 (nP) the equal-time
+        <P2(u_i . u_j)>, Ct and dCt (F//2, nP) = <P2(u_i(t) . u_j(t + k))>, k = 1 .. F//2, mean and error over the R chunks like ct();
+        sym = 1: the mean of C_ij and C_ji.  want_dP0: (P0, dP0, Ct, dCt), dP0 the error of P0 over the chunks (sr_vectors_ct_cross_err_f32)"""
+        pi, pj = pair_columns(pairs)
+        L = F // 2
+        P0 = np.empty(pi.size)
+        Ct = np.empty((L, pi.size))
+        dCt = np.empty((L, pi.size))
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        if cs is not None and cs.shape != (R,):
+            raise ValueError('chunk_start must have R entries')
+        if want_dP0:
+            dP0 = np.empty(pi.size)
+            check(self.ctx.lib.sr_vectors_ct_cross_err_f32(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
+                                                           int(mode), _ptr(P0), _ptr(dP0), _ptr(Ct), _ptr(dCt)), 'sr_vectors_ct_cross_err_f32')
+            return P0, dP0, Ct, dCt
+        check(self.ctx.lib.sr_vectors_ct_cross_f32(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
+                                                   int(mode), _ptr(P0), _ptr(Ct), _ptr(dCt)), 'sr_vectors_ct_cross_f32')
+        return P0, Ct, dCt
 
     def ct_sums(self, R, F, chunk_start=None, mode=0):
         """raw sums S[v, r, d-1] = sum_j (u_j . u_{j+d})^2 of the R chunks held, (nV, R, F//2) float64 (replicate sharding)"""

@@ -332,7 +332,7 @@ int sr_vectors_ired_mode_ct_f32(sr_ctx *, sr_vectors *, const int64_t *win_start
  *   dP0 (nP)     its error over the chunks by the same formula as dC (optional, may be NULL)
  *   Ct, dCt      (L, nP) float64, lags 1 .. L like kernel 1
  * One workgroup stages both series of a (pair, chunk) in LDS, 24 bytes per frame: F up to sr_ct_cross_max_frames() (6624 with the
- * 160 KiB of gfx950); a longer chunk is refused with -4 (there is no blocked form).  The pair tables are HOST arrays, consumed on
+ * 160 KiB of gfx950); a longer chunk is refused with -4 (the sr_*ct_cross_long_* functions below take it).  The pair tables are HOST arrays, consumed on
  * return; an index outside [0, nV) is refused with -3.  Every refusal comes before anything is launched.
  * _dev: packed planes in, P0 / dP0 / Ct / dCt DEVICE arrays, asynchronous behind the upload of the tables; psum_ws (optional, may be NULL):
  * (nP, R, sr_ct_psum_stride(F)) float64 raw sums, S[0] in slot 0.  sr_vectors_: kernel 0 once per object, results on the HOST, blocking; _err_ is the same call
@@ -347,6 +347,24 @@ int sr_vectors_ct_cross_f32(sr_ctx *, sr_vectors *, int64_t R, int64_t F, const 
 int sr_vectors_ct_cross_err_f32(sr_ctx *, sr_vectors *, int64_t R, int64_t F, const int64_t *chunk_start_host,
                                 const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode,
                                 double *P0, double *dP0, double *Ct, double *dCt);
+
+/* The same functions for longer chunks (sr_ct_cross_long.hip): the blocked transforms of kernel 1's long form on the two series of a
+ * pair, 5462 <= F <= sr_ct_cross_long_max_frames() = 262144 frames per chunk; a longer chunk is refused with -4, a shorter one with -3,
+ * a pair index outside the vectors with -3, all before anything is launched.  Arguments and results as the functions above.  Mode 0:
+ * float32 block transforms (once per (vector, chunk) that the pairs name), float64 from the cross-spectra on, lag 0 a float64 sum;
+ * mode 1: the definition in float64, lag by lag.  No atomics: equal input gives bit-equal output, whatever "ct_long_ws_mb" tiles.
+ * Each entry point runs its own kernel at every length it takes; choosing between the two is the caller's (spinrelax_amd/ct.py goes by
+ * sr_set_option("ct_cross_long_min_frames", F0): 5462 .. 262144, default 6625, the first length the functions above refuse). */
+int64_t sr_ct_cross_long_max_frames(sr_ctx *);
+int sr_ct_cross_long_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                             const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode, double *psum_ws,
+                             double *P0, double *dP0, double *Ct, double *dCt);
+int sr_vectors_ct_cross_long_f32(sr_ctx *, sr_vectors *, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                 const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode,
+                                 double *P0, double *Ct, double *dCt);
+int sr_vectors_ct_cross_long_err_f32(sr_ctx *, sr_vectors *, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                     const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode,
+                                     double *P0, double *dP0, double *Ct, double *dCt);
 
 /* ---- kernel 3b: multi-exponential C(t) model --------------------------------------------
  * Model of curvefit_exponential (fitting_Ct_functions.py:419-427): params = [C_1..C_K, tau_1..tau_K

@@ -81,7 +81,8 @@ def build_parser():
                         'the fitted vectors, chunked by --tau like --Ct: <o>_crossCtint.dat (the format of _Ctint.dat, one block per pair, '
                         'labelled by the ordinal of the pair; calculate-fitted-Ct.py reads it) and <o>_crossPairs.dat (ordinal, i, j, their '
                         'residue ids, the equal-time value P0 = <P2(u_i.u_j)> and its standard error over the chunks).  Dot products do '
-                        'not change under a rotation: --vecRot has no effect on these files.  Single process only.')
+                        'not change under a rotation: --vecRot has no effect on these files.  Any --tau that --Ct accepts (up to '
+                        '262144 frames per chunk: long chunks run by blocked transforms).  Single process only.')
     p.add_argument('--pairs', type=str, dest='pairs_fn', default=None,
                    help='[extension] pair file of --crossCt: two integers per line, 0-based indices into the list of vectors; # starts a comment.')
     p.add_argument('--asym', dest='bCrossAsym', action='store_true', default=False,

@@ -143,6 +143,14 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p]),
     'sr_vectors_ct_cross_err_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the blocked form for longer chunks (sr_ct_cross_long.hip): the same arguments
+    'sr_ct_cross_long_max_frames': (c_int64, [c_void_p]),
+    'sr_ct_cross_long_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'sr_vectors_ct_cross_long_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                             c_void_p, c_void_p, c_void_p]),
+    'sr_vectors_ct_cross_long_err_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     'sr_counter': (c_int, [c_void_p, c_char_p, POINTER(ctypes.c_uint64)]),
     'sr_transpose_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'sr_jomega_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),

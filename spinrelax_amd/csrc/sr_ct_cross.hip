@@ -16,7 +16,8 @@
 //     atomics and the bits do not change from run to run.  For i = j the symmetric sum is the autocorrelation's, to rounding;
 //   * serpentine assignment of the lag blocks to the waves as in the direct kernel (at F = 4096: 16 blocks, two per wave, equal work);
 //   * lags that do not fill a block, and every lag in the validation mode (mode 1), take a float64 path in the same launch.
-// A chunk whose two series do not fit the LDS is refused (sr_ct_cross_max_frames); a blocked form is not built.
+// A chunk whose two series do not fit the LDS is refused here (sr_ct_cross_max_frames); the entry points sr_*ct_cross_long_* give such
+// chunks to the blocked form (sr_ct_cross_long.hip).
 #include "sr_ct_shift.h"
 
 namespace {
@@ -129,15 +130,22 @@ int64_t cross_max_frames(size_t lds_limit)
 }  // namespace
 
 int sr_ct_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                      const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode)
+                      const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, int blocked)
 {
     SR_REQUIRE(pair_i && pair_j, -2, "%s: null pointer", who);
     SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1 && nP >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld nP=%lld", who, (long long)R, (long long)F,
                (long long)nV, (long long)nP);
     SR_REQUIRE((mode == 0 || mode == 1) && (sym == 0 || sym == 1), -3, "%s: mode and sym must be 0 or 1", who);
-    SR_REQUIRE(cross_lds_bytes(F) <= sr_lds_limit(ctx), -4,
-               "%s: the two series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (no blocked form for cross-correlations)",
-               who, (long long)F, cross_lds_bytes(F), sr_lds_limit(ctx), (long long)cross_max_frames(sr_lds_limit(ctx)));
+    if (blocked) {
+        SR_REQUIRE(F <= SR_CT_LONG_MAX_FRAMES, -4, "%s: the blocked form takes chunks of at most %d frames, F=%lld", who, SR_CT_LONG_MAX_FRAMES,
+                   (long long)F);
+        SR_REQUIRE(F >= SR_CT_CROSS_LONG_FLOOR, -3, "%s: the blocked form takes chunks of at least %d frames, F=%lld", who,
+                   SR_CT_CROSS_LONG_FLOOR, (long long)F);
+    } else {
+        SR_REQUIRE(cross_lds_bytes(F) <= sr_lds_limit(ctx), -4,
+                   "%s: the two series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (no blocked form for cross-correlations)",
+                   who, (long long)F, cross_lds_bytes(F), sr_lds_limit(ctx), (long long)cross_max_frames(sr_lds_limit(ctx)));
+    }
     SR_REQUIRE(R * nP < (int64_t)1 << 30, -3, "%s: too many series", who);
     if (chunk_start_host) {
         for (int64_t r = 0; r < R; ++r)
@@ -160,34 +168,60 @@ int64_t sr_ct_cross_max_frames(sr_ctx *ctx)
     return cross_max_frames(sr_lds_limit(ctx));
 }
 
-int sr_ct_cross_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                        const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode, double *psum_ws,
-                        double *P0, double *dP0, double *Ct, double *dCt)
+static int cross_f32_dev(sr_ctx *ctx, const char *who, int blocked, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F,
+                         const int64_t *chunk_start_host, const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode,
+                         double *psum_ws, double *P0, double *dP0, double *Ct, double *dCt)
 {
     SR_CHECK_CTX(ctx);
-    SR_REQUIRE(soa && P0 && Ct && dCt, -2, "sr_ct_cross_f32_dev: null pointer");
-    if (int rc = sr_ct_cross_check(ctx, "sr_ct_cross_f32_dev", Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode)) return rc;
+    SR_REQUIRE(soa && P0 && Ct && dCt, -2, "%s: null pointer", who);
+    if (int rc = sr_ct_cross_check(ctx, who, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, blocked)) return rc;
     const int64_t Lp = sr_ct_psum_stride(F);
     double *psum = psum_ws;
     if (!psum) {
         psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(nP * R * Lp) * sizeof(double));
         if (!psum) return -5;
     }
-    // ---- stage the chunk starts and the pair table ----
-    sr_stage st(ctx);
-    st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 2 * (size_t)nP * sizeof(int32_t));
-    CtCrossArgs a;
-    a.chunk_start = st.put(chunk_start_host, (size_t)R);
-    a.pair_i = st.put(pair_i_host, (size_t)nP);
-    a.pair_j = st.put(pair_j_host, (size_t)nP);
-    if (int rc = st.finish()) return rc;            // small tables: the caller's arrays are free again when this returns
-    // ---- launch ----
-    a.soa = soa; a.Npad = Npad; a.psum = psum;
-    a.R = (int)R; a.F = (int)F; a.Fp = (int)(sr_ct_direct_lds_bytes(F) / 12); a.L = (int)(F / 2); a.Lp = (int)Lp; a.sym = sym; a.mode = mode;
-    if (int rc = sr_launch(ctx, k_ct_cross, dim3((unsigned)(nP * R)), dim3(kCrossWaves * 64), cross_lds_bytes(F), a)) return rc;
+    if (blocked) {
+        if (int rc = sr_launch_ct_cross_long(ctx, soa, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, psum)) return rc;
+    } else {
+        // ---- stage the chunk starts and the pair table ----
+        sr_stage st(ctx);
+        st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 2 * (size_t)nP * sizeof(int32_t));
+        CtCrossArgs a;
+        a.chunk_start = st.put(chunk_start_host, (size_t)R);
+        a.pair_i = st.put(pair_i_host, (size_t)nP);
+        a.pair_j = st.put(pair_j_host, (size_t)nP);
+        if (int rc = st.finish()) return rc;            // small tables: the caller's arrays are free again when this returns
+        // ---- launch ----
+        a.soa = soa; a.Npad = Npad; a.psum = psum;
+        a.R = (int)R; a.F = (int)F; a.Fp = (int)(sr_ct_direct_lds_bytes(F) / 12); a.L = (int)(F / 2); a.Lp = (int)Lp; a.sym = sym; a.mode = mode;
+        if (int rc = sr_launch(ctx, k_ct_cross, dim3((unsigned)(nP * R)), dim3(kCrossWaves * 64), cross_lds_bytes(F), a)) return rc;
+    }
     hipLaunchKernelGGL(k_ct_cross_p0, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, ctx->stream, psum, (int)R, (int)F, (int)Lp, nP, P0, dP0);
     SR_HIP(hipGetLastError());
     return sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt);
+}
+
+int sr_ct_cross_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                        const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode, double *psum_ws,
+                        double *P0, double *dP0, double *Ct, double *dCt)
+{
+    return cross_f32_dev(ctx, "sr_ct_cross_f32_dev", 0, soa, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, psum_ws, P0,
+                         dP0, Ct, dCt);
+}
+
+int64_t sr_ct_cross_long_max_frames(sr_ctx *ctx)
+{
+    if (!ctx) return -1;
+    return SR_CT_LONG_MAX_FRAMES;
+}
+
+int sr_ct_cross_long_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                             const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode, double *psum_ws,
+                             double *P0, double *dP0, double *Ct, double *dCt)
+{
+    return cross_f32_dev(ctx, "sr_ct_cross_long_f32_dev", 1, soa, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, psum_ws,
+                         P0, dP0, Ct, dCt);
 }
 
 }  // extern "C"

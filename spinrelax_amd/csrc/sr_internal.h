@@ -29,6 +29,8 @@ struct sr_ctx {
     int ct_long_ws_mb;  // blocked C(t) (sr_ct_long.hip): the series of a launch go in tiles whose block spectra fit this many MiB
     int ct_long_min_frames;   // blocked C(t): beyond one transform (F + L > 8192), chunks of at least this many frames take it, and the
                         // shorter ones that the direct kernel cannot stage; default SR_CT_LONG_MIN_FRAMES
+    int ct_cross_long_min_frames;   // pair cross-correlation: spinrelax_amd/ct.py gives chunks of at least this many frames to the blocked form
+                        // (sr_ct_cross_long.hip); the library's entry points do not dispatch, each runs its own kernel
     int ired_ksplit;    // iRED matrix (sr_ired.hip): workgroups that share a window's frames per tile pair; 0 (default) = sr_ired_ksplit()'s rule
     int ired_ws_mb;     // iRED mode correlation functions (sr_ired_modes.hip): the windows of a call go in batches whose amplitudes fit this many MiB
     int fft_table_ready;
@@ -120,10 +122,18 @@ int64_t sr_ct_direct_max_frames(size_t lds_limit);
 int sr_launch_ct_fft64(sr_ctx *ctx, const sr_ct_job &job);
 int sr_launch_ct_rfft64(sr_ctx *ctx, const sr_ct_job &job);
 
-// sr_ct_cross.hip: what both entry points of the pair cross-correlation refuse, before anything is queued: shapes, a chunk whose two
-// series do not fit the LDS (-4), chunk starts and pair indices outside the `frames` frames / nV vectors held (-3)
+// sr_ct_cross.hip: what the entry points of the pair cross-correlation refuse, before anything is queued: shapes, a chunk whose two
+// series do not fit the LDS (-4; blocked = 1: a chunk of more than SR_CT_LONG_MAX_FRAMES frames, and -3 below SR_CT_CROSS_LONG_FLOOR),
+// chunk starts and pair indices outside the `frames` frames / nV vectors held (-3)
 int sr_ct_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                      const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode);
+                      const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, int blocked);
+
+// sr_ct_cross_long.hip: the blocked form of the pair cross-correlation (raw sums in kernel 1's layout, lag 0 in slot 0), for what
+// sr_ct_cross_check(blocked = 1) admits: the range in which the kernels it shares with sr_ct_long.hip are tested
+#define SR_CT_CROSS_LONG_FLOOR 5462
+#define SR_CT_CROSS_LONG_MIN_FRAMES 6625   /* default of "ct_cross_long_min_frames": the first length k_ct_cross cannot stage */
+int sr_launch_ct_cross_long(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                            const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *psum);
 
 // sr_ired_modes.hip
 #define SR_IRED_WS_MB 1024

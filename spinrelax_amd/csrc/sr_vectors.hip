@@ -288,27 +288,22 @@ int sr_vectors_ct_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, const in
     return 0;
 }
 
-int sr_vectors_ct_cross_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, const int64_t *chunk_start_host, const int32_t *pair_i,
-                            const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *Ct, double *dCt)
-{
-    return sr_vectors_ct_cross_err_f32(ctx, h, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, P0, nullptr, Ct, dCt);
-}
-
-int sr_vectors_ct_cross_err_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, const int64_t *chunk_start_host, const int32_t *pair_i,
-                                const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0, double *Ct, double *dCt)
+static int vectors_ct_cross(sr_ctx *ctx, const char *who, int blocked, sr_vectors *h, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                            const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0, double *Ct,
+                            double *dCt)
 {
     SR_CHECK_CTX(ctx);
-    SR_REQUIRE(h && P0 && Ct && dCt, -2, "sr_vectors_ct_cross_f32: null pointer");
+    SR_REQUIRE(h && P0 && Ct && dCt, -2, "%s: null pointer", who);
     // refusals come before kernel 0: a bad pair table or a chunk that does not fit launches nothing
-    if (int rc = sr_ct_cross_check(ctx, "sr_vectors_ct_cross_f32", h->N, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode)) return rc;
+    if (int rc = sr_ct_cross_check(ctx, who, h->N, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, blocked)) return rc;
     if (int rc = pack(ctx, h)) return rc;
     const int64_t L = F / 2;
     double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nP) * sizeof(double));
     double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * nP) * sizeof(double));
     double *P0_d = (double *)sr_workspace(ctx, SR_WS_OUT2, 2 * (size_t)nP * sizeof(double));        // P0 | dP0
     if (!Ct_d || !dCt_d || !P0_d) return -5;
-    int rc = sr_ct_cross_f32_dev(ctx, h->soa, h->Npad, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, nullptr, P0_d,
-                                 dP0 ? P0_d + nP : nullptr, Ct_d, dCt_d);
+    int rc = (blocked ? sr_ct_cross_long_f32_dev : sr_ct_cross_f32_dev)(ctx, h->soa, h->Npad, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym,
+                                                                        mode, nullptr, P0_d, dP0 ? P0_d + nP : nullptr, Ct_d, dCt_d);
     if (rc) return rc;
     SR_HIP(hipMemcpyAsync(P0, P0_d, (size_t)nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (dP0) SR_HIP(hipMemcpyAsync(dP0, P0_d + nP, (size_t)nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -316,6 +311,30 @@ int sr_vectors_ct_cross_err_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F
     SR_HIP(hipMemcpyAsync(dCt, dCt_d, (size_t)(L * nP) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SR_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+int sr_vectors_ct_cross_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, const int64_t *chunk_start_host, const int32_t *pair_i,
+                            const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *Ct, double *dCt)
+{
+    return vectors_ct_cross(ctx, "sr_vectors_ct_cross_f32", 0, h, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, P0, nullptr, Ct, dCt);
+}
+
+int sr_vectors_ct_cross_err_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, const int64_t *chunk_start_host, const int32_t *pair_i,
+                                const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0, double *Ct, double *dCt)
+{
+    return vectors_ct_cross(ctx, "sr_vectors_ct_cross_f32", 0, h, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, P0, dP0, Ct, dCt);
+}
+
+int sr_vectors_ct_cross_long_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, const int64_t *chunk_start_host, const int32_t *pair_i,
+                                 const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *Ct, double *dCt)
+{
+    return vectors_ct_cross(ctx, "sr_vectors_ct_cross_long_f32", 1, h, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, P0, nullptr, Ct, dCt);
+}
+
+int sr_vectors_ct_cross_long_err_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, const int64_t *chunk_start_host, const int32_t *pair_i,
+                                     const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0, double *Ct, double *dCt)
+{
+    return vectors_ct_cross(ctx, "sr_vectors_ct_cross_long_f32", 1, h, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, P0, dP0, Ct, dCt);
 }
 
 /* raw sums S[v][r][d-1] = sum_j (u_j . u_{j+d})^2 per (vector, chunk, lag) on the HOST, (nV, R, L) compact: what a rank that

@@ -123,6 +123,19 @@ def _check_pairs(pairs, nV):
     return np.stack(hip.pair_columns(pairs, nV), axis=1)
 
 
+def _ct_cross(rv, R, F, pairs, **kw):
+    """The dispatch of the pair cross-correlation: chunks that k_ct_cross can stage go to it (rv.ct_cross), longer ones -- and, under
+    sr_set_option("ct_cross_long_min_frames", n), every chunk of at least n frames -- to the blocked form (rv.ct_cross_long)."""
+    c = rv.ctx
+    direct_max, long_max = c.ct_cross_max_frames(), c.ct_cross_long_max_frames()
+    if F > long_max:
+        raise ValueError('cross-correlation functions: a chunk of %d frames is beyond both forms (the staged kernel takes %d frames, the '
+                         'blocked transforms %d)' % (F, direct_max, long_max))
+    if F > direct_max or F >= c.ct_cross_long_min_frames:
+        return rv.ct_cross_long(R, F, pairs, **kw)
+    return rv.ct_cross(R, F, pairs, **kw)
+
+
 def calculate_Ct_cross(vecs, pairs, symmetric=True, ctx=None, mode=0):
     """Time-lagged P2 cross-correlation functions between pairs of vectors, C_ij(k) = <P2(u_i(t) . u_j(t + k))>, an extension beyond
     the reference.  vecs (nReplicates, nFrames, nVectors, 3) as calculate_Ct_Palmer takes them, pairs (nP, 2) indices into the vectors.
@@ -137,7 +150,7 @@ def calculate_Ct_cross(vecs, pairs, symmetric=True, ctx=None, mode=0):
     flat = np.ascontiguousarray(vecs, dtype=np.float32).reshape(R * F, V, 3)
     with _ctx(ctx).vectors(V, R * F) as rv:
         rv.append(flat)
-        return rv.ct_cross(R, F, pairs, sym=int(bool(symmetric)), mode=mode)
+        return _ct_cross(rv, R, F, pairs, sym=int(bool(symmetric)), mode=mode)
 
 
 def calculate_Ct_cross_from_files(vec_list, dt, tau, pairs, symmetric=True, ctx=None, mode=0):
@@ -150,7 +163,7 @@ def calculate_Ct_cross_from_files(vec_list, dt, tau, pairs, symmetric=True, ctx=
     pairs = _check_pairs(pairs, cat.shape[1])
     with _ctx(ctx).vectors(cat.shape[1], cat.shape[0]) as rv:
         rv.append(cat)
-        return rv.ct_cross(R, F, pairs, chunk_start=starts, sym=int(bool(symmetric)), mode=mode)
+        return _ct_cross(rv, R, F, pairs, chunk_start=starts, sym=int(bool(symmetric)), mode=mode)
 
 
 def calculate_Ct_cross_resident(rv, pairs, R, F, symmetric=True, mode=0, chunk_start=None, want_dP0=False):
@@ -158,7 +171,7 @@ def calculate_Ct_cross_resident(rv, pairs, R, F, symmetric=True, mode=0, chunk_s
     one GPU: rv holds ALL vectors (a single process), not a rank's range.  want_dP0: (P0, dP0, Ct, dCt), dP0 the error of P0 over the
     chunks, std / (sqrt(R) - 1) like dCt."""
     pairs = _check_pairs(pairs, rv.nV)
-    return rv.ct_cross(R, F, pairs, chunk_start=chunk_start, sym=int(bool(symmetric)), mode=mode, want_dP0=want_dP0)
+    return _ct_cross(rv, R, F, pairs, chunk_start=chunk_start, sym=int(bool(symmetric)), mode=mode, want_dP0=want_dP0)
 
 
 def upload_shard(vec_list, frames_per_chunk=None, ctx=None):

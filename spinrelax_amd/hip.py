@@ -84,6 +84,8 @@ class Context:
 
     def set_option(self, name, value):
         check(self.lib.sr_set_option(self.h, name.encode(), int(value)), 'sr_set_option')
+        if name == 'ct_cross_long_min_frames':        # the one option that Python code acts on (ct.py's dispatch): keep what was accepted
+            self.ct_cross_long_min_frames = int(value)
 
     def stream_create(self, cu_mask_words=None, priority=0):
         """hipStream_t handle (int); cu_mask_words = iterable of 32-bit words, bit set = CU usable."""
@@ -198,6 +200,20 @@ class Context:
         cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
         check(self.lib.sr_ct_cross_f32_dev(self.h, soa_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
                                            int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr), 'sr_ct_cross_f32_dev')
+
+    ct_cross_long_min_frames = 6625     # the library's default of the option: the first length ct_cross refuses
+
+    def ct_cross_long_max_frames(self):
+        """longest chunk the blocked form of the pair cross-correlation takes (sr_ct_cross_long_max_frames)"""
+        return int(self.lib.sr_ct_cross_long_max_frames(self.h))
+
+    def ct_cross_long_dev(self, soa_ptr, Npad, nV, R, F, pairs, P0_ptr, Ct_ptr, dCt_ptr, chunk_start=None, sym=1, mode=0, psum_ptr=None,
+                          dP0_ptr=None):
+        """ct_cross_dev for chunks of 5462 .. ct_cross_long_max_frames() frames, by blocked transforms (sr_ct_cross_long_f32_dev)"""
+        pi, pj = pair_columns(pairs)
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        check(self.lib.sr_ct_cross_long_f32_dev(self.h, soa_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
+                                                int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr), 'sr_ct_cross_long_f32_dev')
 
     # ---- iRED matrix (sr_ired.hip) ----
     def ired_matrix_dev(self, soa_ptr, Npad, nV, win_start, win_len, M_ptr):
@@ -682,6 +698,14 @@ class ResidentVectors:
         """time-lagged P2 cross-correlation of the pairs (nP, 2) of resident vectors (sr_vectors_ct_cross_f32): P0 (nP) the equal-time
         <P2(u_i . u_j)>, Ct and dCt (F//2, nP) = <P2(u_i(t) . u_j(t + k))>, k = 1 .. F//2, mean and error over the R chunks like ct();
         sym = 1: the mean of C_ij and C_ji.  want_dP0: (P0, dP0, Ct, dCt), dP0 the error of P0 over the chunks (sr_vectors_ct_cross_err_f32)"""
+        return self._ct_cross('sr_vectors_ct_cross', R, F, pairs, chunk_start, sym, mode, want_dP0)
+
+    def ct_cross_long(self, R, F, pairs, chunk_start=None, sym=1, mode=0, want_dP0=False):
+        """ct_cross for chunks of 5462 .. Context.ct_cross_long_max_frames() frames, by blocked transforms (sr_vectors_ct_cross_long_f32,
+        sr_vectors_ct_cross_long_err_f32): the same arguments and results"""
+        return self._ct_cross('sr_vectors_ct_cross_long', R, F, pairs, chunk_start, sym, mode, want_dP0)
+
+    def _ct_cross(self, stem, R, F, pairs, chunk_start, sym, mode, want_dP0):
         pi, pj = pair_columns(pairs)
         L = F // 2
         P0 = np.empty(pi.size)
@@ -692,11 +716,11 @@ class ResidentVectors:
             raise ValueError('chunk_start must have R entries')
         if want_dP0:
             dP0 = np.empty(pi.size)
-            check(self.ctx.lib.sr_vectors_ct_cross_err_f32(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
-                                                           int(mode), _ptr(P0), _ptr(dP0), _ptr(Ct), _ptr(dCt)), 'sr_vectors_ct_cross_err_f32')
+            check(getattr(self.ctx.lib, stem + '_err_f32')(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
+                                                           int(mode), _ptr(P0), _ptr(dP0), _ptr(Ct), _ptr(dCt)), stem + '_err_f32')
             return P0, dP0, Ct, dCt
-        check(self.ctx.lib.sr_vectors_ct_cross_f32(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
-                                                   int(mode), _ptr(P0), _ptr(Ct), _ptr(dCt)), 'sr_vectors_ct_cross_f32')
+        check(getattr(self.ctx.lib, stem + '_f32')(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
+                                                   int(mode), _ptr(P0), _ptr(Ct), _ptr(dCt)), stem + '_f32')
         return P0, Ct, dCt
 
     def ct_sums(self, R, F, chunk_start=None, mode=0):

@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
+#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross and sr_ct_dipolar entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -365,6 +365,46 @@ int sr_vectors_ct_cross_long_f32(sr_ctx *, sr_vectors *, int64_t R, int64_t F, c
 int sr_vectors_ct_cross_long_err_f32(sr_ctx *, sr_vectors *, int64_t R, int64_t F, const int64_t *chunk_start_host,
                                      const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode,
                                      double *P0, double *dP0, double *Ct, double *dCt);
+
+/* ---- distance-weighted dipolar correlation function of a flexible spin pair (sr_ct_dipolar.hip; beyond the reference) -----------------
+ * Every function above takes the inter-spin vector as a unit vector: right for a bonded N-H or C-H pair.  Between two spins whose
+ * distance fluctuates with the orientation (an inter-proton NOE, a methyl proton against a backbone proton, a ligand-protein contact)
+ * the relaxation-active function is
+ *     C_dd(k) = < P2(u(t) . u(t+k)) r(t)^-3 r(t+k)^-3 > / < r^-6 >
+ * (Brueschweiler et al., J. Am. Chem. Soc. 114, 2289 (1992); Peter, Daura & van Gunsteren, J. Biomol. NMR 20, 297 (2001)), on the Palmer
+ * chunk table of kernel 1 (R chunks of F frames, chunk_start_host as there).  Per vector, r_ref = min over the frames held of r(t),
+ * w(t) = (r_ref / r(t))^3 in (0, 1], a(t) = u(t) sqrt(w(t)); P2(u . u') w w' = 1.5 (a . a')^2 - 0.5 w w'.  Per chunk r
+ *     c_r(k) = [1.5 sum_t (a(t) . a(t+k))^2 - 0.5 sum_t w(t) w(t+k)] / (F - k),     n_r = sum_t w(t)^2 / F
+ *     C_dd(k) = mean_r c_r(k) / mean_r n_r   (a ratio of chunk means; C_dd(0) = 1),   k = 1 .. L = F / 2
+ *     dC_dd(k) = [std_r c_r(k) / (sqrt(R) - 1)] / mean_r n_r   -- the scatter of the normaliser itself is ignored
+ * Mean and std of c_r come from kernel 1's own reduction over the chunks, so R = 1 gives the dC it gives.  Arithmetic and modes as the
+ * direct form of kernel 1 (mode 0: float32 products, float32 partial sums of at most 16 terms folded into float64; mode 1: float64
+ * throughout); no atomics, equal input gives bit-equal output.
+ *   sr_pack_dipolar_f32_dev  frame-major vectors (N, Vtot, 3) float32 of ANY length, columns [v0, v0 + nV) -> four planes per vector
+ *                            a_x, a_y, a_z, w in kernel 0's layout, planes[(v * 4 + c) * Npad + n], zero for n in [N, Npad), and
+ *                            r_ref (nV) float64.  dist_dev (N, Vtot) float32, optional: when given it holds the distances and the
+ *                            vectors only give the direction; when NULL the length of a vector is the distance.  float64 arithmetic,
+ *                            rounded once to float32.  A vector with a frame that is not finite, or whose direction is (0, 0, 0),
+ *                            gets r_ref = NaN; a zero-length vector without dist_dev gives r_ref = 0.  Asynchronous.
+ *   sr_ct_dipolar_f32_dev    those planes -> Ct, dCt (L, nV) float64 and wmean (nV, 2) = <w>, <w^2> over the frames of all chunks, DEVICE
+ *                            arrays; psum_ws (optional, may be NULL): (nV, R, sr_ct_psum_stride(F)) float64.  Asynchronous (behind the
+ *                            upload of a chunk table); every argument check comes before the first launch.
+ *   sr_vectors_ct_dipolar_f32  the same of resident vectors, results on the HOST, blocking: Ct, dCt (L, nV) and per vector
+ *                            reff6 = r_ref <w^2>^(-1/6) = <r^-6>^(-1/6),  reff3 = r_ref <w>^(-1/3) = <r^-3>^(-1/3) and the radial order
+ *                            parameter S2rad = <w>^2 / <w^2>, in the units of the input.  dist_host (frames held, nV) float32, optional,
+ *                            as dist_dev above; an entry <= 0 or not finite is refused (-3), and so is, after the r_ref pass and by
+ *                            name, a vector whose r_ref is <= 0 or not finite.  The four-plane pack is the object's own: it is kept
+ *                            like the three planes of the other analyses, dropped by the same events (append, truncate) and does not
+ *                            disturb them; a pack made with dist_host is never reused (the array is the caller's).
+ * One workgroup stages the four series of a (vector, chunk) in LDS, 16 bytes per frame: F up to sr_ct_dipolar_max_frames() (10016 with the
+ * 160 KiB of gfx950); a longer chunk is refused with -4 before anything is launched (there is no blocked form). */
+int64_t sr_ct_dipolar_max_frames(sr_ctx *);
+int sr_pack_dipolar_f32_dev(sr_ctx *, const float *vecs_dev, const float *dist_dev, int64_t N, int64_t Vtot, int64_t v0, int64_t nV,
+                            float *planes_dev, int64_t Npad, double *rref_dev);
+int sr_ct_dipolar_f32_dev(sr_ctx *, const float *planes_dev, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                          int mode, double *psum_ws, double *Ct, double *dCt, double *wmean);
+int sr_vectors_ct_dipolar_f32(sr_ctx *, sr_vectors *, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
+                              double *Ct, double *dCt, double *reff6, double *reff3, double *S2rad);
 
 /* ---- kernel 3b: multi-exponential C(t) model --------------------------------------------
  * Model of curvefit_exponential (fitting_Ct_functions.py:419-427): params = [C_1..C_K, tau_1..tau_K

@@ -4,8 +4,8 @@ Drop-in for the reference's calculate-Ct-from-traj.py (run-all.bash:476-481): sa
 files (<o>_Ctext.dat, <o>_Ctint.dat, <o>_vecHistogram.npz | _vecPhiTheta.npz|.dat, <o>_avgvec.dat,
 <o>_S2.dat; with the [extension] --iRED also <o>_iRED_S2.dat, <o>_iRED_eig.dat and, with --binary, <o>_iRED_matrix.npz; with --iRED_Ct
 also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat; with the [extension] --crossCt --pairs FILE also <o>_crossCtint.dat
-and <o>_crossPairs.dat).  C(t), the rotation into the PAF, the spherical histogram, the mean vector and S2 are
-computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
+and <o>_crossPairs.dat; with the [extension] --dipolarCt also <o>_dipolarCtint.dat and <o>_dipolarDist.dat).  C(t), the rotation into
+the PAF, the spherical histogram, the mean vector and S2 are computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
 Several GPUs: run under torchrun (`torchrun --nproc-per-node N scripts/calculate-Ct-from-traj.py ...`): rank r computes the
 contiguous vector range spinrelax_amd.dist.shard_range gives it, the results are all-gathered (RCCL) and rank 0 writes the
@@ -20,6 +20,9 @@ Trajectory input:
     and `fit_indices` -- which go through the same GPU front end, or precomputed unit vectors `vecs` (frames, bonds, 3;
     body frame) with optional `vecs_lab` (lab frame for _Ctext.dat; defaults to `vecs`); plus `names` (resSeq per bond;
     default 2..V+1) and `dt` (ps; default --dt).  A .npy holds unit vectors.  -s is still parsed and ignored then.
+    For --dipolarCt the distances come from the same file: |x_H - x_X| of the coordinates; `dist` (frames, bonds) beside `vecs`, or
+    the lengths of `vecs` without it; the lengths of the vectors of a .npy -- every other analysis of the same run still expects
+    unit vectors.
 """
 import argparse
 import os
@@ -87,7 +90,39 @@ def build_parser():
                    help='[extension] pair file of --crossCt: two integers per line, 0-based indices into the list of vectors; # starts a comment.')
     p.add_argument('--asym', dest='bCrossAsym', action='store_true', default=False,
                    help='[extension] --crossCt writes C_ij and C_ji of every pair as two blocks, one after the other, instead of their mean.')
+    p.add_argument('--dipolarCt', dest='bDoDipolarCt', action='store_true', default=False,
+                   help='[extension, needs --tau] distance-weighted dipolar correlation functions of flexible spin pairs, '
+                        '<P2(u(t).u(t+k)) r(t)^-3 r(t+k)^-3> / <r^-6>, chunked by --tau like --Ct: <o>_dipolarCtint.dat (the format of '
+                        '_Ctint.dat, labelled by residue; calculate-fitted-Ct.py reads it) and <o>_dipolarDist.dat (resid, the effective '
+                        'distances <r^-6>^(-1/6) and <r^-3>^(-1/3) in the units of the input, and the radial order parameter '
+                        '<r^-3>^2 / <r^-6>).  Vector-file input only (.npy/.npz): distances from `xyz`, from `dist` or from the lengths '
+                        'of the vectors; then the other analyses of the run still expect unit vectors.  At most 10016 frames per chunk.  '
+                        '--exact: float64 throughout.  Dot products and distances do not change under a rotation: --vecRot has no '
+                        'effect on these files.  Single process only.')
     return p
+
+
+def load_distance_files(files, frames_per_chunk):
+    """The distances of --dipolarCt from .npy / .npz vector input, cut to whole chunks like the vectors (hostct.upload_shard) and
+    concatenated: (frames kept, bonds) float32, or None when the lengths of the vectors are the distances."""
+    out = []
+    for fn in files:
+        d = None
+        if not fn.endswith('.npy'):
+            z = np.load(fn, allow_pickle=True)
+            if 'xyz' in z:
+                x = np.asarray(z['xyz'], dtype=np.float64)
+                d = np.linalg.norm(x[:, np.asarray(z['indexH'])] - x[:, np.asarray(z['indexX'])], axis=-1)
+            elif 'dist' in z:
+                d = np.asarray(z['dist'])
+                if d.ndim != 2 or d.shape != z['vecs'].shape[:2]:
+                    raise ValueError('%s: dist must be (frames, bonds) = %s, got %s' % (fn, z['vecs'].shape[:2], d.shape))
+        out.append(d)
+    if all(d is None for d in out):
+        return None
+    if any(d is None for d in out):
+        raise ValueError('some of the files hold distances and some do not')
+    return np.ascontiguousarray(np.concatenate([d[:(d.shape[0] // frames_per_chunk) * frames_per_chunk] for d in out], axis=0), dtype=np.float32)
 
 
 def load_vector_files(files, default_dt):
@@ -211,8 +246,19 @@ def main():
     args = parser.parse_args()
     if args.bDoCrossCt and args.pairs_fn is None:
         parser.error('--crossCt needs --pairs FILE')
+    if args.bDoDipolarCt and args.tau is None:
+        print("= = = Refusing to do dipolar correlation analysis without using a block averaging over memory_time tau!", file=sys.stderr)
+        sys.exit(1)
+    if args.bDoDipolarCt and not all(f.endswith('.npy') or f.endswith('.npz') for f in args.infn):
+        print("= = = ERROR: --dipolarCt works on vector-file input (.npy/.npz), not on MDTraj input: the streaming front end keeps no "
+              "distances.", file=sys.stderr)
+        sys.exit(1)
     time_start = time.time()
     rank, world = srdist.start()
+    if args.bDoDipolarCt and world > 1:
+        # the ranks hold ranges of vectors; the distances and the output are not sharded
+        print("= = = ERROR: --dipolarCt does not run under torchrun with more than one rank; run it as a single process.", file=sys.stderr)
+        sys.exit(1)
     if args.help_sel:
         print("Notes: This program uses MDTraj selection syntax, e.g. 'chain A and resname GLY and name HA1 HA2'.")
         sys.exit(0)
@@ -376,6 +422,20 @@ def main():
             print("# pair i j resid_i resid_j P0 dP0", file=fp)
             for n, (i, j) in enumerate(pairs):
                 print("%d %d %d %s %s %.8g %.8g" % (ordinals[n], i, j, resXH[i], resXH[j], P0[n], dP0[n]), file=fp)
+        print("      ...complete.")
+    if args.bDoDipolarCt:
+        print("= = = Conducting distance-weighted dipolar correlation analysis of the fitted vectors using Palmer's approach.")
+        try:
+            dist = load_distance_files(args.infn, F)
+            Cd, dCd, reff6, reff3, S2rad = hostct.calculate_Ct_dipolar_resident(rv_fit, R, F, dist=dist, mode=1 if args.exact else 0)
+        except (ValueError, hostct.hip.SpinRelaxHipError) as exc:      # a bad distance, a zero-length vector, a chunk beyond the LDS
+            print("= = = ERROR: %s" % exc, file=sys.stderr)
+            sys.exit(1)
+        gs.print_sxylist(out_pref + '_dipolarCtint.dat', resXH, hostct.calculate_dt(deltaT, tau_memory), np.stack((Cd.T, dCd.T), axis=-1))
+        with open(out_pref + '_dipolarDist.dat', 'w') as fp:
+            print("# resid reff6 reff3 S2rad", file=fp)
+            for n in range(V):
+                print("%s %.8g %.8g %.8g" % (resXH[n], reff6[n], reff3[n], S2rad[n]), file=fp)
         print("      ...complete.")
 
     need_dist = args.bDoVecAverage or args.bDoS2 or (bDoVecDistrib and args.bDoVecHist)

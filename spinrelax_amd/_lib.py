@@ -151,6 +151,15 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_void_p]),
     'sr_vectors_ct_cross_long_err_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the distance-weighted dipolar correlation function (sr_ct_dipolar.hip):
+    # (ctx, vecs_dev, dist_dev, N, Vtot, v0, nV, planes_dev, Npad, rref_dev) / (ctx, planes, Npad, nV, R, F, chunk_start, mode, psum_ws, Ct_dev,
+    # dCt_dev, wmean_dev) / (ctx, vectors, dist_host, R, F, chunk_start, mode, Ct_host, dCt_host, reff6, reff3, S2rad)
+    'sr_ct_dipolar_max_frames': (c_int64, [c_void_p]),
+    'sr_pack_dipolar_f32_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    'sr_ct_dipolar_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    'sr_vectors_ct_dipolar_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
     'sr_counter': (c_int, [c_void_p, c_char_p, POINTER(ctypes.c_uint64)]),
     'sr_transpose_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'sr_jomega_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
@@ -160,7 +169,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13      # unchanged by the sr_ct_cross entry points: they only add symbols, and load() fails at a missing one
+ABI_VERSION = 13      # unchanged by the sr_ct_cross and sr_ct_dipolar entry points: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -1,0 +1,433 @@
+// sr_ct_dipolar.hip -- distance-weighted dipolar correlation function of a flexible spin pair (k_ct_dipolar), an extension beyond
+// the reference, whose correlation functions all take the inter-spin vector as a unit vector:
+//     C_dd(k) = < P2(u(t) . u(t+k)) r(t)^-3 r(t+k)^-3 > / < r^-6 >
+// (Brueschweiler et al., J. Am. Chem. Soc. 114, 2289 (1992); Peter, Daura & van Gunsteren, J. Biomol. NMR 20, 297 (2001)), on the
+// Palmer chunk table of kernel 1.
+//
+// Formulation.  Per vector, r_ref = min over the frames held of r(t), w(t) = (r_ref / r(t))^3 in (0, 1] and a(t) = u(t) sqrt(w(t)),
+// so |a|^2 = w <= 1 and
+//     P2(u . u') w w' = 1.5 (a . a')^2 - 0.5 w w'.
+// Per (vector, chunk) two shifted-product sums: S_a(k) = sum_t (a(t) . a(t+k))^2 -- what ct_shift_block (sr_ct_shift.h) accumulates;
+// every term stays in [0, 1], which its centred float32 partial sums rely on: the reason for the r_ref scaling -- and
+// S_w(k) = sum_t w(t) w(t+k).
+// The raw sums leave as S'(k) = S_a(k) - S_w(k) / 3 + (F - k) / 3 in kernel 1's psum layout, so that the unchanged k_ct_finalize
+// (1.5 S' / (F - k) - 0.5 = [1.5 S_a - 0.5 S_w] / (F - k)) gives the chunk mean of the unnormalised function and its
+// std / (sqrt(R) - 1); k_ct_dipolar_norm divides both by the chunk mean of n_r = sum_t w^2 / F.
+//
+// Kernels:
+//   k_dipolar_rmin   r_ref per vector: a workgroup min over the frames, no atomics
+//   k_pack_dipolar   frame-major vectors (and optional distances) -> four planes per vector a_x, a_y, a_z, w in kernel 0's layout
+//                    (soa[(v * 4 + c) * Npad + n], zero for n in [N, Npad)); float64 arithmetic, rounded once to float32
+//   k_ct_dipolar<W>  one (vector, chunk) per workgroup or per slab of one, the dispatch of sr_launch_ct_direct: the three a planes staged
+//                    as the direct kernel stages them, the w series behind them (parity-split 16-byte chunks, so that the 16 lag-lanes
+//                    of a ds_read_b128 group read 256 consecutive bytes), 16 bytes per frame in all; per lag block ct_shift_block for
+//                    S_a and the same (strip, lag-lane) partition, 8-frame window rotation and float32 partial sums of at most 16 terms
+//                    for S_w (dip_shift_block_w), both started at -8 <w^2> of the chunk instead of -kCenter; remaining lags and every
+//                    lag in mode 1 by a float64 path; while staging, wave 0 of slab 0 sums w and w^2 of the chunk in float64.  No
+//                    atomics, no scratch: equal input gives bit-equal output
+//   k_ct_dipolar_norm  chunk means of the two sums; Ct and dCt scaled by 1 / mean n_r; <w> and <w^2> per vector
+// A chunk must fit 16 ct_Fp(F) bytes of LDS: F <= 10016 at 160 KiB.  A blocked form for longer chunks does not exist.
+#include "sr_ct_shift.h"
+#include <cmath>
+
+namespace {
+
+// ------------------------------------------------------------------------------------------
+// r_ref and the four-plane pack
+// ------------------------------------------------------------------------------------------
+constexpr int kDipVecs = 32;            // vectors per tile: a frame's 32 vectors are 96 consecutive floats
+constexpr int kDipRows = 32;            // frame rows of k_dipolar_rmin
+constexpr int kDipFrames = 64;          // frames per tile of k_pack_dipolar
+
+// min that keeps a NaN once it has one (a frame that is not finite must reach the host)
+__device__ __forceinline__ double min_nan(double m, double r) { return (r < m || r != r) ? r : m; }
+
+// distance of one frame: dist when given, else |v|; NaN for a frame that cannot be used (not finite, or no direction)
+__device__ __forceinline__ double dip_distance(const float *__restrict__ p, const float *__restrict__ dist, int64_t di, double &len)
+{
+    const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+    len = sqrt(x * x + y * y + z * z);
+    double r = dist ? (double)dist[di] : len;
+    if (isinf(r) || isinf(len) || len != len || (dist && !(len > 0.0))) r = NAN;
+    return r;
+}
+
+__global__ __launch_bounds__(kDipVecs *kDipRows) void k_dipolar_rmin(const float *__restrict__ vecs, const float *__restrict__ dist, int64_t N,
+                                                                     int64_t Vtot, int64_t v0, int64_t nV, double *__restrict__ rref)
+{
+    __shared__ double part[kDipRows][kDipVecs + 1];
+    const int k = threadIdx.x % kDipVecs, row = threadIdx.x / kDipVecs;
+    const int64_t v = (int64_t)blockIdx.x * kDipVecs + k;
+    double m = INFINITY;
+    if (v < nV) {
+        for (int64_t f = row; f < N; f += kDipRows) {
+            double len;
+            m = min_nan(m, dip_distance(vecs + (f * Vtot + v0 + v) * 3, dist, f * Vtot + v0 + v, len));
+        }
+    }
+    part[row][k] = m;
+    __syncthreads();
+    if (row == 0 && v < nV) {
+        for (int i = 1; i < kDipRows; ++i) m = min_nan(m, part[i][k]);
+        rref[v] = m;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pack_dipolar(const float *__restrict__ vecs, const float *__restrict__ dist, int64_t N, int64_t Vtot,
+                                                      int64_t v0, int64_t nV, const double *__restrict__ rref, float *__restrict__ soa,
+                                                      int64_t Npad)
+{
+#pragma clang fp contract(off)
+    __shared__ float tile[kDipVecs * 4][kDipFrames + 1];
+    const int64_t n0 = (int64_t)blockIdx.x * kDipFrames;
+    const int64_t vb = (int64_t)blockIdx.y * kDipVecs;
+    const int nvec = (int)min((int64_t)kDipVecs, nV - vb);
+    const int tid = threadIdx.x;
+    for (int idx = tid; idx < kDipFrames * nvec; idx += 256) {
+        const int n = idx / nvec, k = idx - n * nvec;
+        const int64_t fr = n0 + n;
+        float ox = 0.f, oy = 0.f, oz = 0.f, ow = 0.f;
+        if (fr < N) {
+            const float *p = vecs + (fr * Vtot + v0 + vb + k) * 3;
+            double len;
+            const double r = dip_distance(p, dist, fr * Vtot + v0 + vb + k, len);
+            const double q = rref[vb + k] / r;
+            const double w = q * q * q;
+            const double s = sqrt(w) / len;
+            ox = (float)((double)p[0] * s);
+            oy = (float)((double)p[1] * s);
+            oz = (float)((double)p[2] * s);
+            ow = (float)w;
+        }
+        tile[k * 4 + 0][n] = ox;
+        tile[k * 4 + 1][n] = oy;
+        tile[k * 4 + 2][n] = oz;
+        tile[k * 4 + 3][n] = ow;
+    }
+    __syncthreads();
+    const int row = nvec * 4;
+    for (int idx = tid; idx < kDipFrames * row; idx += 256) {
+        const int k = idx / kDipFrames, n = idx - k * kDipFrames;
+        const int64_t fr = n0 + n;
+        if (fr < Npad) soa[(vb * 4 + k) * Npad + fr] = tile[k][n];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// the correlation kernel
+// ------------------------------------------------------------------------------------------
+struct CtDipArgs {
+    const float *soa;             // (nV, 4, Npad)
+    int64_t Npad;
+    const int64_t *chunk_start;   // device, may be null
+    double *psum;                 // (nV, R, Lp)
+    double *wsum;                 // (nV, R, 2): sum of w and of w^2 over the chunk
+    int R, F, Fp, L, Lp, nslab, mode;
+};
+
+// float index of frame e of the w series: 16-byte chunk c (4 frames) lives in half (c & 1) at slot (c >> 1); Hw = Fp / 2 floats per half
+__device__ __forceinline__ int lds_wpos(int e, int Hw)
+{
+    const int c = e >> 2;
+    return (c & 1) * Hw + (c >> 1) * 4 + (e & 3);
+}
+
+// ct_shift_block for the scalar series: one wave, the block of kLagBlock lags that starts at lag dw; lane (strip g, lag-lane l16) ADDS
+// to acc64[d] its strip's part of sum_j w(j) w(j + lag), lag = dw + kLagsPerLane l16 + d.  The same strips, the same window rotation
+// (one new 8-frame half per step: 2 + 2 ds_read_b128 per 64 FMAs), float32 partial sums of at most 16 terms in [0, 1] started at
+// -center, folded into float64 every kFlush steps.
+__device__ __forceinline__ void dip_shift_block_w(const float *lw, int Hw, int F, int dw, int g, int l16, double (&acc64)[kLagsPerLane],
+                                                  const float center)
+{
+    const int nj = F - dw;
+    const int S = (((nj + 3) >> 2) + 15) & ~15;
+    const int iters = S >> 3;
+    const float *pa0 = lw + ((g * S) >> 3) * 4;
+    const float *pa1 = pa0 + Hw;
+    const float *pb0 = lw + ((g * S + dw + kLagsPerLane * l16) >> 3) * 4;
+    const float *pb1 = pb0 + Hw;
+    float P[8], Q[8];
+#define SR_DIP_LOAD_HALF(H, OFF)                                                                 \
+    {                                                                                        \
+        const float4 t0 = *reinterpret_cast<const float4 *>(pb0 + (OFF));                   \
+        const float4 u0 = *reinterpret_cast<const float4 *>(pb1 + (OFF));                   \
+        H[0] = t0.x; H[1] = t0.y; H[2] = t0.z; H[3] = t0.w; H[4] = u0.x; H[5] = u0.y; H[6] = u0.z; H[7] = u0.w; \
+    }
+#define SR_DIP_STEP(LO, HI)                                                                      \
+    {                                                                                        \
+        float a[kJT], b[16];                                                                 \
+        {                                                                                    \
+            const float4 t = *reinterpret_cast<const float4 *>(pa0);                        \
+            const float4 u = *reinterpret_cast<const float4 *>(pa1);                        \
+            a[0] = t.x; a[1] = t.y; a[2] = t.z; a[3] = t.w; a[4] = u.x; a[5] = u.y; a[6] = u.z; a[7] = u.w; \
+        }                                                                                    \
+        SR_DIP_LOAD_HALF(HI, 4)                                                              \
+        _Pragma("unroll") for (int t = 0; t < 8; ++t) { b[t] = LO[t]; b[8 + t] = HI[t]; }    \
+        _Pragma("unroll") for (int jj = 0; jj < kJT; ++jj) {                                 \
+            _Pragma("unroll") for (int d = 0; d < kLagsPerLane; ++d)                         \
+                acc[d][jj & 3] = fmaf(a[jj], b[jj + d], acc[d][jj & 3]);                     \
+        }                                                                                    \
+        pa0 += 4; pa1 += 4; pb0 += 4; pb1 += 4;                                              \
+    }
+    SR_DIP_LOAD_HALF(P, 0)
+    for (int it0 = 0; it0 < iters; it0 += kFlush) {
+        float acc[kLagsPerLane][4];
+#pragma unroll
+        for (int d = 0; d < kLagsPerLane; ++d)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[d][q] = -center;
+        const int n = min(kFlush, iters - it0);            // even
+        for (int ii = 0; ii < n; ii += 2) {
+            SR_DIP_STEP(P, Q)
+            SR_DIP_STEP(Q, P)
+        }
+#pragma unroll
+        for (int d = 0; d < kLagsPerLane; ++d) {
+            const float s = (acc[d][0] + acc[d][1]) + (acc[d][2] + acc[d][3]);
+            acc64[d] += (double)s + 4.0 * (double)center;
+        }
+    }
+#undef SR_DIP_STEP
+#undef SR_DIP_LOAD_HALF
+}
+
+#ifndef SR_CT_DIP_WAVES_EU
+#define SR_CT_DIP_WAVES_EU 3
+#endif
+template <int W>
+__global__ __launch_bounds__(W * 64, SR_CT_DIP_WAVES_EU) void k_ct_dipolar(CtDipArgs a)
+{
+    extern __shared__ __align__(16) float lds[];
+    const int Fp = a.Fp, Hf = (Fp >> 3) * 12, Hw = Fp >> 1, F = a.F;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int series = blockIdx.x / a.nslab;
+    const int slab = blockIdx.x - series * a.nslab;
+    const int v = series / a.R;
+    const int r = series - v * a.R;
+    float *lw = lds + 2 * Hf;              // the w series, behind the 3 Fp floats of the a planes
+
+    // ---- stage the four series (coalesced dword loads; zero padding behind frame F) ----
+    {
+        const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
+        const float *px = a.soa + ((int64_t)v * 4 + 0) * a.Npad + start;
+        const float *py = px + a.Npad;
+        const float *pz = py + a.Npad;
+        const float *pw = pz + a.Npad;
+        ct_stage_series<W * 64>(lds, px, py, pz, F, Fp, Hf, tid);
+        for (int e = tid; e < Fp; e += W * 64) lw[lds_wpos(e, Hw)] = e < F ? pw[e] : 0.f;
+    }
+    __syncthreads();
+
+    const int nb = (a.mode == 0) ? (a.L + 1) / kLagBlock : 0;
+
+    // ---- sum of w and of w^2 over the chunk, float64, fixed order: wave 0 of slab 0 writes them out; every wave with a lag block takes
+    // the centre of its float32 partial sums from them.  The terms of both sums are about w w' <= 1, on average <w^2> of the chunk, which
+    // can be far below 1: a run of 16 that starts at -8 <w^2> stays near zero, where float32 is finest (started at -kCenter it would sit
+    // near -8 and round every term to 5e-7 absolute) ----
+    float center = kCenter;
+    if (nb > 0 || (slab == 0 && wave == 0)) {
+        double s1 = 0.0, s2 = 0.0;
+        for (int t = lane; t < F; t += 64) {
+            const double w = (double)lw[lds_wpos(t, Hw)];
+            s1 += w;
+            s2 += w * w;
+        }
+        s1 = wave_sum_f64(s1);
+        s2 = wave_sum_f64(s2);
+        if (slab == 0 && wave == 0 && lane == 0) {
+            double *o = a.wsum + ((int64_t)v * a.R + r) * 2;
+            o[0] = s1;
+            o[1] = s2;
+        }
+        center = fminf(kCenter, (float)(8.0 * s2 / (double)F));
+    }
+
+    const int NW = a.nslab * W;            // workers (waves) per series
+    const int wid = slab * W + wave;
+    double *out = a.psum + ((int64_t)v * a.R + r) * a.Lp;
+
+    // ---- fast path: full lag blocks (lag 0 included), serpentine assignment balances the (F - lag) work ----
+    int g, l16;
+    lane_to_strip(lane, g, l16);
+    for (int i = 0; i * NW < nb; ++i) {
+        const int k = (i & 1) ? i * NW + (NW - 1 - wid) : i * NW + wid;
+        if (k >= nb) continue;
+        const int dw = k * kLagBlock;
+        double sa[kLagsPerLane], sw[kLagsPerLane];
+#pragma unroll
+        for (int d = 0; d < kLagsPerLane; ++d) sa[d] = sw[d] = 0.0;
+        ct_shift_block(lds, lds, Hf, F, dw, g, l16, sa, center);
+        ct_combine_strips(sa, l16);
+        dip_shift_block_w(lw, Hw, F, dw, g, l16, sw, center);
+        ct_combine_strips(sw, l16);
+        if (g == 0) {
+            const int lag0 = dw + kLagsPerLane * l16;
+            double *o = out + lag0;
+#pragma unroll
+            for (int d = 0; d < kLagsPerLane; ++d) o[d] = sa[d] - sw[d] / 3.0 + (double)(F - lag0 - d) / 3.0;
+        }
+    }
+
+    // ---- float64 path: remaining lags (and every lag in validation mode) ----
+    for (int d = nb * kLagBlock + wid; d <= a.L; d += NW) {
+        double s = 0.0, q = 0.0;
+        for (int j = lane; j + d < F; j += 64) {
+            const int pa = lds_pos(j, 0, Hf), pb = lds_pos(j + d, 0, Hf);
+            const double x = (double)lds[pa] * (double)lds[pb] + (double)lds[pa + 4] * (double)lds[pb + 4] +
+                             (double)lds[pa + 8] * (double)lds[pb + 8];
+            s += x * x;
+            q += (double)lw[lds_wpos(j, Hw)] * (double)lw[lds_wpos(j + d, Hw)];
+        }
+        s = wave_sum_f64(s);
+        q = wave_sum_f64(q);
+        if (lane == 0) out[d] = s - q / 3.0 + (double)(F - d) / 3.0;
+    }
+}
+
+// Ct, dCt (L, nV) of k_ct_finalize scaled in place by 1 / (mean over the chunks of n_r = sum_t w^2 / F); wmean (nV, 2) = <w>, <w^2> over
+// the frames of all chunks.  One workgroup: 64 vectors x 64 lags; the chunk sums are added in chunk order.
+__global__ __launch_bounds__(256) void k_ct_dipolar_norm(const double *__restrict__ wsum, int R, int F, int L, int64_t nV, double *__restrict__ Ct,
+                                                         double *__restrict__ dCt, double *__restrict__ wmean)
+{
+    __shared__ double inv[64];
+    const int tid = threadIdx.x;
+    const int64_t v0 = (int64_t)blockIdx.y * 64;
+    if (tid < 64 && v0 + tid < nV) {
+        const double *s = wsum + (v0 + tid) * R * 2;
+        double m1 = 0.0, m2 = 0.0, n = 0.0;
+        for (int r = 0; r < R; ++r) {
+            m1 += s[2 * r];
+            m2 += s[2 * r + 1];
+            n += s[2 * r + 1] / (double)F;
+        }
+        inv[tid] = 1.0 / (n / (double)R);
+        if (blockIdx.x == 0) {
+            wmean[(v0 + tid) * 2] = m1 / ((double)R * (double)F);
+            wmean[(v0 + tid) * 2 + 1] = m2 / ((double)R * (double)F);
+        }
+    }
+    __syncthreads();
+    const int vl = tid & 63;
+    const int64_t v = v0 + vl;
+    if (v >= nV) return;
+    for (int i = tid >> 6; i < 64; i += 4) {
+        const int d = blockIdx.x * 64 + i;              // lag index - 1
+        if (d >= L) break;
+        const int64_t o = (int64_t)d * nV + v;
+        Ct[o] *= inv[vl];
+        dCt[o] *= inv[vl];
+    }
+}
+
+size_t dip_lds_bytes(int64_t F) { return (size_t)ct_Fp(F) * 4 * sizeof(float); }
+
+int64_t dip_max_frames(size_t lds_limit)
+{
+    int64_t F = (int64_t)lds_limit / 16 - kPad;         // an upper bound: ct_Fp(F) >= F + kPad
+    while (F >= 2 && dip_lds_bytes(F) > lds_limit) --F;
+    return F >= 2 ? F : 0;
+}
+
+template <int W>
+int launch_dip(sr_ctx *ctx, const CtDipArgs &a, int64_t nblocks, size_t lds_bytes)
+{
+    return sr_launch(ctx, k_ct_dipolar<W>, dim3((unsigned)nblocks), dim3(W * 64), lds_bytes, a);
+}
+
+}  // namespace
+
+int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode)
+{
+    SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld", who, (long long)R, (long long)F, (long long)nV);
+    SR_REQUIRE(mode == 0 || mode == 1, -3, "%s: mode must be 0 or 1", who);
+    SR_REQUIRE(dip_lds_bytes(F) <= sr_lds_limit(ctx), -4,
+               "%s: the four series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (no blocked form for the dipolar "
+               "correlation function)",
+               who, (long long)F, dip_lds_bytes(F), sr_lds_limit(ctx), (long long)dip_max_frames(sr_lds_limit(ctx)));
+    SR_REQUIRE(R * nV < (int64_t)1 << 30, -3, "%s: too many series", who);
+    if (chunk_start_host) {
+        for (int64_t r = 0; r < R; ++r)
+            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= frames, -3, "%s: chunk %lld start %lld out of range", who,
+                       (long long)r, (long long)chunk_start_host[r]);
+    } else {
+        SR_REQUIRE(R * F <= frames, -3, "%s: R*F=%lld exceeds the %lld frames held", who, (long long)(R * F), (long long)frames);
+    }
+    return 0;
+}
+
+extern "C" {
+
+int64_t sr_ct_dipolar_max_frames(sr_ctx *ctx)
+{
+    if (!ctx) return -1;
+    return dip_max_frames(sr_lds_limit(ctx));
+}
+
+int sr_pack_dipolar_f32_dev(sr_ctx *ctx, const float *vecs, const float *dist, int64_t N, int64_t Vtot, int64_t v0, int64_t nV, float *planes,
+                            int64_t Npad, double *rref)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(vecs && planes && rref, -2, "sr_pack_dipolar_f32_dev: null pointer");
+    SR_REQUIRE(N > 0 && Vtot > 0 && nV > 0 && v0 >= 0 && v0 + nV <= Vtot, -3, "sr_pack_dipolar_f32_dev: bad shape N=%lld Vtot=%lld v0=%lld nV=%lld",
+               (long long)N, (long long)Vtot, (long long)v0, (long long)nV);
+    SR_REQUIRE(Npad >= N && Npad % 4 == 0, -3, "sr_pack_dipolar_f32_dev: Npad=%lld must be >= N and a multiple of 4", (long long)Npad);
+    const int64_t gx = (Npad + kDipFrames - 1) / kDipFrames;
+    const int64_t gy = (nV + kDipVecs - 1) / kDipVecs;
+    SR_REQUIRE(gy <= 65535, -3, "sr_pack_dipolar_f32_dev: too many vectors in one call (%lld)", (long long)nV);
+    hipLaunchKernelGGL(k_dipolar_rmin, dim3((unsigned)gy), dim3(kDipVecs * kDipRows), 0, ctx->stream, vecs, dist, N, Vtot, v0, nV, rref);
+    SR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_pack_dipolar, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, ctx->stream, vecs, dist, N, Vtot, v0, nV, rref, planes, Npad);
+    SR_HIP(hipGetLastError());
+    return 0;
+}
+
+int sr_ct_dipolar_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                          int mode, double *psum_ws, double *Ct, double *dCt, double *wmean)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(planes && Ct && dCt && wmean, -2, "sr_ct_dipolar_f32_dev: null pointer");
+    if (int rc = sr_ct_dipolar_check(ctx, "sr_ct_dipolar_f32_dev", Npad, nV, R, F, chunk_start_host, mode)) return rc;
+    const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
+    SR_REQUIRE((nV + 15) / 16 <= 65535, -3, "sr_ct_dipolar_f32_dev: too many vectors in one call (%lld)", (long long)nV);   // k_ct_finalize's grid
+    double *psum = psum_ws;
+    if (!psum) {
+        psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(nV * R * Lp) * sizeof(double));
+        if (!psum) return -5;
+    }
+    // ---- stage the chunk starts; the chunk sums of w and w^2 live behind them ----
+    sr_stage st(ctx);
+    st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 2 * (size_t)(nV * R) * sizeof(double));
+    CtDipArgs a;
+    a.chunk_start = st.put(chunk_start_host, (size_t)R);
+    a.wsum = st.take<double>(2 * (size_t)(nV * R));
+    if (st.rc) return st.rc;
+    if (chunk_start_host)
+        if (int rc = st.finish()) return rc;            // tiny table: the caller's array is free again when this returns
+    // ---- launch: the dispatch of sr_launch_ct_direct ----
+    a.soa = planes; a.Npad = Npad; a.psum = psum;
+    a.R = (int)R; a.F = (int)F; a.Fp = (int)ct_Fp(F); a.L = (int)L; a.Lp = (int)Lp; a.mode = mode;
+    const size_t lds_bytes = dip_lds_bytes(F);
+    const int nb = mode == 0 ? (int)((L + 1) / kLagBlock) : 0;
+    const int64_t series = R * nV;
+    int rc;
+    if (mode == 1) {
+        a.nslab = 1;
+        rc = launch_dip<4>(ctx, a, series, lds_bytes);
+    } else if (nb >= 16) {
+        a.nslab = nb >= 64 ? nb / 32 : 1;            // about 4-8 lag blocks per wave
+        rc = launch_dip<4>(ctx, a, series * a.nslab, lds_bytes);
+    } else {
+        a.nslab = nb > 0 ? nb : 1;                   // one wave per workgroup, one lag block per wave
+        rc = launch_dip<1>(ctx, a, series * a.nslab, lds_bytes);
+    }
+    if (rc) return rc;
+    if (int rc2 = sr_ct_finalize_f64_dev(ctx, psum, R, F, nV, Ct, dCt)) return rc2;
+    hipLaunchKernelGGL(k_ct_dipolar_norm, dim3((unsigned)((L + 63) / 64), (unsigned)((nV + 63) / 64)), dim3(256), 0, ctx->stream, a.wsum, (int)R,
+                       (int)F, (int)L, nV, Ct, dCt, wmean);
+    SR_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -73,9 +73,10 @@ __device__ __forceinline__ void ct_stage_series(float *s, const float *px, const
 // One wave, the block of kLagBlock lags that starts at lag dw, of the staged series la (the earlier frame) and lb (the later one):
 // lane (strip g, lag-lane l16) ADDS to acc64[d] its strip's part of sum_j (a(j) . b(j + lag))^2, lag = dw + kLagsPerLane l16 + d,
 // j + lag < F.  float32 dot products; float32 partial sums, 4 independent accumulators per lag, at most 16 terms each, folded into
-// float64 every kFlush steps.
+// float64 every kFlush steps.  The accumulators start at -center, which the fold adds back exactly: kCenter for unit vectors, whose
+// terms are close to 1; a caller whose terms are smaller (k_ct_dipolar, sr_ct_dipolar.hip) passes half of what 16 of them come to.
 __device__ __forceinline__ void ct_shift_block(const float *la, const float *lb, int Hf, int F, int dw, int g, int l16,
-                                               double (&acc64)[kLagsPerLane])
+                                               double (&acc64)[kLagsPerLane], const float center = kCenter)
 {
     const int nj = F - dw;
     const int S = (((nj + 3) >> 2) + 15) & ~15;        // strip length, multiple of 16: an even number of steps
@@ -136,7 +137,7 @@ __device__ __forceinline__ void ct_shift_block(const float *la, const float *lb,
 #pragma unroll
         for (int d = 0; d < kLagsPerLane; ++d)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc[d][q] = -kCenter;
+            for (int q = 0; q < 4; ++q) acc[d][q] = -center;
         const int n = min(kFlush, iters - it0);            // even
         for (int ii = 0; ii < n; ii += 2) {
             SR_CT_STEP(Px, Py, Pz, Qx, Qy, Qz)
@@ -145,7 +146,7 @@ __device__ __forceinline__ void ct_shift_block(const float *la, const float *lb,
 #pragma unroll
         for (int d = 0; d < kLagsPerLane; ++d) {
             const float s = (acc[d][0] + acc[d][1]) + (acc[d][2] + acc[d][3]);
-            acc64[d] += (double)s + 4.0 * (double)kCenter;
+            acc64[d] += (double)s + 4.0 * (double)center;
         }
     }
 #undef SR_CT_STEP

@@ -135,6 +135,10 @@ int sr_ct_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, 
 int sr_launch_ct_cross_long(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
                             const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *psum);
 
+// sr_ct_dipolar.hip: what the entry points of the dipolar correlation function refuse, before anything is queued: shapes and mode (-3), a
+// chunk whose four series do not fit the LDS (-4), chunk starts outside the `frames` frames held (-3)
+int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode);
+
 // sr_ired_modes.hip
 #define SR_IRED_WS_MB 1024
 int sr_ired_mode_ct_check(const char *who, int64_t frames, int64_t nV, const int64_t *win_start_host, const int64_t *win_len_host, int W, int K,

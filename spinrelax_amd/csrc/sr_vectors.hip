@@ -10,6 +10,7 @@
 // kernel 2 (and the iRED kernels, sr_ired.hip and sr_ired_modes.hip) as often as the caller asks.  The host-pointer entry points sr_ct_palmer_f32 / sr_rotate_hist_f32 are this
 // object used once.
 #include "sr_internal.h"
+#include <cmath>
 #include <cstdlib>
 
 struct sr_vectors {
@@ -20,6 +21,13 @@ struct sr_vectors {
     float *soa;            // (nV, 3, Npad) planes, device; built by the first computation
     int64_t Npad;
     int packed;            // planes are current
+    // the four-plane pack of the dipolar correlation function (sr_ct_dipolar.hip): a_x, a_y, a_z, w per vector.  The object's own,
+    // beside the three planes the other analyses read; invalidated by the same events
+    float *soa4;           // (nV, 4, Npad4) planes, device
+    int64_t Npad4;
+    int packed4;           // current, and packed from the vectors alone (a pack with a host distance array is never reused)
+    double *rref_dev;      // (nV) r_ref, device
+    double *rref;          // (nV) r_ref of the current pack, host
     hipEvent_t ready;      // recorded behind the last append / pack on the stream that did it: a consumer on ANOTHER stream
                            // (sr_set_stream between an append and the next use) waits for it on the device
 };
@@ -97,6 +105,50 @@ int pack(sr_ctx *ctx, sr_vectors *h)
     return mark_ready(ctx, h);
 }
 
+/* the four planes a_x, a_y, a_z, w and r_ref of the vectors held (dist_host, (N, nV) float32, gives the distances when not null) */
+int pack_dipolar(sr_ctx *ctx, sr_vectors *h, const float *dist_host)
+{
+    if (int rc = wait_ready(ctx, h)) return rc;
+    if (h->packed4 && !dist_host) return 0;
+    SR_REQUIRE(h->N > 0, -3, "sr_vectors: no frames appended");
+    h->packed4 = 0;
+    const int64_t Npad = sr_round_up(h->N, 64);
+    if (!h->soa4 || Npad != h->Npad4) {
+        if (h->soa4) {
+            SR_HIP(hipStreamSynchronize(ctx->stream));
+            SR_HIP(hipFree(h->soa4));
+            h->soa4 = nullptr;
+        }
+        SR_HIP(hipMalloc((void **)&h->soa4, (size_t)h->nV * 4 * Npad * sizeof(float)));
+        h->Npad4 = Npad;
+    }
+    if (!h->rref_dev) SR_HIP(hipMalloc((void **)&h->rref_dev, (size_t)h->nV * sizeof(double)));
+    if (!h->rref) {
+        h->rref = (double *)malloc((size_t)h->nV * sizeof(double));
+        SR_REQUIRE(h->rref != nullptr, -5, "sr_vectors: out of host memory");
+    }
+    float *dist_d = nullptr;
+    if (dist_host) {
+        const size_t bytes = (size_t)h->N * h->nV * sizeof(float);
+        dist_d = (float *)sr_workspace(ctx, SR_WS_VECS, bytes);
+        if (!dist_d) return -5;
+        SR_HIP(hipMemcpyAsync(dist_d, dist_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    int rc = sr_pack_dipolar_f32_dev(ctx, h->fm, dist_d, h->N, h->nV, 0, h->nV, h->soa4, Npad, h->rref_dev);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);        // the upload reads the caller's array
+        return rc;
+    }
+    SR_HIP(hipMemcpyAsync(h->rref, h->rref_dev, (size_t)h->nV * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t v = 0; v < h->nV; ++v)
+        SR_REQUIRE(h->rref[v] > 0.0 && std::isfinite(h->rref[v]), -3,
+                   "sr_vectors_ct_dipolar_f32: vector %lld has no usable shortest distance (r_ref = %g): a frame of zero length or one that is not finite",
+                   (long long)v, h->rref[v]);
+    h->packed4 = dist_host ? 0 : 1;
+    return mark_ready(ctx, h);
+}
+
 }  // namespace
 
 extern "C" {
@@ -132,6 +184,9 @@ void sr_vectors_destroy(sr_ctx *ctx, sr_vectors *h)
     }
     if (h->fm) (void)hipFree(h->fm);
     if (h->soa) (void)hipFree(h->soa);
+    if (h->soa4) (void)hipFree(h->soa4);
+    if (h->rref_dev) (void)hipFree(h->rref_dev);
+    free(h->rref);
     if (h->ready) (void)hipEventDestroy(h->ready);
     free(h);
 }
@@ -151,7 +206,7 @@ int sr_vectors_truncate(sr_ctx *ctx, sr_vectors *h, int64_t n_frames)
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(h != nullptr, -2, "sr_vectors_truncate: null pointer");
     SR_REQUIRE(n_frames >= 0 && n_frames <= h->N, -3, "sr_vectors_truncate: %lld of %lld frames", (long long)n_frames, (long long)h->N);
-    if (n_frames != h->N) { h->N = n_frames; h->packed = 0; }
+    if (n_frames != h->N) { h->N = n_frames; h->packed = h->packed4 = 0; }
     return 0;
 }
 
@@ -181,7 +236,7 @@ int sr_vectors_append_f32(sr_ctx *ctx, sr_vectors *h, const float *vecs, int64_t
             ctx->h2d_bytes += (unsigned long long)n * row;
             ctx->h2d_calls += 1;
             h->N += n;
-            h->packed = 0;
+            h->packed = h->packed4 = 0;
             return mark_ready(ctx, h);
         }
         (void)hipGetLastError();                        // pageable memory: the attribute query reports an error, not a type
@@ -211,7 +266,7 @@ int sr_vectors_append_f32(sr_ctx *ctx, sr_vectors *h, const float *vecs, int64_t
     ctx->h2d_bytes += (unsigned long long)n * row;
     ctx->h2d_calls += 1;
     h->N += n;
-    h->packed = 0;
+    h->packed = h->packed4 = 0;
     return mark_ready(ctx, h);               // the copies are still in flight on ctx->stream: a later use on another stream waits
 }
 
@@ -226,7 +281,7 @@ int sr_vectors_append_dev(sr_ctx *ctx, sr_vectors *h, const float *vecs_dev, int
     SR_HIP(hipMemcpyAsync(reinterpret_cast<char *>(h->fm) + (size_t)h->N * row, vecs_dev, (size_t)n * row, hipMemcpyDeviceToDevice,
                           ctx->stream));
     h->N += n;
-    h->packed = 0;
+    h->packed = h->packed4 = 0;
     return mark_ready(ctx, h);
 }
 
@@ -249,8 +304,8 @@ int sr_vectors_append_xyz_f32(sr_ctx *ctx, sr_vectors *lab, sr_vectors *fit, con
                                    lab ? lab->fm + (size_t)lab->N * row : nullptr, fit ? fit->fm + (size_t)fit->N * row : nullptr, nullptr);
     if (rc) return rc;
     SR_HIP(hipStreamSynchronize(ctx->stream));          // the caller may reuse xyz / the index tables now
-    if (lab) { lab->N += nFrames; lab->packed = 0; }
-    if (fit) { fit->N += nFrames; fit->packed = 0; }
+    if (lab) { lab->N += nFrames; lab->packed = lab->packed4 = 0; }
+    if (fit) { fit->N += nFrames; fit->packed = fit->packed4 = 0; }
     return 0;
 }
 
@@ -335,6 +390,41 @@ int sr_vectors_ct_cross_long_err_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int6
                                      const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0, double *Ct, double *dCt)
 {
     return vectors_ct_cross(ctx, "sr_vectors_ct_cross_long_f32", 1, h, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, P0, dP0, Ct, dCt);
+}
+
+int sr_vectors_ct_dipolar_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
+                              double *Ct, double *dCt, double *reff6, double *reff3, double *S2rad)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(h && Ct && dCt && reff6 && reff3 && S2rad, -2, "sr_vectors_ct_dipolar_f32: null pointer");
+    // refusals come before the pack: a chunk that does not fit or a bad distance launches nothing
+    if (int rc = sr_ct_dipolar_check(ctx, "sr_vectors_ct_dipolar_f32", h->N, h->nV, R, F, chunk_start_host, mode)) return rc;
+    if (dist_host)
+        for (int64_t i = 0; i < h->N * h->nV; ++i)
+            SR_REQUIRE(dist_host[i] > 0.f && std::isfinite(dist_host[i]), -3,
+                       "sr_vectors_ct_dipolar_f32: the distance of frame %lld, vector %lld is %g: distances must be positive and finite",
+                       (long long)(i / h->nV), (long long)(i % h->nV), (double)dist_host[i]);
+    if (int rc = pack_dipolar(ctx, h, dist_host)) return rc;
+    const int64_t L = F / 2, nV = h->nV;
+    double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nV) * sizeof(double));
+    double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * nV) * sizeof(double));
+    double *wm_d = (double *)sr_workspace(ctx, SR_WS_OUT2, 2 * (size_t)nV * sizeof(double));
+    if (!Ct_d || !dCt_d || !wm_d) return -5;
+    int rc = sr_ct_dipolar_f32_dev(ctx, h->soa4, h->Npad4, nV, R, F, chunk_start_host, mode, nullptr, Ct_d, dCt_d, wm_d);
+    if (rc) return rc;
+    SR_HIP(hipMemcpyAsync(Ct, Ct_d, (size_t)(L * nV) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipMemcpyAsync(dCt, dCt_d, (size_t)(L * nV) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    // <w> and <w^2> arrive as two strided columns in the caller's arrays and are turned into the three results in place
+    SR_HIP(hipMemcpy2DAsync(reff3, sizeof(double), wm_d, 2 * sizeof(double), sizeof(double), (size_t)nV, hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipMemcpy2DAsync(reff6, sizeof(double), wm_d + 1, 2 * sizeof(double), sizeof(double), (size_t)nV, hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t v = 0; v < nV; ++v) {
+        const double w1 = reff3[v], w2 = reff6[v];
+        reff6[v] = h->rref[v] * pow(w2, -1.0 / 6.0);
+        reff3[v] = h->rref[v] * pow(w1, -1.0 / 3.0);
+        S2rad[v] = w1 * w1 / w2;
+    }
+    return 0;
 }
 
 /* raw sums S[v][r][d-1] = sum_j (u_j . u_{j+d})^2 per (vector, chunk, lag) on the HOST, (nV, R, L) compact: what a rank that

@@ -174,6 +174,45 @@ def calculate_Ct_cross_resident(rv, pairs, R, F, symmetric=True, mode=0, chunk_s
     return _ct_cross(rv, R, F, pairs, chunk_start=chunk_start, sym=int(bool(symmetric)), mode=mode, want_dP0=want_dP0)
 
 
+def _check_dist(dist, shape):
+    """shape and values of a distance array, before any device call: float32 (what the library takes), positive and finite"""
+    d = np.ascontiguousarray(dist, dtype=np.float32)
+    if d.shape != tuple(shape):
+        raise ValueError('dist must have the shape %s of the vectors without their last axis, got %s' % (tuple(shape), d.shape))
+    if not (np.all(np.isfinite(d)) and np.all(d > 0)):
+        raise ValueError('dist holds an entry that is not positive and finite')
+    return d
+
+
+def calculate_Ct_dipolar(vecs, dist=None, ctx=None, mode=0):
+    """Distance-weighted dipolar correlation function of flexible spin pairs, an extension beyond the reference:
+    C_dd(k) = <P2(u(t) . u(t + k)) r(t)^-3 r(t + k)^-3> / <r^-6> (Brueschweiler et al. 1992; Peter, Daura & van Gunsteren 2001).
+    vecs (nReplicates, nFrames, nVectors, 3) as calculate_Ct_Palmer takes them, but of any length: the length of a vector is the
+    distance r, unless dist (nReplicates, nFrames, nVectors) gives it -- then the vectors only give the direction.
+    Returns (Ct, dCt, reff6, reff3, S2rad): Ct, dCt (nFrames // 2, nVectors) for the lags 1 .. nFrames // 2, the ratio of the mean over
+    the replicates of the unnormalised function to the mean of its lag-0 value, and std / (sqrt(nReplicates) - 1) of the former over
+    the same normaliser (whose own scatter is ignored); per vector the effective distances reff6 = <r^-6>^(-1/6), reff3 = <r^-3>^(-1/3)
+    and the radial order parameter S2rad = <r^-3>^2 / <r^-6>, over all frames, in the units of the input."""
+    sh = np.shape(vecs)
+    if len(sh) != 4 or sh[3] != 3:
+        raise ValueError('vecs must be (replicates, frames, vectors, 3), got %s' % (sh,))
+    R, F, V = sh[0], sh[1], sh[2]
+    if dist is not None:
+        dist = _check_dist(dist, (R, F, V)).reshape(R * F, V)
+    flat = np.ascontiguousarray(vecs, dtype=np.float32).reshape(R * F, V, 3)
+    with _ctx(ctx).vectors(V, R * F) as rv:
+        rv.append(flat)
+        return rv.ct_dipolar(R, F, dist=dist, mode=mode)
+
+
+def calculate_Ct_dipolar_resident(rv, R, F, dist=None, mode=0, chunk_start=None):
+    """calculate_Ct_dipolar of resident vectors (regular chunks r * F unless chunk_start is given); dist (frames held, vectors).  r_ref is
+    the shortest distance among all frames held; the averages behind reff6, reff3 and S2rad run over the frames of the chunks used."""
+    if dist is not None:
+        dist = _check_dist(dist, (rv.frames, rv.nV))
+    return rv.ct_dipolar(R, F, dist=dist, chunk_start=chunk_start, mode=mode)
+
+
 def upload_shard(vec_list, frames_per_chunk=None, ctx=None):
     """The product path's single upload: this rank's vector range (srdist.my_range; everything in a single process) of the
     files' vectors, each file cut to whole chunks of frames_per_chunk frames when given (reformat_vecs_by_tau,

@@ -215,6 +215,25 @@ class Context:
         check(self.lib.sr_ct_cross_long_f32_dev(self.h, soa_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
                                                 int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr), 'sr_ct_cross_long_f32_dev')
 
+    # ---- distance-weighted dipolar correlation function (sr_ct_dipolar.hip) ----
+    def ct_dipolar_max_frames(self):
+        """longest chunk whose four series a_x, a_y, a_z, w fit the LDS of a workgroup (sr_ct_dipolar_max_frames)"""
+        return int(self.lib.sr_ct_dipolar_max_frames(self.h))
+
+    def pack_dipolar_dev(self, vecs_ptr, dist_ptr, N, Vtot, v0, nV, planes_ptr, Npad, rref_ptr):
+        """frame-major vectors (N, Vtot, 3) float32 of any length (and, when dist_ptr is not None, distances (N, Vtot) float32 that
+        replace their lengths) -> planes (nV, 4, Npad) float32 a_x, a_y, a_z, w and r_ref (nV) float64 (sr_pack_dipolar_f32_dev);
+        asynchronous on the context's stream"""
+        check(self.lib.sr_pack_dipolar_f32_dev(self.h, vecs_ptr, dist_ptr, int(N), int(Vtot), int(v0), int(nV), planes_ptr, int(Npad), rref_ptr),
+              'sr_pack_dipolar_f32_dev')
+
+    def ct_dipolar_dev(self, planes_ptr, Npad, nV, R, F, Ct_ptr, dCt_ptr, wmean_ptr, chunk_start=None, mode=0, psum_ptr=None):
+        """C_dd(t) and dC_dd(t) (F//2, nV) and wmean (nV, 2) = <w>, <w^2> from the four planes of pack_dipolar_dev into device arrays
+        (sr_ct_dipolar_f32_dev); asynchronous on the context's stream"""
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        check(self.lib.sr_ct_dipolar_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), int(mode), psum_ptr, Ct_ptr,
+                                             dCt_ptr, wmean_ptr), 'sr_ct_dipolar_f32_dev')
+
     # ---- iRED matrix (sr_ired.hip) ----
     def ired_matrix_dev(self, soa_ptr, Npad, nV, win_start, win_len, M_ptr):
         """M[w] = mean over frames [win_start[w], win_start[w] + win_len[w]) of P2(u_i . u_j) from packed planes, into the device
@@ -722,6 +741,27 @@ class ResidentVectors:
         check(getattr(self.ctx.lib, stem + '_f32')(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
                                                    int(mode), _ptr(P0), _ptr(Ct), _ptr(dCt)), stem + '_f32')
         return P0, Ct, dCt
+
+    def ct_dipolar(self, R, F, dist=None, chunk_start=None, mode=0):
+        """distance-weighted dipolar correlation function of the resident vectors (sr_vectors_ct_dipolar_f32):
+        C_dd(k) = <P2(u(t) . u(t+k)) r(t)^-3 r(t+k)^-3> / <r^-6>, k = 1 .. F//2, mean and error over the R chunks like ct().  dist
+        (frames held, nV): the distances, the vectors then give the direction only; None: the length of a vector is its distance.
+        Returns Ct, dCt (F//2, nV) and per vector reff6 = <r^-6>^(-1/6), reff3 = <r^-3>^(-1/3), S2rad = <r^-3>^2 / <r^-6>."""
+        L = F // 2
+        d = None
+        if dist is not None:
+            d = _f32(dist)
+            if d.shape != (self.frames, self.nV):
+                raise ValueError('dist must be (frames held, vectors) = (%d, %d), got %s' % (self.frames, self.nV, d.shape))
+        Ct = np.empty((L, self.nV))
+        dCt = np.empty((L, self.nV))
+        reff6, reff3, S2rad = np.empty(self.nV), np.empty(self.nV), np.empty(self.nV)
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        if cs is not None and cs.shape != (R,):
+            raise ValueError('chunk_start must have R entries')
+        check(self.ctx.lib.sr_vectors_ct_dipolar_f32(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), int(mode), _ptr(Ct), _ptr(dCt),
+                                                     _ptr(reff6), _ptr(reff3), _ptr(S2rad)), 'sr_vectors_ct_dipolar_f32')
+        return Ct, dCt, reff6, reff3, S2rad
 
     def ct_sums(self, R, F, chunk_start=None, mode=0):
         """raw sums S[v, r, d-1] = sum_j (u_j . u_{j+d})^2 of the R chunks held, (nV, R, F//2) float64 (replicate sharding)"""

@@ -197,7 +197,10 @@ int sr_ct_palmer_f32(sr_ctx *, const float *vecs, int64_t N, int64_t Vtot, int64
  * (general_maths.py:118-158), the per-bond np.histogramdd loop (calculate-Ct-from-traj.py:600-626),
  * the mean vector (:579-583) and calculate_S2_by_outerProduct (:96-145) in one pass over the planes.
  *   q           : 4 doubles (w,x,y,z), normalised inside like the reference; NULL = no rotation;
- *   edges_phi   : nphi+1 doubles, edges_cos: ncos+1 doubles -- the numpy.linspace edges; binning is
+ *   edges_phi   : nphi+1 doubles, edges_cos: ncos+1 doubles -- numpy.linspace(-pi, pi, nphi+1) and numpy.linspace(-1, 1, ncos+1),
+ *                 the edges np.histogramdd builds for range=((-pi, pi), (-1, 1)).  The kernel places most samples by arithmetic on
+ *                 equal bins, so the call returns -3 unless each array is strictly increasing, starts and ends at those values to
+ *                 1e-12 and has every edge within 1e-9 bin widths of its uniform position; binning is
  *                 numpy's: searchsorted(edges, x, 'right')-1, last edge inclusive, outside/NaN dropped;
  *   hist        : (nV, nphi, ncos) float64 counts (the dtype the reference stores);
  *   vecsum      : (nV, 3) float64 sum over the first N frames of the rotated vectors (may be NULL);
@@ -210,6 +213,13 @@ int sr_rotate_hist_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t N, 
 int sr_rotate_hist_f32(sr_ctx *, const float *vecs, int64_t N, int64_t Vtot, int64_t v0, int64_t nV,
                        const double *q, const double *edges_phi, int nphi, const double *edges_cos, int ncos,
                        double *hist, double *vecsum, double *outer, int64_t block_len);
+/* How kernel 2 cuts the N frames of a call with nV vectors into ranges -- the computation of sr_rotate_hist_f32_dev itself, as a host
+ * function that needs no context and no GPU (like sr_ct_formulation).  Fb = block_len when 0 < block_len <= N, else N; nB = N / Fb
+ * full S2 blocks; every block is cut into m ranges of sub frames (sub % 4 == 0, sub <= 8192, the last one shorter); the frames behind
+ * the last full block form further ranges of sub frames; nranges counts all of them.  Range rid < nB * m starts at frame
+ * (rid / m) * Fb + (rid % m) * sub, a later one at nB * Fb + (rid - nB * m) * sub; ranges 4 k .. 4 k + 3 share a workgroup.  Any
+ * output pointer may be NULL.  Returns -3 for N < 1 or nV < 1. */
+int sr_vechist_plan(int64_t N, int64_t nV, int64_t block_len, int64_t *Fb, int *nB, int *m, int64_t *sub, int *nranges);
 /* rotated vectors themselves, float64 (N, nV, 3) like the reference returns (for --vecDist output). */
 int sr_rotate_vectors_f32(sr_ctx *, const float *vecs, int64_t N, int64_t Vtot, int64_t v0, int64_t nV,
                           const double *q, double *out);

@@ -67,6 +67,9 @@ SIGNATURES = {
                                        c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64]),
     'sr_rotate_hist_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int,
                                    c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64]),
+    # (N, nV, block_len, Fb, nB, m, sub, nranges): a host function, no context
+    'sr_vechist_plan': (c_int, [c_int64, c_int64, c_int64, POINTER(c_int64), POINTER(c_int), POINTER(c_int), POINTER(c_int64),
+                                POINTER(c_int)]),
     'sr_rotate_vectors_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     'sr_rotate_vectors_perframe_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     'sr_expfit_resjac_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
@@ -169,7 +172,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13      # unchanged by the sr_ct_cross and sr_ct_dipolar entry points: they only add symbols, and load() fails at a missing one
+ABI_VERSION = 13      # unchanged by the sr_ct_cross and sr_ct_dipolar entry points and sr_vechist_plan: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -20,7 +20,12 @@
 //     bin; samples within a guard band of a bin edge, near the poles (where the float32 rotation error is amplified
 //     in phi), NaNs and out-of-range values take the exact path -- float64 rotation in the reference's operation
 //     order, atan2 / acos / cos, numpy's searchsorted rule -- so the counts stay bit-identical to numpy's
-//     (tests/test_gpu_parity.py::test_vechist_*).
+//     (tests/test_gpu_parity.py::test_vechist_*, and tests/test_gpu_vechist.py on vectors that cover the sphere, sit on the
+//     poles and overflow the list of undecided samples).  The estimate needs UNIFORM edges from -pi to pi and from -1 to 1:
+//     sr_rotate_hist_f32_dev refuses any others (uniform_edges below).
+//
+// sr_vechist_plan is the cut of the frames into ranges as a host function of (N, nV, block_len) alone: the launch uses it and a
+// test can tell from it which frames share a workgroup.
 //
 // Work decomposition: grid = (frame ranges, vectors).  A workgroup owns one vector and a frame range
 // that lies inside one S2 block; its histogram lives in LDS as 32-bit counters (nphi*ncos*4 B = 10 KB
@@ -258,7 +263,7 @@ __global__ __launch_bounds__(256, 4) void k_vechist(VhArgs a)
     if (tid == 0) *qcount = 0u;
     __syncthreads();
     const double *ephi = edges, *ecos = edges + a.nphi + 1;
-    // the float32 estimate assumes the uniform numpy.linspace edges of calculate-Ct-from-traj.py:618
+    // the float32 estimate assumes the uniform numpy.linspace edges of calculate-Ct-from-traj.py:618 (the host checks them)
     const float phi_scale = (float)((double)a.nphi / (ephi[a.nphi] - ephi[0]));
     const float cos_scale = (float)((double)a.ncos / (ecos[a.ncos] - ecos[0]));
     const float hp = 0.5f - fmaxf(kEdgeGuard, kPhiGuardRad * phi_scale), hc = 0.5f - fmaxf(kEdgeGuard, kCosGuard * cos_scale);
@@ -415,9 +420,51 @@ void normalise_q(const double *q, double *o)
     }
 }
 
+// The float32 estimate of k_vechist places a sample by (x - lo) * n / (hi - lo): it is only right for n equal bins between lo and
+// hi.  e[k] must lie within 1e-9 bin widths of lo + k (hi - lo) / n (numpy.linspace does, to rounding; the guard band of the
+// estimate is 2e-4 bin widths), strictly increasing, with (e[0], e[n]) = (lo, hi) to 1e-12.  NaN edges fail every comparison.
+bool uniform_edges(const double *e, int n, double lo, double hi)
+{
+    if (!(fabs(e[0] - lo) <= 1e-12) || !(fabs(e[n] - hi) <= 1e-12)) return false;
+    const double w = (e[n] - e[0]) / (double)n;
+    for (int k = 0; k <= n; ++k) {
+        if (!(fabs(e[k] - (e[0] + (double)k * w)) <= 1e-9 * w)) return false;
+        if (k > 0 && !(e[k] > e[k - 1])) return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sr_vechist_plan(int64_t N, int64_t nV, int64_t block_len, int64_t *Fb_out, int *nB_out, int *m_out, int64_t *sub_out,
+                    int *nranges_out)
+{
+    SR_REQUIRE(N >= 1 && nV >= 1, -3, "sr_vechist_plan: bad shape N=%lld nV=%lld", (long long)N, (long long)nV);
+    const int64_t Fb = (block_len > 0 && block_len <= N) ? block_len : N;
+    const int nB = (int)(N / Fb);
+    // ranges: every S2 block is cut into m ranges of `sub` frames (a multiple of 4, at most kMaxRange: the LDS mask and
+    // list of undecided samples are sized for it); enough of them that the grid fills the chip (>= ~1024 workgroups of
+    // kRangesPerWG ranges each), each at least 1024 frames; the frames behind the last full block form further ranges
+    int64_t want = (1024 * kRangesPerWG + nV - 1) / nV;
+    int64_t per_block = (want + nB - 1) / nB;
+    if (per_block < 1) per_block = 1;
+    const int64_t maxm = (Fb + 1023) / 1024, minm = (Fb + kMaxRange - 1) / kMaxRange;
+    if (per_block > maxm) per_block = maxm;
+    if (per_block < minm) per_block = minm;
+    int m = (int)per_block;
+    int64_t sub = sr_round_up((Fb + m - 1) / m, 4);
+    if (sub > kMaxRange) sub = kMaxRange;
+    m = (int)((Fb + sub - 1) / sub);
+    const int64_t tail = N - (int64_t)nB * Fb;
+    if (Fb_out) *Fb_out = Fb;
+    if (nB_out) *nB_out = nB;
+    if (m_out) *m_out = m;
+    if (sub_out) *sub_out = sub;
+    if (nranges_out) *nranges_out = nB * m + (int)((tail + sub - 1) / sub);
+    return 0;
+}
 
 int sr_rotate_hist_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t N, int64_t nV, const double *q_host,
                            const double *edges_phi_host, int nphi, const double *edges_cos_host, int ncos,
@@ -430,26 +477,13 @@ int sr_rotate_hist_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t 
     SR_REQUIRE(nphi >= 1 && ncos >= 1 && nphi + ncos + 2 <= kMaxEdges && (int64_t)nphi * ncos <= 32768, -3,
                "sr_rotate_hist_f32_dev: unsupported histogram size %d x %d", nphi, ncos);
     SR_REQUIRE(nV <= 65535, -3, "sr_rotate_hist_f32_dev: at most 65535 vectors per call");
+    SR_REQUIRE(uniform_edges(edges_phi_host, nphi, -M_PI, M_PI) && uniform_edges(edges_cos_host, ncos, -1.0, 1.0), -3,
+               "sr_rotate_hist_f32_dev: the edges must be numpy.linspace(-pi, pi, %d) and numpy.linspace(-1, 1, %d) "
+               "(uniform to 1e-9 bin widths, strictly increasing)", nphi + 1, ncos + 1);
     const int nbins = nphi * ncos;
     VhArgs a;
     a.soa = soa; a.Npad = Npad; a.N = N;
-    a.Fb = (block_len > 0 && block_len <= N) ? block_len : N;
-    a.nB = (int)(N / a.Fb);
-    // ranges: every S2 block is cut into m ranges of `sub` frames (a multiple of 4, at most kMaxRange: the LDS mask and
-    // list of undecided samples are sized for it); enough of them that the grid fills the chip (>= ~1024 workgroups of
-    // kRangesPerWG ranges each), each at least 1024 frames; the frames behind the last full block form further ranges
-    int64_t want = (1024 * kRangesPerWG + nV - 1) / nV;
-    int64_t per_block = (want + a.nB - 1) / a.nB;
-    if (per_block < 1) per_block = 1;
-    const int64_t maxm = (a.Fb + 1023) / 1024, minm = (a.Fb + kMaxRange - 1) / kMaxRange;
-    if (per_block > maxm) per_block = maxm;
-    if (per_block < minm) per_block = minm;
-    a.m = (int)per_block;
-    a.sub = sr_round_up((a.Fb + a.m - 1) / a.m, 4);
-    if (a.sub > kMaxRange) a.sub = kMaxRange;
-    a.m = (int)((a.Fb + a.sub - 1) / a.sub);
-    const int64_t tail = N - (int64_t)a.nB * a.Fb;
-    a.nranges = a.nB * a.m + (int)((tail + a.sub - 1) / a.sub);
+    if (int rc = sr_vechist_plan(N, nV, block_len, &a.Fb, &a.nB, &a.m, &a.sub, &a.nranges)) return rc;
     a.nphi = nphi; a.ncos = ncos;
     a.rotate = q_host ? 1 : 0;
     a.qw = 1; a.qx = a.qy = a.qz = 0;

@@ -45,6 +45,18 @@ def _windows(win_start, win_len):
     return ws, wl
 
 
+def vechist_plan(N, nV, block_len=0):
+    """How kernel 2 cuts a call of N frames and nV vectors into frame ranges (sr_vechist_plan: a host function, no Context and no
+    GPU): dict(Fb, nB, m, sub, nranges).  Range rid < nB * m starts at frame (rid // m) * Fb + (rid % m) * sub and ends with its
+    block, a later one (the frames behind the last full block) at nB * Fb + (rid - nB * m) * sub; ranges 4 k .. 4 k + 3 share a
+    workgroup."""
+    Fb, sub = ctypes.c_int64(), ctypes.c_int64()
+    nB, m, nranges = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_lib.load().sr_vechist_plan(int(N), int(nV), int(block_len or 0), ctypes.byref(Fb), ctypes.byref(nB), ctypes.byref(m),
+                                      ctypes.byref(sub), ctypes.byref(nranges)), 'sr_vechist_plan')
+    return dict(Fb=Fb.value, nB=nB.value, m=m.value, sub=sub.value, nranges=nranges.value)
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = _lib.load()
@@ -274,7 +286,8 @@ class Context:
 
     # ---- kernel 2 ----
     def rotate_hist(self, vecs, q, edges_phi, edges_cos, v0=0, nV=None, block_len=0, want_outer=True):
-        """vecs (N, Vtot, 3) float32 -> hist (nV, nphi, ncos), vecsum (nV,3), outer (nB, nV, 6)."""
+        """vecs (N, Vtot, 3) float32 -> hist (nV, nphi, ncos), vecsum (nV,3), outer (nB, nV, 6).  The edges must be
+        numpy.linspace(-pi, pi, nphi + 1) and numpy.linspace(-1, 1, ncos + 1); any others are refused."""
         vecs = _f32(vecs)
         N, Vtot, _ = vecs.shape
         nV = Vtot - v0 if nV is None else nV

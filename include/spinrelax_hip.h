@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross and sr_ct_dipolar entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
+#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross, sr_ct_dipolar and sr_ct_dipolar_cross entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -415,6 +415,33 @@ int sr_ct_dipolar_f32_dev(sr_ctx *, const float *planes_dev, int64_t Npad, int64
                           int mode, double *psum_ws, double *Ct, double *dCt, double *wmean);
 int sr_vectors_ct_dipolar_f32(sr_ctx *, sr_vectors *, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
                               double *Ct, double *dCt, double *reff6, double *reff3, double *S2rad);
+
+/* ---- distance-weighted cross-correlation between pairs of flexible spin pairs (sr_ct_dipolar_cross.hip; beyond the reference) --------
+ * The two functions above at once, what dipole-dipole cross-correlated relaxation between two spin pairs of fluctuating distance needs:
+ *     C_ij(k) = < P2(u_i(t) . u_j(t+k)) r_i(t)^-3 r_j(t+k)^-3 > / sqrt(< r_i^-6 > < r_j^-6 >),   k = 1 .. L = F / 2
+ * and P0 = C_ij(0), from the four planes of sr_pack_dipolar_f32_dev and a pair table as sr_ct_cross_f32_dev takes it (HOST arrays, consumed
+ * on return; the later frame from vector j; sym = 1: the mean of C_ij and C_ji, sym = 0: C_ij alone; mode as there).  Per chunk r
+ *     c_r(k) = [1.5 sum_t (a_i(t) . a_j(t+k))^2 - 0.5 sum_t w_i(t) w_j(t+k)] / (F - k),     n_v = mean_r sum_t w_v(t)^2 / F
+ *     C_ij(k) = mean_r c_r(k) / sqrt(n_i n_j),   dC_ij(k) = [std_r c_r(k) / (sqrt(R) - 1)] / sqrt(n_i n_j);   P0 and dP0 alike from c_r(0)
+ * (ratios of chunk means: the scatter of the normaliser is ignored, the r_ref factors cancel).  For i = j: C_dd of sr_ct_dipolar_f32_dev
+ * and P0 = 1, to rounding.  No atomics: equal input gives bit-equal output, a repeated pair the same bits.
+ *   sr_ct_dipolar_cross_f32_dev       planes (nV, 4, Npad) -> P0, dP0 (nP; dP0 may be NULL), Ct, dCt (L, nP) and wsum2 (nP, R, 2) = the sums
+ *                                     of w_i^2 and w_j^2 over every chunk, float64 DEVICE arrays; psum_ws (optional, may be NULL):
+ *                                     (nP, R, sr_ct_psum_stride(F)) float64.  Asynchronous behind the upload of the small tables; every
+ *                                     argument check comes before the first launch.
+ *   sr_vectors_ct_dipolar_cross_f32   the same of resident vectors, results on the HOST, blocking, and reff6 (nP, 2) = <r^-6>^(-1/6) of the
+ *                                     two vectors of each pair over the frames of the chunks, in the units of the input.  dist_host, its
+ *                                     refusals and the reuse of the object's four-plane pack exactly as sr_vectors_ct_dipolar_f32.
+ * One workgroup stages the eight series of a (pair, chunk) in LDS, 32 bytes per frame: F up to sr_ct_dipolar_cross_max_frames() (4896 with
+ * the 160 KiB of gfx950); a longer chunk is refused with -4 before anything is launched (there is no blocked form).  A pair index or a
+ * chunk start outside what is held, a bad mode or sym: -3. */
+int64_t sr_ct_dipolar_cross_max_frames(sr_ctx *);
+int sr_ct_dipolar_cross_f32_dev(sr_ctx *, const float *planes_dev, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode, double *psum_ws,
+                                double *P0, double *dP0, double *Ct, double *dCt, double *wsum2);
+int sr_vectors_ct_dipolar_cross_f32(sr_ctx *, sr_vectors *, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                    const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0,
+                                    double *Ct, double *dCt, double *reff6);
 
 /* ---- kernel 3b: multi-exponential C(t) model --------------------------------------------
  * Model of curvefit_exponential (fitting_Ct_functions.py:419-427): params = [C_1..C_K, tau_1..tau_K

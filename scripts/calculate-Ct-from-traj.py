@@ -4,7 +4,8 @@ Drop-in for the reference's calculate-Ct-from-traj.py (run-all.bash:476-481): sa
 files (<o>_Ctext.dat, <o>_Ctint.dat, <o>_vecHistogram.npz | _vecPhiTheta.npz|.dat, <o>_avgvec.dat,
 <o>_S2.dat; with the [extension] --iRED also <o>_iRED_S2.dat, <o>_iRED_eig.dat and, with --binary, <o>_iRED_matrix.npz; with --iRED_Ct
 also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat; with the [extension] --crossCt --pairs FILE also <o>_crossCtint.dat
-and <o>_crossPairs.dat; with the [extension] --dipolarCt also <o>_dipolarCtint.dat and <o>_dipolarDist.dat).  C(t), the rotation into
+and <o>_crossPairs.dat; with the [extension] --dipolarCt also <o>_dipolarCtint.dat and <o>_dipolarDist.dat; with the
+[extension] --dipolarCrossCt --pairs FILE also <o>_dipolarCrossCtint.dat and <o>_dipolarCrossPairs.dat).  C(t), the rotation into
 the PAF, the spherical histogram, the mean vector and S2 are computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
 Several GPUs: run under torchrun (`torchrun --nproc-per-node N scripts/calculate-Ct-from-traj.py ...`): rank r computes the
@@ -20,7 +21,7 @@ Trajectory input:
     and `fit_indices` -- which go through the same GPU front end, or precomputed unit vectors `vecs` (frames, bonds, 3;
     body frame) with optional `vecs_lab` (lab frame for _Ctext.dat; defaults to `vecs`); plus `names` (resSeq per bond;
     default 2..V+1) and `dt` (ps; default --dt).  A .npy holds unit vectors.  -s is still parsed and ignored then.
-    For --dipolarCt the distances come from the same file: |x_H - x_X| of the coordinates; `dist` (frames, bonds) beside `vecs`, or
+    For --dipolarCt and --dipolarCrossCt the distances come from the same file: |x_H - x_X| of the coordinates; `dist` (frames, bonds) beside `vecs`, or
     the lengths of `vecs` without it; the lengths of the vectors of a .npy -- every other analysis of the same run still expects
     unit vectors.
 """
@@ -99,6 +100,15 @@ def build_parser():
                         'of the vectors; then the other analyses of the run still expect unit vectors.  At most 10016 frames per chunk.  '
                         '--exact: float64 throughout.  Dot products and distances do not change under a rotation: --vecRot has no '
                         'effect on these files.  Single process only.')
+    p.add_argument('--dipolarCrossCt', dest='bDoDipolarCrossCt', action='store_true', default=False,
+                   help='[extension, needs --pairs and --tau] distance-weighted P2 cross-correlation functions between pairs of flexible '
+                        'spin pairs, <P2(u_i(t).u_j(t+k)) r_i(t)^-3 r_j(t+k)^-3> / sqrt(<r_i^-6><r_j^-6>), the function of dipole-dipole '
+                        'cross-correlated relaxation: --crossCt with the distance weights of --dipolarCt.  <o>_dipolarCrossCtint.dat (the '
+                        'format of _crossCtint.dat, one block per pair) and <o>_dipolarCrossPairs.dat (ordinal, i, j, their residue ids, '
+                        'the equal-time value P0 and its standard error over the chunks, and the effective distances <r^-6>^(-1/6) of '
+                        'the two vectors).  Pairs from --pairs, --asym as for --crossCt; distances as for --dipolarCt (vector-file input '
+                        'only).  At most 4896 frames per chunk.  --exact: float64 throughout.  --vecRot has no effect on these files.  '
+                        'Single process only.')
     return p
 
 
@@ -246,6 +256,14 @@ def main():
     args = parser.parse_args()
     if args.bDoCrossCt and args.pairs_fn is None:
         parser.error('--crossCt needs --pairs FILE')
+    if args.bDoDipolarCrossCt and args.pairs_fn is None:
+        parser.error('--dipolarCrossCt needs --pairs FILE')
+    if args.bDoDipolarCrossCt and args.tau is None:
+        parser.error('--dipolarCrossCt needs --tau: the functions are block averages over the memory time')
+    if args.bDoDipolarCrossCt and not all(f.endswith('.npy') or f.endswith('.npz') for f in args.infn):
+        print("= = = ERROR: --dipolarCrossCt works on vector-file input (.npy/.npz), not on MDTraj input: the streaming front end keeps no "
+              "distances.", file=sys.stderr)
+        sys.exit(1)
     if args.bDoDipolarCt and args.tau is None:
         print("= = = Refusing to do dipolar correlation analysis without using a block averaging over memory_time tau!", file=sys.stderr)
         sys.exit(1)
@@ -258,6 +276,11 @@ def main():
     if args.bDoDipolarCt and world > 1:
         # the ranks hold ranges of vectors; the distances and the output are not sharded
         print("= = = ERROR: --dipolarCt does not run under torchrun with more than one rank; run it as a single process.", file=sys.stderr)
+        sys.exit(1)
+    if args.bDoDipolarCrossCt and world > 1:
+        # the ranks hold ranges of vectors and a pair needs both of its vectors; the distances and the output are not sharded
+        print("= = = ERROR: --dipolarCrossCt needs all vectors on one GPU and does not run under torchrun with more than one rank; "
+              "run it as a single process.", file=sys.stderr)
         sys.exit(1)
     if args.help_sel:
         print("Notes: This program uses MDTraj selection syntax, e.g. 'chain A and resname GLY and name HA1 HA2'.")
@@ -436,6 +459,30 @@ def main():
             print("# resid reff6 reff3 S2rad", file=fp)
             for n in range(V):
                 print("%s %.8g %.8g %.8g" % (resXH[n], reff6[n], reff3[n], S2rad[n]), file=fp)
+        print("      ...complete.")
+    if args.bDoDipolarCrossCt:
+        try:
+            pairs = hostct.read_pairs(args.pairs_fn, V)
+        except (OSError, ValueError) as exc:
+            print("= = = ERROR: %s" % exc, file=sys.stderr)
+            sys.exit(1)
+        if args.bCrossAsym:
+            pairs = np.stack((pairs, pairs[:, ::-1]), axis=1).reshape(-1, 2)      # (i, j) then (j, i)
+        print("= = = Conducting distance-weighted cross-correlation analysis of %i pairs of fitted vectors using Palmer's approach." % len(pairs))
+        try:
+            dist = load_distance_files(args.infn, F)
+            P0, dP0, Cx, dCx, reff6 = hostct.calculate_Ct_dipolar_cross_resident(rv_fit, pairs, R, F, dist=dist, symmetric=not args.bCrossAsym,
+                                                                                 mode=1 if args.exact else 0)
+        except (ValueError, hostct.hip.SpinRelaxHipError) as exc:      # a bad distance, a zero-length vector, a chunk beyond the LDS
+            print("= = = ERROR: %s" % exc, file=sys.stderr)
+            sys.exit(1)
+        ordinals = list(range(1, len(pairs) + 1))
+        gs.print_sxylist(out_pref + '_dipolarCrossCtint.dat', ordinals, hostct.calculate_dt(deltaT, tau_memory), np.stack((Cx.T, dCx.T), axis=-1))
+        with open(out_pref + '_dipolarCrossPairs.dat', 'w') as fp:
+            print("# pair i j resid_i resid_j P0 dP0 reff6_i reff6_j", file=fp)
+            for n, (i, j) in enumerate(pairs):
+                print("%d %d %d %s %s %.8g %.8g %.8g %.8g" % (ordinals[n], i, j, resXH[i], resXH[j], P0[n], dP0[n], reff6[n, 0], reff6[n, 1]),
+                      file=fp)
         print("      ...complete.")
 
     need_dist = args.bDoVecAverage or args.bDoS2 or (bDoVecDistrib and args.bDoVecHist)

@@ -163,6 +163,13 @@ SIGNATURES = {
                                       c_void_p]),
     'sr_vectors_ct_dipolar_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
+    # the distance-weighted pair cross-correlation (sr_ct_dipolar_cross.hip): sr_ct_cross_f32_dev's arguments on the four planes and wsum2_dev
+    # behind them / (ctx, vectors, dist_host, R, F, chunk_start, pair_i, pair_j, nP, sym, mode, P0, dP0, Ct, dCt, reff6), all on the host
+    'sr_ct_dipolar_cross_max_frames': (c_int64, [c_void_p]),
+    'sr_ct_dipolar_cross_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                            c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'sr_vectors_ct_dipolar_cross_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                                c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'sr_counter': (c_int, [c_void_p, c_char_p, POINTER(ctypes.c_uint64)]),
     'sr_transpose_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'sr_jomega_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
@@ -172,7 +179,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13      # unchanged by the sr_ct_cross and sr_ct_dipolar entry points and sr_vechist_plan: they only add symbols, and load() fails at a missing one
+ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar and sr_ct_dipolar_cross entry points and sr_vechist_plan: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

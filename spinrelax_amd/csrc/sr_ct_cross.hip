@@ -160,6 +160,14 @@ int sr_ct_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, 
     return 0;
 }
 
+int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nP, double *P0, double *dP0)
+{
+    hipLaunchKernelGGL(k_ct_cross_p0, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, ctx->stream, psum, (int)R, (int)F,
+                       (int)sr_ct_psum_stride(F), nP, P0, dP0);
+    SR_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 int64_t sr_ct_cross_max_frames(sr_ctx *ctx)
@@ -197,8 +205,7 @@ static int cross_f32_dev(sr_ctx *ctx, const char *who, int blocked, const float 
         a.R = (int)R; a.F = (int)F; a.Fp = (int)(sr_ct_direct_lds_bytes(F) / 12); a.L = (int)(F / 2); a.Lp = (int)Lp; a.sym = sym; a.mode = mode;
         if (int rc = sr_launch(ctx, k_ct_cross, dim3((unsigned)(nP * R)), dim3(kCrossWaves * 64), cross_lds_bytes(F), a)) return rc;
     }
-    hipLaunchKernelGGL(k_ct_cross_p0, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, ctx->stream, psum, (int)R, (int)F, (int)Lp, nP, P0, dP0);
-    SR_HIP(hipGetLastError());
+    if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, P0, dP0)) return rc;
     return sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt);
 }
 

@@ -1,0 +1,261 @@
+// sr_ct_dipolar_cross.hip -- distance-weighted P2 cross-correlation between pairs of flexible spin pairs (k_ct_dipolar_cross), the
+// function of dipole-dipole cross-correlated relaxation; k_ct_cross (sr_ct_cross.hip) with the r^-3 weights of k_ct_dipolar
+// (sr_ct_dipolar.hip):
+//     C_ij(k) = < P2(u_i(t) . u_j(t+k)) r_i(t)^-3 r_j(t+k)^-3 > / sqrt(< r_i^-6 > < r_j^-6 >)
+// on the Palmer chunk table of kernel 1, from the four-plane pack a_x, a_y, a_z, w of k_pack_dipolar (per vector w = (r_ref / r)^3,
+// a = u sqrt(w), so P2(u_i . u_j') w_i w_j' = 1.5 (a_i . a_j')^2 - 0.5 w_i w_j').
+//
+// Per (pair, chunk), the later frame from vector j as in k_ct_cross:
+//     S_a(k) = sum_t (a_i(t) . a_j(t+k))^2,   S_w(k) = sum_t w_i(t) w_j(t+k),   k = 0 .. L = F/2
+// (sym = 1: the mean of both directions, summed by the same lane in a fixed order).  The raw sums leave as
+// S'(k) = S_a(k) - S_w(k) / 3 + (F - k) / 3 in kernel 1's psum layout, row (pair, chunk), lag 0 in slot 0: the unchanged k_ct_finalize
+// and k_ct_cross_p0 give the chunk mean of the unnormalised function, its std / (sqrt(R) - 1) and the equal-time value with its error;
+// k_ct_dipolar_cross_norm scales all four by 1 / sqrt(n_i n_j), n_v the mean over the chunks of sum_t w_v^2 / F (k_ct_dipolar_norm's
+// convention: a ratio of chunk means, the normaliser's own scatter is ignored; the r_ref factors cancel).  For i = j the result is
+// C_dd of k_ct_dipolar with P0 = 1, to rounding.
+//
+// Kernel: one workgroup of 8 waves per (pair, chunk) (k_ct_cross's shape) stages eight series in LDS: for i and for j the three a planes
+// (ct_stage_series) and the w series behind them (lds_wpos), 32 bytes per frame, 138 240 B at F = 4096: one workgroup per CU.  Per
+// block of 128 lags a wave runs ct_shift_block(a_i, a_j) and dip_shift_block_w(w_i, w_j), with sym both again with the series
+// exchanged; the float32 partial sums start at -min(kCenter, 8 sqrt(sum w_i^2 sum w_j^2) / F), the adaptive centre of k_ct_dipolar
+// (the terms are <= w_i w_j').  Remaining lags and every lag in mode 1 take a float64 path.  While at it every wave sums w_i^2 and
+// w_j^2 of the chunk in float64 and wave 0 writes them out.  No atomics, no scratch: equal input gives bit-equal output.
+// A chunk must fit 32 ct_Fp(F) bytes of LDS: F <= 4896 at 160 KiB.  A blocked form for longer chunks does not exist.
+#include "sr_ct_dipolar.h"
+#include <cmath>
+
+namespace {
+
+constexpr int kDipCrossWaves = 8;
+
+struct CtDipCrossArgs {
+    const float *soa;             // (nV, 4, Npad)
+    int64_t Npad;
+    const int64_t *chunk_start;   // device, may be null
+    const int32_t *pair_i, *pair_j;   // device
+    double *psum;                 // (nP, R, Lp)
+    double *wsum2;                // (nP, R, 2): sum of w_i^2 and of w_j^2 over the chunk
+    int R, F, Fp, L, Lp, sym, mode;
+};
+
+__global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtDipCrossArgs a)
+{
+    extern __shared__ __align__(16) float lds[];
+    const int Fp = a.Fp, Hf = (Fp >> 3) * 12, Hw = Fp >> 1, F = a.F;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int p = blockIdx.x / a.R;
+    const int r = blockIdx.x - p * a.R;
+    // per vector 4 Fp floats: the three a planes (2 Hf = 3 Fp floats) and the w series behind them
+    float *ai = lds, *wi = lds + 2 * Hf;
+    float *aj = lds + 4 * Fp, *wj = aj + 2 * Hf;
+
+    // ---- stage the eight series (coalesced dword loads; zero padding behind frame F) ----
+    {
+        const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
+        const float *pi = a.soa + (int64_t)a.pair_i[p] * 4 * a.Npad + start;
+        const float *pj = a.soa + (int64_t)a.pair_j[p] * 4 * a.Npad + start;
+        const float *pwi = pi + 3 * a.Npad, *pwj = pj + 3 * a.Npad;
+        ct_stage_series<kDipCrossWaves * 64>(ai, pi, pi + a.Npad, pi + 2 * a.Npad, F, Fp, Hf, tid);
+        ct_stage_series<kDipCrossWaves * 64>(aj, pj, pj + a.Npad, pj + 2 * a.Npad, F, Fp, Hf, tid);
+        for (int e = tid; e < Fp; e += kDipCrossWaves * 64) {
+            const int q = lds_wpos(e, Hw);
+            const bool in = e < F;
+            wi[q] = in ? pwi[e] : 0.f;
+            wj[q] = in ? pwj[e] : 0.f;
+        }
+    }
+    __syncthreads();
+
+    double *out = a.psum + ((int64_t)p * a.R + r) * a.Lp;
+    const int nb = (a.mode == 0) ? (a.L + 1) / kLagBlock : 0;
+    const double scale = a.sym ? 0.5 : 1.0;
+
+    // ---- sum of w_i^2 and of w_j^2 over the chunk, float64, fixed order: wave 0 writes them out; every wave with a lag block takes the
+    // centre of its float32 partial sums from them (k_ct_dipolar's adaptive centre: the terms of both sums are <= w_i w_j', on average
+    // about sqrt(<w_i^2> <w_j^2>)) ----
+    float center = kCenter;
+    if (nb > 0 || wave == 0) {
+        double si = 0.0, sj = 0.0;
+        for (int t = lane; t < F; t += 64) {
+            const int q = lds_wpos(t, Hw);
+            const double x = (double)wi[q], y = (double)wj[q];
+            si += x * x;
+            sj += y * y;
+        }
+        si = wave_sum_f64(si);
+        sj = wave_sum_f64(sj);
+        if (wave == 0 && lane == 0) {
+            double *o = a.wsum2 + ((int64_t)p * a.R + r) * 2;
+            o[0] = si;
+            o[1] = sj;
+        }
+        center = fminf(kCenter, (float)(8.0 * sqrt(si * sj) / (double)F));
+    }
+
+    // ---- fast path: full lag blocks (lag 0 included), serpentine assignment balances the (F - lag) work ----
+    int g, l16;
+    lane_to_strip(lane, g, l16);
+    for (int i = 0; i * kDipCrossWaves < nb; ++i) {
+        const int k = (i & 1) ? i * kDipCrossWaves + (kDipCrossWaves - 1 - wave) : i * kDipCrossWaves + wave;
+        if (k >= nb) continue;
+        const int dw = k * kLagBlock;
+        double sa[kLagsPerLane], sw[kLagsPerLane];
+#pragma unroll
+        for (int d = 0; d < kLagsPerLane; ++d) sa[d] = sw[d] = 0.0;
+        ct_shift_block(ai, aj, Hf, F, dw, g, l16, sa, center);                 // S_a of (i, j)
+        dip_shift_block_w(wi, wj, Hw, F, dw, g, l16, sw, center);              // S_w of (i, j)
+        if (a.sym) {
+            ct_shift_block(aj, ai, Hf, F, dw, g, l16, sa, center);             // + (j, i)
+            dip_shift_block_w(wj, wi, Hw, F, dw, g, l16, sw, center);
+        }
+        ct_combine_strips(sa, l16);
+        ct_combine_strips(sw, l16);
+        if (g == 0) {
+            const int lag0 = dw + kLagsPerLane * l16;
+            double *o = out + lag0;
+#pragma unroll
+            for (int d = 0; d < kLagsPerLane; ++d) o[d] = scale * (sa[d] - sw[d] / 3.0) + (double)(F - lag0 - d) / 3.0;
+        }
+    }
+
+    // ---- float64 path: remaining lags (and every lag in validation mode) ----
+    for (int d = nb * kLagBlock + wave; d <= a.L; d += kDipCrossWaves) {
+        double s = 0.0, q = 0.0;
+        for (int t = lane; t + d < F; t += 64) {
+            const int pa = lds_pos(t, 0, Hf), pb = lds_pos(t + d, 0, Hf);
+            const int wa = lds_wpos(t, Hw), wb = lds_wpos(t + d, Hw);
+            const double x = (double)ai[pa] * (double)aj[pb] + (double)ai[pa + 4] * (double)aj[pb + 4] +
+                             (double)ai[pa + 8] * (double)aj[pb + 8];
+            s += x * x;
+            q += (double)wi[wa] * (double)wj[wb];
+            if (a.sym) {
+                const double y = (double)aj[pa] * (double)ai[pb] + (double)aj[pa + 4] * (double)ai[pb + 4] +
+                                 (double)aj[pa + 8] * (double)ai[pb + 8];
+                s += y * y;
+                q += (double)wj[wa] * (double)wi[wb];
+            }
+        }
+        s = wave_sum_f64(s);
+        q = wave_sum_f64(q);
+        if (lane == 0) out[d] = scale * (s - q / 3.0) + (double)(F - d) / 3.0;
+    }
+}
+
+// Ct, dCt (L, nP) of k_ct_finalize and P0, dP0 (nP; dP0 may be null) of k_ct_cross_p0 scaled in place by 1 / sqrt(n_i n_j), n_v the mean
+// over the chunks of sum_t w_v^2 / F, the chunk sums added in chunk order.  One workgroup: 64 pairs x 64 lags; those of blockIdx.x = 0
+// also scale P0 and dP0.
+__global__ __launch_bounds__(256) void k_ct_dipolar_cross_norm(const double *__restrict__ wsum2, int R, int F, int L, int64_t nP,
+                                                               double *__restrict__ Ct, double *__restrict__ dCt, double *__restrict__ P0,
+                                                               double *__restrict__ dP0)
+{
+    __shared__ double inv[64];
+    const int tid = threadIdx.x;
+    const int64_t p0 = (int64_t)blockIdx.y * 64;
+    if (tid < 64 && p0 + tid < nP) {
+        const double *s = wsum2 + (p0 + tid) * R * 2;
+        double ni = 0.0, nj = 0.0;
+        for (int r = 0; r < R; ++r) {
+            ni += s[2 * r] / (double)F;
+            nj += s[2 * r + 1] / (double)F;
+        }
+        inv[tid] = 1.0 / sqrt((ni / (double)R) * (nj / (double)R));
+        if (blockIdx.x == 0) {
+            P0[p0 + tid] *= inv[tid];
+            if (dP0) dP0[p0 + tid] *= inv[tid];
+        }
+    }
+    __syncthreads();
+    const int pl = tid & 63;
+    const int64_t p = p0 + pl;
+    if (p >= nP) return;
+    for (int i = tid >> 6; i < 64; i += 4) {
+        const int d = blockIdx.x * 64 + i;              // lag index - 1
+        if (d >= L) break;
+        const int64_t o = (int64_t)d * nP + p;
+        Ct[o] *= inv[pl];
+        dCt[o] *= inv[pl];
+    }
+}
+
+size_t dipx_lds_bytes(int64_t F) { return (size_t)ct_Fp(F) * 8 * sizeof(float); }
+
+int64_t dipx_max_frames(size_t lds_limit)
+{
+    int64_t F = (int64_t)lds_limit / 32 - kPad;         // an upper bound: ct_Fp(F) >= F + kPad
+    while (F >= 2 && dipx_lds_bytes(F) > lds_limit) --F;
+    return F >= 2 ? F : 0;
+}
+
+}  // namespace
+
+int sr_ct_dipolar_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                              const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode)
+{
+    SR_REQUIRE(pair_i && pair_j, -2, "%s: null pointer", who);
+    SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1 && nP >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld nP=%lld", who, (long long)R, (long long)F,
+               (long long)nV, (long long)nP);
+    SR_REQUIRE((mode == 0 || mode == 1) && (sym == 0 || sym == 1), -3, "%s: mode and sym must be 0 or 1", who);
+    SR_REQUIRE(dipx_lds_bytes(F) <= sr_lds_limit(ctx), -4,
+               "%s: the eight series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (no blocked form for the dipolar "
+               "cross-correlation function)",
+               who, (long long)F, dipx_lds_bytes(F), sr_lds_limit(ctx), (long long)dipx_max_frames(sr_lds_limit(ctx)));
+    SR_REQUIRE(R * nP < (int64_t)1 << 30, -3, "%s: too many series", who);
+    SR_REQUIRE((nP + 15) / 16 <= 65535, -3, "%s: too many pairs in one call (%lld)", who, (long long)nP);       // k_ct_finalize's grid
+    if (chunk_start_host) {
+        for (int64_t r = 0; r < R; ++r)
+            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= frames, -3, "%s: chunk %lld start %lld out of range", who,
+                       (long long)r, (long long)chunk_start_host[r]);
+    } else {
+        SR_REQUIRE(R * F <= frames, -3, "%s: R*F=%lld exceeds the %lld frames held", who, (long long)(R * F), (long long)frames);
+    }
+    for (int64_t p = 0; p < nP; ++p)
+        SR_REQUIRE(pair_i[p] >= 0 && pair_i[p] < nV && pair_j[p] >= 0 && pair_j[p] < nV, -3, "%s: pair %lld = (%d, %d) is outside the %lld vectors",
+                   who, (long long)p, (int)pair_i[p], (int)pair_j[p], (long long)nV);
+    return 0;
+}
+
+extern "C" {
+
+int64_t sr_ct_dipolar_cross_max_frames(sr_ctx *ctx)
+{
+    if (!ctx) return -1;
+    return dipx_max_frames(sr_lds_limit(ctx));
+}
+
+int sr_ct_dipolar_cross_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode, double *psum_ws,
+                                double *P0, double *dP0, double *Ct, double *dCt, double *wsum2)
+{
+    const char *who = "sr_ct_dipolar_cross_f32_dev";
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(planes && P0 && Ct && dCt && wsum2, -2, "%s: null pointer", who);
+    if (int rc = sr_ct_dipolar_cross_check(ctx, who, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode)) return rc;
+    const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
+    double *psum = psum_ws;
+    if (!psum) {
+        psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(nP * R * Lp) * sizeof(double));
+        if (!psum) return -5;
+    }
+    // ---- stage the chunk starts and the pair table ----
+    sr_stage st(ctx);
+    st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 2 * (size_t)nP * sizeof(int32_t));
+    CtDipCrossArgs a;
+    a.chunk_start = st.put(chunk_start_host, (size_t)R);
+    a.pair_i = st.put(pair_i_host, (size_t)nP);
+    a.pair_j = st.put(pair_j_host, (size_t)nP);
+    if (int rc = st.finish()) return rc;            // small tables: the caller's arrays are free again when this returns
+    // ---- launch ----
+    a.soa = planes; a.Npad = Npad; a.psum = psum; a.wsum2 = wsum2;
+    a.R = (int)R; a.F = (int)F; a.Fp = (int)ct_Fp(F); a.L = (int)L; a.Lp = (int)Lp; a.sym = sym; a.mode = mode;
+    if (int rc = sr_launch(ctx, k_ct_dipolar_cross, dim3((unsigned)(nP * R)), dim3(kDipCrossWaves * 64), dipx_lds_bytes(F), a)) return rc;
+    if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, P0, dP0)) return rc;
+    if (int rc = sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt)) return rc;
+    hipLaunchKernelGGL(k_ct_dipolar_cross_norm, dim3((unsigned)((L + 63) / 64), (unsigned)((nP + 63) / 64)), dim3(256), 0, ctx->stream, wsum2,
+                       (int)R, (int)F, (int)L, nP, Ct, dCt, P0, dP0);
+    SR_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -128,6 +128,10 @@ int sr_launch_ct_rfft64(sr_ctx *ctx, const sr_ct_job &job);
 int sr_ct_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
                       const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, int blocked);
 
+// sr_ct_cross.hip: k_ct_cross_p0 on raw sums (nP, R, sr_ct_psum_stride(F)) whose slot 0 holds lag 0: P0 (nP) the chunk mean of
+// 1.5 S / F - 0.5 and, when dP0 is not null, its std / (sqrt(R) - 1); device arrays, asynchronous on ctx->stream
+int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nP, double *P0, double *dP0);
+
 // sr_ct_cross_long.hip: the blocked form of the pair cross-correlation (raw sums in kernel 1's layout, lag 0 in slot 0), for what
 // sr_ct_cross_check(blocked = 1) admits: the range in which the kernels it shares with sr_ct_long.hip are tested
 #define SR_CT_CROSS_LONG_FLOOR 5462
@@ -138,6 +142,12 @@ int sr_launch_ct_cross_long(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t
 // sr_ct_dipolar.hip: what the entry points of the dipolar correlation function refuse, before anything is queued: shapes and mode (-3), a
 // chunk whose four series do not fit the LDS (-4), chunk starts outside the `frames` frames held (-3)
 int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode);
+
+// sr_ct_dipolar_cross.hip: what the entry points of the dipolar cross-correlation function refuse, before anything is queued: shapes, mode
+// and sym (-3), a chunk whose eight series do not fit the LDS (-4), chunk starts and pair indices outside the `frames` frames / nV
+// vectors held (-3)
+int sr_ct_dipolar_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                              const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode);
 
 // sr_ired_modes.hip
 #define SR_IRED_WS_MB 1024

@@ -106,7 +106,7 @@ int pack(sr_ctx *ctx, sr_vectors *h)
 }
 
 /* the four planes a_x, a_y, a_z, w and r_ref of the vectors held (dist_host, (N, nV) float32, gives the distances when not null) */
-int pack_dipolar(sr_ctx *ctx, sr_vectors *h, const float *dist_host)
+int pack_dipolar(sr_ctx *ctx, const char *who, sr_vectors *h, const float *dist_host)
 {
     if (int rc = wait_ready(ctx, h)) return rc;
     if (h->packed4 && !dist_host) return 0;
@@ -143,10 +143,21 @@ int pack_dipolar(sr_ctx *ctx, sr_vectors *h, const float *dist_host)
     SR_HIP(hipStreamSynchronize(ctx->stream));
     for (int64_t v = 0; v < h->nV; ++v)
         SR_REQUIRE(h->rref[v] > 0.0 && std::isfinite(h->rref[v]), -3,
-                   "sr_vectors_ct_dipolar_f32: vector %lld has no usable shortest distance (r_ref = %g): a frame of zero length or one that is not finite",
+                   "%s: vector %lld has no usable shortest distance (r_ref = %g): a frame of zero length or one that is not finite", who,
                    (long long)v, h->rref[v]);
     h->packed4 = dist_host ? 0 : 1;
     return mark_ready(ctx, h);
+}
+
+/* a host distance array (N, nV): every entry positive and finite */
+int check_dist(const char *who, const sr_vectors *h, const float *dist_host)
+{
+    if (dist_host)
+        for (int64_t i = 0; i < h->N * h->nV; ++i)
+            SR_REQUIRE(dist_host[i] > 0.f && std::isfinite(dist_host[i]), -3,
+                       "%s: the distance of frame %lld, vector %lld is %g: distances must be positive and finite", who, (long long)(i / h->nV),
+                       (long long)(i % h->nV), (double)dist_host[i]);
+    return 0;
 }
 
 }  // namespace
@@ -399,12 +410,8 @@ int sr_vectors_ct_dipolar_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host
     SR_REQUIRE(h && Ct && dCt && reff6 && reff3 && S2rad, -2, "sr_vectors_ct_dipolar_f32: null pointer");
     // refusals come before the pack: a chunk that does not fit or a bad distance launches nothing
     if (int rc = sr_ct_dipolar_check(ctx, "sr_vectors_ct_dipolar_f32", h->N, h->nV, R, F, chunk_start_host, mode)) return rc;
-    if (dist_host)
-        for (int64_t i = 0; i < h->N * h->nV; ++i)
-            SR_REQUIRE(dist_host[i] > 0.f && std::isfinite(dist_host[i]), -3,
-                       "sr_vectors_ct_dipolar_f32: the distance of frame %lld, vector %lld is %g: distances must be positive and finite",
-                       (long long)(i / h->nV), (long long)(i % h->nV), (double)dist_host[i]);
-    if (int rc = pack_dipolar(ctx, h, dist_host)) return rc;
+    if (int rc = check_dist("sr_vectors_ct_dipolar_f32", h, dist_host)) return rc;
+    if (int rc = pack_dipolar(ctx, "sr_vectors_ct_dipolar_f32", h, dist_host)) return rc;
     const int64_t L = F / 2, nV = h->nV;
     double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nV) * sizeof(double));
     double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * nV) * sizeof(double));
@@ -424,6 +431,51 @@ int sr_vectors_ct_dipolar_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host
         reff3[v] = h->rref[v] * pow(w1, -1.0 / 3.0);
         S2rad[v] = w1 * w1 / w2;
     }
+    return 0;
+}
+
+int sr_vectors_ct_dipolar_cross_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                    const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0,
+                                    double *Ct, double *dCt, double *reff6)
+{
+    const char *who = "sr_vectors_ct_dipolar_cross_f32";
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(h && P0 && dP0 && Ct && dCt && reff6, -2, "%s: null pointer", who);
+    // refusals come before the pack: a bad pair table, a chunk that does not fit or a bad distance launches nothing
+    if (int rc = sr_ct_dipolar_cross_check(ctx, who, h->N, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode)) return rc;
+    if (int rc = check_dist(who, h, dist_host)) return rc;
+    if (int rc = pack_dipolar(ctx, who, h, dist_host)) return rc;
+    const int64_t L = F / 2;
+    double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nP) * sizeof(double));
+    double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * nP) * sizeof(double));
+    double *P0_d = (double *)sr_workspace(ctx, SR_WS_OUT2, 2 * (size_t)nP * sizeof(double));        // P0 | dP0
+    double *ws_d = (double *)sr_workspace(ctx, SR_WS_OUT3, 2 * (size_t)(nP * R) * sizeof(double));  // sum w_i^2, sum w_j^2 per (pair, chunk)
+    if (!Ct_d || !dCt_d || !P0_d || !ws_d) return -5;
+    double *ws = (double *)malloc(2 * (size_t)(nP * R) * sizeof(double));
+    SR_REQUIRE(ws != nullptr, -5, "%s: out of host memory", who);
+    int rc = sr_ct_dipolar_cross_f32_dev(ctx, h->soa4, h->Npad4, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, nullptr, P0_d,
+                                         P0_d + nP, Ct_d, dCt_d, ws_d);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemcpyAsync(P0, P0_d, (size_t)nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dP0, P0_d + nP, (size_t)nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(Ct, Ct_d, (size_t)(L * nP) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dCt, dCt_d, (size_t)(L * nP) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ws, ws_d, 2 * (size_t)(nP * R) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    if (!rc && e == hipSuccess) {
+        // <r^-6>^(-1/6) = r_ref <w^2>^(-1/6), <w^2> over the frames of all chunks, the chunk sums added in chunk order
+        for (int64_t p = 0; p < nP; ++p)
+            for (int c = 0; c < 2; ++c) {
+                double m2 = 0.0;
+                for (int64_t r = 0; r < R; ++r) m2 += ws[(p * R + r) * 2 + c];
+                reff6[2 * p + c] = h->rref[c ? pair_j[p] : pair_i[p]] * pow(m2 / ((double)R * (double)F), -1.0 / 6.0);
+            }
+    }
+    free(ws);
+    if (rc) return rc;
+    SR_HIP(e);
     return 0;
 }
 

@@ -213,6 +213,39 @@ def calculate_Ct_dipolar_resident(rv, R, F, dist=None, mode=0, chunk_start=None)
     return rv.ct_dipolar(R, F, dist=dist, chunk_start=chunk_start, mode=mode)
 
 
+def calculate_Ct_dipolar_cross(vecs, pairs, dist=None, symmetric=True, ctx=None, mode=0):
+    """Distance-weighted P2 cross-correlation functions between pairs of flexible spin pairs, the function of dipole-dipole
+    cross-correlated relaxation, an extension beyond the reference:
+    C_ij(k) = <P2(u_i(t) . u_j(t + k)) r_i(t)^-3 r_j(t + k)^-3> / sqrt(<r_i^-6> <r_j^-6>).
+    vecs and dist as calculate_Ct_dipolar takes them, pairs (nP, 2) and symmetric as calculate_Ct_cross.  Returns
+    (P0, dP0, Ct, dCt, reff6): the equal-time value and its error over the replicates (nP), Ct, dCt (nFrames // 2, nP) for the lags
+    1 .. nFrames // 2 -- ratios of the replicate means to sqrt(n_i n_j), n_v the replicate mean of <w_v^2>, whose own scatter is
+    ignored -- and reff6 (nP, 2), the effective distances <r^-6>^(-1/6) of the two vectors of each pair.  For i = j: C_dd of
+    calculate_Ct_dipolar and P0 = 1.  At most Context.ct_dipolar_cross_max_frames() frames per replicate: there is no blocked form, a
+    longer one is refused by the library (SpinRelaxHipError, -4)."""
+    sh = np.shape(vecs)
+    if len(sh) != 4 or sh[3] != 3:
+        raise ValueError('vecs must be (replicates, frames, vectors, 3), got %s' % (sh,))
+    R, F, V = sh[0], sh[1], sh[2]
+    pairs = _check_pairs(pairs, V)
+    if dist is not None:
+        dist = _check_dist(dist, (R, F, V)).reshape(R * F, V)
+    flat = np.ascontiguousarray(vecs, dtype=np.float32).reshape(R * F, V, 3)
+    with _ctx(ctx).vectors(V, R * F) as rv:
+        rv.append(flat)
+        return rv.ct_dipolar_cross(R, F, pairs, dist=dist, sym=int(bool(symmetric)), mode=mode)
+
+
+def calculate_Ct_dipolar_cross_resident(rv, pairs, R, F, dist=None, symmetric=True, mode=0, chunk_start=None):
+    """calculate_Ct_dipolar_cross of resident vectors (regular chunks r * F unless chunk_start is given); dist (frames held, vectors).  rv
+    holds ALL vectors (a single process).  r_ref is the shortest distance among all frames held; the averages behind reff6 run over the
+    frames of the chunks used."""
+    pairs = _check_pairs(pairs, rv.nV)
+    if dist is not None:
+        dist = _check_dist(dist, (rv.frames, rv.nV))
+    return rv.ct_dipolar_cross(R, F, pairs, dist=dist, chunk_start=chunk_start, sym=int(bool(symmetric)), mode=mode)
+
+
 def upload_shard(vec_list, frames_per_chunk=None, ctx=None):
     """The product path's single upload: this rank's vector range (srdist.my_range; everything in a single process) of the
     files' vectors, each file cut to whole chunks of frames_per_chunk frames when given (reformat_vecs_by_tau,

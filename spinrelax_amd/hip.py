@@ -246,6 +246,23 @@ class Context:
         check(self.lib.sr_ct_dipolar_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), int(mode), psum_ptr, Ct_ptr,
                                              dCt_ptr, wmean_ptr), 'sr_ct_dipolar_f32_dev')
 
+    # ---- distance-weighted pair cross-correlation functions (sr_ct_dipolar_cross.hip) ----
+    def ct_dipolar_cross_max_frames(self):
+        """longest chunk whose eight series (a_x, a_y, a_z, w of both vectors of a pair) fit the LDS of a workgroup
+        (sr_ct_dipolar_cross_max_frames)"""
+        return int(self.lib.sr_ct_dipolar_cross_max_frames(self.h))
+
+    def ct_dipolar_cross_dev(self, planes_ptr, Npad, nV, R, F, pairs, P0_ptr, Ct_ptr, dCt_ptr, wsum2_ptr, chunk_start=None, sym=1, mode=0,
+                             psum_ptr=None, dP0_ptr=None):
+        """P0 (nP) (and its error dP0 when dP0_ptr is given), C(t) and dC(t) (F//2, nP) of the pairs (nP, 2) and wsum2 (nP, R, 2), the sums
+        of w_i^2 and w_j^2 over every chunk, from the four planes of pack_dipolar_dev into device arrays (sr_ct_dipolar_cross_f32_dev);
+        asynchronous on the context's stream"""
+        pi, pj = pair_columns(pairs)
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        check(self.lib.sr_ct_dipolar_cross_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
+                                                   int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr, wsum2_ptr),
+              'sr_ct_dipolar_cross_f32_dev')
+
     # ---- iRED matrix (sr_ired.hip) ----
     def ired_matrix_dev(self, soa_ptr, Npad, nV, win_start, win_len, M_ptr):
         """M[w] = mean over frames [win_start[w], win_start[w] + win_len[w]) of P2(u_i . u_j) from packed planes, into the device
@@ -775,6 +792,30 @@ class ResidentVectors:
         check(self.ctx.lib.sr_vectors_ct_dipolar_f32(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), int(mode), _ptr(Ct), _ptr(dCt),
                                                      _ptr(reff6), _ptr(reff3), _ptr(S2rad)), 'sr_vectors_ct_dipolar_f32')
         return Ct, dCt, reff6, reff3, S2rad
+
+    def ct_dipolar_cross(self, R, F, pairs, dist=None, chunk_start=None, sym=1, mode=0):
+        """distance-weighted P2 cross-correlation of the pairs (nP, 2) of resident vectors (sr_vectors_ct_dipolar_cross_f32):
+        C_ij(k) = <P2(u_i(t) . u_j(t+k)) r_i(t)^-3 r_j(t+k)^-3> / sqrt(<r_i^-6> <r_j^-6>), k = 1 .. F//2, mean and error over the R chunks
+        like ct(); sym = 1: the mean of C_ij and C_ji.  dist as in ct_dipolar.  Returns (P0, dP0, Ct, dCt, reff6): P0, dP0 (nP) the
+        equal-time value and its error, Ct, dCt (F//2, nP), reff6 (nP, 2) = <r^-6>^(-1/6) of the two vectors of each pair."""
+        pi, pj = pair_columns(pairs)
+        L = F // 2
+        d = None
+        if dist is not None:
+            d = _f32(dist)
+            if d.shape != (self.frames, self.nV):
+                raise ValueError('dist must be (frames held, vectors) = (%d, %d), got %s' % (self.frames, self.nV, d.shape))
+        P0, dP0 = np.empty(pi.size), np.empty(pi.size)
+        Ct = np.empty((L, pi.size))
+        dCt = np.empty((L, pi.size))
+        reff6 = np.empty((pi.size, 2))
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        if cs is not None and cs.shape != (R,):
+            raise ValueError('chunk_start must have R entries')
+        check(self.ctx.lib.sr_vectors_ct_dipolar_cross_f32(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
+                                                           int(sym), int(mode), _ptr(P0), _ptr(dP0), _ptr(Ct), _ptr(dCt), _ptr(reff6)),
+              'sr_vectors_ct_dipolar_cross_f32')
+        return P0, dP0, Ct, dCt, reff6
 
     def ct_sums(self, R, F, chunk_start=None, mode=0):
         """raw sums S[v, r, d-1] = sum_j (u_j . u_{j+d})^2 of the R chunks held, (nV, R, F//2) float64 (replicate sharding)"""

@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross, sr_ct_dipolar and sr_ct_dipolar_cross entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
+#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross and sr_noe entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -327,6 +327,45 @@ int sr_ired_mode_ct_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t nV
 /* the same of resident vectors, coefficient matrices and result on the HOST.  Blocks until Cm is there. */
 int sr_vectors_ired_mode_ct_f32(sr_ctx *, sr_vectors *, const int64_t *win_start_host, const int64_t *win_len_host, int W,
                                 const double *coef_host, int K, int n_lags, double *Cm_host);
+
+/* ---- all-pairs dipolar map: <r^-6>, <r^-3> and the order tensor of every pair of a set of spins (sr_noe.hip; beyond the reference) ----
+ * The screening step in front of the dipolar correlation functions (Brueschweiler et al., JACS 114, 2289 (1992); Peter, Daura &
+ * van Gunsteren, J. Biomol. NMR 20, 297 (2001)).  For the P atoms index[0 .. P) of coordinates xyz (nFrames, nAtoms, 3) float32, per
+ * frame block b = frames [block_start[b], block_start[b] + block_len[b]) and per pair i < j (positions in `index`), with
+ * d = x_index[j] - x_index[i], r = |d| and d' = R(quat[t]) d:
+ *     sums[b][k(i, j)][0]      = sum_t r^-6
+ *     sums[b][k(i, j)][1 .. 6] = sum_t d'_a d'_b r^-5   for ab = xx, yy, zz, xy, xz, yz        (xx + yy + zz = sum_t r^-3)
+ * k(i, j) = i (2 P - i - 1) / 2 + (j - i - 1): row-major over i < j.  The averages, effective distances and order parameters are host
+ * work (spinrelax_amd/noe.py).  d is the difference of the raw float32 coordinates, taken first and in the lab frame; r and its
+ * powers come from it, and only the tensor sees the rotation (applied to d, never to the coordinates).
+ *   mode 0: float32 per pair and frame: d, r^2 = fma(dz, dz, fma(dy, dy, dx dx)), v_rsq_f32, r^-3 = (ri ri) ri, r^-5 = r^-3 (ri ri),
+ *           r^-6 = r^-3 r^-3, R rounded to float32; float32 partial sums of at most 8 frames, then float64.
+ *   mode 1: float64 throughout (the on-device check).
+ * k_noe_pairs: one workgroup of 256 threads per (block, frame split, tile pair ti <= tj) of T x T atoms, T = sr_noe_tile(), 2 x 2
+ * pairs per thread; the two tiles' coordinates of sr_noe_frame_batch() frames are gathered into LDS, the frame's rotation matrix is
+ * formed once per workgroup.  Of a diagonal tile only i < j is kept.  k_noe_finish adds the S partial tiles in the order s = 0 .. S-1.
+ * No atomics: equal input gives bit-equal sums.  S is a function of the shape alone: min(256, max(1, Fmax / 128),
+ * ceil(4096 / (B tile pairs))).  With S > 1 the partial tiles are a work area of S times 1.03 to 1.13 times the bytes of sums (whole
+ * tiles); with S = 1 -- every map of 4096 or more tile pairs, P > 2850 or so in one block -- k_noe_pairs writes sums itself and the call
+ * needs no memory beside its result.
+ *   index_host (P) distinct atom indices, block tables (B): HOST arrays, checked before anything is queued and consumed on return;
+ *   quat: DEVICE (nFrames, 4) float64 unit quaternions (w, x, y, z) as sr_xh_vectors_f32_dev writes them, NULL = identity;
+ *   sums: DEVICE (B, P (P - 1) / 2, 7) float64.  Asynchronous on the context's stream.
+ * Refused with -3, before anything is queued: P < 2, an index out of range or duplicated, B < 1, a block shorter than one frame or
+ * outside the frames, a mode other than 0 or 1, and a result of B P (P - 1) / 2 * 56 bytes (plus the partial tiles) beyond the
+ * device's memory.  A pair that coincides in some frame gives a non-finite sum (the caller's to report). */
+int sr_noe_pairs_f32_dev(sr_ctx *, const float *xyz, int64_t nFrames, int64_t nAtoms, const int32_t *index_host, int64_t P,
+                         const double *quat, const int64_t *block_start_host, const int64_t *block_len_host, int B, int mode,
+                         double *sums);
+/* the same with xyz, quat (may be NULL) and sums on the HOST.  Blocks until sums is there. */
+int sr_noe_pairs_f32(sr_ctx *, const float *xyz, int64_t nFrames, int64_t nAtoms, const int32_t *index, int64_t P, const double *quat,
+                     const int64_t *block_start, const int64_t *block_len, int B, int mode, double *sums);
+/* What the two calls above refuse with -3, with their message, and nothing else: all host work, nothing allocated or queued.  For a
+ * caller that has to allocate sums itself and wants to hear of a map beyond the device's memory first. */
+int sr_noe_pairs_check(sr_ctx *, int64_t nFrames, int64_t nAtoms, const int32_t *index, int64_t P, const int64_t *block_start,
+                       const int64_t *block_len, int B, int mode);
+int sr_noe_tile(void);          /* T: atoms per tile side (tests aim at tile edges) */
+int sr_noe_frame_batch(void);   /* frames per LDS stage of k_noe_pairs */
 
 /* ---- time-lagged P2 cross-correlation between pairs of vectors (sr_ct_cross.hip; beyond the reference) ---------------------------
  * For pair p = (i, j) = (pair_i[p], pair_j[p]) on the Palmer chunk table of kernel 1 (R chunks of F frames, chunk_start_host as there):

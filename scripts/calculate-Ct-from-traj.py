@@ -5,7 +5,8 @@ files (<o>_Ctext.dat, <o>_Ctint.dat, <o>_vecHistogram.npz | _vecPhiTheta.npz|.da
 <o>_S2.dat; with the [extension] --iRED also <o>_iRED_S2.dat, <o>_iRED_eig.dat and, with --binary, <o>_iRED_matrix.npz; with --iRED_Ct
 also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat; with the [extension] --crossCt --pairs FILE also <o>_crossCtint.dat
 and <o>_crossPairs.dat; with the [extension] --dipolarCt also <o>_dipolarCtint.dat and <o>_dipolarDist.dat; with the
-[extension] --dipolarCrossCt --pairs FILE also <o>_dipolarCrossCtint.dat and <o>_dipolarCrossPairs.dat).  C(t), the rotation into
+[extension] --dipolarCrossCt --pairs FILE also <o>_dipolarCrossCtint.dat and <o>_dipolarCrossPairs.dat; with the [extension] --noeMap
+also <o>_noeMap.dat and, with --binary, <o>_noeMap.npz).  C(t), the rotation into
 the PAF, the spherical histogram, the mean vector and S2 are computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
 Several GPUs: run under torchrun (`torchrun --nproc-per-node N scripts/calculate-Ct-from-traj.py ...`): rank r computes the
@@ -109,7 +110,71 @@ def build_parser():
                         'the two vectors).  Pairs from --pairs, --asym as for --crossCt; distances as for --dipolarCt (vector-file input '
                         'only).  At most 4896 frames per chunk.  --exact: float64 throughout.  --vecRot has no effect on these files.  '
                         'Single process only.')
+    p.add_argument('--noeMap', dest='bDoNoeMap', action='store_true', default=False,
+                   help='[extension] all-pairs dipolar map (Brueschweiler et al. 1992; Peter, Daura & van Gunsteren 2001): for EVERY pair of '
+                        'the atoms `indexP` of an .npz coordinate file (default: the union of `indexX` and `indexH`; optional `namesP`) the '
+                        'effective distances <r^-6>^(-1/6) and <r^-3>^(-1/3), the order parameter S2 of the pair vector -- the plateau '
+                        'of the --dipolarCt function -- and the radial order parameter, in the frame of the superposition onto `ref_xyz` '
+                        'over `fit_indices` (without them: the lab frame, S2 then includes overall tumbling): <o>_noeMap.dat with the '
+                        'columns i j name_i name_j reff6 dreff6 reff3 S2 dS2 S2rad; with --binary also <o>_noeMap.npz.  Errors over the '
+                        '--tau chunks, one block per file without --tau.  --exact: float64 throughout.  The screening step in front '
+                        'of --dipolarCt.  Single process only.')
+    p.add_argument('--noeCutoff', type=float, dest='noe_cutoff', default=None,
+                   help='[extension] --noeMap lists only the pairs with reff6 <= this distance, in the units of the coordinates.')
     return p
+
+
+def run_noe_map(args, out_pref):
+    """--noeMap: the coordinates of all files, one after the other, through spinrelax_amd.noe; the blocks are the --tau chunks of
+    every file (a tail that does not fill one is dropped), without --tau every file as a whole"""
+    from spinrelax_amd import ired, noe
+    xyz, frames, first = [], [], None
+    for fn in args.infn:
+        z = np.load(fn, allow_pickle=True) if fn.endswith('.npz') else {}
+        if 'xyz' not in z:
+            print("= = = ERROR: --noeMap needs .npz coordinate input that holds `xyz`; %s does not." % fn, file=sys.stderr)
+            sys.exit(1)
+        if first is None:
+            first = z
+        xyz.append(np.ascontiguousarray(z['xyz'], dtype=np.float32))
+        frames.append(xyz[-1].shape[0])
+    z = first
+    if 'indexP' in z:
+        index = np.asarray(z['indexP'], dtype=np.int64)
+    elif 'indexX' in z and 'indexH' in z:
+        index = np.union1d(np.asarray(z['indexX'], dtype=np.int64), np.asarray(z['indexH'], dtype=np.int64))
+    else:
+        print("= = = ERROR: --noeMap needs `indexP`, or `indexX` and `indexH`, in the coordinate file.", file=sys.stderr)
+        sys.exit(1)
+    names = [str(n) for n in z['namesP']] if 'namesP' in z else None
+    dt = float(z['dt']) if 'dt' in z else float(args.dt)
+    if args.tau is not None and dt > 0.5 * args.tau:
+        print("= = = ERROR: delta-t form the trajectory is too small relative to tau! %g vs. %g" % (dt, args.tau), file=sys.stderr)
+        sys.exit(1)
+    blocks = ired.ired_windows(frames, dt, window=args.tau)
+    if blocks[0].size < 1:
+        print("= = = ERROR: no trajectory holds a full block of memory time tau!", file=sys.stderr)
+        sys.exit(1)
+    allxyz = xyz[0] if len(xyz) == 1 else np.concatenate(xyz, axis=0)
+    mode = 1 if args.exact else 0
+    print("= = = Conducting the all-pairs dipolar map of %i atoms (%i pairs) over %i blocks." % (index.size, noe.n_pairs(index.size), blocks[0].size))
+    try:
+        if 'ref_xyz' in z and 'fit_indices' in z:
+            res = noe.dipolar_map_superposed(allxyz, z['ref_xyz'], z['fit_indices'], index, blocks=blocks, mode=mode)
+        else:
+            print("= = = WARNING: no `ref_xyz` / `fit_indices` in the input: the map is computed in the lab frame and its S2 includes "
+                  "overall tumbling.", file=sys.stderr)
+            res = noe.dipolar_map(allxyz, index, blocks=blocks, mode=mode)
+        rows = noe.write_map(out_pref + '_noeMap.dat', res, names=names, cutoff=args.noe_cutoff)
+    except (ValueError, hostct.hip.SpinRelaxHipError) as exc:        # coinciding atoms, a bad index list, a map beyond the device
+        print("= = = ERROR: %s" % exc, file=sys.stderr)
+        sys.exit(1)
+    if args.binary:
+        keep = ('pairs', 'index', 'A6', 'A3', 'T', 'reff6', 'reff3', 'S2', 'S2rad', 'dS2', 'dreff6', 'dreff3', 'A6_b', 'A3_b', 'T_b',
+                'reff6_b', 'reff3_b', 'S2_b', 'S2rad_b', 'block_len', 'sums')
+        np.savez(out_pref + '_noeMap.npz', block_start=blocks[0], **{k: res[k] for k in keep})
+    print("      ...%i of %i pairs written; complete." % (rows, res['reff6'].size))
+    return all(('indexX' in np.load(fn, allow_pickle=True)) for fn in args.infn)
 
 
 def load_distance_files(files, frames_per_chunk):
@@ -315,6 +380,19 @@ def main():
     if len(args.topfn) > 1 and len(args.topfn) != len(args.infn):
         print("= = ERROR: When giving multiple reference files, you must have one for each trajecfile file given!", file=sys.stderr)
         sys.exit(1)
+    if args.noe_cutoff is not None and not args.bDoNoeMap:
+        print("= = = ERROR: --noeCutoff belongs to --noeMap; give both.", file=sys.stderr)
+        sys.exit(1)
+    if args.bDoNoeMap:
+        if world > 1:
+            # the tile pairs are not sharded over ranks
+            print("= = = ERROR: --noeMap does not run under torchrun with more than one rank; run it as a single process.", file=sys.stderr)
+            sys.exit(1)
+        if not run_noe_map(args, srdist.output_prefix(args.out_pref)):
+            # a file of `indexP` alone holds no bonds: nothing else to analyse
+            print("= = Finished. Total seconds elapsed: %g" % (time.time() - time_start))
+            srdist.finish()
+            return
 
     def frames_per_chunk_of(dt):
         if tau_memory is None:

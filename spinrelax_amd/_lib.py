@@ -170,6 +170,14 @@ SIGNATURES = {
                                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'sr_vectors_ct_dipolar_cross_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the all-pairs dipolar map (sr_noe.hip): (ctx, xyz, nFrames, nAtoms, index_host, P, quat, block_start_host, block_len_host, B, mode, sums),
+    # xyz / quat / sums on the device or all three on the host
+    'sr_noe_pairs_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'sr_noe_pairs_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    # (ctx, nFrames, nAtoms, index, P, block_start, block_len, B, mode): the refusals of the two above alone
+    'sr_noe_pairs_check': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int]),
+    'sr_noe_tile': (c_int, []),
+    'sr_noe_frame_batch': (c_int, []),
     'sr_counter': (c_int, [c_void_p, c_char_p, POINTER(ctypes.c_uint64)]),
     'sr_transpose_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'sr_jomega_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
@@ -179,7 +187,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar and sr_ct_dipolar_cross entry points and sr_vechist_plan: they only add symbols, and load() fails at a missing one
+ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross and sr_noe entry points and sr_vechist_plan: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -280,6 +280,72 @@ class Context:
         check(self.lib.sr_ired_mode_ct_f32_dev(self.h, soa_ptr, int(Npad), int(nV), _ptr(ws), _ptr(wl), ws.size, coef_ptr, int(K),
                                                int(n_lags), Cm_ptr), 'sr_ired_mode_ct_f32_dev')
 
+    # ---- all-pairs dipolar map (sr_noe.hip) ----
+    def noe_pairs_dev(self, xyz_ptr, nFrames, nAtoms, index, quat_ptr, block_start, block_len, sums_ptr, mode=0):
+        """Block sums of r^-6 and d'_a d'_b r^-5 (xx, yy, zz, xy, xz, yz) of every pair i < j of the atoms `index` from the device
+        coordinates xyz_ptr (nFrames, nAtoms, 3) float32, d' = d rotated by the frame's unit quaternion of the device array quat_ptr
+        (nFrames, 4) float64 (None: identity), into the device array sums_ptr (B, P (P - 1) / 2, 7) float64, pairs in the order of
+        noe.pair_index (sr_noe_pairs_f32_dev); asynchronous on the context's stream"""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError('index must be 1-D')
+        bs, bl = _windows(block_start, block_len)
+        check(self.lib.sr_noe_pairs_f32_dev(self.h, xyz_ptr, int(nFrames), int(nAtoms), _ptr(idx), idx.size, quat_ptr, _ptr(bs), _ptr(bl),
+                                            bs.size, int(mode), sums_ptr), 'sr_noe_pairs_f32_dev')
+
+    def noe_pairs(self, xyz, index, quat=None, block_start=None, block_len=None, mode=0):
+        """The same of host arrays: xyz (nFrames, nAtoms, 3) float32, quat (nFrames, 4) float64 or None -> sums (B, P (P - 1) / 2, 7)
+        float64; without block tables one block of all frames (sr_noe_pairs_f32)"""
+        xyz = _f32(xyz)
+        if xyz.ndim != 3 or xyz.shape[2] != 3:
+            raise ValueError('xyz must be (frames, atoms, 3)')
+        nF, nA, _ = xyz.shape
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError('index must be 1-D')
+        qq = None if quat is None else _f64(quat)
+        if qq is not None and qq.shape != (nF, 4):
+            raise ValueError('quat must be (frames, 4)')
+        if block_start is None:
+            block_start, block_len = [0], [nF]
+        bs, bl = _windows(block_start, block_len)
+        P = idx.size
+        self.noe_pairs_check(nF, nA, idx, bs, bl, mode)      # a map beyond the device's memory is refused before its host array exists
+        sums = np.empty((bs.size, P * (P - 1) // 2, 7))
+        check(self.lib.sr_noe_pairs_f32(self.h, _ptr(xyz), nF, nA, _ptr(idx), P, _ptr(qq), _ptr(bs), _ptr(bl), bs.size, int(mode),
+                                        _ptr(sums)), 'sr_noe_pairs_f32')
+        return sums
+
+    def noe_pairs_check(self, nFrames, nAtoms, index, block_start, block_len, mode=0):
+        """raises what noe_pairs / noe_pairs_dev would refuse (-3) for these arguments, the size of the result included; allocates and
+        queues nothing (sr_noe_pairs_check)"""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError('index must be 1-D')
+        bs, bl = _windows(block_start, block_len)
+        check(self.lib.sr_noe_pairs_check(self.h, int(nFrames), int(nAtoms), _ptr(idx), idx.size, _ptr(bs), _ptr(bl), bs.size, int(mode)),
+              'sr_noe_pairs_check')
+
+    def noe_tile(self):
+        """atoms per tile side of k_noe_pairs"""
+        return int(self.lib.sr_noe_tile())
+
+    def noe_frame_batch(self):
+        """frames per LDS stage of k_noe_pairs"""
+        return int(self.lib.sr_noe_frame_batch())
+
+    def xh_quat_dev(self, xyz_ptr, nFrames, nAtoms, fit_indices, ref_xyz, quat_ptr):
+        """The front end's superposition alone: the unit quaternions (w, x, y, z) that rotate every frame of the device coordinates
+        onto ref_xyz over fit_indices, into the device array quat_ptr (nFrames, 4) float64 (sr_xh_vectors_f32_dev with no vector
+        output); asynchronous on the context's stream"""
+        fi = np.ascontiguousarray(fit_indices, dtype=np.int32)
+        rx = _f32(ref_xyz)
+        if rx.shape != (nAtoms, 3):
+            raise ValueError('ref_xyz must be (atoms, 3)')
+        bond = np.zeros(1, dtype=np.int32)              # the entry point wants one bond; none is written
+        check(self.lib.sr_xh_vectors_f32_dev(self.h, xyz_ptr, int(nFrames), int(nAtoms), _ptr(bond), _ptr(bond), 1, _ptr(fi), fi.size,
+                                             _ptr(rx), None, None, quat_ptr), 'sr_xh_vectors_f32_dev')
+
     # ---- resident vectors (sr_vectors.hip) ----
     def vectors(self, nV, capacity=0):
         """An empty ResidentVectors object for nV vectors (this rank's columns)."""

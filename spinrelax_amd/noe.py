@@ -1,0 +1,218 @@
+"""
+All-pairs dipolar map: effective distances and order parameters of EVERY pair of a set of spins, the screening step in front of the
+distance-weighted correlation functions (ct.calculate_Ct_dipolar), which need their pairs named in advance.
+
+With d = x_j - x_i in the molecule-fixed frame and r = |d|, per pair (Brueschweiler et al., J. Am. Chem. Soc. 114, 2289 (1992);
+Peter, Daura & van Gunsteren, J. Biomol. NMR 20, 297 (2001)):
+
+    A6   = <r^-6>                 reff6 = A6^(-1/6)      (fast-motion effective distance)
+    A3   = <r^-3>                 reff3 = A3^(-1/3)      (slow-motion effective distance)
+    T_ab = <d_a d_b r^-5>         (symmetric 3 x 3, tr T = A3)
+    S2    = 1.5 (sum_ab T_ab^2 - A3^2 / 3) / A6          (the plateau of C_dd(k) as calculate_Ct_dipolar normalises it:
+                                                          P2(u . u') = 1.5 Q : Q' with Q = u u - 1/3)
+    S2rad = A3^2 / A6                                    (the radial order parameter calculate_Ct_dipolar returns)
+
+The block sums of r^-6 and d_a d_b r^-5, the loop that is quadratic in the number of spins, are computed on the MI355X
+(csrc/sr_noe.hip) and nowhere else: without a GPU dipolar_map raises SpinRelaxHipError.  Everything after the sums is finalize(),
+pure numpy.
+"""
+import warnings
+
+import numpy as np
+
+from . import hip
+from .ired import ired_reduce
+
+# the seven sums per block and pair, in the library's order
+COMPONENTS = ('r-6', 'xx', 'yy', 'zz', 'xy', 'xz', 'yz')
+
+
+def _ctx(ctx):
+    return ctx if ctx is not None else hip.default_context()
+
+
+def n_pairs(P):
+    return P * (P - 1) // 2
+
+
+def pair_index(i, j, P):
+    """position of the pair i < j (positions in the index list of P atoms) in the library's order, row-major over i < j:
+    k = i (2 P - i - 1) / 2 + (j - i - 1); arrays broadcast"""
+    i, j = np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64)
+    if np.any(i < 0) or np.any(j <= i) or np.any(j >= P):
+        raise ValueError('pair_index needs 0 <= i < j < P')
+    return i * (2 * P - i - 1) // 2 + (j - i - 1)
+
+
+def pair_list(P):
+    """(P (P - 1) / 2, 2) int64: the pairs (i, j) in the library's order, the inverse of pair_index"""
+    k = np.arange(n_pairs(P), dtype=np.int64)
+    # row i starts at i (2 P - i - 1) / 2: the largest i with that start <= k
+    i = np.floor(((2 * P - 1) - np.sqrt((2.0 * P - 1) ** 2 - 8.0 * k)) / 2).astype(np.int64)
+    i -= (i * (2 * P - i - 1) // 2 > k)                   # the square root may round across a row start, either way
+    i += ((i + 1) * (2 * P - i - 2) // 2 <= k)
+    j = k - i * (2 * P - i - 1) // 2 + i + 1
+    return np.stack([i, j], axis=1)
+
+
+def _tensor(s):
+    """sums or averages (..., 7) -> (..., 3, 3)"""
+    T = np.empty(s.shape[:-1] + (3, 3))
+    T[..., 0, 0], T[..., 1, 1], T[..., 2, 2] = s[..., 1], s[..., 2], s[..., 3]
+    T[..., 0, 1] = T[..., 1, 0] = s[..., 4]
+    T[..., 0, 2] = T[..., 2, 0] = s[..., 5]
+    T[..., 1, 2] = T[..., 2, 1] = s[..., 6]
+    return T
+
+
+def _derive(avg):
+    """averages (..., 7) -> A6, A3, T, reff6, reff3, S2, S2rad"""
+    A6 = avg[..., 0]
+    T = _tensor(avg)
+    A3 = avg[..., 1] + avg[..., 2] + avg[..., 3]
+    TT = np.einsum('...ab,...ab->...', T, T)
+    return A6, A3, T, A6 ** (-1.0 / 6.0), A3 ** (-1.0 / 3.0), 1.5 * (TT - A3 * A3 / 3.0) / A6, A3 * A3 / A6
+
+
+def _error(v_b):
+    """per-block values (B, n) -> their error by the convention of ired.ired_reduce: std(ddof = 0) / (sqrt(B) - 1), 0 for B = 1"""
+    return ired_reduce(v_b)[1]
+
+
+def finalize(sums, block_len):
+    """sums (B, npairs, 7) float64 as the library writes them, block_len (B) frames per block -> dict:
+      A6, A3 (npairs), T (npairs, 3, 3), reff6, reff3, S2, S2rad (npairs) from the sums over ALL blocks (S2 is not linear in the
+        averages: totals, not the mean of the block values);
+      dS2, dreff6, dreff3 (npairs) from the per-block values, std(ddof = 0) / (sqrt(B) - 1) like ired.ired_reduce, 0 for one block;
+      A6_b, A3_b, reff6_b, reff3_b, S2_b, S2rad_b (B, npairs) and T_b (B, npairs, 3, 3), the per-block values; block_len.
+    A non-finite sum means that two of the atoms coincided in some frame: ValueError, naming the first such pair."""
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim != 3 or sums.shape[2] != 7:
+        raise ValueError('sums must be (blocks, pairs, 7), got %s' % (sums.shape,))
+    bl = np.atleast_1d(np.asarray(block_len, dtype=np.int64))
+    if bl.shape != (sums.shape[0],) or np.any(bl < 1):
+        raise ValueError('block_len must give one length >= 1 per block')
+    bad = np.nonzero(~np.isfinite(sums).all(axis=(0, 2)))[0]
+    if bad.size:
+        # P from npairs = P (P - 1) / 2
+        P = int(round((1 + np.sqrt(1.0 + 8.0 * sums.shape[1])) / 2))
+        i, j = pair_list(P)[bad[0]]
+        raise ValueError('dipolar map: the sums of pair %d (positions %d and %d of the index list) are not finite: the two atoms '
+                         'coincide in some frame' % (bad[0], i, j))
+    A6, A3, T, reff6, reff3, S2, S2rad = _derive(sums.sum(axis=0) / float(bl.sum()))
+    A6_b, A3_b, T_b, reff6_b, reff3_b, S2_b, S2rad_b = _derive(sums / bl[:, None, None].astype(np.float64))
+    return dict(A6=A6, A3=A3, T=T, reff6=reff6, reff3=reff3, S2=S2, S2rad=S2rad,
+                dS2=_error(S2_b), dreff6=_error(reff6_b), dreff3=_error(reff3_b),
+                A6_b=A6_b, A3_b=A3_b, T_b=T_b, reff6_b=reff6_b, reff3_b=reff3_b, S2_b=S2_b, S2rad_b=S2rad_b, block_len=bl)
+
+
+def _blocks(blocks, n_frames):
+    """None -> one block of all frames; otherwise (block_start, block_len)"""
+    if blocks is None:
+        return np.zeros(1, dtype=np.int64), np.full(1, n_frames, dtype=np.int64)
+    bs, bl = blocks
+    return np.ascontiguousarray(np.atleast_1d(bs), dtype=np.int64), np.ascontiguousarray(np.atleast_1d(bl), dtype=np.int64)
+
+
+def _result(sums, bl, index):
+    index = np.asarray(index)
+    out = finalize(sums, bl)
+    out['pairs'] = pair_list(index.size)
+    out['index'] = index.astype(np.int64)
+    out['sums'] = sums
+    return out
+
+
+def dipolar_map(xyz, index, quat=None, blocks=None, mode=0, ctx=None):
+    """The map of every pair of the atoms `index` of the coordinates xyz (frames, atoms, 3) float32.  quat (frames, 4) float64: the
+    unit quaternion (w, x, y, z) that takes each frame into the molecule-fixed frame (what ct.superpose_XHvecs(..., want_quat=True)
+    returns); None: the lab frame, S2 then includes overall tumbling.  blocks = (block_start, block_len) in frames (ragged lengths
+    allowed), None: one block.  mode 0: float32 per pair and frame, 1: float64 throughout.
+    Returns finalize()'s dict and pairs (npairs, 2) positions in `index`, index, sums (B, npairs, 7)."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    bs, bl = _blocks(blocks, xyz.shape[0])
+    sums = _ctx(ctx).noe_pairs(xyz, index, quat=quat, block_start=bs, block_len=bl, mode=mode)
+    return _result(sums, bl, index)
+
+
+def dipolar_map_superposed(xyz, ref_xyz, fit_indices, index, blocks=None, mode=0, ctx=None):
+    """dipolar_map in the frame of the per-frame least-squares superposition onto ref_xyz (atoms, 3) over fit_indices, the front end's
+    (Context.xh_vectors / ct.superpose_XHvecs): the coordinates are uploaded once, the front end's kernel leaves its quaternions on
+    the device and the map reads them there.  The result also holds quat (frames, 4)."""
+    import torch
+    c = _ctx(ctx)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    if xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError('xyz must be (frames, atoms, 3)')
+    nF, nA, _ = xyz.shape
+    index = np.asarray(index)
+    bs, bl = _blocks(blocks, nF)
+    c.noe_pairs_check(nF, nA, index, bs, bl, mode)  # the library's refusals, a map beyond the device's memory among them, before torch allocates
+    dev = torch.device('cuda', c.device)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', UserWarning)    # a read-only array: it is only read
+        xyz_d = torch.from_numpy(xyz).to(dev)
+    quat_d = torch.empty((nF, 4), dtype=torch.float64, device=dev)
+    sums_d = torch.empty((bs.size, n_pairs(index.size), 7), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)                     # the upload is torch's, the kernels run on the context's stream
+    c.xh_quat_dev(xyz_d.data_ptr(), nF, nA, fit_indices, ref_xyz, quat_d.data_ptr())
+    c.noe_pairs_dev(xyz_d.data_ptr(), nF, nA, index, quat_d.data_ptr(), bs, bl, sums_d.data_ptr(), mode=mode)
+    c.sync()
+    out = _result(sums_d.cpu().numpy(), bl, index)
+    out['quat'] = quat_d.cpu().numpy()
+    return out
+
+
+def select_pairs(result, cutoff):
+    """The pairs of a map with reff6 <= cutoff (units of the coordinates) as (indexX, indexH): ATOM indices, int64, in the form
+    ct.superpose_XHvecs takes -- their vectors then go to ct.calculate_Ct_dipolar."""
+    keep = np.nonzero(result['reff6'] <= cutoff)[0]
+    pr = result['pairs'][keep]
+    idx = np.asarray(result['index'], dtype=np.int64)
+    return idx[pr[:, 0]], idx[pr[:, 1]]
+
+
+COLUMNS = ('i', 'j', 'name_i', 'name_j', 'reff6', 'dreff6', 'reff3', 'S2', 'dS2', 'S2rad')
+
+
+def write_map(path, result, names=None, cutoff=None):
+    """<o>_noeMap.dat: one row per pair, columns i j name_i name_j reff6 dreff6 reff3 S2 dS2 S2rad (i, j atom indices, the numbers
+    as %.8g); cutoff keeps the pairs with reff6 <= cutoff.  names: one per entry of the index list, default the atom index.
+    Returns the number of rows."""
+    idx = np.asarray(result['index'], dtype=np.int64)
+    names = [str(a) for a in idx] if names is None else [str(n) for n in names]
+    if len(names) != idx.size:
+        raise ValueError('names must give one name per selected atom')
+    if any((not n) or any(ch.isspace() for ch in n) for n in names):
+        raise ValueError('names must be non-empty and free of white space')
+    keep = np.arange(result['reff6'].size) if cutoff is None else np.nonzero(result['reff6'] <= cutoff)[0]
+    with open(path, 'w') as fp:
+        fp.write('# ' + ' '.join(COLUMNS) + '\n')
+        for k in keep:
+            i, j = result['pairs'][k]
+            fp.write('%d %d %s %s %s\n' % (idx[i], idx[j], names[i], names[j], ' '.join(
+                '%.8g' % result[c][k] for c in COLUMNS[4:])))
+    return int(keep.size)
+
+
+def read_map(path):
+    """parse write_map's file back: dict of arrays, i and j int64, the names as lists of str, the rest float64"""
+    cols = {c: [] for c in COLUMNS}
+    with open(path) as fp:
+        for line in fp:
+            if line.startswith('#') or not line.strip():
+                continue
+            w = line.split()
+            if len(w) != len(COLUMNS):
+                raise ValueError('%s: a row with %d columns, expected %d' % (path, len(w), len(COLUMNS)))
+            for c, v in zip(COLUMNS, w):
+                cols[c].append(v)
+    out = {}
+    for c in COLUMNS:
+        if c in ('i', 'j'):
+            out[c] = np.array(cols[c], dtype=np.int64)
+        elif c.startswith('name'):
+            out[c] = cols[c]
+        else:
+            out[c] = np.array(cols[c], dtype=np.float64)
+    return out

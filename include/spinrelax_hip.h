@@ -61,7 +61,8 @@ int          sr_sync(sr_ctx *);
  * per point: (3 + 2 t/tau) u), 17 % less time per batch
  * with the chip full; 0 = exp() per point whatever the axis, "ct_fft" = formulation of kernel 1 for the chunks that fit one transform
  * in LDS, 1024 < F + L <= 8192: 3 (default) the
- * FLOAT32 real-input FFT for 4096 < F + L <= 8192 (the reference's own arithmetic type; C(t) to 4e-8) and the float64 complex
+ * FLOAT32 real-input FFT for 4096 < F + L <= 8192 (the reference's own arithmetic type; C(t) to 6e-8 of C(0) on ordered vectors,
+ * 1.6e-7 on tumbling or jumping ones) and the float64 complex
  * FFT below, 4 float32 transforms at every such length, 2 the float64 real-input FFT for 4096 < F + L <= 8192 (C(t) to
  * 1e-15) and the complex one below, 1 the float64 complex FFT at every such length, 0 always direct; 2 and more also admit the
  * blocked transforms for longer chunks (sr_ct_formulation() below is the rule itself);
@@ -137,19 +138,22 @@ int sr_pack_soa_rot_f32_dev(sr_ctx *, const float *vecs, int64_t N, int64_t Vtot
  *           1024 < F + L <= 8192: Wiener-Khinchin, (u.u')^2 = sum_c w_c a_c a_c' with a_c products of two components, one
  *           workgroup per (chunk, vector) with the whole transform in LDS.  4096 < F + L <= 8192 (cfg3 / cfg4): float32
  *           transforms of the five mean-removed traceless components, the mean terms restored in float64 (k_ct_rfft32:
- *           C(t) to ~4e-8, the class of the direct kernel and of the reference's own float32); shorter chunks: float64
+ *           C(t) to 6e-8 on ordered vectors -- S2 near 0.9, the synthetic trajectories -- and to 1.6e-7 of C(0) on vectors that
+ *           tumble, jump or sit on few sites, absolute where C(t) passes through zero: docs/EXPERIMENTS.md section 27; the class of
+ *           the direct kernel and of the reference's own float32); shorter chunks: float64
  *           transforms (~1e-15).  sr_set_option("ct_fft", 2) selects float64 transforms everywhere, 0 disables the
  *           formulation;
  *           chunks beyond what the direct kernel can stage in LDS (about 13400 frames), up to sr_ct_max_frames_per_chunk() =
  *           262144 frames per chunk: the same decomposition with
  *           BLOCKED transforms (sr_ct_long.hip): blocks of 4096 samples, float32 forward transforms to a work area in device
- *           memory, cross-spectra per block offset and the inverse transforms in float64 (C(t) to 1e-7).  The series of a
+ *           memory, cross-spectra per block offset and the inverse transforms in float64 (C(t) to 3.1e-8 on ordered vectors, to 1e-7
+ *           of C(0) on mobile ones: section 27).  The series of a
  *           launch go in tiles whose spectra fit sr_set_option("ct_long_ws_mb", MiB) (default 256; results do not depend on it);
  *           sr_set_option("ct_long_min_frames", F0) (5462 .. 262144, default 16384) also gives them the chunks of F0 frames
  *           and more that the direct kernel could stage (F + L > 8192); by default the direct kernel keeps those.  Longer
  *           chunks are refused (-4);
  *           otherwise (short chunks, ct_fft = 0 or 1 beyond the transform lengths): direct shifted products, float32 dot products and short float32 partial sums folded into
- *           float64 (accurate to ~1e-8);
+ *           float64 (accurate to 3.5e-8 on ordered vectors, to 9e-8 of C(0) on mobile ones: the same section 27);
  * mode 1: direct shifted products, every product and sum in float64 (validation path).
  * The direct kernels stage a whole chunk in LDS (12 bytes per frame): mode 1 and ct_fft = 0 / 1 refuse chunks beyond about
  * 13400 frames (-4).

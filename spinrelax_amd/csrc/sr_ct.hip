@@ -9,8 +9,8 @@
 //                                                  is staged in LDS, 12 bytes per frame: F up to about 13400
 //   SR_CT_FFT64    sr_ct_fft64.hip   k_ct_fft      Wiener-Khinchin, complex float64 transforms of 2048 .. 8192 points in LDS (1e-15)
 //   SR_CT_RFFT64   sr_ct_fft64.hip   k_ct_rfft     the same with real-input transforms of half the length, 6144 and 8192 points
-//   SR_CT_RFFT32   sr_ct32.hip       k_ct_rfft32   float32 real-input transforms of the mean-removed traceless components (4e-8, the
-//                                                  class of the direct kernel and of the reference): what the pipeline runs
+//   SR_CT_RFFT32   sr_ct32.hip       k_ct_rfft32   float32 real-input transforms of the mean-removed traceless components (6e-8 on
+//                                                  ordered, 1.6e-7 on mobile vectors: the class of the direct kernel): the pipeline's
 //   SR_CT_BLOCKED  sr_ct_long.hip    k_ctl_*       blocked float32 transforms through device memory: F up to 262144
 // Kernel 0, which packs the planes they all read, is sr_pack.hip.
 //

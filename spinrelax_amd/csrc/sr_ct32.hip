@@ -23,9 +23,16 @@
 // |eps| < 5e-7: float32-rounded unit vectors) the trace term is (F - d)/3 + window sums of eps/3 + O(F eps^2): eps/3 simply
 // joins e[j] and 1/3 joins K -- five forward transforms instead of six.  A series with any |eps| >= 5e-7 (zero vectors of
 // the 0/0 guard of vecnorm_NDarray, unnormalised input) transforms |u|^2 (weight 1/3) as a sixth signal, same launch.
-// Accuracy on the cfg3 trajectory: C(t) 2-3e-8 relative, dC(t) 2-3e-9 absolute against the float64 oracle -- the class of the
-// direct float32 kernel k_ct_palmer; the reference chain (fit orders, R1/R2/NOE) stays within 2e-7 (scripts/dev/
-// f32fft_feasibility.py, tests/test_gpu_chain.py).
+// Accuracy on the cfg3 trajectory (ORDERED vectors: a wobble of ~0.1 rad about a fixed mean, S2 near 0.9, every d_c small beside
+// its m_c): C(t) 2-3e-8 relative (up to 5.8e-8 on such vectors at other chunk lengths), dC(t) 2-3e-9 absolute against the float64 oracle -- the class of the direct float32 kernel
+// k_ct_palmer; the reference chain (fit orders, R1/R2/NOE) stays within 2e-7 (scripts/dev/f32fft_feasibility.py,
+// tests/test_gpu_chain.py).  On MOBILE vectors (rotational diffusion, jumps between random directions: the d_c are of size 1 and
+// C(t) passes through zero) the error is absolute at the scale of C(0) and three to four times larger: up to 1.6e-7 on C(t),
+// 1.4e-7 on the replicate means behind dC(t), at F = 684 .. 5461; strictly periodic series (x, y, z, x, ...: all energy in a few
+// frequencies) 3.8e-7 -- the size a numpy emulation of this arithmetic with pocketfft's float32 transforms has on the same chunks
+// (tests/ct_inputs.py, tests/test_gpu_ct_mobile.py, docs/EXPERIMENTS.md section 27).  Two more float32 roundings than the one of
+// d = fma(a, b, -m_c) enter: the squares x^2, y^2, z^2 of the first two signals are rounded before they are combined, and e[j] is
+// held in float32; on a series whose products are constant but lie on no axis they add up instead of averaging out (1.3e-8).
 //
 // Structure: one 256-thread workgroup per (chunk, vector) series, real-input transforms of half length H = N1 * 256
 // (N1 = 12: M = 6144, F <= 4096;  N1 = 16: M = 8192, F <= 5461), three steps N1 x 16 x 16 in registers with two LDS

@@ -17,8 +17,9 @@
 // gives both pieces with ONE inverse transform per offset, of which the first B outputs are the lags d B .. d B + B - 1
 // (at m = 0 the second piece is c_{d+1}[B], the one lag of the zero-padded correlation that no pair of samples reaches: zero
 // in exact arithmetic, the rounding of the float32 transforms otherwise -- the error class of every other lag).
-// Precision (the CPU emulation behind this design: float32 everywhere 0.4-1.2e-7, float64 from the cross-spectra on
-// 1.3-2.3e-8 at every length): the forward transforms are float32 (where the work is: 5-6 nb per series), the sums over
+// Precision (the CPU emulation behind this design, on the ordered vectors of synth_vectors: float32 everywhere 0.4-1.2e-7,
+// float64 from the cross-spectra on 1.3-2.3e-8 at every length; measured on the GPU 3e-8 on such vectors and up to 1.0e-7 of C(0)
+// on tumbling and jumping ones, docs/EXPERIMENTS.md section 27): the forward transforms are float32 (where the work is: 5-6 nb per series), the sums over
 // blocks, P_d, Q_d and the nd = L / B + 1 inverse transforms are float64.
 //
 // Launches (all on ctx->stream, in order; no atomics, every sum in a fixed order: results are bit-identical from run to

@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross and sr_noe entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
+#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long and sr_noe entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -450,7 +450,7 @@ int sr_vectors_ct_cross_long_err_f32(sr_ctx *, sr_vectors *, int64_t R, int64_t 
  *                            like the three planes of the other analyses, dropped by the same events (append, truncate) and does not
  *                            disturb them; a pack made with dist_host is never reused (the array is the caller's).
  * One workgroup stages the four series of a (vector, chunk) in LDS, 16 bytes per frame: F up to sr_ct_dipolar_max_frames() (10016 with the
- * 160 KiB of gfx950); a longer chunk is refused with -4 before anything is launched (there is no blocked form). */
+ * 160 KiB of gfx950); a longer chunk is refused with -4 before anything is launched and belongs to the blocked form below. */
 int64_t sr_ct_dipolar_max_frames(sr_ctx *);
 int sr_pack_dipolar_f32_dev(sr_ctx *, const float *vecs_dev, const float *dist_dev, int64_t N, int64_t Vtot, int64_t v0, int64_t nV,
                             float *planes_dev, int64_t Npad, double *rref_dev);
@@ -476,8 +476,8 @@ int sr_vectors_ct_dipolar_f32(sr_ctx *, sr_vectors *, const float *dist_host, in
  *                                     two vectors of each pair over the frames of the chunks, in the units of the input.  dist_host, its
  *                                     refusals and the reuse of the object's four-plane pack exactly as sr_vectors_ct_dipolar_f32.
  * One workgroup stages the eight series of a (pair, chunk) in LDS, 32 bytes per frame: F up to sr_ct_dipolar_cross_max_frames() (4896 with
- * the 160 KiB of gfx950); a longer chunk is refused with -4 before anything is launched (there is no blocked form).  A pair index or a
- * chunk start outside what is held, a bad mode or sym: -3. */
+ * the 160 KiB of gfx950); a longer chunk is refused with -4 before anything is launched and belongs to the blocked form below.  A pair
+ * index or a chunk start outside what is held, a bad mode or sym: -3. */
 int64_t sr_ct_dipolar_cross_max_frames(sr_ctx *);
 int sr_ct_dipolar_cross_f32_dev(sr_ctx *, const float *planes_dev, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
                                 const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym, int mode, double *psum_ws,
@@ -485,6 +485,33 @@ int sr_ct_dipolar_cross_f32_dev(sr_ctx *, const float *planes_dev, int64_t Npad,
 int sr_vectors_ct_dipolar_cross_f32(sr_ctx *, sr_vectors *, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
                                     const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0,
                                     double *Ct, double *dCt, double *reff6);
+
+/* ---- the two distance-weighted functions for long chunks: blocked transforms (sr_ct_dipolar_long.hip) -----------------------------------
+ * The same functions, arguments and results as the four entry points above for chunks of up to sr_ct_dipolar_long_max_frames() =
+ * sr_ct_dipolar_cross_long_max_frames() = 262144 frames, by the blocked float32 transforms of kernel 1's long-chunk form on the five
+ * traceless signals of a: with |a|^2 = w, 1.5 (a . a')^2 - 0.5 w w' = 1.5 Q : Q', Q = a (x) a - (|a|^2 / 3) I.  |a|^2 = w holds to the
+ * float32 rounding of the pack, so the planes MUST come from sr_pack_dipolar_f32_dev (the difference to the definition on such planes:
+ * 1.5e-9 of C); on other four-plane input the result is Q : Q', not the definition.  The normalisers and the distance outputs come
+ * from the w plane in float64, and so does lag 0 of a pair.  mode 1: the definition from the planes in float64, one thread per lag
+ * (the on-device check, slow).  No atomics: equal input gives bit-equal output whatever the tiling of the work area (option
+ * "ct_long_ws_mb"), a repeated pair the same bits.
+ * Every argument check comes before the first launch: -4 beyond 262144 frames per chunk, -3 below 5462 (pair form: 4097) frames, where
+ * the block structure would leave what the shared kernels are tested at, and -3 / -2 for what the direct forms refuse so.  The entry
+ * points do not dispatch: each runs its own kernels.  spinrelax_amd/ct.py gives a chunk to the blocked form when the direct one
+ * cannot stage it or when it has at least "ct_dipolar_long_min_frames" (default 10017, 5462 .. 262144) / "ct_dipolar_cross_long_min_frames"
+ * (default 4897, 4097 .. 262144) frames (sr_set_option). */
+int64_t sr_ct_dipolar_long_max_frames(sr_ctx *);
+int64_t sr_ct_dipolar_cross_long_max_frames(sr_ctx *);
+int sr_ct_dipolar_long_f32_dev(sr_ctx *, const float *planes_dev, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                               int mode, double *psum_ws, double *Ct, double *dCt, double *wmean);
+int sr_vectors_ct_dipolar_long_f32(sr_ctx *, sr_vectors *, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
+                                   double *Ct, double *dCt, double *reff6, double *reff3, double *S2rad);
+int sr_ct_dipolar_cross_long_f32_dev(sr_ctx *, const float *planes_dev, int64_t Npad, int64_t nV, int64_t R, int64_t F,
+                                     const int64_t *chunk_start_host, const int32_t *pair_i_host, const int32_t *pair_j_host, int64_t nP, int sym,
+                                     int mode, double *psum_ws, double *P0, double *dP0, double *Ct, double *dCt, double *wsum2);
+int sr_vectors_ct_dipolar_cross_long_f32(sr_ctx *, sr_vectors *, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                         const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0,
+                                         double *Ct, double *dCt, double *reff6);
 
 /* ---- kernel 3b: multi-exponential C(t) model --------------------------------------------
  * Model of curvefit_exponential (fitting_Ct_functions.py:419-427): params = [C_1..C_K, tau_1..tau_K

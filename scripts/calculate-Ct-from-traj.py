@@ -98,7 +98,8 @@ def build_parser():
                         '_Ctint.dat, labelled by residue; calculate-fitted-Ct.py reads it) and <o>_dipolarDist.dat (resid, the effective '
                         'distances <r^-6>^(-1/6) and <r^-3>^(-1/3) in the units of the input, and the radial order parameter '
                         '<r^-3>^2 / <r^-6>).  Vector-file input only (.npy/.npz): distances from `xyz`, from `dist` or from the lengths '
-                        'of the vectors; then the other analyses of the run still expect unit vectors.  At most 10016 frames per chunk.  '
+                        'of the vectors; then the other analyses of the run still expect unit vectors.  Any --tau that --Ct accepts (up to 262144 frames per '
+                        'chunk: chunks beyond 10016 frames run by blocked transforms).  '
                         '--exact: float64 throughout.  Dot products and distances do not change under a rotation: --vecRot has no '
                         'effect on these files.  Single process only.')
     p.add_argument('--dipolarCrossCt', dest='bDoDipolarCrossCt', action='store_true', default=False,
@@ -108,7 +109,7 @@ def build_parser():
                         'format of _crossCtint.dat, one block per pair) and <o>_dipolarCrossPairs.dat (ordinal, i, j, their residue ids, '
                         'the equal-time value P0 and its standard error over the chunks, and the effective distances <r^-6>^(-1/6) of '
                         'the two vectors).  Pairs from --pairs, --asym as for --crossCt; distances as for --dipolarCt (vector-file input '
-                        'only).  At most 4896 frames per chunk.  --exact: float64 throughout.  --vecRot has no effect on these files.  '
+                        'only).  Any --tau that --Ct accepts (chunks beyond 4896 frames run by blocked transforms).  --exact: float64 throughout.  --vecRot has no effect on these files.  '
                         'Single process only.')
     p.add_argument('--noeMap', dest='bDoNoeMap', action='store_true', default=False,
                    help='[extension] all-pairs dipolar map (Brueschweiler et al. 1992; Peter, Daura & van Gunsteren 2001): for EVERY pair of '
@@ -529,7 +530,7 @@ def main():
         try:
             dist = load_distance_files(args.infn, F)
             Cd, dCd, reff6, reff3, S2rad = hostct.calculate_Ct_dipolar_resident(rv_fit, R, F, dist=dist, mode=1 if args.exact else 0)
-        except (ValueError, hostct.hip.SpinRelaxHipError) as exc:      # a bad distance, a zero-length vector, a chunk beyond the LDS
+        except (ValueError, hostct.hip.SpinRelaxHipError) as exc:      # a bad distance, a zero-length vector, a chunk beyond both forms
             print("= = = ERROR: %s" % exc, file=sys.stderr)
             sys.exit(1)
         gs.print_sxylist(out_pref + '_dipolarCtint.dat', resXH, hostct.calculate_dt(deltaT, tau_memory), np.stack((Cd.T, dCd.T), axis=-1))
@@ -551,7 +552,7 @@ def main():
             dist = load_distance_files(args.infn, F)
             P0, dP0, Cx, dCx, reff6 = hostct.calculate_Ct_dipolar_cross_resident(rv_fit, pairs, R, F, dist=dist, symmetric=not args.bCrossAsym,
                                                                                  mode=1 if args.exact else 0)
-        except (ValueError, hostct.hip.SpinRelaxHipError) as exc:      # a bad distance, a zero-length vector, a chunk beyond the LDS
+        except (ValueError, hostct.hip.SpinRelaxHipError) as exc:      # a bad distance, a zero-length vector, a chunk beyond both forms
             print("= = = ERROR: %s" % exc, file=sys.stderr)
             sys.exit(1)
         ordinals = list(range(1, len(pairs) + 1))

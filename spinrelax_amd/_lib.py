@@ -170,6 +170,17 @@ SIGNATURES = {
                                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'sr_vectors_ct_dipolar_cross_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the blocked forms of both for longer chunks (sr_ct_dipolar_long.hip): the same arguments
+    'sr_ct_dipolar_long_max_frames': (c_int64, [c_void_p]),
+    'sr_ct_dipolar_cross_long_max_frames': (c_int64, [c_void_p]),
+    'sr_ct_dipolar_long_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
+    'sr_vectors_ct_dipolar_long_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]),
+    'sr_ct_dipolar_cross_long_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                 c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'sr_vectors_ct_dipolar_cross_long_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # the all-pairs dipolar map (sr_noe.hip): (ctx, xyz, nFrames, nAtoms, index_host, P, quat, block_start_host, block_len_host, B, mode, sums),
     # xyz / quat / sums on the device or all three on the host
     'sr_noe_pairs_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -187,7 +198,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross and sr_noe entry points and sr_vechist_plan: they only add symbols, and load() fails at a missing one
+ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long and sr_noe entry points and sr_vechist_plan: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -94,6 +94,8 @@ sr_ctx *sr_create(int device)
     ctx->ct_long_ws_mb = SR_CT_LONG_WS_MB;
     ctx->ct_long_min_frames = SR_CT_LONG_MIN_FRAMES;
     ctx->ct_cross_long_min_frames = SR_CT_CROSS_LONG_MIN_FRAMES;
+    ctx->ct_dipolar_long_min_frames = SR_CT_DIPOLAR_LONG_MIN_FRAMES;
+    ctx->ct_dipolar_cross_long_min_frames = SR_CT_DIPOLAR_CROSS_LONG_MIN_FRAMES;
     ctx->ired_ws_mb = SR_IRED_WS_MB;
     ctx->fft_table_ready = 0;
     ctx->fft32_table_ready = 0;
@@ -167,6 +169,18 @@ int sr_set_option(sr_ctx *ctx, const char *name, int value)
         SR_REQUIRE(value >= SR_CT_CROSS_LONG_FLOOR && value <= SR_CT_LONG_MAX_FRAMES, -3, "sr_set_option: ct_cross_long_min_frames must be %d .. %d",
                    SR_CT_CROSS_LONG_FLOOR, SR_CT_LONG_MAX_FRAMES);
         ctx->ct_cross_long_min_frames = value;
+        return 0;
+    }
+    if (!strcmp(name, "ct_dipolar_long_min_frames")) {
+        SR_REQUIRE(value >= SR_CT_DIPOLAR_LONG_FLOOR && value <= SR_CT_LONG_MAX_FRAMES, -3,
+                   "sr_set_option: ct_dipolar_long_min_frames must be %d .. %d", SR_CT_DIPOLAR_LONG_FLOOR, SR_CT_LONG_MAX_FRAMES);
+        ctx->ct_dipolar_long_min_frames = value;
+        return 0;
+    }
+    if (!strcmp(name, "ct_dipolar_cross_long_min_frames")) {
+        SR_REQUIRE(value >= SR_CT_DIPOLAR_CROSS_LONG_FLOOR && value <= SR_CT_LONG_MAX_FRAMES, -3,
+                   "sr_set_option: ct_dipolar_cross_long_min_frames must be %d .. %d", SR_CT_DIPOLAR_CROSS_LONG_FLOOR, SR_CT_LONG_MAX_FRAMES);
+        ctx->ct_dipolar_cross_long_min_frames = value;
         return 0;
     }
     if (!strcmp(name, "ct_traceless")) {

@@ -190,7 +190,7 @@ static int cross_f32_dev(sr_ctx *ctx, const char *who, int blocked, const float 
         if (!psum) return -5;
     }
     if (blocked) {
-        if (int rc = sr_launch_ct_cross_long(ctx, soa, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, psum)) return rc;
+        if (int rc = sr_launch_ct_cross_long(ctx, soa, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, psum, 3, 0)) return rc;
     } else {
         // ---- stage the chunk starts and the pair table ----
         sr_stage st(ctx);

@@ -30,6 +30,8 @@
 //   k_ctl_spectra   per (series, block), ONCE per (vector, chunk) that the tile's pairs name, however many name it
 //   k_ctlx_cross    per (pair, chunk, 64 frequencies): the block spectra of both series once -> Q_d, float64
 //   k_ctl_inverse   per (pair, chunk, offset): psum completed
+// The distance-weighted pair form (sr_ct_dipolar_long.hip) runs the same launches on the four-plane dipolar pack with traceless = 1: five
+// signals whatever |a| is (k_ctlx_promote is skipped), no eps term, and S_a(0) - S_w(0) / 3 + F / 3 from the a and w planes in slot 0.
 // psum has kernel 1's layout (pair, chunk, sr_ct_psum_stride(F)) with pairs in the place of vectors, so k_ct_cross_p0 and k_ct_finalize
 // follow unchanged (sr_ct_cross_finish).  Mode 1 (float64 validation) is k_ctlx_f64: the definition, lag by lag from the planes.
 #include <algorithm>
@@ -52,6 +54,8 @@ struct CtlxArgs {
     int64_t nPR;
     int R, F, L, Lp, nb, nd, sym;
     int p0, r0, nr;                      // the tile: its first pair, first chunk, number of chunks
+    int planes;                          // planes per vector in soa: 3, or 4 for the dipolar pack (whose fourth plane is w)
+    int traceless;                       // 1: five traceless signals whatever |a| is, no eps term, S_a - S_w / 3 + F / 3 in slot 0
 };
 
 // ---- six signals for both series of a pair if one of them is not a unit-vector series --------------------------------------------
@@ -91,8 +95,8 @@ __global__ __launch_bounds__(256) void k_ctlx_scan(CtlxArgs a)
     const int p = (int)(s / a.R), r = (int)(s - (int64_t)p * a.R), F = a.F, L = a.L;
     const int vi = a.pair_i[p], vj = a.pair_j[p];
     const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
-    const float *ix = a.soa + (int64_t)vi * 3 * a.Npad + start, *iy = ix + a.Npad, *iz = iy + a.Npad;
-    const float *jx = a.soa + (int64_t)vj * 3 * a.Npad + start, *jy = jx + a.Npad, *jz = jy + a.Npad;
+    const float *ix = a.soa + (int64_t)vi * a.planes * a.Npad + start, *iy = ix + a.Npad, *iz = iy + a.Npad;
+    const float *jx = a.soa + (int64_t)vj * a.planes * a.Npad + start, *jy = jx + a.Npad, *jz = jy + a.Npad;
     const CtlConst *ci = a.consts + (int64_t)vi * a.R + r, *cj = a.consts + (int64_t)vj * a.R + r;
     float mi[6], mj[6];
     double wi[6], wj[6];
@@ -103,13 +107,13 @@ __global__ __launch_bounds__(256) void k_ctlx_scan(CtlxArgs a)
         wi[c] = (double)uniform_f(ci->wm[c]);
         wj[c] = (double)uniform_f(cj->wm[c]);
     }
-    const bool unit = uniform_f(ci->weps) != 0.f && uniform_f(cj->weps) != 0.f;
+    const bool unit = a.traceless || (uniform_f(ci->weps) != 0.f && uniform_f(cj->weps) != 0.f);
     double K6 = unit ? 2.0 : 0.0;
 #pragma unroll
     for (int c = 0; c < 6; ++c)
         if (c < 5 || !unit) K6 = fma(wi[c], (double)mj[c], K6);
     double *out = a.psum + s * a.Lp;
-    double carry = 0.0, s0 = 0.0;
+    double carry = 0.0, s0 = 0.0, sw0 = 0.0;
     for (int base = ((F - 1) / 2048) * 2048; base >= 0; base -= 2048) {
 #pragma unroll 2
         for (int n = 0; n < 8; ++n) {
@@ -121,7 +125,10 @@ __global__ __launch_bounds__(256) void k_ctlx_scan(CtlxArgs a)
             ctlx_signals(xj, yj, zj, mj, dj);
             // e_ij = sum_c 6 w_c m^j_c d^i_c and e_ji, each at t' (.x) and at its mirror (.y)
             double eij_x, eij_y, eji_x, eji_y;
-            if (unit) {
+            if (a.traceless) {
+                eij_x = eij_y = eji_x = eji_y = 0.0;
+                sw0 += t < F ? (double)iz[a.Npad + tc] * (double)jz[a.Npad + tc] : 0.0;      // the w planes
+            } else if (unit) {
                 eij_x = 2.0 * fma((double)xi.x, (double)xi.x, fma((double)yi.x, (double)yi.x, fma((double)zi.x, (double)zi.x, -1.0)));
                 eij_y = 2.0 * fma((double)xi.y, (double)xi.y, fma((double)yi.y, (double)yi.y, fma((double)zi.y, (double)zi.y, -1.0)));
                 eji_x = 2.0 * fma((double)xj.x, (double)xj.x, fma((double)yj.x, (double)yj.x, fma((double)zj.x, (double)zj.x, -1.0)));
@@ -172,8 +179,21 @@ __global__ __launch_bounds__(256) void k_ctlx_scan(CtlxArgs a)
     s0 = sr_wave_sum_f64(s0);
     if ((tid & 63) == 0) tot[tid >> 6] = s0;
     __syncthreads();
+    const double s0t = (tot[0] + tot[1]) + (tot[2] + tot[3]);
+    if (!a.traceless) {
+        if (tid == 0) {
+            out[0] = s0t;
+            a.pconsts[s].G0 = 0.0;
+        }
+        return;
+    }
+    // the distance-weighted pair: S_a(0) - S_w(0) / 3 + F / 3, the raw sum k_ct_dipolar_cross leaves in slot 0
+    __syncthreads();
+    sw0 = sr_wave_sum_f64(sw0);
+    if ((tid & 63) == 0) tot[tid >> 6] = sw0;
+    __syncthreads();
     if (tid == 0) {
-        out[0] = (tot[0] + tot[1]) + (tot[2] + tot[3]);
+        out[0] = s0t - ((tot[0] + tot[1]) + (tot[2] + tot[3])) / 3.0 + (double)F / 3.0;
         a.pconsts[s].G0 = 0.0;
     }
 }
@@ -192,7 +212,8 @@ __global__ __launch_bounds__(256) void k_ctlx_cross(CtlxArgs a)
     const int tid = threadIdx.x, kk = tid & 63, dg = tid >> 6, sl = blockIdx.y;
     const int pl = sl / a.nr, rr = sl - pl * a.nr, p = a.p0 + pl, r = a.r0 + rr;
     const int j = blockIdx.x * kKTile + kk;
-    const bool six = a.consts[(int64_t)a.pair_i[p] * a.R + r].weps == 0.f || a.consts[(int64_t)a.pair_j[p] * a.R + r].weps == 0.f;
+    const bool six = !a.traceless &&
+                     (a.consts[(int64_t)a.pair_i[p] * a.R + r].weps == 0.f || a.consts[(int64_t)a.pair_j[p] * a.R + r].weps == 0.f);
     const int nsig = __builtin_amdgcn_readfirstlane(six ? 6 : 5);
     const int64_t per_sig = (int64_t)nb * kSpecLen;
     const c32 *bi = a.spec + ((int64_t)a.slot_i[p] * a.nr + rr) * 6 * per_sig + blockIdx.x * kKTile;
@@ -255,8 +276,8 @@ __global__ __launch_bounds__(256) void k_ctlx_f64(CtlxArgs a)
     const int64_t s = blockIdx.x;
     const int p = (int)(s / a.R), r = (int)(s - (int64_t)p * a.R);
     const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
-    const float *ix = a.soa + (int64_t)a.pair_i[p] * 3 * a.Npad + start, *iy = ix + a.Npad, *iz = iy + a.Npad;
-    const float *jx = a.soa + (int64_t)a.pair_j[p] * 3 * a.Npad + start, *jy = jx + a.Npad, *jz = jy + a.Npad;
+    const float *ix = a.soa + (int64_t)a.pair_i[p] * a.planes * a.Npad + start, *iy = ix + a.Npad, *iz = iy + a.Npad;
+    const float *jx = a.soa + (int64_t)a.pair_j[p] * a.planes * a.Npad + start, *jy = jx + a.Npad, *jz = jy + a.Npad;
     double sij = 0.0, sji = 0.0;
     for (int t = 0; t + k < F; ++t) {
         const double x = (double)ix[t] * (double)jx[t + k] + (double)iy[t] * (double)jy[t + k] + (double)iz[t] * (double)jz[t + k];
@@ -278,13 +299,15 @@ struct CtlxTile {
 
 // what sr_ct_cross_f32_dev does behind its checks, for the chunks of sr_ct_cross_check(blocked = 1)
 int sr_launch_ct_cross_long(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                            const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *psum)
+                            const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *psum, int planes, int traceless)
 {
+    SR_REQUIRE(!(traceless && mode == 1), -3, "blocked pair form: the traceless form has no float64 mode of its own");
     const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
     const int nb = (int)((F + kB - 1) / kB), nd = (int)(L / kB + 1);
     CtlxArgs x;
     x.soa = soa; x.Npad = Npad; x.psum = psum; x.nPR = nP * R;
     x.R = (int)R; x.F = (int)F; x.L = (int)L; x.Lp = (int)Lp; x.nb = nb; x.nd = nd; x.sym = sym;
+    x.planes = planes; x.traceless = traceless;
     x.consts = x.pconsts = nullptr; x.spec = nullptr; x.Q = nullptr; x.slot_i = x.slot_j = nullptr; x.p0 = x.r0 = 0; x.nr = (int)R;
     sr_stage st(ctx);
     st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 4 * (size_t)nP * sizeof(int32_t));
@@ -346,20 +369,23 @@ int sr_launch_ct_cross_long(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t
     a.soa = soa; a.Npad = Npad; a.chunk_start = x.chunk_start; a.psum = psum; a.consts = x.consts;
     a.spec = nullptr; a.Q = nullptr;
     a.R = (int)R; a.F = (int)F; a.L = (int)L; a.Lp = (int)Lp; a.nb = nb; a.nd = nd; a.s0 = 0;
+    a.planes = planes; a.traceless = traceless;
 
     // chunk constants of the named vectors, runs of consecutive vectors in one launch (k_ctl_consts counts its series from 0)
     for (size_t u = 0; u < all.size();) {
         size_t e = u + 1;
         while (e < all.size() && all[e] == all[e - 1] + 1) ++e;
         CtlArgs c = a;
-        c.soa = soa + (int64_t)all[u] * 3 * Npad;
+        c.soa = soa + (int64_t)all[u] * planes * Npad;
         c.consts = x.consts + (int64_t)all[u] * R;
         hipLaunchKernelGGL(k_ctl_consts, dim3((unsigned)((int64_t)(e - u) * R)), dim3(256), 0, ctx->stream, c);
         SR_HIP(hipGetLastError());
         u = e;
     }
-    hipLaunchKernelGGL(k_ctlx_promote, dim3((unsigned)((nP * R + 255) / 256)), dim3(256), 0, ctx->stream, x);
-    SR_HIP(hipGetLastError());
+    if (!traceless) {                                // (the traceless form has five signals whatever weps says)
+        hipLaunchKernelGGL(k_ctlx_promote, dim3((unsigned)((nP * R + 255) / 256)), dim3(256), 0, ctx->stream, x);
+        SR_HIP(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_ctlx_scan, dim3((unsigned)(nP * R)), dim3(256), 0, ctx->stream, x);
     SR_HIP(hipGetLastError());
 

@@ -26,7 +26,7 @@
 //                    lag in mode 1 by a float64 path; while staging, wave 0 of slab 0 sums w and w^2 of the chunk in float64.  No
 //                    atomics, no scratch: equal input gives bit-equal output
 //   k_ct_dipolar_norm  chunk means of the two sums; Ct and dCt scaled by 1 / mean n_r; <w> and <w^2> per vector
-// A chunk must fit 16 ct_Fp(F) bytes of LDS: F <= 10016 at 160 KiB.  A blocked form for longer chunks does not exist.
+// A chunk must fit 16 ct_Fp(F) bytes of LDS: F <= 10016 at 160 KiB.  Longer chunks take the blocked form (sr_ct_dipolar_long.hip).
 #include "sr_ct_dipolar.h"
 #include <cmath>
 
@@ -272,14 +272,22 @@ int launch_dip(sr_ctx *ctx, const CtDipArgs &a, int64_t nblocks, size_t lds_byte
 
 }  // namespace
 
-int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode)
+int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
+                        int blocked)
 {
     SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld", who, (long long)R, (long long)F, (long long)nV);
     SR_REQUIRE(mode == 0 || mode == 1, -3, "%s: mode must be 0 or 1", who);
-    SR_REQUIRE(dip_lds_bytes(F) <= sr_lds_limit(ctx), -4,
-               "%s: the four series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (no blocked form for the dipolar "
-               "correlation function)",
-               who, (long long)F, dip_lds_bytes(F), sr_lds_limit(ctx), (long long)dip_max_frames(sr_lds_limit(ctx)));
+    if (blocked) {
+        SR_REQUIRE(F <= SR_CT_LONG_MAX_FRAMES, -4, "%s: the blocked form takes chunks of at most %d frames, F=%lld", who, SR_CT_LONG_MAX_FRAMES,
+                   (long long)F);
+        SR_REQUIRE(F >= SR_CT_DIPOLAR_LONG_FLOOR, -3, "%s: the blocked form takes chunks of at least %d frames, F=%lld", who,
+                   SR_CT_DIPOLAR_LONG_FLOOR, (long long)F);
+    } else {
+        SR_REQUIRE(dip_lds_bytes(F) <= sr_lds_limit(ctx), -4,
+                   "%s: the four series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (longer chunks: the blocked form, "
+                   "sr_ct_dipolar_long_f32_dev)",
+                   who, (long long)F, dip_lds_bytes(F), sr_lds_limit(ctx), (long long)dip_max_frames(sr_lds_limit(ctx)));
+    }
     SR_REQUIRE(R * nV < (int64_t)1 << 30, -3, "%s: too many series", who);
     if (chunk_start_host) {
         for (int64_t r = 0; r < R; ++r)
@@ -288,6 +296,15 @@ int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV
     } else {
         SR_REQUIRE(R * F <= frames, -3, "%s: R*F=%lld exceeds the %lld frames held", who, (long long)(R * F), (long long)frames);
     }
+    return 0;
+}
+
+int sr_ct_dipolar_norm_dev(sr_ctx *ctx, const double *wsum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt, double *wmean)
+{
+    const int64_t L = F / 2;
+    hipLaunchKernelGGL(k_ct_dipolar_norm, dim3((unsigned)((L + 63) / 64), (unsigned)((nV + 63) / 64)), dim3(256), 0, ctx->stream, wsum, (int)R,
+                       (int)F, (int)L, nV, Ct, dCt, wmean);
+    SR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -322,7 +339,7 @@ int sr_ct_dipolar_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, int64_
 {
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(planes && Ct && dCt && wmean, -2, "sr_ct_dipolar_f32_dev: null pointer");
-    if (int rc = sr_ct_dipolar_check(ctx, "sr_ct_dipolar_f32_dev", Npad, nV, R, F, chunk_start_host, mode)) return rc;
+    if (int rc = sr_ct_dipolar_check(ctx, "sr_ct_dipolar_f32_dev", Npad, nV, R, F, chunk_start_host, mode, 0)) return rc;
     const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
     SR_REQUIRE((nV + 15) / 16 <= 65535, -3, "sr_ct_dipolar_f32_dev: too many vectors in one call (%lld)", (long long)nV);   // k_ct_finalize's grid
     double *psum = psum_ws;
@@ -358,10 +375,7 @@ int sr_ct_dipolar_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, int64_
     }
     if (rc) return rc;
     if (int rc2 = sr_ct_finalize_f64_dev(ctx, psum, R, F, nV, Ct, dCt)) return rc2;
-    hipLaunchKernelGGL(k_ct_dipolar_norm, dim3((unsigned)((L + 63) / 64), (unsigned)((nV + 63) / 64)), dim3(256), 0, ctx->stream, a.wsum, (int)R,
-                       (int)F, (int)L, nV, Ct, dCt, wmean);
-    SR_HIP(hipGetLastError());
-    return 0;
+    return sr_ct_dipolar_norm_dev(ctx, a.wsum, R, F, nV, Ct, dCt, wmean);
 }
 
 }  // extern "C"

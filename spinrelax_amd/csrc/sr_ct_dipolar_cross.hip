@@ -20,7 +20,7 @@
 // exchanged; the float32 partial sums start at -min(kCenter, 8 sqrt(sum w_i^2 sum w_j^2) / F), the adaptive centre of k_ct_dipolar
 // (the terms are <= w_i w_j').  Remaining lags and every lag in mode 1 take a float64 path.  While at it every wave sums w_i^2 and
 // w_j^2 of the chunk in float64 and wave 0 writes them out.  No atomics, no scratch: equal input gives bit-equal output.
-// A chunk must fit 32 ct_Fp(F) bytes of LDS: F <= 4896 at 160 KiB.  A blocked form for longer chunks does not exist.
+// A chunk must fit 32 ct_Fp(F) bytes of LDS: F <= 4896 at 160 KiB.  Longer chunks take the blocked form (sr_ct_dipolar_long.hip).
 #include "sr_ct_dipolar.h"
 #include <cmath>
 
@@ -191,16 +191,23 @@ int64_t dipx_max_frames(size_t lds_limit)
 }  // namespace
 
 int sr_ct_dipolar_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                              const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode)
+                              const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, int blocked)
 {
     SR_REQUIRE(pair_i && pair_j, -2, "%s: null pointer", who);
     SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1 && nP >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld nP=%lld", who, (long long)R, (long long)F,
                (long long)nV, (long long)nP);
     SR_REQUIRE((mode == 0 || mode == 1) && (sym == 0 || sym == 1), -3, "%s: mode and sym must be 0 or 1", who);
-    SR_REQUIRE(dipx_lds_bytes(F) <= sr_lds_limit(ctx), -4,
-               "%s: the eight series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (no blocked form for the dipolar "
-               "cross-correlation function)",
-               who, (long long)F, dipx_lds_bytes(F), sr_lds_limit(ctx), (long long)dipx_max_frames(sr_lds_limit(ctx)));
+    if (blocked) {
+        SR_REQUIRE(F <= SR_CT_LONG_MAX_FRAMES, -4, "%s: the blocked form takes chunks of at most %d frames, F=%lld", who, SR_CT_LONG_MAX_FRAMES,
+                   (long long)F);
+        SR_REQUIRE(F >= SR_CT_DIPOLAR_CROSS_LONG_FLOOR, -3, "%s: the blocked form takes chunks of at least %d frames, F=%lld", who,
+                   SR_CT_DIPOLAR_CROSS_LONG_FLOOR, (long long)F);
+    } else {
+        SR_REQUIRE(dipx_lds_bytes(F) <= sr_lds_limit(ctx), -4,
+                   "%s: the eight series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (longer chunks: the blocked form, "
+                   "sr_ct_dipolar_cross_long_f32_dev)",
+                   who, (long long)F, dipx_lds_bytes(F), sr_lds_limit(ctx), (long long)dipx_max_frames(sr_lds_limit(ctx)));
+    }
     SR_REQUIRE(R * nP < (int64_t)1 << 30, -3, "%s: too many series", who);
     SR_REQUIRE((nP + 15) / 16 <= 65535, -3, "%s: too many pairs in one call (%lld)", who, (long long)nP);       // k_ct_finalize's grid
     if (chunk_start_host) {
@@ -213,6 +220,16 @@ int sr_ct_dipolar_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int6
     for (int64_t p = 0; p < nP; ++p)
         SR_REQUIRE(pair_i[p] >= 0 && pair_i[p] < nV && pair_j[p] >= 0 && pair_j[p] < nV, -3, "%s: pair %lld = (%d, %d) is outside the %lld vectors",
                    who, (long long)p, (int)pair_i[p], (int)pair_j[p], (long long)nV);
+    return 0;
+}
+
+int sr_ct_dipolar_cross_norm_dev(sr_ctx *ctx, const double *wsum2, int64_t R, int64_t F, int64_t nP, double *Ct, double *dCt, double *P0,
+                                 double *dP0)
+{
+    const int64_t L = F / 2;
+    hipLaunchKernelGGL(k_ct_dipolar_cross_norm, dim3((unsigned)((L + 63) / 64), (unsigned)((nP + 63) / 64)), dim3(256), 0, ctx->stream, wsum2,
+                       (int)R, (int)F, (int)L, nP, Ct, dCt, P0, dP0);
+    SR_HIP(hipGetLastError());
     return 0;
 }
 
@@ -231,7 +248,7 @@ int sr_ct_dipolar_cross_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, 
     const char *who = "sr_ct_dipolar_cross_f32_dev";
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(planes && P0 && Ct && dCt && wsum2, -2, "%s: null pointer", who);
-    if (int rc = sr_ct_dipolar_cross_check(ctx, who, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode)) return rc;
+    if (int rc = sr_ct_dipolar_cross_check(ctx, who, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, 0)) return rc;
     const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
     double *psum = psum_ws;
     if (!psum) {
@@ -252,10 +269,7 @@ int sr_ct_dipolar_cross_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, 
     if (int rc = sr_launch(ctx, k_ct_dipolar_cross, dim3((unsigned)(nP * R)), dim3(kDipCrossWaves * 64), dipx_lds_bytes(F), a)) return rc;
     if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, P0, dP0)) return rc;
     if (int rc = sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt)) return rc;
-    hipLaunchKernelGGL(k_ct_dipolar_cross_norm, dim3((unsigned)((L + 63) / 64), (unsigned)((nP + 63) / 64)), dim3(256), 0, ctx->stream, wsum2,
-                       (int)R, (int)F, (int)L, nP, Ct, dCt, P0, dP0);
-    SR_HIP(hipGetLastError());
-    return 0;
+    return sr_ct_dipolar_cross_norm_dev(ctx, wsum2, R, F, nP, Ct, dCt, P0, dP0);
 }
 
 }  // extern "C"

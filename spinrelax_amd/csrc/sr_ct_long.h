@@ -2,6 +2,8 @@
 // sr_ct_cross_long.hip (the same algebra on the two series of a pair).  The chunk constants, the float32 block spectra and the
 // float64 inverse transform depend on one series (or one cross-spectrum) only, so both sources run the same kernels on the same
 // work area (slot SR_WS_CTLONG); each source has its own cross-spectrum pass and its own restoration of the subtracted means.
+// sr_ct_dipolar_long.hip runs both on the four-plane dipolar pack: CtlArgs::planes is the plane stride of a vector and
+// CtlArgs::traceless asks for the five traceless signals alone (its header has the algebra); 3 and 0 are the unit-vector forms.
 #pragma once
 #include "sr_internal.h"
 #include "sr_ct32_fft.h"
@@ -34,6 +36,8 @@ struct CtlArgs {
     const double2 *itab;             // exp(+2 pi i e / 8192), e < 4096
     int R, F, L, Lp, nb, nd;
     int s0;                          // first series of the tile
+    int planes;                      // planes per vector in soa: 3 (unit-vector pack) or 4 (the dipolar pack a_x, a_y, a_z, w)
+    int traceless;                   // 1: the five traceless signals only, whatever |a| is (sr_ct_dipolar_long.hip)
 };
 
 __device__ __forceinline__ float uniform_f(float v)
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(256) void k_ctl_consts(CtlArgs a)
     const int tid = threadIdx.x, s = blockIdx.x;
     const int v = s / a.R, r = s - v * a.R, F = a.F;
     const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
-    const float *px = a.soa + (int64_t)v * 3 * a.Npad + start, *py = px + a.Npad, *pz = py + a.Npad;
+    const float *px = a.soa + (int64_t)v * a.planes * a.Npad + start, *py = px + a.Npad, *pz = py + a.Npad;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f, emax = 0.f;
     for (int j = tid; j < F; j += 256) {
         const float x = px[j], y = py[j], z = pz[j];
@@ -73,7 +77,9 @@ __global__ __launch_bounds__(256) void k_ctl_consts(CtlArgs a)
         // m_c: the chunk mean with its low four mantissa bits cleared, as in k_ct_rfft32 (3 m_c and 12 m_c exact in float32)
         const float wgt[6] = {1.0f, 3.0f, 12.0f, 12.0f, 12.0f, 2.0f};
         const float invF = 1.0f / (float)F;
-        const bool unit = fmaxf(fmaxf(red[0][6], red[1][6]), fmaxf(red[2][6], red[3][6])) < kUnitTolF;
+        // traceless: five signals and the constant 1/3 per product as for unit vectors, but no eps term (weps = 0): the caller's
+        // function has no trace part (sr_ct_dipolar_long.hip)
+        const bool unit = a.traceless || fmaxf(fmaxf(red[0][6], red[1][6]), fmaxf(red[2][6], red[3][6])) < kUnitTolF;
         CtlConst c;
         double Kc = unit ? 2.0 : 0.0;
         for (int i = 0; i < 6; ++i) {
@@ -82,7 +88,7 @@ __global__ __launch_bounds__(256) void k_ctl_consts(CtlArgs a)
             c.wm[i] = wgt[i] * c.m[i];
             if (i < 5 || !unit) Kc = fma((double)wgt[i] * (double)c.m[i], (double)c.m[i], Kc);
         }
-        c.weps = unit ? 2.0f : 0.f;
+        c.weps = unit && !a.traceless ? 2.0f : 0.f;
         c.nsig = unit ? 5 : 6;
         c.Kc = Kc;
         c.G0 = 0.0;
@@ -123,7 +129,7 @@ __global__ __launch_bounds__(256, 3) void k_ctl_spectra(CtlArgs a)
     const int v = s / a.R, r = s - v * a.R;
     const int64_t start = (a.chunk_start ? a.chunk_start[r] : (int64_t)r * a.F) + (int64_t)blk * kB;
     const int Fb = min(kB, a.F - blk * kB);                        // frames of the chunk in this block (>= 1)
-    const float *px = a.soa + (int64_t)v * 3 * a.Npad + start;
+    const float *px = a.soa + (int64_t)v * a.planes * a.Npad + start;
     const bool even = ((start | a.Npad | (int64_t)Fb) & 1) == 0;   // frames 2m, 2m + 1 of every plane share an aligned 8 bytes
     {
         const int j = ((tid0 & 15) * (tid0 >> 4)) & 255;

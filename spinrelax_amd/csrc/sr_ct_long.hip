@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void k_ctl_scan(CtlArgs a)
     const int tid = threadIdx.x, s = blockIdx.x;
     const int v = s / a.R, r = s - v * a.R, F = a.F, L = a.L;
     const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
-    const float *px = a.soa + (int64_t)v * 3 * a.Npad + start, *py = px + a.Npad, *pz = py + a.Npad;
+    const float *px = a.soa + (int64_t)v * a.planes * a.Npad + start, *py = px + a.Npad, *pz = py + a.Npad;
     const CtlConst *cc = a.consts + s;
     float mm[6], wm[6];
 #pragma unroll
@@ -188,6 +188,7 @@ int sr_launch_ct_long(sr_ctx *ctx, const sr_ct_job &j)
     a.spec = reinterpret_cast<c32 *>(ws + const_bytes);
     a.Q = reinterpret_cast<double2 *>(ws + const_bytes + (size_t)tile * 6 * nb * kSpecLen * sizeof(c32));
     a.R = j.R; a.F = F; a.L = L; a.Lp = j.Lp; a.nb = nb; a.nd = nd; a.s0 = 0;
+    a.planes = j.planes; a.traceless = j.traceless;
     hipLaunchKernelGGL(k_ctl_consts, dim3((unsigned)series), dim3(256), 0, ctx->stream, a);
     SR_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_ctl_scan, dim3((unsigned)series), dim3(256), 0, ctx->stream, a);

@@ -31,7 +31,9 @@ struct sr_ctx {
                         // shorter ones that the direct kernel cannot stage; default SR_CT_LONG_MIN_FRAMES
     int ct_cross_long_min_frames;   // pair cross-correlation: spinrelax_amd/ct.py gives chunks of at least this many frames to the blocked form
                         // (sr_ct_cross_long.hip); the library's entry points do not dispatch, each runs its own kernel
-    int ired_ksplit;    // iRED matrix (sr_ired.hip): workgroups that share a window's frames per tile pair; 0 (default) = sr_ired_ksplit()'s rule
+    int ct_dipolar_long_min_frames, ct_dipolar_cross_long_min_frames;   // the same for the two distance-weighted functions
+                        // (sr_ct_dipolar_long.hip)
+    int ired_ksplit;   // iRED matrix (sr_ired.hip): workgroups that share a window's frames per tile pair; 0 (default) = sr_ired_ksplit()'s rule
     int ired_ws_mb;     // iRED mode correlation functions (sr_ired_modes.hip): the windows of a call go in batches whose amplitudes fit this many MiB
     int fft_table_ready;
     int fft32_table_ready;
@@ -111,6 +113,8 @@ struct sr_ct_job {
     double *psum;                       // (nV, R, Lp)
     int R, F, L, Lp;
     int64_t series;                     // R nV
+    int planes = 3;                     // planes per vector in soa; 4: the dipolar pack a_x, a_y, a_z, w (sr_launch_ct_long only)
+    int traceless = 0;                  // sr_launch_ct_long only: the five traceless signals whatever |a| is (sr_ct_dipolar_long.hip)
 };
 
 // sr_ct_direct.hip: shifted products (k_ct_palmer); mode as in sr_ct_palmer_sums_f32_dev.  The series is staged in LDS, so the
@@ -137,18 +141,34 @@ int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, in
 // sr_ct_cross_check(blocked = 1) admits: the range in which the kernels it shares with sr_ct_long.hip are tested
 #define SR_CT_CROSS_LONG_FLOOR 5462
 #define SR_CT_CROSS_LONG_MIN_FRAMES 6625   /* default of "ct_cross_long_min_frames": the first length k_ct_cross cannot stage */
+// planes = 3, traceless = 0: unit-vector planes (sr_ct_cross.hip).  planes = 4, traceless = 1: the dipolar pack, five traceless signals
+// and S_a - S_w / 3 + F / 3 in slot 0 (sr_ct_dipolar_long.hip, mode 0 only)
 int sr_launch_ct_cross_long(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                            const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *psum);
+                            const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *psum, int planes,
+                            int traceless);
 
 // sr_ct_dipolar.hip: what the entry points of the dipolar correlation function refuse, before anything is queued: shapes and mode (-3), a
-// chunk whose four series do not fit the LDS (-4), chunk starts outside the `frames` frames held (-3)
-int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode);
+// chunk whose four series do not fit the LDS (-4; blocked = 1: a chunk of more than SR_CT_LONG_MAX_FRAMES frames, and -3 below
+// SR_CT_DIPOLAR_LONG_FLOOR), chunk starts outside the `frames` frames held (-3)
+int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
+                        int blocked);
 
 // sr_ct_dipolar_cross.hip: what the entry points of the dipolar cross-correlation function refuse, before anything is queued: shapes, mode
-// and sym (-3), a chunk whose eight series do not fit the LDS (-4), chunk starts and pair indices outside the `frames` frames / nV
-// vectors held (-3)
+// and sym (-3), a chunk whose eight series do not fit the LDS (-4; blocked = 1: a chunk of more than SR_CT_LONG_MAX_FRAMES frames, and -3
+// below SR_CT_DIPOLAR_CROSS_LONG_FLOOR), chunk starts and pair indices outside the `frames` frames / nV vectors held (-3)
 int sr_ct_dipolar_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                              const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode);
+                              const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, int blocked);
+
+// sr_ct_dipolar_long.hip: the blocked forms of both, on planes from sr_pack_dipolar_f32_dev.  The floors are the shortest chunks at
+// which the shared kernels keep a block structure they are tested at (5462: F + L > 8192; 4097: two blocks, one offset)
+#define SR_CT_DIPOLAR_LONG_FLOOR 5462
+#define SR_CT_DIPOLAR_LONG_MIN_FRAMES 10017        /* default of "ct_dipolar_long_min_frames": the first length k_ct_dipolar cannot stage */
+#define SR_CT_DIPOLAR_CROSS_LONG_FLOOR 4097
+#define SR_CT_DIPOLAR_CROSS_LONG_MIN_FRAMES 4897   /* default of "ct_dipolar_cross_long_min_frames": the first k_ct_dipolar_cross cannot stage */
+// sr_ct_dipolar.hip, sr_ct_dipolar_cross.hip: the normalising kernels behind k_ct_finalize (and k_ct_cross_p0), shared with the blocked forms
+int sr_ct_dipolar_norm_dev(sr_ctx *ctx, const double *wsum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt, double *wmean);
+int sr_ct_dipolar_cross_norm_dev(sr_ctx *ctx, const double *wsum2, int64_t R, int64_t F, int64_t nP, double *Ct, double *dCt, double *P0,
+                                 double *dP0);
 
 // sr_ired_modes.hip
 #define SR_IRED_WS_MB 1024

@@ -403,21 +403,22 @@ int sr_vectors_ct_cross_long_err_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int6
     return vectors_ct_cross(ctx, "sr_vectors_ct_cross_long_f32", 1, h, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, P0, dP0, Ct, dCt);
 }
 
-int sr_vectors_ct_dipolar_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
-                              double *Ct, double *dCt, double *reff6, double *reff3, double *S2rad)
+static int vectors_ct_dipolar(sr_ctx *ctx, const char *who, int blocked, sr_vectors *h, const float *dist_host, int64_t R, int64_t F,
+                              const int64_t *chunk_start_host, int mode, double *Ct, double *dCt, double *reff6, double *reff3, double *S2rad)
 {
     SR_CHECK_CTX(ctx);
-    SR_REQUIRE(h && Ct && dCt && reff6 && reff3 && S2rad, -2, "sr_vectors_ct_dipolar_f32: null pointer");
+    SR_REQUIRE(h && Ct && dCt && reff6 && reff3 && S2rad, -2, "%s: null pointer", who);
     // refusals come before the pack: a chunk that does not fit or a bad distance launches nothing
-    if (int rc = sr_ct_dipolar_check(ctx, "sr_vectors_ct_dipolar_f32", h->N, h->nV, R, F, chunk_start_host, mode)) return rc;
-    if (int rc = check_dist("sr_vectors_ct_dipolar_f32", h, dist_host)) return rc;
-    if (int rc = pack_dipolar(ctx, "sr_vectors_ct_dipolar_f32", h, dist_host)) return rc;
+    if (int rc = sr_ct_dipolar_check(ctx, who, h->N, h->nV, R, F, chunk_start_host, mode, blocked)) return rc;
+    if (int rc = check_dist(who, h, dist_host)) return rc;
+    if (int rc = pack_dipolar(ctx, who, h, dist_host)) return rc;
     const int64_t L = F / 2, nV = h->nV;
     double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nV) * sizeof(double));
     double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * nV) * sizeof(double));
     double *wm_d = (double *)sr_workspace(ctx, SR_WS_OUT2, 2 * (size_t)nV * sizeof(double));
     if (!Ct_d || !dCt_d || !wm_d) return -5;
-    int rc = sr_ct_dipolar_f32_dev(ctx, h->soa4, h->Npad4, nV, R, F, chunk_start_host, mode, nullptr, Ct_d, dCt_d, wm_d);
+    int rc = (blocked ? sr_ct_dipolar_long_f32_dev : sr_ct_dipolar_f32_dev)(ctx, h->soa4, h->Npad4, nV, R, F, chunk_start_host, mode, nullptr, Ct_d,
+                                                                            dCt_d, wm_d);
     if (rc) return rc;
     SR_HIP(hipMemcpyAsync(Ct, Ct_d, (size_t)(L * nV) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SR_HIP(hipMemcpyAsync(dCt, dCt_d, (size_t)(L * nV) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -434,15 +435,26 @@ int sr_vectors_ct_dipolar_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host
     return 0;
 }
 
-int sr_vectors_ct_dipolar_cross_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                                    const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0,
-                                    double *Ct, double *dCt, double *reff6)
+int sr_vectors_ct_dipolar_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
+                              double *Ct, double *dCt, double *reff6, double *reff3, double *S2rad)
 {
-    const char *who = "sr_vectors_ct_dipolar_cross_f32";
+    return vectors_ct_dipolar(ctx, "sr_vectors_ct_dipolar_f32", 0, h, dist_host, R, F, chunk_start_host, mode, Ct, dCt, reff6, reff3, S2rad);
+}
+
+int sr_vectors_ct_dipolar_long_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                   int mode, double *Ct, double *dCt, double *reff6, double *reff3, double *S2rad)
+{
+    return vectors_ct_dipolar(ctx, "sr_vectors_ct_dipolar_long_f32", 1, h, dist_host, R, F, chunk_start_host, mode, Ct, dCt, reff6, reff3, S2rad);
+}
+
+static int vectors_ct_dipolar_cross(sr_ctx *ctx, const char *who, int blocked, sr_vectors *h, const float *dist_host, int64_t R, int64_t F,
+                                    const int64_t *chunk_start_host, const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode,
+                                    double *P0, double *dP0, double *Ct, double *dCt, double *reff6)
+{
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(h && P0 && dP0 && Ct && dCt && reff6, -2, "%s: null pointer", who);
     // refusals come before the pack: a bad pair table, a chunk that does not fit or a bad distance launches nothing
-    if (int rc = sr_ct_dipolar_cross_check(ctx, who, h->N, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode)) return rc;
+    if (int rc = sr_ct_dipolar_cross_check(ctx, who, h->N, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, blocked)) return rc;
     if (int rc = check_dist(who, h, dist_host)) return rc;
     if (int rc = pack_dipolar(ctx, who, h, dist_host)) return rc;
     const int64_t L = F / 2;
@@ -453,8 +465,9 @@ int sr_vectors_ct_dipolar_cross_f32(sr_ctx *ctx, sr_vectors *h, const float *dis
     if (!Ct_d || !dCt_d || !P0_d || !ws_d) return -5;
     double *ws = (double *)malloc(2 * (size_t)(nP * R) * sizeof(double));
     SR_REQUIRE(ws != nullptr, -5, "%s: out of host memory", who);
-    int rc = sr_ct_dipolar_cross_f32_dev(ctx, h->soa4, h->Npad4, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, nullptr, P0_d,
-                                         P0_d + nP, Ct_d, dCt_d, ws_d);
+    int rc = (blocked ? sr_ct_dipolar_cross_long_f32_dev : sr_ct_dipolar_cross_f32_dev)(ctx, h->soa4, h->Npad4, h->nV, R, F, chunk_start_host, pair_i,
+                                                                                        pair_j, nP, sym, mode, nullptr, P0_d, P0_d + nP, Ct_d,
+                                                                                        dCt_d, ws_d);
     hipError_t e = hipSuccess;
     if (!rc) {
         e = hipMemcpyAsync(P0, P0_d, (size_t)nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
@@ -477,6 +490,22 @@ int sr_vectors_ct_dipolar_cross_f32(sr_ctx *ctx, sr_vectors *h, const float *dis
     if (rc) return rc;
     SR_HIP(e);
     return 0;
+}
+
+int sr_vectors_ct_dipolar_cross_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                    const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0,
+                                    double *Ct, double *dCt, double *reff6)
+{
+    return vectors_ct_dipolar_cross(ctx, "sr_vectors_ct_dipolar_cross_f32", 0, h, dist_host, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode,
+                                    P0, dP0, Ct, dCt, reff6);
+}
+
+int sr_vectors_ct_dipolar_cross_long_f32(sr_ctx *ctx, sr_vectors *h, const float *dist_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                                         const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0,
+                                         double *Ct, double *dCt, double *reff6)
+{
+    return vectors_ct_dipolar_cross(ctx, "sr_vectors_ct_dipolar_cross_long_f32", 1, h, dist_host, R, F, chunk_start_host, pair_i, pair_j, nP, sym,
+                                    mode, P0, dP0, Ct, dCt, reff6);
 }
 
 /* raw sums S[v][r][d-1] = sum_j (u_j . u_{j+d})^2 per (vector, chunk, lag) on the HOST, (nV, R, L) compact: what a rank that

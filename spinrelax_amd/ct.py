@@ -184,6 +184,32 @@ def _check_dist(dist, shape):
     return d
 
 
+def _ct_dipolar(rv, R, F, **kw):
+    """The dispatch of the dipolar correlation function: chunks that k_ct_dipolar can stage go to it (rv.ct_dipolar), longer ones -- and,
+    under sr_set_option("ct_dipolar_long_min_frames", n), every chunk of at least n frames -- to the blocked form (rv.ct_dipolar_long)."""
+    c = rv.ctx
+    direct_max, long_max = c.ct_dipolar_max_frames(), c.ct_dipolar_long_max_frames()
+    if F > long_max:
+        raise ValueError('dipolar correlation function: a chunk of %d frames is beyond both forms (the staged kernel takes %d frames, the '
+                         'blocked transforms %d)' % (F, direct_max, long_max))
+    if F > direct_max or F >= c.ct_dipolar_long_min_frames:
+        return rv.ct_dipolar_long(R, F, **kw)
+    return rv.ct_dipolar(R, F, **kw)
+
+
+def _ct_dipolar_cross(rv, R, F, pairs, **kw):
+    """The same for the dipolar pair cross-correlation: rv.ct_dipolar_cross, or rv.ct_dipolar_cross_long beyond what k_ct_dipolar_cross can
+    stage and from sr_set_option("ct_dipolar_cross_long_min_frames", n) frames on."""
+    c = rv.ctx
+    direct_max, long_max = c.ct_dipolar_cross_max_frames(), c.ct_dipolar_cross_long_max_frames()
+    if F > long_max:
+        raise ValueError('dipolar cross-correlation functions: a chunk of %d frames is beyond both forms (the staged kernel takes %d frames, '
+                         'the blocked transforms %d)' % (F, direct_max, long_max))
+    if F > direct_max or F >= c.ct_dipolar_cross_long_min_frames:
+        return rv.ct_dipolar_cross_long(R, F, pairs, **kw)
+    return rv.ct_dipolar_cross(R, F, pairs, **kw)
+
+
 def calculate_Ct_dipolar(vecs, dist=None, ctx=None, mode=0):
     """Distance-weighted dipolar correlation function of flexible spin pairs, an extension beyond the reference:
     C_dd(k) = <P2(u(t) . u(t + k)) r(t)^-3 r(t + k)^-3> / <r^-6> (Brueschweiler et al. 1992; Peter, Daura & van Gunsteren 2001).
@@ -192,7 +218,8 @@ def calculate_Ct_dipolar(vecs, dist=None, ctx=None, mode=0):
     Returns (Ct, dCt, reff6, reff3, S2rad): Ct, dCt (nFrames // 2, nVectors) for the lags 1 .. nFrames // 2, the ratio of the mean over
     the replicates of the unnormalised function to the mean of its lag-0 value, and std / (sqrt(nReplicates) - 1) of the former over
     the same normaliser (whose own scatter is ignored); per vector the effective distances reff6 = <r^-6>^(-1/6), reff3 = <r^-3>^(-1/3)
-    and the radial order parameter S2rad = <r^-3>^2 / <r^-6>, over all frames, in the units of the input."""
+    and the radial order parameter S2rad = <r^-3>^2 / <r^-6>, over all frames, in the units of the input.  Replicates longer than
+    Context.ct_dipolar_max_frames() frames take the blocked form, up to Context.ct_dipolar_long_max_frames() frames (_ct_dipolar)."""
     sh = np.shape(vecs)
     if len(sh) != 4 or sh[3] != 3:
         raise ValueError('vecs must be (replicates, frames, vectors, 3), got %s' % (sh,))
@@ -202,7 +229,7 @@ def calculate_Ct_dipolar(vecs, dist=None, ctx=None, mode=0):
     flat = np.ascontiguousarray(vecs, dtype=np.float32).reshape(R * F, V, 3)
     with _ctx(ctx).vectors(V, R * F) as rv:
         rv.append(flat)
-        return rv.ct_dipolar(R, F, dist=dist, mode=mode)
+        return _ct_dipolar(rv, R, F, dist=dist, mode=mode)
 
 
 def calculate_Ct_dipolar_resident(rv, R, F, dist=None, mode=0, chunk_start=None):
@@ -210,7 +237,7 @@ def calculate_Ct_dipolar_resident(rv, R, F, dist=None, mode=0, chunk_start=None)
     the shortest distance among all frames held; the averages behind reff6, reff3 and S2rad run over the frames of the chunks used."""
     if dist is not None:
         dist = _check_dist(dist, (rv.frames, rv.nV))
-    return rv.ct_dipolar(R, F, dist=dist, chunk_start=chunk_start, mode=mode)
+    return _ct_dipolar(rv, R, F, dist=dist, chunk_start=chunk_start, mode=mode)
 
 
 def calculate_Ct_dipolar_cross(vecs, pairs, dist=None, symmetric=True, ctx=None, mode=0):
@@ -221,8 +248,8 @@ def calculate_Ct_dipolar_cross(vecs, pairs, dist=None, symmetric=True, ctx=None,
     (P0, dP0, Ct, dCt, reff6): the equal-time value and its error over the replicates (nP), Ct, dCt (nFrames // 2, nP) for the lags
     1 .. nFrames // 2 -- ratios of the replicate means to sqrt(n_i n_j), n_v the replicate mean of <w_v^2>, whose own scatter is
     ignored -- and reff6 (nP, 2), the effective distances <r^-6>^(-1/6) of the two vectors of each pair.  For i = j: C_dd of
-    calculate_Ct_dipolar and P0 = 1.  At most Context.ct_dipolar_cross_max_frames() frames per replicate: there is no blocked form, a
-    longer one is refused by the library (SpinRelaxHipError, -4)."""
+    calculate_Ct_dipolar and P0 = 1.  Replicates longer than Context.ct_dipolar_cross_max_frames() frames take the blocked form, up to
+    Context.ct_dipolar_cross_long_max_frames() frames (_ct_dipolar_cross)."""
     sh = np.shape(vecs)
     if len(sh) != 4 or sh[3] != 3:
         raise ValueError('vecs must be (replicates, frames, vectors, 3), got %s' % (sh,))
@@ -233,7 +260,7 @@ def calculate_Ct_dipolar_cross(vecs, pairs, dist=None, symmetric=True, ctx=None,
     flat = np.ascontiguousarray(vecs, dtype=np.float32).reshape(R * F, V, 3)
     with _ctx(ctx).vectors(V, R * F) as rv:
         rv.append(flat)
-        return rv.ct_dipolar_cross(R, F, pairs, dist=dist, sym=int(bool(symmetric)), mode=mode)
+        return _ct_dipolar_cross(rv, R, F, pairs, dist=dist, sym=int(bool(symmetric)), mode=mode)
 
 
 def calculate_Ct_dipolar_cross_resident(rv, pairs, R, F, dist=None, symmetric=True, mode=0, chunk_start=None):
@@ -243,7 +270,7 @@ def calculate_Ct_dipolar_cross_resident(rv, pairs, R, F, dist=None, symmetric=Tr
     pairs = _check_pairs(pairs, rv.nV)
     if dist is not None:
         dist = _check_dist(dist, (rv.frames, rv.nV))
-    return rv.ct_dipolar_cross(R, F, pairs, dist=dist, chunk_start=chunk_start, sym=int(bool(symmetric)), mode=mode)
+    return _ct_dipolar_cross(rv, R, F, pairs, dist=dist, chunk_start=chunk_start, sym=int(bool(symmetric)), mode=mode)
 
 
 def upload_shard(vec_list, frames_per_chunk=None, ctx=None):

@@ -96,8 +96,8 @@ class Context:
 
     def set_option(self, name, value):
         check(self.lib.sr_set_option(self.h, name.encode(), int(value)), 'sr_set_option')
-        if name == 'ct_cross_long_min_frames':        # the one option that Python code acts on (ct.py's dispatch): keep what was accepted
-            self.ct_cross_long_min_frames = int(value)
+        if name in ('ct_cross_long_min_frames', 'ct_dipolar_long_min_frames', 'ct_dipolar_cross_long_min_frames'):
+            setattr(self, name, int(value))           # the options that Python code acts on (ct.py's dispatch): keep what was accepted
 
     def stream_create(self, cu_mask_words=None, priority=0):
         """hipStream_t handle (int); cu_mask_words = iterable of 32-bit words, bit set = CU usable."""
@@ -262,6 +262,35 @@ class Context:
         check(self.lib.sr_ct_dipolar_cross_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
                                                    int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr, wsum2_ptr),
               'sr_ct_dipolar_cross_f32_dev')
+
+    # ---- both for long chunks: blocked transforms (sr_ct_dipolar_long.hip) ----
+    ct_dipolar_long_min_frames = 10017          # the library's defaults of the two options: the first lengths that ct_dipolar and
+    ct_dipolar_cross_long_min_frames = 4897     # ct_dipolar_cross refuse
+
+    def ct_dipolar_long_max_frames(self):
+        """longest chunk the blocked form of the dipolar correlation function takes (sr_ct_dipolar_long_max_frames)"""
+        return int(self.lib.sr_ct_dipolar_long_max_frames(self.h))
+
+    def ct_dipolar_cross_long_max_frames(self):
+        """longest chunk the blocked form of the dipolar pair cross-correlation takes (sr_ct_dipolar_cross_long_max_frames)"""
+        return int(self.lib.sr_ct_dipolar_cross_long_max_frames(self.h))
+
+    def ct_dipolar_long_dev(self, planes_ptr, Npad, nV, R, F, Ct_ptr, dCt_ptr, wmean_ptr, chunk_start=None, mode=0, psum_ptr=None):
+        """ct_dipolar_dev for chunks of 5462 .. ct_dipolar_long_max_frames() frames, by blocked transforms (sr_ct_dipolar_long_f32_dev); the
+        planes must come from pack_dipolar_dev"""
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        check(self.lib.sr_ct_dipolar_long_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), int(mode), psum_ptr, Ct_ptr,
+                                                  dCt_ptr, wmean_ptr), 'sr_ct_dipolar_long_f32_dev')
+
+    def ct_dipolar_cross_long_dev(self, planes_ptr, Npad, nV, R, F, pairs, P0_ptr, Ct_ptr, dCt_ptr, wsum2_ptr, chunk_start=None, sym=1, mode=0,
+                                  psum_ptr=None, dP0_ptr=None):
+        """ct_dipolar_cross_dev for chunks of 4097 .. ct_dipolar_cross_long_max_frames() frames, by blocked transforms
+        (sr_ct_dipolar_cross_long_f32_dev); the planes must come from pack_dipolar_dev"""
+        pi, pj = pair_columns(pairs)
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        check(self.lib.sr_ct_dipolar_cross_long_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj),
+                                                        pi.size, int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr, wsum2_ptr),
+              'sr_ct_dipolar_cross_long_f32_dev')
 
     # ---- iRED matrix (sr_ired.hip) ----
     def ired_matrix_dev(self, soa_ptr, Npad, nV, win_start, win_len, M_ptr):
@@ -843,6 +872,14 @@ class ResidentVectors:
         C_dd(k) = <P2(u(t) . u(t+k)) r(t)^-3 r(t+k)^-3> / <r^-6>, k = 1 .. F//2, mean and error over the R chunks like ct().  dist
         (frames held, nV): the distances, the vectors then give the direction only; None: the length of a vector is its distance.
         Returns Ct, dCt (F//2, nV) and per vector reff6 = <r^-6>^(-1/6), reff3 = <r^-3>^(-1/3), S2rad = <r^-3>^2 / <r^-6>."""
+        return self._ct_dipolar('sr_vectors_ct_dipolar_f32', R, F, dist, chunk_start, mode)
+
+    def ct_dipolar_long(self, R, F, dist=None, chunk_start=None, mode=0):
+        """ct_dipolar for chunks of 5462 .. Context.ct_dipolar_long_max_frames() frames, by blocked transforms
+        (sr_vectors_ct_dipolar_long_f32): the same arguments and results"""
+        return self._ct_dipolar('sr_vectors_ct_dipolar_long_f32', R, F, dist, chunk_start, mode)
+
+    def _ct_dipolar(self, name, R, F, dist, chunk_start, mode):
         L = F // 2
         d = None
         if dist is not None:
@@ -855,8 +892,8 @@ class ResidentVectors:
         cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
         if cs is not None and cs.shape != (R,):
             raise ValueError('chunk_start must have R entries')
-        check(self.ctx.lib.sr_vectors_ct_dipolar_f32(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), int(mode), _ptr(Ct), _ptr(dCt),
-                                                     _ptr(reff6), _ptr(reff3), _ptr(S2rad)), 'sr_vectors_ct_dipolar_f32')
+        check(getattr(self.ctx.lib, name)(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), int(mode), _ptr(Ct), _ptr(dCt), _ptr(reff6),
+                                          _ptr(reff3), _ptr(S2rad)), name)
         return Ct, dCt, reff6, reff3, S2rad
 
     def ct_dipolar_cross(self, R, F, pairs, dist=None, chunk_start=None, sym=1, mode=0):
@@ -864,6 +901,14 @@ class ResidentVectors:
         C_ij(k) = <P2(u_i(t) . u_j(t+k)) r_i(t)^-3 r_j(t+k)^-3> / sqrt(<r_i^-6> <r_j^-6>), k = 1 .. F//2, mean and error over the R chunks
         like ct(); sym = 1: the mean of C_ij and C_ji.  dist as in ct_dipolar.  Returns (P0, dP0, Ct, dCt, reff6): P0, dP0 (nP) the
         equal-time value and its error, Ct, dCt (F//2, nP), reff6 (nP, 2) = <r^-6>^(-1/6) of the two vectors of each pair."""
+        return self._ct_dipolar_cross('sr_vectors_ct_dipolar_cross_f32', R, F, pairs, dist, chunk_start, sym, mode)
+
+    def ct_dipolar_cross_long(self, R, F, pairs, dist=None, chunk_start=None, sym=1, mode=0):
+        """ct_dipolar_cross for chunks of 4097 .. Context.ct_dipolar_cross_long_max_frames() frames, by blocked transforms
+        (sr_vectors_ct_dipolar_cross_long_f32): the same arguments and results"""
+        return self._ct_dipolar_cross('sr_vectors_ct_dipolar_cross_long_f32', R, F, pairs, dist, chunk_start, sym, mode)
+
+    def _ct_dipolar_cross(self, name, R, F, pairs, dist, chunk_start, sym, mode):
         pi, pj = pair_columns(pairs)
         L = F // 2
         d = None
@@ -878,9 +923,8 @@ class ResidentVectors:
         cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
         if cs is not None and cs.shape != (R,):
             raise ValueError('chunk_start must have R entries')
-        check(self.ctx.lib.sr_vectors_ct_dipolar_cross_f32(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
-                                                           int(sym), int(mode), _ptr(P0), _ptr(dP0), _ptr(Ct), _ptr(dCt), _ptr(reff6)),
-              'sr_vectors_ct_dipolar_cross_f32')
+        check(getattr(self.ctx.lib, name)(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym), int(mode),
+                                          _ptr(P0), _ptr(dP0), _ptr(Ct), _ptr(dCt), _ptr(reff6)), name)
         return P0, dP0, Ct, dCt, reff6
 
     def ct_sums(self, R, F, chunk_start=None, mode=0):

@@ -118,6 +118,11 @@ int          sr_timer_stop_ms(sr_ctx *, float *elapsed_ms);     /* synchronises 
  * vector range [v0, v0+nV): the shard a GPU owns.  Npad >= N, Npad % 4 == 0. */
 int sr_pack_soa_f32_dev(sr_ctx *, const float *vecs, int64_t N, int64_t Vtot, int64_t v0, int64_t nV,
                         float *soa, int64_t Npad);
+/* Register tiles (128 frames x 32 vectors, one workgroup each) of the production form of kernel 0 for a shape, as a host function
+ * that needs no context and no GPU: ceil(Npad / 128) * nV / 32 when the shape has whole 32-vector tiles and 16-byte rows (nV % 32 == 0,
+ * Vtot * 3 and v0 * 3 multiples of 4, Npad a positive multiple of 4, 0 <= v0, v0 + nV <= Vtot), else 0: such a shape goes through the
+ * LDS tile, as do arrays that are not 16-byte aligned. */
+int64_t sr_pack_reg_tiles(int64_t Npad, int64_t Vtot, int64_t v0, int64_t nV);
 /* The same with per-frame de-tumbling folded in: frame n is rotated by the unit
  * quaternion quat[n] = (w, x, y, z) -- rotate_vector_simd(v, q[:, None, :]), transforms3d_supplement.py:270-296, in
  * float64 -- before it is rounded into the float32 planes.  quat: DEVICE pointer, (N, 4) float64, already
@@ -183,6 +188,28 @@ int64_t sr_ct_max_frames_per_chunk(sr_ctx *);
  * duration of the dominant kernel. */
 int sr_ct_palmer_sums_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV,
                               const int64_t *chunk_start_host, int mode, double *psum);
+/* sr_ct_palmer_sums_f32_dev, and kernel 0 of the NEXT batch with it: next_vecs (next_N, next_Vtot, 3), columns [next_v0, next_v0 +
+ * next_nV), are packed into next_soa (next_Npad floats per plane) exactly as sr_pack_soa_f32_dev packs them -- an independent job,
+ * validated like that call; next_soa must overlap neither soa nor psum (-3).  When sr_ct_pack_fused() admits the pair, ONE launch does
+ * both: every workgroup of the C(t) kernel moves one or two register tiles of the pack in front of its own work, so the pack needs no
+ * wave slot beside the C(t) grids and its planes are complete when the launch is.  Otherwise kernel 0 is launched in front of the
+ * C(t) kernel on the same stream.  Planes and sums are the same bits either way, and what is refused queues nothing. */
+int sr_ct_palmer_sums_pack_f32_dev(sr_ctx *, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV,
+                                   const int64_t *chunk_start_host, int mode, double *psum,
+                                   const float *next_vecs, int64_t next_N, int64_t next_Vtot, int64_t next_v0, int64_t next_nV,
+                                   float *next_soa, int64_t next_Npad);
+/* What that call would do with the same arguments, without queueing anything: 1 = one launch carries the pack, 0 = kernel 0 in front of
+ * the C(t) kernel, negative = the refusal.  (A pipeline that keeps its pack on another stream unless it is carried asks first.) */
+int sr_ct_palmer_sums_pack_plan(sr_ctx *, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV,
+                                const int64_t *chunk_start_host, int mode, const double *psum,
+                                const float *next_vecs, int64_t next_N, int64_t next_Vtot, int64_t next_v0, int64_t next_nV,
+                                const float *next_soa, int64_t next_Npad);
+/* The rule of that choice, as a host function (no context, no GPU): 1 when the launch carries the pack.  formulation: what
+ * sr_ct_formulation() gives for the C(t) job; F its chunk length; series = R * nV, its workgroups; tiles = sr_pack_reg_tiles() of the
+ * pack job; aligned: the planes read are 8-byte aligned with even Npad and chunk starts (the kernel without frame masks), and
+ * next_vecs, next_soa are 16-byte aligned.  Carried: float32 transforms at F = 4096 (cfg3 / cfg4: the one instantiation built), aligned,
+ * and 1 <= tiles <= 2 * series. */
+int sr_ct_pack_fused(int formulation, int64_t F, int64_t series, int64_t tiles, int aligned);
 int sr_ct_finalize_f64_dev(sr_ctx *, const double *psum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt);
 /* the same launch also leaves the transposed copies CtT, dCtT (nV, L) the fits read (fitting_Ct_functions.py:149 works
  * per residue); both NULL = not wanted. */

@@ -57,6 +57,12 @@ SIGNATURES = {
     'sr_ct_formulation': (c_int, [c_int, c_int64, c_int, c_int64, c_int64]),       # (ct_fft, ct_long_min_frames, mode, F, lds_limit)
     'sr_ct_max_frames_per_chunk': (c_int64, [c_void_p]),
     'sr_ct_palmer_sums_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p]),
+    'sr_ct_palmer_sums_pack_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p,
+                                               c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64]),
+    'sr_ct_palmer_sums_pack_plan': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p,
+                                            c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64]),
+    'sr_ct_pack_fused': (c_int, [c_int, c_int64, c_int64, c_int64, c_int]),        # (formulation, F, series, tiles, aligned)
+    'sr_pack_reg_tiles': (c_int64, [c_int64, c_int64, c_int64, c_int64]),          # (Npad, Vtot, v0, nV)
     'sr_ct_finalize_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     'sr_ct_finalize_t_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     'sr_ct_palmer_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int,
@@ -198,7 +204,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long and sr_noe entry points and sr_vechist_plan: they only add symbols, and load() fails at a missing one
+ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long and sr_noe entry points, sr_vechist_plan and the sr_ct_palmer_sums_pack_* / sr_ct_pack_fused / sr_pack_reg_tiles group: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

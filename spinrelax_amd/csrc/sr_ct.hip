@@ -27,6 +27,7 @@
 // above sr_launch_ct_rfft32).  ct_long_min_frames defaults to SR_CT_LONG_MIN_FRAMES = 16384, above what fits: by default the
 // blocked form takes exactly the chunks the direct kernel cannot stage, and the option hands it shorter ones (from 5462 frames).
 #include "sr_internal.h"
+#include "sr_pack_tile.h"
 
 namespace {
 
@@ -157,34 +158,78 @@ int sr_ct_formulation(int ct_fft, int64_t ct_long_min_frames, int mode, int64_t 
     return SR_CT_FFT64;
 }
 
-int sr_ct_palmer_sums_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV,
-                              const int64_t *chunk_start_host, int mode, double *psum)
+int sr_ct_pack_fused(int formulation, int64_t F, int64_t series, int64_t tiles, int aligned)
 {
-    // ---- validate ----
-    SR_CHECK_CTX(ctx);
-    SR_REQUIRE(soa && psum, -2, "sr_ct_palmer_sums_f32_dev: null pointer");
-    SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1, -3, "sr_ct_palmer_sums_f32_dev: bad shape R=%lld F=%lld nV=%lld", (long long)R,
-               (long long)F, (long long)nV);
-    SR_REQUIRE(mode == 0 || mode == 1, -3, "sr_ct_palmer_sums_f32_dev: mode must be 0 or 1");
-    SR_REQUIRE(F <= SR_CT_LONG_MAX_FRAMES, -4, "sr_ct_palmer_sums_f32_dev: F=%lld frames per chunk; max F is %lld", (long long)F,
+    // k_ct_rfft32<12, true, true> is the one instantiation that carries a pack (sr_ct32.hip); a workgroup takes tiles b, b + series, ...:
+    // more than two each and the pack is no longer a passenger
+    return formulation == SR_CT_RFFT32 && F == 4096 && aligned != 0 && series >= 1 && tiles >= 1 && tiles <= 2 * series;
+}
+
+}  // extern "C"
+
+namespace {
+
+// what sr_ct_palmer_sums_f32_dev refuses, before anything is queued; *form: the formulation that runs
+int ct_sums_check(sr_ctx *ctx, const char *who, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV,
+                  const int64_t *chunk_start_host, int mode, const double *psum, int *form)
+{
+    SR_REQUIRE(soa && psum, -2, "%s: null pointer", who);
+    SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld", who, (long long)R, (long long)F, (long long)nV);
+    SR_REQUIRE(mode == 0 || mode == 1, -3, "%s: mode must be 0 or 1", who);
+    SR_REQUIRE(F <= SR_CT_LONG_MAX_FRAMES, -4, "%s: F=%lld frames per chunk; max F is %lld", who, (long long)F,
                (long long)SR_CT_LONG_MAX_FRAMES);
-    const int form = sr_ct_formulation(ctx->ct_fft, ctx->ct_long_min_frames, mode, F, (int64_t)sr_lds_limit(ctx));
-    SR_REQUIRE(form != SR_CT_REFUSED, -4,
-               "sr_ct_palmer_sums_f32_dev: F=%lld frames per chunk need %zu B of LDS (> %zu) in the direct kernel (mode 1 or ct_fft < 2), "
+    *form = sr_ct_formulation(ctx->ct_fft, ctx->ct_long_min_frames, mode, F, (int64_t)sr_lds_limit(ctx));
+    SR_REQUIRE(*form != SR_CT_REFUSED, -4,
+               "%s: F=%lld frames per chunk need %zu B of LDS (> %zu) in the direct kernel (mode 1 or ct_fft < 2), "
                "whose max F is %lld; the default dispatch takes up to %lld",
-               (long long)F, sr_ct_direct_lds_bytes(F), sr_lds_limit(ctx), (long long)sr_ct_direct_max_frames(sr_lds_limit(ctx)),
+               who, (long long)F, sr_ct_direct_lds_bytes(F), sr_lds_limit(ctx), (long long)sr_ct_direct_max_frames(sr_lds_limit(ctx)),
                (long long)SR_CT_LONG_MAX_FRAMES);
-    SR_REQUIRE(R * nV < (int64_t)1 << 30, -3, "sr_ct_palmer_sums_f32_dev: too many series");
+    SR_REQUIRE(R * nV < (int64_t)1 << 30, -3, "%s: too many series", who);
     if (chunk_start_host) {
         for (int64_t r = 0; r < R; ++r)
-            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= Npad, -3,
-                       "sr_ct_palmer_sums_f32_dev: chunk %lld start %lld out of range", (long long)r,
-                       (long long)chunk_start_host[r]);
+            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= Npad, -3, "%s: chunk %lld start %lld out of range", who,
+                       (long long)r, (long long)chunk_start_host[r]);
     } else {
-        SR_REQUIRE(R * F <= Npad, -3, "sr_ct_palmer_sums_f32_dev: R*F=%lld exceeds Npad=%lld", (long long)(R * F),
-                   (long long)Npad);
+        SR_REQUIRE(R * F <= Npad, -3, "%s: R*F=%lld exceeds Npad=%lld", who, (long long)(R * F), (long long)Npad);
     }
-    // ---- stage the chunk starts ----
+    return 0;
+}
+
+// sr_ct_pack_fused on a checked pair of jobs
+bool ct_carries(int form, const sr_ct_job &job, const sr_pack_job &next)
+{
+    const bool aligned = form == SR_CT_RFFT32 && sr_ct_rfft32_carries_pack(job) && (((uintptr_t)next.vecs | (uintptr_t)next.soa) & 15) == 0;
+    return sr_ct_pack_fused(form, job.F, job.series, next.tiles, aligned) != 0;
+}
+
+sr_pack_job ct_next_job(const float *next_vecs, int64_t next_N, int64_t next_Vtot, int64_t next_v0, int64_t next_nV, float *next_soa,
+                        int64_t next_Npad)
+{
+    const int64_t tiles = sr_pack_reg_tiles(next_Npad, next_Vtot, next_v0, next_nV);
+    return {next_vecs, next_soa, next_N, next_Vtot, next_v0, next_Npad, (int)((next_Npad + 127) / 128),
+            (int)(tiles < ((int64_t)1 << 30) ? tiles : 0)};
+}
+
+// what sr_ct_palmer_sums_pack_f32_dev refuses, before anything is queued
+int ct_sums_pack_check(sr_ctx *ctx, const char *who, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV,
+                       const int64_t *chunk_start_host, int mode, const double *psum, const float *next_vecs, int64_t next_N,
+                       int64_t next_Vtot, int64_t next_v0, int64_t next_nV, const float *next_soa, int64_t next_Npad, int *form)
+{
+    if (int rc = sr_pack_soa_check(who, next_vecs, next_N, next_Vtot, next_v0, next_nV, next_soa, next_Npad)) return rc;
+    if (int rc = ct_sums_check(ctx, who, soa, Npad, R, F, nV, chunk_start_host, mode, psum, form)) return rc;
+    // the planes written must not be the planes read (nor the raw sums): whichever kernel packs, this launch reads `soa` to its end
+    const uintptr_t s0 = (uintptr_t)soa, s1 = s0 + (size_t)(nV * 3 * Npad) * sizeof(float);
+    const uintptr_t d0 = (uintptr_t)next_soa, d1 = d0 + (size_t)(next_nV * 3 * next_Npad) * sizeof(float);
+    const uintptr_t p0 = (uintptr_t)psum, p1 = p0 + (size_t)(nV * R * sr_ct_psum_stride(F)) * sizeof(double);
+    SR_REQUIRE((d1 <= s0 || s1 <= d0) && (d1 <= p0 || p1 <= d0), -3, "%s: the next batch's planes overlap this batch's planes or sums", who);
+    return 0;
+}
+
+// stage the chunk starts and launch a checked job; `next` (optional): a pack for the same launch to carry when it can
+// (sr_ct_pack_fused), else kernel 0 runs in front of it on the same stream
+int ct_sums_launch(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV, const int64_t *chunk_start_host,
+                   int mode, double *psum, int form, const sr_pack_job *next, int64_t next_nV)
+{
     int64_t *cs_dev = nullptr;
     if (chunk_start_host) {
         cs_dev = (int64_t *)sr_workspace(ctx, SR_WS_MISC, (size_t)R * sizeof(int64_t));
@@ -192,8 +237,11 @@ int sr_ct_palmer_sums_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64
         SR_HIP(hipMemcpyAsync(cs_dev, chunk_start_host, (size_t)R * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
         SR_HIP(hipStreamSynchronize(ctx->stream));      // tiny table: the caller's array is free again when this returns
     }
-    // ---- launch ----
     const sr_ct_job job = {soa, Npad, chunk_start_host, cs_dev, psum, (int)R, (int)F, (int)(F / 2), (int)sr_ct_psum_stride(F), R * nV};
+    if (next) {
+        if (ct_carries(form, job, *next)) return sr_launch_ct_rfft32(ctx, job, next);
+        if (int rc = sr_pack_soa_f32_dev(ctx, next->vecs, next->N, next->Vtot, next->v0, next_nV, next->soa, next->Npad)) return rc;
+    }
     switch (form) {
         case SR_CT_DIRECT: return sr_launch_ct_direct(ctx, job, mode);
         case SR_CT_FFT64: return sr_launch_ct_fft64(ctx, job);
@@ -201,6 +249,45 @@ int sr_ct_palmer_sums_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64
         case SR_CT_RFFT32: return sr_launch_ct_rfft32(ctx, job);
         default: return sr_launch_ct_long(ctx, job);
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sr_ct_palmer_sums_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV,
+                              const int64_t *chunk_start_host, int mode, double *psum)
+{
+    SR_CHECK_CTX(ctx);
+    int form;
+    if (int rc = ct_sums_check(ctx, "sr_ct_palmer_sums_f32_dev", soa, Npad, R, F, nV, chunk_start_host, mode, psum, &form)) return rc;
+    return ct_sums_launch(ctx, soa, Npad, R, F, nV, chunk_start_host, mode, psum, form, nullptr, 0);
+}
+
+int sr_ct_palmer_sums_pack_f32_dev(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV,
+                                   const int64_t *chunk_start_host, int mode, double *psum, const float *next_vecs, int64_t next_N,
+                                   int64_t next_Vtot, int64_t next_v0, int64_t next_nV, float *next_soa, int64_t next_Npad)
+{
+    SR_CHECK_CTX(ctx);
+    int form;
+    if (int rc = ct_sums_pack_check(ctx, "sr_ct_palmer_sums_pack_f32_dev", soa, Npad, R, F, nV, chunk_start_host, mode, psum, next_vecs, next_N,
+                                    next_Vtot, next_v0, next_nV, next_soa, next_Npad, &form))
+        return rc;
+    const sr_pack_job next = ct_next_job(next_vecs, next_N, next_Vtot, next_v0, next_nV, next_soa, next_Npad);
+    return ct_sums_launch(ctx, soa, Npad, R, F, nV, chunk_start_host, mode, psum, form, &next, next_nV);
+}
+
+int sr_ct_palmer_sums_pack_plan(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t R, int64_t F, int64_t nV,
+                                const int64_t *chunk_start_host, int mode, const double *psum, const float *next_vecs, int64_t next_N,
+                                int64_t next_Vtot, int64_t next_v0, int64_t next_nV, const float *next_soa, int64_t next_Npad)
+{
+    SR_CHECK_CTX(ctx);
+    int form;
+    if (int rc = ct_sums_pack_check(ctx, "sr_ct_palmer_sums_pack_plan", soa, Npad, R, F, nV, chunk_start_host, mode, psum, next_vecs, next_N,
+                                    next_Vtot, next_v0, next_nV, next_soa, next_Npad, &form))
+        return rc;
+    const sr_ct_job job = {soa, Npad, chunk_start_host, nullptr, nullptr, (int)R, (int)F, (int)(F / 2), (int)sr_ct_psum_stride(F), R * nV};
+    return ct_carries(form, job, ct_next_job(next_vecs, next_N, next_Vtot, next_v0, next_nV, const_cast<float *>(next_soa), next_Npad)) ? 1 : 0;
 }
 
 int sr_ct_finalize_t_f64_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt,

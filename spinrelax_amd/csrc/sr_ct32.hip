@@ -62,7 +62,13 @@ namespace {
 #endif
 // FULL: the chunk fills the loaded input blocks exactly (F = 512 NZ) and frames 2m, 2m + 1 share an aligned 8 bytes: no
 // frame masks, 8-byte loads only (cfg3 / cfg4: F = 4096 with N1 = 12).
-template <int N1, bool FULL>
+// PACK: the launch also carries kernel 0 of a COMING batch (a.pk, an independent job on another plane buffer): workgroup b moves the
+// register tiles b, b + gridDim.x, ... of sr_pack_tile.h -- one per workgroup at cfg3 (12 288 series, 12 512 tiles).  The tile's loads
+// are issued behind the prologue's sample loads (vector-memory loads return in order: nothing of the workgroup's own waits for the
+// tile) and its stores leave between the prologue's steps, while a thread holds little but the samples; the bytes travel while the
+// transforms leave the memory system idle, and the pack needs no wave slot of its own beside this kernel's grids.  Alone the launch
+// takes 0.60 ms against 0.50 (k_pack_soa alone: 0.22); docs/EXPERIMENTS.md section 29.
+template <int N1, bool FULL, bool PACK = false>
 __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) void k_ct_rfft32(Ct32Args a)
 {
     extern __shared__ __align__(16) unsigned char f32_smem[];
@@ -128,9 +134,27 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
     {
         // ---- prologue: chunk means of the signals, eps = |u|^2 - 1, signal 0 ----
         c32 xr[NZ], yr[NZ], zr[NZ];
-        SR_F32_LOAD1(xr, 0, tid0)
-        SR_F32_LOAD1(yr, 1, tid0)
-        SR_F32_LOAD1NT(zr, 2, tid0)
+        sr_v4f pr[3][4];
+        int ptx = 0, pty = 0;
+        bool carried = false;
+        if constexpr (PACK) {
+            const int t0 = (int)blockIdx.x;
+            carried = t0 < a.pk.tiles;                          // workgroup-uniform
+            // tiles > series: a second tile, rarely -- first, while the thread holds nothing
+            for (int t = t0 + (int)gridDim.x; t < a.pk.tiles; t += (int)gridDim.x)
+                sr_pack_tile(a.pk.vecs, a.pk.N, a.pk.Vtot, a.pk.v0, a.pk.soa, a.pk.Npad, t % a.pk.tiles_x, t / a.pk.tiles_x);
+            ptx = t0 % a.pk.tiles_x, pty = t0 / a.pk.tiles_x;
+            // the samples first, the tile's twelve loads behind them: vector-memory loads return in order, and nothing the
+            // workgroup itself needs waits for the tile; its stores go out behind the sums below
+            SR_F32_LOAD1(xr, 0, tid0)
+            SR_F32_LOAD1(yr, 1, tid0)
+            SR_F32_LOAD1NT(zr, 2, tid0)
+            if (carried) sr_pack_tile_load<0, 2>(pr, a.pk.vecs, a.pk.N, a.pk.Vtot, a.pk.v0, ptx, pty);
+        } else {
+            SR_F32_LOAD1(xr, 0, tid0)
+            SR_F32_LOAD1(yr, 1, tid0)
+            SR_F32_LOAD1NT(zr, 2, tid0)
+        }
         c32 s0 = {0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0, s4 = s0, s5 = s0;
         float emax = 0.f;
 #pragma unroll
@@ -151,6 +175,12 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
         const float t0 = wave_total_f32(s0.x + s0.y), t1 = wave_total_f32(s1.x + s1.y), t2 = wave_total_f32(s2.x + s2.y);
         const float t3 = wave_total_f32(s3.x + s3.y), t4 = wave_total_f32(s4.x + s4.y), t5 = wave_total_f32(s5.x + s5.y);
         emax = wave_max_f32(emax);
+        if constexpr (PACK) {
+            if (carried) {
+                sr_pack_tile_store<0, 2>(pr, a.pk.N, a.pk.soa, a.pk.Npad, ptx, pty);
+                sr_pack_tile_load<2, 3>(pr, a.pk.vecs, a.pk.N, a.pk.Vtot, a.pk.v0, ptx, pty);
+            }
+        }
         if ((tid0 & 63) == 63) {
             float *o = aux + 8 * (tid0 >> 6);
             o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3; o[4] = t4; o[5] = t5; o[6] = emax;
@@ -187,6 +217,9 @@ __global__ __launch_bounds__(256, (N1 == 16 ? SR_CT32_WAVES16 : SR_CT32_WAVES)) 
             c32 d = f32_sig0(xr[n1], yr[n1], zr[n1], m[0]);
             SR_F32_MASK(d.x, d.y, tid0, n1)
             sig[n1] = d;
+        }
+        if constexpr (PACK) {
+            if (carried) sr_pack_tile_store<2, 3>(pr, a.pk.N, a.pk.soa, a.pk.Npad, ptx, pty);
         }
     }
     // power spectrum by pairs of frequencies (k, H - k), see k_ct_rfft: W2[q] = (P[k], P[H - k]) for the thread's k with k2b = q
@@ -445,7 +478,7 @@ constexpr size_t f32_lds_bytes()
     return (size_t)(rfft_img_slots(N1) + 256 + 1024 + 256) * sizeof(c32) + 64 * sizeof(float);
 }
 
-template <int N1, bool FULL>
+template <int N1, bool FULL, bool PACK = false>
 int launch_ct_rfft32_h(sr_ctx *ctx, const Ct32Args &a, int64_t series)
 {
     size_t lds = f32_lds_bytes<N1>();
@@ -460,7 +493,7 @@ int launch_ct_rfft32_h(sr_ctx *ctx, const Ct32Args &a, int64_t series)
     constexpr size_t Fmax = N1 == 4 ? 1365 : (N1 == 8 ? 2730 : (N1 == 12 ? 4096 : 5461));
     static_assert((size_t)rfft_img_slots(N1) * sizeof(c32) >= (Fmax + 3) * 4, "k_ct_rfft32: E does not fit the image");
     static_assert((size_t)rfft_img_slots(N1) * sizeof(c32) >= (Fmax / 2 + 2) * 8, "k_ct_rfft32: Tt does not fit the image");
-    return sr_launch(ctx, k_ct_rfft32<N1, FULL>, dim3((unsigned)series), dim3(256), lds, a);
+    return sr_launch(ctx, k_ct_rfft32<N1, FULL, PACK>, dim3((unsigned)series), dim3(256), lds, a);
 }
 
 }  // namespace
@@ -484,17 +517,29 @@ const void *sr_ct32_tables(sr_ctx *ctx)
 // ITS TEXT FILES -- _Ctint.dat keeps 8 digits -- reproduces the reference's printed digits only with float64 C(t); with float32 C(t) one
 // of 16 cfg2 residues lands 1.1e-6 from the reference's through-files table, tests/test_gpu_cli.py.)  Of the chunk starts, the host copy is
 // what decides the aligned fast path, the device copy is what the kernel reads.
-int sr_launch_ct_rfft32(sr_ctx *ctx, const sr_ct_job &j)
+// `pk` (optional): the next batch's pack, carried by this launch -- only for a job that sr_ct_rfft32_carries_pack() admits (the
+// caller asks first; anything else is refused here, -3, and nothing is queued).
+static bool f32_aligned(const sr_ct_job &j)
 {
+    bool aligned = (j.Npad & 1) == 0 && (j.F & 1) == 0 && (((uintptr_t)j.soa) & 7) == 0;
+    if (j.cs_host)
+        for (int r = 0; r < j.R; ++r) aligned = aligned && (j.cs_host[r] & 1) == 0;
+    return aligned;
+}
+
+bool sr_ct_rfft32_carries_pack(const sr_ct_job &j) { return j.F == 4096 && f32_aligned(j); }     // k_ct_rfft32<12, true, true>
+
+int sr_launch_ct_rfft32(sr_ctx *ctx, const sr_ct_job &j, const sr_pack_job *pk)
+{
+    SR_REQUIRE(!pk || sr_ct_rfft32_carries_pack(j), -3, "k_ct_rfft32: no instantiation carries a pack at F=%d", j.F);
     const Ct32Tab *tab = (const Ct32Tab *)sr_ct32_tables(ctx);
     if (!tab) return -5;
     const int F = j.F;
     Ct32Args a;
     a.soa = j.soa; a.Npad = j.Npad; a.chunk_start = j.cs_dev; a.psum = j.psum;
     a.R = j.R; a.F = F; a.L = j.L; a.Lp = j.Lp;
-    bool aligned = (j.Npad & 1) == 0 && (F & 1) == 0 && (((uintptr_t)j.soa) & 7) == 0;
-    if (j.cs_host)
-        for (int r = 0; r < j.R; ++r) aligned = aligned && (j.cs_host[r] & 1) == 0;
+    a.pk = pk ? *pk : sr_pack_job{nullptr, nullptr, 0, 0, 0, 0, 1, 0};
+    const bool aligned = f32_aligned(j);
     const int need = F + j.L;
     SR_REQUIRE(need > 1024 && need <= 8192, -3, "k_ct_rfft32: F=%d outside the transform lengths", F);
     if (need <= 2048) {
@@ -507,6 +552,7 @@ int sr_launch_ct_rfft32(sr_ctx *ctx, const sr_ct_job &j)
     }
     if (need <= 6144) {
         a.tab = tab + f32_tab_set(12);
+        if (pk) return launch_ct_rfft32_h<12, true, true>(ctx, a, j.series);
         return aligned && F == 4096 ? launch_ct_rfft32_h<12, true>(ctx, a, j.series) : launch_ct_rfft32_h<12, false>(ctx, a, j.series);
     }
     a.tab = tab + f32_tab_set(16);

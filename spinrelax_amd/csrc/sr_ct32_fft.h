@@ -4,6 +4,7 @@
 // size and wave scans: sr_fft_common.h.
 #pragma once
 #include "sr_fft_common.h"
+#include "sr_pack_tile.h"
 
 namespace {
 
@@ -296,6 +297,7 @@ struct Ct32Args {
     const Ct32Tab *tab;
     double *psum;                 // (nV, R, Lp)
     int R, F, L, Lp;
+    sr_pack_job pk;               // k_ct_rfft32<.., .., true> only: the next batch's pack, carried by this launch (sr_pack_tile.h)
 };
 
 #ifdef SR_CT32_STAMPS           // development: s_memtime stamps around the phases of a pass, summed per wave, left behind lag L of the

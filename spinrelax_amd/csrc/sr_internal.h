@@ -175,8 +175,13 @@ int sr_ct_dipolar_cross_norm_dev(sr_ctx *ctx, const double *wsum2, int64_t R, in
 int sr_ired_mode_ct_check(const char *who, int64_t frames, int64_t nV, const int64_t *win_start_host, const int64_t *win_len_host, int W, int K,
                           int n_lags);
 
-// sr_ct32.hip: float32 real-input transforms in LDS (k_ct_rfft32: 1024 < F + L <= 8192)
-int sr_launch_ct_rfft32(sr_ctx *ctx, const sr_ct_job &job);
+// sr_ct32.hip: float32 real-input transforms in LDS (k_ct_rfft32: 1024 < F + L <= 8192).  With `pk` the launch also carries the pack of
+// the next batch (sr_pack_tile.h), which only the cfg3 / cfg4 instantiation does: ask sr_ct_rfft32_carries_pack(job) first
+struct sr_pack_job;
+int sr_launch_ct_rfft32(sr_ctx *ctx, const sr_ct_job &job, const sr_pack_job *pk = nullptr);
+bool sr_ct_rfft32_carries_pack(const sr_ct_job &job);
+// sr_pack.hip: what sr_pack_soa_f32_dev refuses (null pointers -2, shapes -3), before anything is queued
+int sr_pack_soa_check(const char *who, const float *vecs, int64_t N, int64_t Vtot, int64_t v0, int64_t nV, const float *soa, int64_t Npad);
 
 // the device tables of the float32 transforms (Ct32Tab[4], sr_ct32_fft.h), created on first use; NULL (error set) on failure
 const void *sr_ct32_tables(sr_ctx *ctx);

@@ -2,14 +2,14 @@
 // form of kernel 1 (sr_ct.hip) and the histogram kernels read.  Three kernels: whole 32-vector tiles in registers (production),
 // any shape through an LDS tile, and the LDS tile with the per-frame de-tumbling rotation folded in.
 #include "sr_internal.h"
+#include "sr_pack_tile.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------
 // kernel 0: (N, Vtot, 3) float32 -> planes soa[(v*3+c)*Npad + n], zero for n in [N, Npad)
 // ------------------------------------------------------------------------------------------
-constexpr int kPackFrames = 64;
-constexpr int kPackVecs = 32;
+constexpr int kPackFrames = 64;          // (kPackVecs = 32, kPackRegFrames = 128: sr_pack_tile.h)
 
 // The general form (any number of vectors, any alignment): a 64-frame x 32-vector tile transposed through LDS.
 // 16-byte accesses on both sides when it can: a frame's 32 vectors are 96 consecutive floats (24 float4 when the row start is
@@ -67,44 +67,10 @@ __global__ __launch_bounds__(256) void k_pack_soa_ragged(const float *__restrict
 // benchmark 2.27-2.32 against 2.35-2.38 ms per step.  The LDS tile's scattered 4-byte LDS writes and its 54 instructions per 16
 // bytes were what the C(t) waves on the same CU paid for.  (An LDS-DMA fill of the same tile: no gain; 16 or 4 columns per wave,
 // temporal accesses, four loads in flight instead of twelve: worse or equal.)
-constexpr int kPackRegFrames = 128;
 __global__ __launch_bounds__(256) void k_pack_soa(const float *__restrict__ vecs, int64_t N, int64_t Vtot,
                                                   int64_t v0, int64_t nV, float *__restrict__ soa, int64_t Npad)
 {
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    const int64_t n0 = (int64_t)blockIdx.x * kPackRegFrames;
-    const int64_t vb = (int64_t)blockIdx.y * kPackVecs;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ql = lane & 7, gl = lane >> 3;
-    v4f r[3][4];
-#pragma unroll
-    for (int it = 0; it < 3; ++it) {
-        const int blk = it * 4 + wave;                        // 12 wave-blocks: 3 column groups x 4 groups of 8 frame groups
-        const int q = (blk % 3) * 8 + ql;                     // 16-byte column of the 96-float row
-        const int64_t fr = n0 + 4 * ((blk / 3) * 8 + gl);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                         // no branch around a load: past the end, frame N - 1 again
-            const int64_t f = min(fr + j, N - 1);
-            r[it][j] = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(vecs + (f * Vtot + v0 + vb) * 3 + 4 * q));
-        }
-    }
-#pragma unroll
-    for (int it = 0; it < 3; ++it) {
-        const int blk = it * 4 + wave;
-        const int q = (blk % 3) * 8 + ql;
-        const int64_t fr = n0 + 4 * ((blk / 3) * 8 + gl);
-        if (fr >= Npad) continue;                             // Npad % 4 == 0: a frame group is inside the planes or outside
-        if (fr + 3 >= N) {                                    // frames in [N, Npad): zeros
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (fr + j >= N) r[it][j] = v4f{0.f, 0.f, 0.f, 0.f};
-        }
-        float *o = soa + (vb * 3 + 4 * q) * Npad + fr;
-        __builtin_nontemporal_store(v4f{r[it][0].x, r[it][1].x, r[it][2].x, r[it][3].x}, reinterpret_cast<v4f *>(o));
-        __builtin_nontemporal_store(v4f{r[it][0].y, r[it][1].y, r[it][2].y, r[it][3].y}, reinterpret_cast<v4f *>(o + Npad));
-        __builtin_nontemporal_store(v4f{r[it][0].z, r[it][1].z, r[it][2].z, r[it][3].z}, reinterpret_cast<v4f *>(o + 2 * Npad));
-        __builtin_nontemporal_store(v4f{r[it][0].w, r[it][1].w, r[it][2].w, r[it][3].w}, reinterpret_cast<v4f *>(o + 3 * Npad));
-    }
+    sr_pack_tile(vecs, N, Vtot, v0, soa, Npad, blockIdx.x, blockIdx.y);      // sr_pack_tile.h: shared with k_ct_rfft32's carried pack
 }
 
 // The same transposition with the de-tumbling folded in: every frame's vectors are rotated by that frame's unit
@@ -153,22 +119,34 @@ __global__ __launch_bounds__(256) void k_pack_soa_rot(const float *__restrict__ 
 
 }  // namespace
 
+// what sr_pack_soa_f32_dev refuses, before anything is queued (shared with sr_ct_palmer_sums_pack_f32_dev, sr_ct.hip)
+int sr_pack_soa_check(const char *who, const float *vecs, int64_t N, int64_t Vtot, int64_t v0, int64_t nV, const float *soa, int64_t Npad)
+{
+    SR_REQUIRE(vecs && soa, -2, "%s: null pointer", who);
+    SR_REQUIRE(N > 0 && Vtot > 0 && nV > 0 && v0 >= 0 && v0 + nV <= Vtot, -3, "%s: bad shape N=%lld Vtot=%lld v0=%lld nV=%lld", who,
+               (long long)N, (long long)Vtot, (long long)v0, (long long)nV);
+    SR_REQUIRE(Npad >= N && Npad % 4 == 0, -3, "%s: Npad=%lld must be >= N and a multiple of 4", who, (long long)Npad);
+    SR_REQUIRE((nV + kPackVecs - 1) / kPackVecs <= 65535, -3, "%s: too many vectors in one call (%lld)", who, (long long)nV);
+    return 0;
+}
+
 extern "C" {
+
+int64_t sr_pack_reg_tiles(int64_t Npad, int64_t Vtot, int64_t v0, int64_t nV)
+{
+    if (Npad < 4 || (Npad & 3) || Vtot < 1 || v0 < 0 || nV < 1 || v0 + nV > Vtot) return 0;
+    if (nV % kPackVecs != 0 || ((Vtot * 3) & 3) != 0 || ((v0 * 3) & 3) != 0) return 0;
+    return ((Npad + kPackRegFrames - 1) / kPackRegFrames) * (nV / kPackVecs);
+}
 
 int sr_pack_soa_f32_dev(sr_ctx *ctx, const float *vecs, int64_t N, int64_t Vtot, int64_t v0, int64_t nV,
                         float *soa, int64_t Npad)
 {
     SR_CHECK_CTX(ctx);
-    SR_REQUIRE(vecs && soa, -2, "sr_pack_soa_f32_dev: null pointer");
-    SR_REQUIRE(N > 0 && Vtot > 0 && nV > 0 && v0 >= 0 && v0 + nV <= Vtot, -3,
-               "sr_pack_soa_f32_dev: bad shape N=%lld Vtot=%lld v0=%lld nV=%lld", (long long)N, (long long)Vtot,
-               (long long)v0, (long long)nV);
-    SR_REQUIRE(Npad >= N && Npad % 4 == 0, -3, "sr_pack_soa_f32_dev: Npad=%lld must be >= N and a multiple of 4",
-               (long long)Npad);
+    if (int rc = sr_pack_soa_check("sr_pack_soa_f32_dev", vecs, N, Vtot, v0, nV, soa, Npad)) return rc;
     const int64_t gx = (Npad + kPackFrames - 1) / kPackFrames;
     const int64_t gy = (nV + kPackVecs - 1) / kPackVecs;
-    SR_REQUIRE(gy <= 65535, -3, "sr_pack_soa_f32_dev: too many vectors in one call (%lld)", (long long)nV);
-    if (nV % kPackVecs == 0 && ((Vtot * 3) & 3) == 0 && ((v0 * 3) & 3) == 0 && (((uintptr_t)vecs | (uintptr_t)soa) & 15) == 0)
+    if (sr_pack_reg_tiles(Npad, Vtot, v0, nV) > 0 && (((uintptr_t)vecs | (uintptr_t)soa) & 15) == 0)
         hipLaunchKernelGGL(k_pack_soa, dim3((unsigned)((Npad + kPackRegFrames - 1) / kPackRegFrames), (unsigned)gy), dim3(256), 0,
                            ctx->stream, vecs, N, Vtot, v0, nV, soa, Npad);
     else

@@ -57,6 +57,18 @@ def vechist_plan(N, nV, block_len=0):
     return dict(Fb=Fb.value, nB=nB.value, m=m.value, sub=sub.value, nranges=nranges.value)
 
 
+def pack_reg_tiles(Npad, Vtot, v0, nV):
+    """register tiles of kernel 0's production form for a shape, 0 when the shape takes the LDS tile (sr_pack_reg_tiles: a host
+    function, no Context and no GPU)"""
+    return int(_lib.load().sr_pack_reg_tiles(int(Npad), int(Vtot), int(v0), int(nV)))
+
+
+def ct_pack_fused(formulation, F, series, tiles, aligned=True):
+    """whether Context.ct_sums_pack_dev carries the pack inside the C(t) launch (sr_ct_pack_fused: a host function, no Context and
+    no GPU)"""
+    return bool(_lib.load().sr_ct_pack_fused(int(formulation), int(F), int(series), int(tiles), 1 if aligned else 0))
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = _lib.load()
@@ -187,6 +199,26 @@ class Context:
         cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
         check(self.lib.sr_ct_palmer_sums_f32_dev(self.h, soa_ptr, Npad, R, F, nV, None if cs is None else _ptr(cs), mode, psum_ptr),
               'sr_ct_palmer_sums_f32_dev')
+
+    def ct_sums_pack_dev(self, soa_ptr, Npad, R, F, nV, psum_ptr, next_vecs_ptr, next_N, next_Vtot, next_v0, next_nV, next_soa_ptr,
+                         next_Npad, chunk_start=None, mode=0):
+        """ct_sums_dev, and pack_soa_dev of the next batch (another plane buffer) with it: one launch when the library can carry
+        the pack inside the C(t) kernel (ct_pack_fused), else the pack in front of the C(t) kernel on the same stream"""
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        check(self.lib.sr_ct_palmer_sums_pack_f32_dev(self.h, soa_ptr, Npad, R, F, nV, None if cs is None else _ptr(cs), mode, psum_ptr,
+                                                      next_vecs_ptr, next_N, next_Vtot, next_v0, next_nV, next_soa_ptr, next_Npad),
+              'sr_ct_palmer_sums_pack_f32_dev')
+
+    def ct_sums_pack_plan(self, soa_ptr, Npad, R, F, nV, psum_ptr, next_vecs_ptr, next_N, next_Vtot, next_v0, next_nV, next_soa_ptr,
+                          next_Npad, chunk_start=None, mode=0):
+        """what ct_sums_pack_dev would do with these arguments, nothing queued: True = one launch carries the pack, False = the pack
+        in front of the C(t) kernel; a refusal raises"""
+        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        rc = self.lib.sr_ct_palmer_sums_pack_plan(self.h, soa_ptr, Npad, R, F, nV, None if cs is None else _ptr(cs), mode, psum_ptr,
+                                                  next_vecs_ptr, next_N, next_Vtot, next_v0, next_nV, next_soa_ptr, next_Npad)
+        if rc < 0:
+            check(rc, 'sr_ct_palmer_sums_pack_plan')
+        return rc == 1
 
     def ct_finalize_dev(self, psum_ptr, R, F, nV, Ct_ptr, dCt_ptr, CtT_ptr=None, dCtT_ptr=None):
         """mean / std over the chunks; with CtT_ptr / dCtT_ptr the same launch also writes the (nV, L) copies the fits read"""

@@ -58,6 +58,10 @@ from . import _hostmath as hm
 from . import spectral_densities as sd
 from .hip import SpinRelaxHipError
 
+# Default of the pipelines' keyword `fused_pack`: the C(t) launches carry the packs of coming batches.  On since it measured faster than
+# the pack on its own stream at 20 steps, 100 steps and in steady state (docs/EXPERIMENTS.md section 29).
+FUSED_PACK_DEFAULT = True
+
 
 # ======================================================================================================================
 # Pure host functions (tests/test_pipeline_hostlogic.py)
@@ -330,12 +334,19 @@ class _Group:
 
 class _PlaneRing:
     """The plane buffers and who may touch them when.  Batch k lives in buffer k % NB: the pack writes it on the auxiliary
-    stream, the C(t) kernel and the histogram read it on theirs.  `packed`, `ct_done`, `hist_done` hold per buffer the
-    event of the last such launch; `ahead` says that the coming batch has been packed already."""
+    stream or inside an earlier C(t) launch, the C(t) kernel and the histogram read it on theirs.  `packed`, `ct_done`, `hist_done` hold per buffer the
+    event of the last such launch; `ahead` holds the coming batches that have been packed already; `nb` is the length of the run
+    in progress (None outside one).  `reach`: how far ahead a C(t) launch packs (pack_in_ct)."""
 
     def __init__(self, pipe, bufs):
         self.pipe, self.bufs, self.NB = pipe, bufs, len(bufs)
-        self.ahead = False
+        self.ahead = set()
+        self.nb = None
+        # A C(t) launch that carries a pack delivers it when the LAUNCH is over.  Packing batch k + 1, the next launch -- on the
+        # other C(t) stream -- could not start before this one has ended, and the two no longer overlap.  So it packs batch k + 2,
+        # the next launch of its OWN stream, which runs behind it anyway; the buffer of batch k + 2 must then not be the one batch
+        # k - 1 may still be read from: four buffers.  With fewer, batch k + 1.
+        self.reach = 2 if self.NB >= 4 else 1
         self.clear()
 
     def clear(self):
@@ -349,7 +360,8 @@ class _PlaneRing:
         device tensor (frames, Vtot, 3), or a FEED -- an object with acquire(k, stream) -> object with data_ptr() / shape of
         that batch's device array (the feed makes `stream` wait until the frames are there) and release(k, stream) (called
         once the pack has been queued: the feed may refill the buffer when `stream` has passed that point).  bench.py's
-        PinnedFeed streams every batch from host memory."""
+        PinnedFeed streams every batch from host memory.  A feed is asked for its batches in order; one that also has an attribute
+        V (vectors per frame of its arrays) lets a C(t) launch carry its packs (pack_in_ct)."""
         pipe, aux, b = self.pipe, self.pipe.aux, k % self.NB
         for ev in (self.ct_done[b], self.hist_done[b]):
             if ev is not None:
@@ -365,17 +377,42 @@ class _PlaneRing:
 
     def pack_now(self, vecs, k):
         """batch k, unless it was packed ahead (the first batch of a run was not)"""
-        if not self.ahead:
+        if k not in self.ahead:
             aux = self.pipe.aux
             self.pipe.ctx.set_stream(aux.cuda_stream)
             with torch.cuda.stream(aux):
                 self._pack(vecs, k)
-        self.ahead = False
+        self.ahead.discard(k)
 
     def pack_ahead(self, vecs, k):
         """batch k + 1 beside the C(t) launch of batch k; the caller has the context on the auxiliary stream"""
         self._pack(vecs, k + 1)
-        self.ahead = True
+        self.ahead.add(k + 1)
+
+    def carries(self, k):
+        """the batch a pack-carrying C(t) launch of batch k would pack, None when the run ends before it"""
+        t = k + self.reach
+        return t if (self.reach == 1 or (self.nb is not None and t < self.nb)) else None
+
+    def pack_in_ct(self, vecs, k, stream, launch):
+        """batch t = k + reach is packed by the C(t) launch of batch k on `stream` (the library carries kernel 0 inside that launch:
+        Context.ct_sums_pack_dev).  `stream` waits for the readers of batch t - NB, the feed hands the frames over on `stream`,
+        `launch(src, dst)` queues the one launch -- the caller's, with its timing events around the kernel alone -- and the
+        planes are there when it has finished."""
+        t = k + self.reach
+        b = t % self.NB
+        for ev in (self.ct_done[b], self.hist_done[b]):
+            if ev is not None:
+                stream.wait_event(ev)
+        if hasattr(vecs, 'acquire'):
+            src = vecs.acquire(t, stream)
+            self.pipe.ctx.set_stream(stream.cuda_stream)       # the feed drives the context from its own stream
+            launch(src, self.bufs[b])
+            vecs.release(t, stream)
+        else:
+            launch(vecs, self.bufs[b])
+        self.packed[b] = _event(stream)
+        self.ahead.add(t)
 
     def wait_packed(self, stream, k):
         stream.wait_event(self.packed[k % self.NB])
@@ -397,8 +434,10 @@ class _Pipeline:
     def __init__(self, ctx, device, frames, V, R, F, dt, q_rot=None, Diso=None, aniso=None, field_MHz=(600.133,),
                  zeta=0.890023, histBinX=72, listDoG=(2, 3, 5, 7, 9), csa=None, depth=1, stream=None, reserve_cus=0,
                  fits_on_reserved_only=False, chiSqThreshold=0.5, q_orient=None, hist_on_aux=True, v0=0, aux_cus=0, fit_priority=0, plane_buffers=3,
-                 pack_cus=0, batch_streams=0):
+                 pack_cus=0, batch_streams=0, fused_pack=None):
         self._closed = False
+        self.fused_pack = bool(FUSED_PACK_DEFAULT if fused_pack is None else fused_pack)   # a C(t) launch carries the pack of a coming batch (_PlaneRing.pack_in_ct)
+        self._fuse_plan = {}
         self.ctx = ctx
         self.dev = device
         self.frames, self.V, self.R, self.F, self.dt = frames, V, R, F, dt
@@ -457,7 +496,10 @@ class _Pipeline:
         # (three plane buffers: the pack of batch k+1 only needs the C(t) launch of batch k-2 to be done, so it is off the
         # critical path of two C(t) launches that overlap each other)
         self.NB = max(2, int(plane_buffers)) if self.depth > 1 else 1
-        self.ring = _PlaneRing(self, [self.soa] + [torch.empty_like(self.soa) for _ in range(self.NB - 1)])
+        # (`fused_pack`: a batch packed by a C(t) launch holds its buffer from that launch's start -- the ring gets one buffer more
+        # than the NB asked for)
+        self.ring = _PlaneRing(self, [self.soa] + [torch.empty_like(self.soa)
+                                                   for _ in range(self.NB - 1 + (1 if self.fused_pack and self.depth > 1 else 0))])
         # `pack_cus`: the auxiliary stream (the pack kernel, per-batch histograms) confined to this many CUs while the compute
         # streams keep the whole chip.  The pack is HBM-bound and hardly issues (83 % of its waves' lifetime parked); spread
         # over all 256 CUs its waves sit beside every C(t) workgroup pair (16 + 2 x 248 VGPRs fill a SIMD exactly) and its
@@ -587,6 +629,47 @@ class _Pipeline:
         if finalize:
             self.stage_ct_finalize(s)
 
+    def _carries_pack(self, vecs, soa, psum, k):
+        """whether the C(t) launch of batch k (planes `soa`) carries the pack of a coming batch (`fused_pack`): not the de-tumbling
+        pack, and only what the library does in ONE launch -- anything else keeps the stand-alone pack on the auxiliary stream"""
+        if not self.fused_pack or vecs is None or self.aux is None or self.quat_dev is not None or self.ring.carries(k) is None:
+            return False
+        dst = self.ring.buf(self.ring.carries(k))
+        if hasattr(vecs, 'acquire'):
+            # a feed's array exists once acquired: its row length must be known before (attribute V), and for the question asked
+            # here a 16-byte aligned stand-in takes the array's place -- the library checks the real one at the launch and packs in
+            # front of the C(t) kernel, on the same stream, should it not be aligned
+            Vtot, src_ptr = getattr(vecs, 'V', None), dst.data_ptr()
+            if Vtot is None:
+                return False
+        else:
+            Vtot, src_ptr = vecs.shape[1], vecs.data_ptr()
+        key = (src_ptr, Vtot, soa.data_ptr(), dst.data_ptr())
+        if key not in self._fuse_plan:
+            self._fuse_plan[key] = self.ctx.ct_sums_pack_plan(soa.data_ptr(), self.Npad, self.R, self.F, self.V, psum.data_ptr(),
+                                                              src_ptr, self.frames, Vtot, self.v0, self.V, dst.data_ptr(), self.Npad)
+        return self._fuse_plan[key]
+
+    def _pack_between(self, vecs, k, carried):
+        """the C(t) launch of batch k is about to carry the pack of batch k + 2 and nobody has packed batch k + 1 (a run's second
+        batch): that one first, on the auxiliary stream -- a feed is asked for its batches in order"""
+        if carried and self.ring.carries(k) != k + 1 and k + 1 not in self.ring.ahead:
+            self.ctx.set_stream(self.aux.cuda_stream)
+            with torch.cuda.stream(self.aux):
+                self.ring.pack_ahead(vecs, k)
+
+    def _ct_launch(self, soa, psum, events, stream):
+        """launch(src, dst) for _PlaneRing.pack_in_ct, launch() for the C(t) kernel alone: events [0], [1] around the kernel"""
+        def launch(src=None, dst=None):
+            _stamp(events, 0, stream)
+            if src is None:
+                self.ctx.ct_sums_dev(soa.data_ptr(), self.Npad, self.R, self.F, self.V, psum.data_ptr())
+            else:
+                self.ctx.ct_sums_pack_dev(soa.data_ptr(), self.Npad, self.R, self.F, self.V, psum.data_ptr(),
+                                          src.data_ptr(), self.frames, src.shape[1], self.v0, self.V, dst.data_ptr(), self.Npad)
+            _stamp(events, 1, stream)
+        return launch
+
     def stage_ct_finalize(self, s=None):
         """mean / std over the chunks, written in both orientations by one launch: (L, V) as the reference holds C(t) and
         (V, L) for the fits (stage_transpose is only needed behind a finalize that did not write them)"""
@@ -703,6 +786,8 @@ class DevicePipeline(_Pipeline):
         ring = self.ring
         buf = ring.buf(k)
         ring.pack_now(vecs, k)
+        carried = self._carries_pack(pack_next, buf, s.psum, k)
+        self._pack_between(pack_next, k, carried)
         prev_done = s.done if s.busy else None       # the batch that used this slot `depth` batches ago, if still in flight
         main = self.main_alt if (k % 2 == 1 and self.main_alt is not None) else self.main
         # the histogram may have to wait for the batch that used this slot before (its relaxation kernel reads the slot's
@@ -722,8 +807,11 @@ class DevicePipeline(_Pipeline):
             ring.wait_packed(main, k)
             if s.busy and s.psum_free is not None:
                 main.wait_event(s.psum_free)         # its raw sums are the only thing of that batch this kernel overwrites
-            _stamp(events, 0, main)
-            self.stage_ct(s, buf, mid_event=None if events is None else events[1], finalize=False)
+            launch = self._ct_launch(buf, s.psum, events, main)
+            if carried:
+                ring.pack_in_ct(pack_next, k, main, launch)
+            else:
+                launch()
             if not self.hist_on_aux:
                 hist()
             ring.ct_done_with(k, main)
@@ -732,11 +820,12 @@ class DevicePipeline(_Pipeline):
         self.ctx.set_stream(self.aux.cuda_stream)
         with torch.cuda.stream(self.aux):
             # the pack of batch k+1 first: the next C(t) launch waits for nothing else
-            if pack_next is not None:
+            if pack_next is not None and k + 1 not in ring.ahead:
                 ring.pack_ahead(pack_next, k)
             if self.hist_on_aux:
+                ring.wait_packed(self.aux, k)       # this batch's planes may have come with a C(t) launch, not down this stream
                 hist()
-                s.hist_done = _event(self.aux)
+                s.hist_done = ring.hist_done[k % ring.NB] = _event(self.aux)      # (a pack carried by a C(t) launch waits for it)
         self.ctx.set_stream(self.main.cuda_stream)
         return s
 
@@ -786,6 +875,7 @@ class DevicePipeline(_Pipeline):
         of batch k + depth is already queued when on_finished(slot) runs for batch k: the host copies -- slot.result, and
         C(t) / dC(t) in HBM -- are still batch k's, the slot's histogram in HBM may already be the next batch's.)"""
         D = self.depth
+        self.ring.nb = nb
 
         def finish(s):
             if s.busy:
@@ -806,6 +896,7 @@ class DevicePipeline(_Pipeline):
                 s.guard = on_enqueued(s)
         for k in range(max(0, nb - D), nb):
             finish(self.slots[k % D])
+        self.ring.nb = None
         self.ctx.set_stream(self.main.cuda_stream)
 
     def prime(self, vecs):
@@ -974,6 +1065,8 @@ class GroupedPipeline(_Pipeline):
         pi = kk % self.NP
         bv.psum = self.psums[pi]
         ring.pack_now(vecs, kk)
+        carried = self._carries_pack(pack_next, buf, bv.psum, kk)
+        self._pack_between(pack_next, kk, carried)
         main = self.main_alt if (kk % 2 == 1 and self.main_alt is not None) else self.main
         self.ctx.set_stream(main.cuda_stream)
         with torch.cuda.stream(main):
@@ -982,12 +1075,14 @@ class GroupedPipeline(_Pipeline):
                 main.wait_event(self._psum_free[pi])      # the chunk statistics of batch kk - NP have read these raw sums
             if j < 2 and not self.overlap and self._prev_done is not None:
                 main.wait_event(self._prev_done)          # strict phases: the previous group's merged launch has finished (both C(t) streams)
-            _stamp(events, 0, main)
             # (Offsetting the two C(t) streams by half a launch -- first launch of a run in two halves, the second stream waiting
             # for the first half -- was measured: the launches then alternate perfectly, 1.25 ms apart, and the group's C(t) phase
             # takes exactly as long as in lockstep: the phase is bound by the kernels' own time, not by coinciding tails.)
-            self.ctx.ct_sums_dev(buf.data_ptr(), self.Npad, self.R, self.F, self.V, bv.psum.data_ptr())
-            _stamp(events, 1, main)
+            launch = self._ct_launch(buf, bv.psum, events, main)
+            if carried:
+                ring.pack_in_ct(pack_next, kk, main, launch)
+            else:
+                launch()
             ct_ev = ring.ct_done_with(kk, main)
         tail = self.tail          # (chunk statistics spread over 3 or 5 streams: measured, no difference)
         self.ctx.set_stream(tail.cuda_stream)
@@ -1001,8 +1096,9 @@ class GroupedPipeline(_Pipeline):
                 self._on_part('ct', bv, ev)          # C(t), dC(t) of this batch are final once `ev` has passed
         self.ctx.set_stream(self.aux.cuda_stream)
         with torch.cuda.stream(self.aux):
-            if pack_next is not None:
+            if pack_next is not None and kk + 1 not in ring.ahead:
                 ring.pack_ahead(pack_next, kk)
+            ring.wait_packed(self.aux, kk)          # this batch's planes may have come with a C(t) launch, not down this stream
             if j == 0 and grp.guard is not None:
                 self.aux.wait_event(grp.guard)
             if self.late_hist:
@@ -1013,6 +1109,8 @@ class GroupedPipeline(_Pipeline):
                     self.stage_hist(bv, buf)
                 _stamp(events, 3, self.aux)
             self._last_hist = ev = _event(self.aux)
+            if not self.late_hist:
+                ring.hist_done[kk % ring.NB] = ev         # a pack carried by a C(t) launch is not behind it in stream order
             if self._on_part is not None and not self.late_hist:
                 self._on_part('hist', bv, ev)
         self.ctx.set_stream(self.main.cuda_stream)
@@ -1108,6 +1206,7 @@ class GroupedPipeline(_Pipeline):
         recorded around the merged launch on the entry of the group's FIRST batch.  `vecs`: a device tensor or a feed object
         (_PlaneRing._pack)."""
         self._on_part = on_part
+        self.ring.nb = nb
         k, gi = 0, self._nbatch
         pending = []
         sizes = list(self.group_sizes(nb))
@@ -1131,6 +1230,7 @@ class GroupedPipeline(_Pipeline):
         for grp in pending:
             self.collect(grp, on_finished)
         self._on_part = None
+        self.ring.nb = None
         self._nbatch = gi
         self.ctx.set_stream(self.main.cuda_stream)
 

@@ -611,7 +611,22 @@ int sr_expfit_order_search_batched_f64_dev(sr_ctx *, const double *t, int t_rows
                                            uint32_t *tail_signal, uint32_t tail_value, double *work,
                                            double *popt, double *dP, double *chisq, int *status, int *nfev, int *best,
                                            double *sel_S2, double *sel_C, double *sel_tau, double *sel_chi, int *sel_K);
-/* the same with HOST pointers throughout (staged through the context's work space, synchronous) */
+/* The batched search fed with kernel 1's RAW SUMS instead of finished C(t) / dC(t): every workgroup computes the chunk statistics of
+ * its residue (the arithmetic of sr_ct_finalize_f64_dev, bit for bit) while it stages it, so no sr_ct_finalize launch -- a pure
+ * bandwidth pass -- runs in front of a kernel that leaves the memory system idle.
+ *   sums        DEVICE (nRes, R, sr_ct_psum_stride(F)) as sr_ct_palmer_sums_f32_dev writes them, series in the place of residues
+ *   R, F        chunks and frames per chunk; L must be F / 2
+ *   CtT, dCtT   DEVICE (nRes, L), OUTPUT: C(t) and dC(t), residue-major (what sr_ct_finalize_t_f64_dev writes there); final when
+ *               the launch has ended.  The (lags, vectors) arrays follow by sr_transpose_batched_f64_dev.
+ * Every other argument as above; with dispatch_order the sums row, the output rows and the tau guesses all follow the residue.
+ * Refused before anything is queued: a null sums / CtT / dCtT -2; R < 1, F < 2 or L != F / 2 -3; then the checks above. */
+int sr_expfit_order_search_sums_f64_dev(sr_ctx *, const double *t, int t_rows, const double *sums, int64_t R, int64_t F,
+                                        double *CtT, double *dCtT, int nRes, int L, const int *orders, int nOrders,
+                                        const double *tau_guess, int tau_guess_rows, double tau_max, double chi_threshold,
+                                        const int *dispatch_order, uint32_t *tail_signal, uint32_t tail_value, double *work,
+                                        double *popt, double *dP, double *chisq, int *status, int *nfev, int *best, double *sel_S2,
+                                        double *sel_C, double *sel_tau, double *sel_chi, int *sel_K);
+/* sr_expfit_order_search_f64_dev with HOST pointers throughout (staged through the context's work space, synchronous) */
 int sr_expfit_order_search_f64(sr_ctx *, const double *t, const double *C, const double *sigma, int nRes, int L,
                                const int *orders, int nOrders, const double *tau_guess, int tau_guess_rows,
                                double tau_max, double chi_threshold, double *popt, double *dP, double *chisq,
@@ -741,6 +756,10 @@ int sr_dq_moments_f64(sr_ctx *, const double *q, int64_t N, const int32_t *lags,
  * out[c*rows + r] = in[r*cols + c] (float64, device pointers): C(t) leaves kernel 1 as (lags, vectors)
  * like the reference, the fit reads (residues, lags). */
 int sr_transpose_f64_dev(sr_ctx *, const double *in, int64_t rows, int64_t cols, double *out);
+/* g matrices (rows, cols), contiguous one behind the other, each to (cols, rows) in ONE launch: the (lags, vectors) arrays of a group
+ * of batches from the (g vectors, lags) rows sr_expfit_order_search_sums_f64_dev leaves.  Caller memory only, like the above.
+ * Null pointer -2; g, rows or cols < 1, or more than 65535 matrices / 2 097 120 rows -3. */
+int sr_transpose_batched_f64_dev(sr_ctx *, const double *in, int64_t g, int64_t rows, int64_t cols, double *out);
 
 /* ---- host-side text I/O of the reference's xmgrace-style files (no device work) ----------------------------------
  * run-all.bash passes C(t) between its scripts as text: `<prefix>_Ctint.dat` is written by print_sxylist

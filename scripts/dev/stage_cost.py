@@ -39,14 +39,27 @@ def measure(label):
     return float(np.median(ts))
 
 
+print('fused_stats: %s' % pipe.fused_stats, flush=True)
 base = measure('all stages')
 saved = {}
-for name in ('stage_pack', 'stage_hist', 'stage_ct_finalize'):
+for name in ('stage_pack', 'stage_hist'):
     saved[name] = getattr(pipe, name)
     setattr(pipe, name, lambda *a, **k: None)
     v = measure('without ' + name)
     print('    -> %s costs the steady state %.3f ms per step' % (name, base - v))
     setattr(pipe, name, saved[name])
+# the chunk statistics: with `fused_stats` no stage_ct_finalize runs at all, so its lines are measured with the fused path OFF (the
+# per-batch launches on the tail stream): what that path costs beside the fused one, and what its launch costs inside it
+was_fused = pipe._fused_ok
+pipe._fused_ok = False
+unfused = measure('fused_stats off')
+print('    -> the per-batch chunk statistics cost the steady state %.3f ms per step more than the fused path' % (unfused - base))
+saved['stage_ct_finalize'] = pipe.stage_ct_finalize
+pipe.stage_ct_finalize = lambda *a, **k: None
+v = measure('without stage_ct_finalize')
+print('    -> stage_ct_finalize costs the steady state (fused_stats off) %.3f ms per step' % (unfused - v))
+pipe.stage_ct_finalize = saved['stage_ct_finalize']
+pipe._fused_ok = was_fused
 for name in ('stage_pack', 'stage_hist'):
     setattr(pipe, name, lambda *a, **k: None)
 v = measure('without pack and histogram')

@@ -122,9 +122,38 @@ __global__ __launch_bounds__(256) void k_transpose_f64(const double *__restrict_
         if (c0 + k < cols && r0 + tx < rows) out[(c0 + k) * rows + r0 + tx] = tile[tx][k];
 }
 
+// g matrices (rows, cols), one behind the other, each to (cols, rows): the tile of k_transpose_f64 with the matrix on grid.z
+__global__ __launch_bounds__(256) void k_transpose_batched_f64(const double *__restrict__ in, int64_t rows, int64_t cols,
+                                                               double *__restrict__ out)
+{
+    __shared__ double tile[32][33];
+    const int64_t c0 = (int64_t)blockIdx.x * 32, r0 = (int64_t)blockIdx.y * 32;
+    const int64_t base = (int64_t)blockIdx.z * rows * cols;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int k = ty; k < 32; k += 8)
+        if (r0 + k < rows && c0 + tx < cols) tile[k][tx] = in[base + (r0 + k) * cols + c0 + tx];
+    __syncthreads();
+    for (int k = ty; k < 32; k += 8)
+        if (c0 + k < cols && r0 + tx < rows) out[base + (c0 + k) * rows + r0 + tx] = tile[tx][k];
+}
+
 }  // namespace
 
 extern "C" {
+
+int sr_transpose_batched_f64_dev(sr_ctx *ctx, const double *in, int64_t g, int64_t rows, int64_t cols, double *out)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(in && out, -2, "sr_transpose_batched_f64_dev: null pointer");
+    SR_REQUIRE(g > 0 && rows > 0 && cols > 0, -3, "sr_transpose_batched_f64_dev: bad shape g=%lld rows=%lld cols=%lld", (long long)g,
+               (long long)rows, (long long)cols);
+    const int64_t gx = (cols + 31) / 32, gy = (rows + 31) / 32;
+    SR_REQUIRE(gy <= 65535 && g <= 65535 && gx < ((int64_t)1 << 31), -3, "sr_transpose_batched_f64_dev: too many rows or matrices");
+    hipLaunchKernelGGL(k_transpose_batched_f64, dim3((unsigned)gx, (unsigned)gy, (unsigned)g), dim3(256), 0, ctx->stream, in, rows, cols,
+                       out);
+    SR_HIP(hipGetLastError());
+    return 0;
+}
 
 int sr_transpose_f64_dev(sr_ctx *ctx, const double *in, int64_t rows, int64_t cols, double *out)
 {

@@ -27,6 +27,7 @@
 // solver -- round identically whatever the optimiser does around them (with -ffp-contract=fast the two differed in
 // the last bit of a few sums, enough to send an ill-conditioned nine-parameter fit down another path).
 #include "sr_internal.h"
+#include "sr_ct_stats.h"
 #include <type_traits>
 
 namespace {
@@ -607,6 +608,57 @@ struct Residue {
             if (!(tstep > 0.0)) odd = 1;
         }
         // workgroup OR through the reduction scratch (free here); the first barrier also publishes the staged residue
+        const bool wave_odd = __builtin_amdgcn_ballot_w64(odd != 0) != 0;
+        if ((tid & 63) == 0) red()[(tid >> 6) * kRedStride] = wave_odd ? 1.0 : 0.0;
+        __syncthreads();
+        double any = 0.0;
+#pragma unroll
+        for (int w = 0; w < W; ++w) any += red()[w * kRedStride];
+        geo = (any == 0.0 && L > NTH && geo_allowed) ? 1 : 0;
+        __syncthreads();
+    }
+
+    // The same from kernel 1's raw sums (k_order_search_sums): C(t) and dC(t) of the residue's L lags are computed
+    // here, where they are first needed, instead of by a k_ct_finalize launch in front -- sums: the residue's (R, Lp) row block, lag d
+    // in slot d (slot 0 and the slots beyond L are never read).  y and the weights go where stage() puts them; m and sd also go to
+    // the residue's rows of the (nRes, L) arrays y_out / sg_out, which the chi^2 (T.sg), the LDS-less paths (yg) and the caller read.
+    // A wave reads 64 consecutive lags of one chunk row per instruction, the R loads of a point in flight together.
+    __device__ void stage_sums(const double *t, const double *sums, int R, int F, int64_t Lp, double *y_out, double *sg_out,
+                               double *wbuf, int geo_allowed)
+    {
+        sg = sg_out;
+        if (LDS) fit_smem[RED + tid] = t[tid < L ? tid : 0];
+        const double rootR = sqrt((double)R) - 1.0;
+        for (int l = tid; l < L; l += NTH) {
+            double m, sd;
+            sr_ct_chunk_stats(sums + (l + 1), Lp, R, (double)(F - (l + 1)), rootR, m, sd);
+            const double w = 1.0 / sd;
+            y_out[l] = m;
+            sg_out[l] = sd;
+            if (LDS) {
+                fit_smem[RED + NTH + l] = m;
+                fit_smem[RED + NTH + L + l] = w;
+            } else {
+                wbuf[l] = w;
+            }
+        }
+        // other threads of the workgroup read these rows from global memory behind the barriers below (np_mean_y without
+        // LDS, the chi^2 always): the stores are visible to the workgroup before any of its waves passes the first of them
+        __threadfence_block();
+        tg = t; yg = y_out; wg = wbuf;
+        // the uniform-grid test of stage(), word for word (a copy, not a shared helper: stage() keeps the instruction stream it had)
+        int odd = 0;
+        tstep = 0.0;
+        if (L > NTH) {
+            tstep = t[NTH] - t[0];
+            const double t0 = t[tid];
+            int j = 0;
+            for (int l = tid; l < L; l += NTH, ++j) {
+                const double tl = t[l];
+                if (!(fabs(tl - fma((double)j, tstep, t0)) <= 1.8e-15 * fabs(tl))) odd = 1;
+            }
+            if (!(tstep > 0.0)) odd = 1;
+        }
         const bool wave_odd = __builtin_amdgcn_ballot_w64(odd != 0) != 0;
         if ((tid & 63) == 0) red()[(tid >> 6) * kRedStride] = wave_odd ? 1.0 : 0.0;
         __syncthreads();
@@ -1203,6 +1255,16 @@ struct SearchArgs {
     int geo;                          // option fit_geo, as in FitArgs
 };
 
+// The raw-sum source of k_order_search_sums: kernel 1's raw sums of the nRes series, row res = (R, Lp) doubles with lag d in slot d.
+// SearchArgs::y and ::sigma are then the OUTPUT rows C(t) / dC(t) (nRes, L) that the staging of a residue fills.  A kernel argument of
+// its own, not fields of SearchArgs: the solvers take SearchArgs by reference, so the kernel keeps a copy of it in its frame, and a
+// longer struct would lengthen the frame of every search kernel.
+struct SumsSource {
+    const double *sums;
+    int R, F;
+    int64_t Lp;
+};
+
 // numpy.mean of n <= 128 contiguous float64 values (pairwise summation of numpy/_core/src/umath/loops_utils.h.src)
 template <class R>
 __device__ __forceinline__ double np_mean_y(const R &T, int start, int n)
@@ -1328,99 +1390,18 @@ __device__ __noinline__ void search_order(const R T, const SearchArgs &a, int j,
 template <int NMAX, int W, bool LDS>
 __global__ __launch_bounds__(W * 64, NMAX <= 5 ? SR_FIT_WAVES_EU_LOW : SR_FIT_WAVES_EU) void k_order_search(SearchArgs a)
 {
-    const int res = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
-    const int tid = threadIdx.x;
-    if (a.tail_signal && blockIdx.x == gridDim.x - 1 && tid == 0)
-        __hip_atomic_store(a.tail_signal, a.tail_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    // The fits are the latency chain of a group: their waves issue before the waves of the bandwidth kernels that fill the
-    // launch's tail (the group's histograms: 24.0 -> 23.1 ms for the merged launch of 20 batches with them beside it).
-    __builtin_amdgcn_s_setprio(SR_FIT_SETPRIO);
-    Residue<W, LDS> T;
-    T.L = a.L;
-    T.tid = tid;
-    const double *sg_res = a.sigma ? a.sigma + (int64_t)res * a.L : nullptr;
-    T.stage(a.t + (int64_t)res * a.t_stride, a.y + (int64_t)res * a.L, sg_res, LDS ? nullptr : a.fws + (int64_t)res * a.L, a.geo);
+#define SR_SEARCH_FROM_SUMS 0
+#include "sr_fit_search_body.h"
+#undef SR_SEARCH_FROM_SUMS
+}
 
-    const int ns = a.L < 10 ? a.L : 10;                 // nSample = 10, fitting_Ct_functions.py:359
-    const double avgBeg = np_mean_y(T, 0, ns);
-    const double avgEnd = np_mean_y(T, a.L - ns, ns);
-
-    if (tid == 0) {
-        for (int j = 0; j < a.nOrders; ++j) {
-            const int64_t o = (int64_t)j * a.nRes + res;
-            for (int i = 0; i < a.Pmax; ++i) { a.popt[o * a.Pmax + i] = NAN; a.dP[o * a.Pmax + i] = NAN; }
-            a.chisq[o] = INFINITY;
-            a.status[o] = -100;
-            a.nfev[o] = 0;
-        }
-    }
-    // The search state lives in LDS, not on the stack: it crosses the (non-inlined) per-order solver calls by reference, and a
-    // stack object costs every lane a scratch frame.  It is workgroup-uniform: every thread stores the same values and reads
-    // them back behind its own stores (LDS operations of a wave complete in order), so no barrier is needed.
-    static_assert(sizeof(SearchState) <= kStateDoubles * sizeof(double), "SearchState does not fit its LDS slot");
-    SearchState &st = *reinterpret_cast<SearchState *>(fit_smem + Residue<W, LDS>::ST);
-    st.first = true; st.done = false; st.best = -1; st.best_chi = INFINITY;
-#pragma unroll
-    for (int i = 0; i < kNmax; ++i) st.xbest[i] = 0.0;
-
-    for (int j = 0; j < a.nOrders && !st.done; ++j) {
-        switch (a.orders[j]) {
-            case 2: search_order<2>(T, a, j, res, avgBeg, avgEnd, st); break;
-            case 3: search_order<3>(T, a, j, res, avgBeg, avgEnd, st); break;
-            case 4: search_order<4>(T, a, j, res, avgBeg, avgEnd, st); break;
-            case 5: search_order<5>(T, a, j, res, avgBeg, avgEnd, st); break;
-            case 6: if (NMAX >= 6) search_order<(NMAX >= 6 ? 6 : 2)>(T, a, j, res, avgBeg, avgEnd, st); break;
-            case 7: if (NMAX >= 7) search_order<(NMAX >= 7 ? 7 : 2)>(T, a, j, res, avgBeg, avgEnd, st); break;
-            case 8: if (NMAX >= 8) search_order<(NMAX >= 8 ? 8 : 2)>(T, a, j, res, avgBeg, avgEnd, st); break;
-            case 9: if (NMAX >= 9) search_order<(NMAX >= 9 ? 9 : 2)>(T, a, j, res, avgBeg, avgEnd, st); break;
-            case 10: if (NMAX >= 10) search_order<(NMAX >= 10 ? 10 : 2)>(T, a, j, res, avgBeg, avgEnd, st); break;
-            case 11: if (NMAX >= 11) search_order<(NMAX >= 11 ? 11 : 2)>(T, a, j, res, avgBeg, avgEnd, st); break;
-            default: break;
-        }
-    }
-
-    // selected model with its components sorted by tau (sort_components, fitting_Ct_functions.py:203-209)
-    if (tid == 0) {
-        a.best[res] = st.best;
-        double Cs[kNmax / 2], ts[kNmax / 2];
-        int K = 0;
-        double S2 = 0.0, chi = NAN;
-        if (st.best >= 0) {
-#pragma clang fp contract(off)
-            const int nP = a.orders[st.best];
-            K = nP / 2;
-            double sum = 0.0;
-            for (int k = 0; k < kNmax / 2; ++k) {
-                // st.xbest is indexed with compile-time constants only (registers): unrolled selects
-                double c = 0.0, tt = 0.0;
-#pragma unroll
-                for (int i = 0; i < kNmax; ++i) {
-                    if (i == k) c = st.xbest[i];
-                    if (i == K + k) tt = st.xbest[i];
-                }
-                if (k < K) { Cs[k] = c; ts[k] = tt; sum += c; }
-            }
-            double last = 0.0;
-#pragma unroll
-            for (int i = 0; i < kNmax; ++i)
-                if (i == nP - 1) last = st.xbest[i];
-            S2 = (nP & 1) ? last : 1.0 - sum;
-            chi = st.best_chi;
-            for (int i = 1; i < K; ++i) {               // stable insertion sort by tau
-                const double tc = ts[i], cc = Cs[i];
-                int q = i - 1;
-                while (q >= 0 && ts[q] > tc) { ts[q + 1] = ts[q]; Cs[q + 1] = Cs[q]; --q; }
-                ts[q + 1] = tc; Cs[q + 1] = cc;
-            }
-        }
-        a.sel_S2[res] = S2;
-        a.sel_chi[res] = chi;
-        a.sel_K[res] = K;
-        for (int k = 0; k < a.Kmax; ++k) {
-            a.sel_C[(int64_t)res * a.Kmax + k] = k < K ? Cs[k] : 0.0;
-            a.sel_tau[(int64_t)res * a.Kmax + k] = k < K ? ts[k] : 1.0;
-        }
-    }
+// k_order_search with a raw-sum source: a kernel of its own name, so that k_order_search<..> stays the kernel it was
+template <int NMAX, int W, bool LDS>
+__global__ __launch_bounds__(W * 64, NMAX <= 5 ? SR_FIT_WAVES_EU_LOW : SR_FIT_WAVES_EU) void k_order_search_sums(SearchArgs a, SumsSource src)
+{
+#define SR_SEARCH_FROM_SUMS 1
+#include "sr_fit_search_body.h"
+#undef SR_SEARCH_FROM_SUMS
 }
 
 // residual + analytic Jacobian for arbitrary parameter sets
@@ -1516,28 +1497,30 @@ __global__ __launch_bounds__(W * 64) void k_fit_probe(ProbeArgs a)
 struct TrfKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_trf<N, W, LDS>; } };
 struct ProbeKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_fit_probe<N, W, LDS>; } };
 struct SearchKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_order_search<N, W, LDS>; } };
+struct SearchSumsKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_order_search_sums<N, W, LDS>; } };
 
 // stage_lds: t, y and 1/sigma of a residue go to LDS when they fit (k_order_search and k_fit_probe pass the option "fit_lds",
 // k_trf stages whenever the residue fits)
-template <class K, int N, int W, class A>
-int launch_fit_w(sr_ctx *ctx, bool stage_lds, const A &a)
+// (more...: further kernel arguments behind `a`)
+template <class K, int N, int W, class A, class... More>
+int launch_fit_w(sr_ctx *ctx, bool stage_lds, const A &a, const More &...more)
 {
     const dim3 grid((unsigned)a.nRes), block(W * 64);
     const size_t lds_full = fit_lds_doubles(W, a.L) * sizeof(double);
-    if (stage_lds && lds_full <= sr_lds_limit(ctx)) return sr_launch(ctx, K::template fn<N, W, true>(), grid, block, lds_full, a);
-    return sr_launch(ctx, K::template fn<N, W, false>(), grid, block, fit_lds_doubles(W, 0) * sizeof(double), a);
+    if (stage_lds && lds_full <= sr_lds_limit(ctx)) return sr_launch(ctx, K::template fn<N, W, true>(), grid, block, lds_full, a, more...);
+    return sr_launch(ctx, K::template fn<N, W, false>(), grid, block, fit_lds_doubles(W, 0) * sizeof(double), a, more...);
 }
 
 // The single-order solver uses the same number of waves per residue as the model-order search (sr_set_option
 // "fit_waves"): the workgroup sums are combined wave by wave, so only equal wave counts give bit-identical fits --
 // which is what lets the host-driven search (one sr_expfit_lm_f64 call per order) reproduce the one-launch search exactly.
-template <class K, int N, class A>
-int launch_fit(sr_ctx *ctx, bool stage_lds, const A &a)
+template <class K, int N, class A, class... More>
+int launch_fit(sr_ctx *ctx, bool stage_lds, const A &a, const More &...more)
 {
     switch (ctx->fit_waves) {
-        case 1: return launch_fit_w<K, N, 1>(ctx, stage_lds, a);
-        case 2: return launch_fit_w<K, N, 2>(ctx, stage_lds, a);
-        default: return launch_fit_w<K, N, 4>(ctx, stage_lds, a);
+        case 1: return launch_fit_w<K, N, 1>(ctx, stage_lds, a, more...);
+        case 2: return launch_fit_w<K, N, 2>(ctx, stage_lds, a, more...);
+        default: return launch_fit_w<K, N, 4>(ctx, stage_lds, a, more...);
     }
 }
 
@@ -1595,14 +1578,15 @@ int sr_expfit_order_search_f64_dev(sr_ctx *ctx, const double *t, const double *C
                                                   sel_S2, sel_C, sel_tau, sel_chi, sel_K);
 }
 
-int sr_expfit_order_search_batched_f64_dev(sr_ctx *ctx, const double *t, int t_rows, const double *C, const double *sigma, int nRes,
-                                           int L, const int *orders, int nOrders, const double *tau_guess, int tau_guess_rows,
-                                           double tau_max, double chi_threshold, const int *dispatch_order,
-                                           uint32_t *tail_signal, uint32_t tail_value, double *work,
-                                           double *popt, double *dP, double *chisq, int *status, int *nfev, int *best,
-                                           double *sel_S2, double *sel_C, double *sel_tau, double *sel_chi, int *sel_K)
+// the one body of the two batched entry points.  sums == nullptr: C / sigma are read; else they are the output rows CtT / dCtT and the
+// residues are staged from the raw sums (R chunks of F frames, row stride sr_ct_psum_stride(F))
+static int order_search_launch(sr_ctx *ctx, const double *t, int t_rows, const double *C, const double *sigma, const double *sums,
+                               int64_t R, int64_t F, int nRes, int L, const int *orders, int nOrders, const double *tau_guess,
+                               int tau_guess_rows, double tau_max, double chi_threshold, const int *dispatch_order,
+                               uint32_t *tail_signal, uint32_t tail_value, double *work, double *popt, double *dP, double *chisq,
+                               int *status, int *nfev, int *best, double *sel_S2, double *sel_C, double *sel_tau, double *sel_chi,
+                               int *sel_K)
 {
-    SR_CHECK_CTX(ctx);
     SR_REQUIRE(t_rows == 1 || t_rows == nRes, -3, "sr_expfit_order_search_batched_f64_dev: t_rows must be 1 or nRes");
     SR_REQUIRE(t && C && orders && tau_guess && popt && dP && chisq && status && nfev && best && sel_S2 && sel_C && sel_tau &&
                    sel_chi && sel_K, -2, "sr_expfit_order_search_f64_dev: null pointer");
@@ -1634,14 +1618,52 @@ int sr_expfit_order_search_batched_f64_dev(sr_ctx *ctx, const double *t, int t_r
     a.Pmax = pmax; a.Kmax = pmax / 2;
     a.popt = popt; a.dP = dP; a.chisq = chisq; a.status = status; a.nfev = nfev; a.best = best;
     a.sel_S2 = sel_S2; a.sel_C = sel_C; a.sel_tau = sel_tau; a.sel_chi = sel_chi; a.sel_K = sel_K; a.fws = fws;
+    const SumsSource src = {sums, (int)R, (int)F, sums ? sr_ct_psum_stride(F) : 0};
 #ifdef SR_FIT_DEV_FAST
     SR_REQUIRE(pmax <= 9, -3, "development build: orders up to 9 only");
+    if (sums) return launch_fit<SearchSumsKernel, 9>(ctx, ctx->fit_lds != 0, a, src);
     return launch_fit<SearchKernel, 9>(ctx, ctx->fit_lds != 0, a);
 #else
+    if (sums) {
+        if (pmax <= 5) return launch_fit<SearchSumsKernel, 5>(ctx, ctx->fit_lds != 0, a, src);
+        if (pmax <= 9) return launch_fit<SearchSumsKernel, 9>(ctx, ctx->fit_lds != 0, a, src);
+        return launch_fit<SearchSumsKernel, 11>(ctx, ctx->fit_lds != 0, a, src);
+    }
     if (pmax <= 5) return launch_fit<SearchKernel, 5>(ctx, ctx->fit_lds != 0, a);
     if (pmax <= 9) return launch_fit<SearchKernel, 9>(ctx, ctx->fit_lds != 0, a);
     return launch_fit<SearchKernel, 11>(ctx, ctx->fit_lds != 0, a);
 #endif
+}
+
+int sr_expfit_order_search_batched_f64_dev(sr_ctx *ctx, const double *t, int t_rows, const double *C, const double *sigma, int nRes,
+                                           int L, const int *orders, int nOrders, const double *tau_guess, int tau_guess_rows,
+                                           double tau_max, double chi_threshold, const int *dispatch_order,
+                                           uint32_t *tail_signal, uint32_t tail_value, double *work,
+                                           double *popt, double *dP, double *chisq, int *status, int *nfev, int *best,
+                                           double *sel_S2, double *sel_C, double *sel_tau, double *sel_chi, int *sel_K)
+{
+    SR_CHECK_CTX(ctx);
+    return order_search_launch(ctx, t, t_rows, C, sigma, nullptr, 0, 0, nRes, L, orders, nOrders, tau_guess, tau_guess_rows, tau_max,
+                               chi_threshold, dispatch_order, tail_signal, tail_value, work, popt, dP, chisq, status, nfev, best, sel_S2,
+                               sel_C, sel_tau, sel_chi, sel_K);
+}
+
+int sr_expfit_order_search_sums_f64_dev(sr_ctx *ctx, const double *t, int t_rows, const double *sums, int64_t R, int64_t F,
+                                        double *CtT, double *dCtT, int nRes, int L, const int *orders, int nOrders,
+                                        const double *tau_guess, int tau_guess_rows, double tau_max, double chi_threshold,
+                                        const int *dispatch_order, uint32_t *tail_signal, uint32_t tail_value, double *work,
+                                        double *popt, double *dP, double *chisq, int *status, int *nfev, int *best, double *sel_S2,
+                                        double *sel_C, double *sel_tau, double *sel_chi, int *sel_K)
+{
+    SR_CHECK_CTX(ctx);
+    // refused before anything is queued (the remaining checks are those of the batched entry point, which queue nothing either)
+    SR_REQUIRE(sums && CtT && dCtT, -2, "sr_expfit_order_search_sums_f64_dev: null pointer");
+    SR_REQUIRE(R >= 1 && F >= 2 && F <= SR_CT_LONG_MAX_FRAMES && (int64_t)L == F / 2, -3,
+               "sr_expfit_order_search_sums_f64_dev: bad shape R=%lld F=%lld L=%d (L must be F / 2)", (long long)R, (long long)F, L);
+    SR_REQUIRE(R < ((int64_t)1 << 31), -3, "sr_expfit_order_search_sums_f64_dev: too many chunks");
+    return order_search_launch(ctx, t, t_rows, CtT, dCtT, sums, R, F, nRes, L, orders, nOrders, tau_guess, tau_guess_rows, tau_max,
+                               chi_threshold, dispatch_order, tail_signal, tail_value, work, popt, dP, chisq, status, nfev, best, sel_S2,
+                               sel_C, sel_tau, sel_chi, sel_K);
 }
 
 int sr_expfit_order_search_f64(sr_ctx *ctx, const double *t, const double *C, const double *sigma, int nRes, int L,

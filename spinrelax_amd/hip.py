@@ -689,6 +689,24 @@ class Context:
                                                               nfev_ptr, best_ptr, S2_ptr, C_ptr, tau_ptr, chi_ptr, K_ptr),
               'sr_expfit_order_search_batched_f64_dev')
 
+    def order_search_sums_dev(self, t_ptr, t_rows, sums_ptr, R, F, CtT_ptr, dCtT_ptr, nRes, L, orders, tau_guess_ptr, tau_rows, tau_max,
+                              chi_threshold, popt_ptr, dP_ptr, chisq_ptr, status_ptr, nfev_ptr, best_ptr, S2_ptr, C_ptr, tau_ptr, chi_ptr,
+                              K_ptr, work_ptr=None, dispatch_order_ptr=None, tail_signal=None, tail_value=0, refusal_ok=False):
+        """order_search_batched_dev on kernel 1's raw sums (nRes, R, psum_stride(F)): the launch computes the chunk statistics of
+        every residue itself and writes C(t) / dC(t) to CtT_ptr / dCtT_ptr (nRes, L) (sr_expfit_order_search_sums_f64_dev).
+        refusal_ok: a refusal of the arguments (-2, -3: nothing has been queued) is returned instead of raised, so that the caller
+        can take the two-launch path; returns 0 otherwise"""
+        orders = np.ascontiguousarray(orders, dtype=np.int32)
+        rc = self.lib.sr_expfit_order_search_sums_f64_dev(self.h, t_ptr, t_rows, sums_ptr, int(R), int(F), CtT_ptr, dCtT_ptr, nRes, L,
+                                                          _ptr(orders), orders.size, tau_guess_ptr, tau_rows, float(tau_max),
+                                                          float(chi_threshold), dispatch_order_ptr, tail_signal, int(tail_value),
+                                                          work_ptr, popt_ptr, dP_ptr, chisq_ptr, status_ptr, nfev_ptr, best_ptr, S2_ptr,
+                                                          C_ptr, tau_ptr, chi_ptr, K_ptr)
+        if refusal_ok and rc in (-2, -3):
+            return rc
+        check(rc, 'sr_expfit_order_search_sums_f64_dev')
+        return 0
+
     def relax_dev(self, model, D, E, omega_ptr, fDD_ptr, fCSA_ptr, tf_ptr, gr_ptr, nRes, Kmax, zeta, S2_ptr, C_ptr, tau_ptr,
                   K_ptr, B, binvecs_ptr, weights_ptr, noe_mode, out_ptr, Jout_ptr=None, stats_ptr=None):
         """Context.relax on device pointers (sr_jomega_relax_f64_dev); model and D as there, model 3 = [Dx, Dy, Dz]"""
@@ -701,6 +719,10 @@ class Context:
 
     def transpose_dev(self, in_ptr, rows, cols, out_ptr):
         check(self.lib.sr_transpose_f64_dev(self.h, in_ptr, rows, cols, out_ptr), 'sr_transpose_f64_dev')
+
+    def transpose_batched_dev(self, in_ptr, g, rows, cols, out_ptr):
+        """g contiguous (rows, cols) matrices, each to (cols, rows), in one launch (sr_transpose_batched_f64_dev)"""
+        check(self.lib.sr_transpose_batched_f64_dev(self.h, in_ptr, int(g), int(rows), int(cols), out_ptr), 'sr_transpose_batched_f64_dev')
 
     # ---- kernel 3a ----
     def jomega(self, x, y):

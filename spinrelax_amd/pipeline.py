@@ -61,6 +61,9 @@ from .hip import SpinRelaxHipError
 # Default of the pipelines' keyword `fused_pack`: the C(t) launches carry the packs of coming batches.  On since it measured faster than
 # the pack on its own stream at 20 steps, 100 steps and in steady state (docs/EXPERIMENTS.md section 29).
 FUSED_PACK_DEFAULT = True
+# Default of GroupedPipeline's keyword `fused_stats`: the merged search launch computes the chunk statistics of its residues from the raw
+# C(t) sums while it stages them, and no k_ct_finalize launch runs per batch (docs/EXPERIMENTS.md section 30).
+FUSED_STATS_DEFAULT = True
 
 
 # ======================================================================================================================
@@ -104,6 +107,18 @@ def group_sizes(group, nb, override=None):
         out.append(g)
         rem -= g
     return out
+
+
+def fused_stats_bytes(group, V, R, Lp):
+    """device memory of GroupedPipeline's `fused_stats` path: the raw sums (R chunks x Lp slots of float64 per vector) of every batch of
+    BOTH group buffers stay until the group's merged launch has read them"""
+    return 2 * int(group) * int(V) * int(R) * int(Lp) * 8
+
+
+def fused_stats_fits(need, free):
+    """whether the raw-sum tensors of `fused_stats` are allocated: they may take at most half of the free device memory (the rule of
+    `late_hist`), else the pipeline keeps the per-batch chunk statistics and their small ring of raw-sum buffers"""
+    return int(need) <= int(free) // 2
 
 
 # ======================================================================================================================
@@ -150,8 +165,11 @@ class _Results:
         self._ctx = ctx
         self.layout = result_layout(nO, Pmax, E)
         nd, ni = self.counts(nmax)
-        self.dres = torch.empty((nd,), device=dev, dtype=torch.float64)
-        self.ires = torch.empty((ni,), device=dev, dtype=torch.int32)
+        # zeroed, not merely allocated: the relaxation kernel indexes C / tau with the component counts K it finds here, and a pipeline
+        # whose search is switched off (`dev_skip_fits`) before its first batch would hand it whatever the allocator left (K = 0: no
+        # component, nothing indexed)
+        self.dres = torch.zeros((nd,), device=dev, dtype=torch.float64)
+        self.ires = torch.zeros((ni,), device=dev, dtype=torch.int32)
         self.h_dres, self._h_dres_addr = _pinned_array(ctx, nd, np.float64)
         self.h_ires, self._h_ires_addr = _pinned_array(ctx, ni, np.int32)
         self._views = {}
@@ -288,6 +306,8 @@ class _Group:
         self.busy = False
         self.batches = []
         self.signal, self.epoch = None, 0      # late histograms: what the merged launch's last workgroup releases
+        self.sums = None           # `fused_stats`: (G, V R Lp) raw sums, batch j of the group in row j (GroupedPipeline allocates it)
+        self.fused = False         # the group in flight takes the fused path
 
     # what a device-side consumer of a finished group reads (bench.py's all-gather): the g batches in flight
     @property
@@ -957,7 +977,17 @@ class GroupedPipeline(_Pipeline):
     plane buffers (12 B per frame and vector each; 21 GB for 32 cfg3 batches) + two group buffers (1.7 GB each); checked
     against the free device memory at construction (falls back to late_hist off, see `late_hist_note`)."""
 
-    def __init__(self, ctx, device, frames, V, R, F, dt, group=32, overlap=True, psum_buffers=3, late_hist=False, **kw):
+    def __init__(self, ctx, device, frames, V, R, F, dt, group=32, overlap=True, psum_buffers=3, late_hist=False, fused_stats=None, **kw):
+        """fused_stats (default on): the chunk statistics (mean / deviation over the R chunks) are computed by the merged search launch
+        itself, from the raw sums, where a residue is staged (sr_expfit_order_search_sums_f64_dev) -- no k_ct_finalize launch per batch, no
+        work on the tail stream; C(t) / dC(t) of the whole group become final behind the merged launch (one batched transposition per
+        array gives the (lags, vectors) orientation; on_part('ct') fires there, once per batch, in batch order).  Every group buffer
+        keeps the raw sums of all its batches: fused_stats_bytes(group, V, R, Lp), 12.9 GB for groups of 32 cfg3 batches.  The path
+        is OFF -- per-batch launches as before -- when that is more than half of the free device memory or cannot be allocated, when the
+        library refuses the call, and while `dev_skip_fits` is set; the attribute `fused_stats` says which way runs, `fused_stats_note`
+        why not.
+        psum_buffers: raw-sum buffers in rotation between a batch's C(t) launch and its chunk statistics -- used by the UNFUSED path
+        only (the fused path keeps a group's raw sums in the group buffer)."""
         kw = dict(kw)
         kw.setdefault('pack_cus', 128)                    # the pack stream on half of the CUs (_Pipeline.__init__)
         kw['depth'] = max(2, int(psum_buffers))           # raw-sum buffers in rotation (reported as the schedule's depth)
@@ -995,9 +1025,12 @@ class GroupedPipeline(_Pipeline):
         self.dev_skip_hist = bool(os.environ.get('SR_DEV_SKIP_HIST'))      # development only: marginal cost of the histogram in phase 1
         # the raw C(t) sums of the batches whose chunk statistics have not run yet: a rotating pool, and per entry the event
         # "the statistics have read it"
+        # (the unfused path only; the ring is small beside a group's raw sums and always there, so that a group can fall back)
         self.NP = self.depth
-        self.psums = [torch.empty((V * R * ctx.psum_stride(F),), device=device, dtype=torch.float64) for _ in range(self.NP)]
+        self.psum_len = V * R * ctx.psum_stride(F)
+        self.psums = [torch.empty((self.psum_len,), device=device, dtype=torch.float64) for _ in range(self.NP)]
         self._psum_free = [None] * self.NP
+        self._last_ct = [None, None]   # fused path: the last C(t) launch of the group on either C(t) stream
         self.tail = torch.cuda.Stream(device=device)
         self.groups = [_Group(ctx, device, self.group, V, self.L, R, self.nbins, len(self.listDoG), max(self.listDoG), len(self.fields),
                               torch.cuda.Stream(device=device)) for _ in range(2)]
@@ -1024,13 +1057,47 @@ class GroupedPipeline(_Pipeline):
                 self.close()
                 raise SpinRelaxHipError('late_hist needs sr_signal_alloc (hipStreamWaitValue32 on signal memory); construct the '
                                         'pipeline with late_hist=False on this device')
+        # `fused_stats`: the raw sums of a whole group, per group buffer
+        self._fused_ok = bool(FUSED_STATS_DEFAULT if fused_stats is None else fused_stats)
+        self._fused_note = None if self._fused_ok else 'fused_stats off: not asked for'
+        if self._fused_ok:
+            need = fused_stats_bytes(self.group, V, R, ctx.psum_stride(F))
+            free = torch.cuda.mem_get_info(device)[0]
+            if not fused_stats_fits(need, free):
+                self._fused_off('the raw sums of two groups need %.1f GB, %.1f GB of device memory are free' % (need / 1e9, free / 1e9))
+            else:
+                try:
+                    for grp in self.groups:
+                        grp.sums = torch.empty((self.group, self.psum_len), device=device, dtype=torch.float64)
+                except torch.cuda.OutOfMemoryError:
+                    for grp in self.groups:
+                        grp.sums = None
+                    self._fused_off('the raw sums of two groups (%.1f GB) could not be allocated' % (need / 1e9))
         torch.cuda.synchronize(device)
+
+    @property
+    def fused_stats(self):
+        """whether the groups queued from now on take the fused path (constructor)"""
+        return self._fused_ok and not self.dev_skip_fits
+
+    @property
+    def fused_stats_note(self):
+        """None, or why the per-batch launches run"""
+        if self._fused_ok and self.dev_skip_fits:
+            return 'fused_stats off: dev_skip_fits is set'
+        return self._fused_note
+
+    def _fused_off(self, why):
+        """(the group tensors, where they exist, stay: a group in flight may still read its own)"""
+        self._fused_ok = False
+        self._fused_note = 'fused_stats off: ' + why
 
     def _free(self):
         for grp in self.groups:
             grp.done = grp.guard = None
             grp.stream = None
             grp.batches = []
+            grp.sums = None
             if grp.signal:
                 self.ctx.signal_free(grp.signal)
                 grp.signal = None
@@ -1039,6 +1106,7 @@ class GroupedPipeline(_Pipeline):
         self.tail = None
         self._late = []
         self._psum_free = [None] * self.NP
+        self._last_ct = [None, None]
         self._last_fin = self._last_hist = self._prev_done = None
 
     def group_sizes(self, nb):
@@ -1056,6 +1124,10 @@ class GroupedPipeline(_Pipeline):
     def _fcsa_for(self, g):
         if g not in self._fcsa:
             self._fcsa[g] = self._relax_dev[2].repeat(1, g).contiguous() if self._relax_dev[2].dim() == 2 else self._relax_dev[2].repeat(g).contiguous()
+            # made by a kernel on the CURRENT group's stream, behind its merged launch; the other group's stream uses the cached tensor
+            # without an order between the two (its relaxation launch could read it unwritten when its own search ends first): wait
+            # here, once per group size and pipeline
+            torch.cuda.current_stream(self.dev).synchronize()
         return self._fcsa[g]
 
     def _front_grouped(self, vecs, kk, grp, j, events, pack_next):
@@ -1063,7 +1135,9 @@ class GroupedPipeline(_Pipeline):
         ring = self.ring
         buf = ring.buf(kk)
         pi = kk % self.NP
-        bv.psum = self.psums[pi]
+        # fused_stats: the batch's raw sums stay in the group's tensor until the merged launch has read them (the buffer is only
+        # taken again once that launch has been collected); else a buffer of the ring, free again behind the batch's chunk statistics
+        bv.psum = grp.sums[j] if grp.fused else self.psums[pi]
         ring.pack_now(vecs, kk)
         carried = self._carries_pack(pack_next, buf, bv.psum, kk)
         self._pack_between(pack_next, kk, carried)
@@ -1071,7 +1145,7 @@ class GroupedPipeline(_Pipeline):
         self.ctx.set_stream(main.cuda_stream)
         with torch.cuda.stream(main):
             ring.wait_packed(main, kk)
-            if self._psum_free[pi] is not None:
+            if not grp.fused and self._psum_free[pi] is not None:
                 main.wait_event(self._psum_free[pi])      # the chunk statistics of batch kk - NP have read these raw sums
             if j < 2 and not self.overlap and self._prev_done is not None:
                 main.wait_event(self._prev_done)          # strict phases: the previous group's merged launch has finished (both C(t) streams)
@@ -1084,16 +1158,20 @@ class GroupedPipeline(_Pipeline):
             else:
                 launch()
             ct_ev = ring.ct_done_with(kk, main)
-        tail = self.tail          # (chunk statistics spread over 3 or 5 streams: measured, no difference)
-        self.ctx.set_stream(tail.cuda_stream)
-        with torch.cuda.stream(tail):
-            tail.wait_event(ct_ev)
-            if j == 0 and grp.guard is not None:
-                tail.wait_event(grp.guard)                # a device-side reader of the group's previous C(t)
-            self.stage_ct_finalize(bv)
-            self._psum_free[pi] = self._last_fin = ev = _event(tail)
-            if self._on_part is not None:
-                self._on_part('ct', bv, ev)          # C(t), dC(t) of this batch are final once `ev` has passed
+        if grp.fused:
+            # nothing more for this batch here: its chunk statistics belong to the merged launch (_back_grouped)
+            self._last_ct[1 if main is self.main_alt else 0] = ct_ev
+        else:
+            tail = self.tail          # (chunk statistics spread over 3 or 5 streams: measured, no difference)
+            self.ctx.set_stream(tail.cuda_stream)
+            with torch.cuda.stream(tail):
+                tail.wait_event(ct_ev)
+                if j == 0 and grp.guard is not None:
+                    tail.wait_event(grp.guard)                # a device-side reader of the group's previous C(t)
+                self.stage_ct_finalize(bv)
+                self._psum_free[pi] = self._last_fin = ev = _event(tail)
+                if self._on_part is not None:
+                    self._on_part('ct', bv, ev)          # C(t), dC(t) of this batch are final once `ev` has passed
         self.ctx.set_stream(self.aux.cuda_stream)
         with torch.cuda.stream(self.aux):
             if pack_next is not None and kk + 1 not in ring.ahead:
@@ -1117,7 +1195,15 @@ class GroupedPipeline(_Pipeline):
 
     def _back_grouped(self, grp, g, events):
         st = grp.stream
-        st.wait_event(self._last_fin)        # the tail and auxiliary streams run in order: their last events cover the group
+        if grp.fused:
+            for ev in self._last_ct:         # the two C(t) streams run in order: their last events cover the group's raw sums
+                if ev is not None:
+                    st.wait_event(ev)
+            self._last_ct = [None, None]
+            if grp.guard is not None:
+                st.wait_event(grp.guard)     # a device-side reader of the group's previous C(t): this stream writes it now
+        else:
+            st.wait_event(self._last_fin)    # the tail and auxiliary streams run in order: their last events cover the group
         st.wait_event(self._last_hist)
         late_guard = grp.guard if self.late_hist else None
         events45 = events if events is not None and len(events) > 5 else None
@@ -1133,16 +1219,38 @@ class GroupedPipeline(_Pipeline):
                 self.ctx.memcpy_h2d_async(grp.order_dev.data_ptr(), grp._h_order_addr, n * 4)
                 order_ptr = grp.order_dev.data_ptr()
             _stamp(events45, 4, st)
-            if not self.dev_skip_fits:
+            res_ptrs = [v[name].data_ptr() for name in ('popt', 'dP', 'chisq', 'status', 'nfev', 'best', 'S2', 'C', 'tau', 'chi', 'K')]
+            fused = grp.fused
+            if fused:
+                # the merged launch stages every residue from its raw sums and writes CtT / dCtT; a refusal (nothing queued) sends
+                # this group and all later ones down the two-launch path
+                rc = self.ctx.order_search_sums_dev(self.t_dev.data_ptr(), 1, grp.sums.data_ptr(), self.R, self.F, grp.CtT.data_ptr(),
+                                                    grp.dCtT.data_ptr(), n, self.L, self.listDoG, self.tau_guess.data_ptr(), 1,
+                                                    self.tau_max, self.chi_thr, *res_ptrs, work_ptr=grp.fitwork.data_ptr(),
+                                                    dispatch_order_ptr=order_ptr, tail_signal=grp.signal,
+                                                    tail_value=grp.epoch + 1 if grp.signal else 0, refusal_ok=True)
+                if rc:
+                    self._fused_off('the library refused the call (%d)' % rc)
+                    fused = False
+                    for bv in grp.batches:
+                        self.stage_ct_finalize(bv)
+                        if self._on_part is not None:
+                            self._on_part('ct', bv, _event(st))
+            if not fused and not self.dev_skip_fits:
                 self.ctx.order_search_batched_dev(self.t_dev.data_ptr(), 1, grp.CtT.data_ptr(), grp.dCtT.data_ptr(), n, self.L, self.listDoG,
-                                                  self.tau_guess.data_ptr(), 1, self.tau_max, self.chi_thr,
-                                                  v['popt'].data_ptr(), v['dP'].data_ptr(), v['chisq'].data_ptr(), v['status'].data_ptr(),
-                                                  v['nfev'].data_ptr(), v['best'].data_ptr(), v['S2'].data_ptr(), v['C'].data_ptr(),
-                                                  v['tau'].data_ptr(), v['chi'].data_ptr(), v['K'].data_ptr(),
+                                                  self.tau_guess.data_ptr(), 1, self.tau_max, self.chi_thr, *res_ptrs,
                                                   work_ptr=grp.fitwork.data_ptr(),
                                                   dispatch_order_ptr=order_ptr,
                                                   tail_signal=grp.signal, tail_value=grp.epoch + 1 if grp.signal else 0)
             _stamp(events45, 5, st)
+            if fused:
+                # C(t), dC(t) as (lags, vectors) for every batch of the group: final behind the merged launch, not before
+                self.ctx.transpose_batched_dev(grp.CtT.data_ptr(), g, self.V, self.L, grp._Ct.data_ptr())
+                self.ctx.transpose_batched_dev(grp.dCtT.data_ptr(), g, self.V, self.L, grp._dCt.data_ptr())
+                if self._on_part is not None:
+                    ev = _event(st)
+                    for bv in grp.batches:
+                        self._on_part('ct', bv, ev)
             if grp.signal:
                 grp.epoch += 1
                 self.ctx.stream_write_signal(grp.signal, grp.epoch)
@@ -1217,6 +1325,7 @@ class GroupedPipeline(_Pipeline):
                 pending.remove(grp)
                 self.collect(grp, on_finished)
             grp.g, grp.first = g, k
+            grp.fused = self.fused_stats and grp.sums is not None
             grp.batches = [grp.batch(j) for j in range(g)]
             for j in range(g):
                 self._front_grouped(vecs, k + j, grp, j, None if events is None else events[k + j],

@@ -555,6 +555,19 @@ int sr_expfit_resjac_f64(sr_ctx *, const double *t /*[nRes,L]*/, const double *C
  * dx (nRes,P) the forward-difference steps (x + h) - x. */
 int sr_expfit_probe_f64(sr_ctx *, const double *t, const double *C, const double *sigma, const double *x, int nRes, int L, int P,
                         double tau_max, int jac_mode, int *geo, double *cost, double *f, double *JtJ, double *Jtf, double *dx);
+/* Test-facing probe of ONE trust-region step of the fit kernels: for each of nRes cases, what one pass of the solver's outer loop
+ * computes between the Jacobian and the trial evaluation, by the solver's own device code (Coleman-Li scaling, B = D A D + diag(g dv),
+ * solve_tr, select_step, strictly_feasible; sr_fit.hip), from x (nRes,P), JtJ (nRes,P,P; the lower triangle is read), Jtf (nRes,P),
+ * the radius Delta (nRes), the Levenberg parameter alpha carried over (nRes), m (nRes; the number of data points of the rank test) and
+ * the bounds the solver builds from tau_max.  No residue data.  mode 0 "step", outputs (host pointers): vec (nRes,8,P) = v, dv, d,
+ * g_h, p_h of solve_tr, step, step_h, xn after strictly_feasible(., 0); B (nRes,P,P); sca (nRes,8) = g_norm, theta, alpha after
+ * solve_tr, predicted, |step_h|, |step|, Delta, 0; flags (nRes,4) = solve_tr took the full-rank path, the branch of select_step
+ * (0 in bounds, 1 theta * step to the bound, 2 reflected, 3 Cauchy), factorisations of B + alpha I that met a non-positive pivot,
+ * passes of the alpha iteration.  mode 1 "init": vec rows 0, 1, 7 = v, dv and x after strictly_feasible(., 1e-10), sca[6] = the
+ * initial radius; everything else 0. */
+int sr_expfit_step_probe_f64(sr_ctx *, const double *x, const double *JtJ, const double *Jtf, const double *Delta,
+                             const double *alpha, const int *m, int nRes, int P, double tau_max, int mode, double *vec, double *B,
+                             double *sca, int *flags);
 /* Batched bounded least-squares fit, one workgroup per residue, whole solve on the device
  * (replaces the scipy curve_fit call of conduct_curve_fitting, fitting_Ct_functions.py:322-324:
  * bounds 0 <= C,S2 <= 1, 0 <= tau <= tau_max).  p0 in / popt out (nRes,P); pcov (nRes,P,P) is the

@@ -258,6 +258,480 @@ def expfit_eval_exact(t, y, w, x, lb, ub, jac_mode=0):
     return dict(f=f0, e=e, J=J, fi=fi, ei=ei, JtJ=J.T @ J, Jtf=J.T @ f0, cost=ld(0.5) * np.sum(f0 * f0), dx=dx)
 
 
+# ---- one trust-region step of the device fit (sr_expfit_step_probe_f64), restated -----------------------------------
+# The operations of sr_fit.hip (cl_scaling_vector, scaled_system, solve_tr, select_step, step_to_bound, min_quad_1d,
+# strictly_feasible) in the order the device states them, in a floating-point type of the caller's choice.  fma(a, b, c) is
+# written a * b + c: exact enough in long double, and in float64 the one-rounding difference is of the order the device's
+# reciprocal-square-root factor differs from a division anyway.
+STEP_EPS = 2.220446049250313e-16
+STEP_INJECT = ('reflect_wrong_sign', 'theta_on_to_tr', 'other_root', 'rank_m_is_N')
+
+
+def fit_bounds(P, tau_max):
+    K = P // 2
+    return np.zeros(P), np.array([tau_max if K <= i < 2 * K else 1.0 for i in range(P)])
+
+
+class _Margins(dict):
+    """smallest relative margin met per decision; `events`: which of the rarer paths the step went through"""
+
+    def __init__(self):
+        super().__init__()
+        self.events = set()
+
+    def note(self, name, a, b, scale=None):
+        a, b = float(a), float(b)
+        if not (np.isfinite(a) and np.isfinite(b)):
+            return
+        s = max(abs(a), abs(b)) if scale is None else max(float(scale), abs(a), abs(b))
+        r = abs(a - b) / s if s > 0 else np.inf
+        self[name] = min(self.get(name, np.inf), r)
+
+
+def _dot(ft, a, b):
+    s = ft(0)
+    for u, w in zip(a, b):
+        s = u * w + s
+    return s
+
+
+def _quad(ft, B, u, s):
+    q = ft(0)
+    n = len(s)
+    for i in range(n):
+        r = ft(0)
+        for j in range(n):
+            r = B[i][j] * s[j] + r
+        q = u[i] * r + q
+    return q
+
+
+def _chol(ft, B, alpha, T, marg, name):
+    """cholN: returns (ok, L strict lower, inv, lmin2, failures)."""
+    n = len(B)
+    L = [[ft(0)] * n for _ in range(n)]
+    inv = [ft(0)] * n
+    lmin2 = ft(1e300)
+    fails = 0
+    for i in range(n):
+        for j in range(i + 1):
+            s = B[i][j] + (alpha if i == j else ft(0))
+            for k in range(j):
+                s = -L[i][k] * L[j][k] + s
+            if i == j:
+                # the pivot's rounding error is of the order u * (what was subtracted from the diagonal)
+                marg.note(name, s, T, scale=1e-8 * float(abs(B[i][i] + alpha - s)))
+                if not (s > 0):
+                    fails += 1
+                    s = ft(1)
+                lmin2 = min(lmin2, s)
+                inv[i] = ft(1) / np.sqrt(s)
+            else:
+                L[i][j] = s * inv[j]
+    return fails == 0, L, inv, lmin2, fails
+
+
+def _fwd(ft, L, inv, b):
+    z = []
+    for i in range(len(b)):
+        s = b[i]
+        for k in range(i):
+            s = -L[i][k] * z[k] + s
+        z.append(s * inv[i])
+    return z
+
+
+def _bwd(ft, L, inv, z):
+    n = len(z)
+    p = [ft(0)] * n
+    for i in range(n - 1, -1, -1):
+        s = z[i]
+        for k in range(i + 1, n):
+            s = -L[k][i] * p[k] + s
+        p[i] = s * inv[i]
+    return p
+
+
+def _phi(ft, L, inv, g, Delta):
+    z = _fwd(ft, L, inv, g)
+    p = [-u for u in _bwd(ft, L, inv, z)]
+    q = _fwd(ft, L, inv, p)
+    pn = np.sqrt(_dot(ft, p, p))
+    return p, pn - Delta, -_dot(ft, q, q) / pn
+
+
+def _ldl_solve(ft, B, alpha, g):
+    """ldl_solveN: (B + alpha I)^-1 g through L D L^T without pivoting, for the indefinite matrix a negative alpha makes."""
+    n = len(g)
+    L = [[ft(0)] * n for _ in range(n)]
+    D, dinv = [ft(0)] * n, [ft(0)] * n
+    for i in range(n):
+        for j in range(i + 1):
+            s = B[i][j] + (alpha if i == j else ft(0))
+            for k in range(j):
+                s = -(L[i][k] * D[k]) * L[j][k] + s
+            if i == j:
+                if s == 0:
+                    s = ft(1)
+                D[i], dinv[i] = s, ft(1) / s
+            else:
+                L[i][j] = s * dinv[j]
+    y = []
+    for i in range(n):
+        s = g[i]
+        for k in range(i):
+            s = -L[i][k] * y[k] + s
+        y.append(s)
+    p = [ft(0)] * n
+    for i in range(n - 1, -1, -1):
+        s = y[i] * dinv[i]
+        for k in range(i + 1, n):
+            s = -L[k][i] * p[k] + s
+        p[i] = s
+    return p
+
+
+def _solve_tr(ft, B, g, m, Delta, alpha, marg, inject):
+    n = len(g)
+    dmax = max(B[i][i] for i in range(n))
+    thr = ft(STEP_EPS) * ft(n if inject == 'rank_m_is_N' else m)
+    T = thr * thr * dmax
+    ok, L, inv, lmin2, _ = _chol(ft, B, ft(0), T, marg, 'rank')
+    full_rank = bool(ok and lmin2 > T)
+    info = dict(full_rank=full_rank, iters=0, piv_fail=0)
+    alpha_upper = np.sqrt(_dot(ft, g, g)) / Delta
+    alpha_lower = ft(0)
+    if full_rank:
+        p, phi, phip = _phi(ft, L, inv, g, Delta)
+        marg.note('phi_le_0', phi + Delta, Delta)
+        if phi <= 0:
+            return p, ft(0), info
+        alpha_lower = -phi / phip
+
+    def restart():
+        a, b = ft(0.001) * alpha_upper, np.sqrt(alpha_lower * alpha_upper)
+        return max(a, b)
+    if not full_rank and alpha == 0:
+        alpha = restart()
+    for _ in range(10):
+        marg.note('alpha_clamp', alpha, alpha_lower)
+        marg.note('alpha_clamp', alpha, alpha_upper)
+        if alpha < alpha_lower or alpha > alpha_upper:
+            marg.events.add('alpha_clamped')
+            alpha = restart()
+        ok, L, inv, lmin2, fails = _chol(ft, B, alpha, ft(0), marg, 'pivot')
+        info['piv_fail'] += 0 if ok else 1
+        info['iters'] += 1
+        p, phi, phip = _phi(ft, L, inv, g, Delta)
+        if not abs(phi) < ft(0.01) * Delta:       # alpha_upper is only read again when the iteration goes on
+            marg.note('phi_lt_0', phi, 0, scale=Delta)
+        if phi < 0:
+            alpha_upper = alpha
+        ratio = phi / phip
+        alpha_lower = max(alpha_lower, alpha - ratio)
+        alpha = alpha - (phi + Delta) * ratio / Delta
+        marg.note('phi_exit', abs(phi), ft(0.01) * Delta)
+        if abs(phi) < ft(0.01) * Delta:
+            break
+    else:
+        marg.events.add('iterations_exhausted')
+    ok, L, inv, lmin2, fails = _chol(ft, B, alpha, ft(0), marg, 'pivot')
+    info['piv_fail'] += 0 if ok else 1
+    p = _bwd(ft, L, inv, _fwd(ft, L, inv, g)) if ok else _ldl_solve(ft, B, alpha, g)
+    sc = -Delta / np.sqrt(_dot(ft, p, p))
+    return [u * sc for u in p], alpha, info
+
+
+def _step_to_bound(ft, x, s, lb, ub, marg):
+    inf = ft(np.inf)
+    steps = [inf if s[i] == 0 else max((lb[i] - x[i]) / s[i], (ub[i] - x[i]) / s[i]) for i in range(len(x))]
+    mn = min(steps)
+    if sum(1 for st in steps if st == mn) > 1:
+        marg.events.add('hits_tie')
+    if any(u == 0 for u in s):
+        marg.events.add('zero_step_component')
+    for st in steps:
+        if st != mn:
+            marg.note('hits', st, mn)
+    hits = [(1 if s[i] > 0 else (-1 if s[i] < 0 else 0)) if steps[i] == mn else 0 for i in range(len(x))]
+    return mn, hits
+
+
+def _min_quad_1d(ft, a, b, lo, hi, c, marg):
+    t, y = lo, lo * (a * lo + b) + c
+    yh = hi * (a * hi + b) + c
+    if hi != lo:
+        marg.note('quad_value', yh - c, y - c)
+    if yh < y:
+        y, t = yh, hi
+    if a != 0:
+        ex = ft(-0.5) * b / a
+        marg.note('quad_interior', ex, lo, scale=abs(hi))
+        marg.note('quad_interior', ex, hi, scale=abs(lo))
+        if lo < ex < hi:
+            ye = ex * (a * ex + b) + c
+            marg.note('quad_value', ye - c, y - c)
+            if ye < y:
+                y, t = ye, ex
+    return t, y
+
+
+def _intersect_tr(ft, x, s, Delta):
+    """common.py:intersect_trust_region as select_step states it: both roots of |x + t s| = Delta, unsorted."""
+    a, b, c = _dot(ft, s, s), _dot(ft, x, s), _dot(ft, x, x) - Delta * Delta
+    dd = np.sqrt(b * b - a * c)
+    q = -(b + np.copysign(dd, b))
+    return q / a, c / q
+
+
+def _select_step(ft, x, B, g_h, p, p_h, d, Delta, lb, ub, theta, marg, inject):
+    n = len(x)
+    R = range(n)
+    inb = True
+    for i in R:
+        xn = x[i] + p[i]
+        sc = max(abs(float(x[i])), abs(float(p[i])))
+        marg.note('in_bounds', xn, lb[i], scale=sc)
+        marg.note('in_bounds', xn, ub[i], scale=sc)
+        inb = inb and xn >= lb[i] and xn <= ub[i]
+    half = ft(0.5)
+    if inb:
+        return list(p), list(p_h), -(half * _quad(ft, B, p_h, p_h) + _dot(ft, g_h, p_h)), 0
+    p_stride, hits = _step_to_bound(ft, x, p, lb, ub, marg)
+    if inject == 'reflect_wrong_sign':
+        hits = [0 if h else 1 for h in hits]
+    r_h = [-p_h[i] if hits[i] != 0 else p_h[i] for i in R]
+    r = [d[i] * r_h[i] for i in R]
+    p = [u * p_stride for u in p]
+    p_h = [u * p_stride for u in p_h]
+    xb = [x[i] + p[i] for i in R]
+    t1, t2 = _intersect_tr(ft, p_h, r_h, Delta)
+    marg.note('root', t1, t2)
+    to_tr = t2 if t1 < t2 else t1
+    if inject == 'other_root':
+        to_tr = t1 if t1 < t2 else t2
+    to_bound, _ = _step_to_bound(ft, xb, r, lb, ub, marg)
+    marg.note('r_stride_eq', to_bound, to_tr)
+    r_stride = min(to_bound, to_tr)
+    marg.note('r_stride_pos', r_stride, 0, scale=max(abs(float(to_bound)), abs(float(to_tr))))
+    if r_stride > 0:
+        r_stride_l = (1 - theta) * p_stride / r_stride
+        if inject == 'theta_on_to_tr':
+            r_stride_u = to_bound if r_stride == to_bound else theta * to_tr
+        else:
+            r_stride_u = theta * to_bound if r_stride == to_bound else to_tr
+    else:
+        marg.events.add('r_stride_nonpositive')
+        r_stride_l, r_stride_u = ft(0), ft(-1)
+    marg.note('r_l_le_u', r_stride_l, r_stride_u)
+    if r_stride_l <= r_stride_u:
+        qa = half * _quad(ft, B, r_h, r_h)
+        qb = _dot(ft, g_h, r_h) + _quad(ft, B, p_h, r_h)
+        qc = half * _quad(ft, B, p_h, p_h) + _dot(ft, g_h, p_h)
+        r_stride, r_value = _min_quad_1d(ft, qa, qb, r_stride_l, r_stride_u, qc, marg)
+        r_h = [r_h[i] * r_stride + p_h[i] for i in R]
+        r = [r_h[i] * d[i] for i in R]
+    else:
+        marg.events.add('r_value_inf')
+        r_value = ft(np.inf)
+    p = [u * theta for u in p]
+    p_h = [u * theta for u in p_h]
+    p_value = half * _quad(ft, B, p_h, p_h) + _dot(ft, g_h, p_h)
+    ag_h = [-u for u in g_h]
+    ag = [d[i] * ag_h[i] for i in R]
+    to_tr2 = Delta / np.sqrt(_dot(ft, ag_h, ag_h))
+    to_bound2, _ = _step_to_bound(ft, x, ag, lb, ub, marg)
+    marg.note('to_bound2_lt_tr2', to_bound2, to_tr2)
+    if to_bound2 < to_tr2:
+        marg.events.add('cauchy_to_bound')
+    ag_stride = theta * to_bound2 if to_bound2 < to_tr2 else to_tr2
+    ag_stride, ag_value = _min_quad_1d(ft, half * _quad(ft, B, ag_h, ag_h), _dot(ft, g_h, ag_h), ft(0), ag_stride, ft(0), marg)
+    ag_h = [u * ag_stride for u in ag_h]
+    ag = [u * ag_stride for u in ag]
+    vals = sorted([float(p_value), float(r_value), float(ag_value)])
+    marg.note('value_cmp', vals[0], vals[1])
+    if p_value < r_value and p_value < ag_value:
+        return p, p_h, -p_value, 1
+    if r_value < p_value and r_value < ag_value:
+        return r, r_h, -r_value, 2
+    return ag, ag_h, -ag_value, 3
+
+
+def _strictly_feasible(ft, x, lb, ub, rstep):
+    out = []
+    for xi, l, u in zip(x, lb, ub):
+        if rstep == 0:
+            lo_act, up_act = xi <= l, xi >= u
+        else:
+            lt, ut = ft(rstep) * max(ft(1), abs(l)), ft(rstep) * max(ft(1), abs(u))
+            lo_act, up_act = (xi - l) <= min(u - xi, lt), (u - xi) <= min(xi - l, ut)
+        xn = xi
+        if rstep == 0:
+            if lo_act:
+                xn = ft(np.nextafter(np.float64(l), np.float64(u)))
+            if up_act:
+                xn = ft(np.nextafter(np.float64(u), np.float64(l)))
+        else:
+            if lo_act:
+                xn = l + ft(rstep) * max(ft(1), abs(l))
+            if up_act:
+                xn = u - ft(rstep) * max(ft(1), abs(u))
+        if xn < l or xn > u:
+            xn = ft(0.5) * (l + u)
+        out.append(xn)
+    return out
+
+
+def _cl_scaling(ft, x, g, lb, ub):
+    v, dv = [], []
+    for xi, gi, l, u in zip(x, g, lb, ub):
+        if gi > 0:
+            v.append(xi - l), dv.append(ft(1))
+        elif gi < 0:
+            v.append(u - xi), dv.append(ft(-1))
+        else:
+            v.append(ft(1)), dv.append(ft(0))
+    return v, dv
+
+
+def _trf_step(ft, x, A, g, tau_max, m, Delta, alpha_in, mode='step', inject=None):
+    assert inject is None or inject in STEP_INJECT
+    x64 = np.asarray(x, dtype=np.float64)
+    n = x64.size
+    lb64, ub64 = fit_bounds(n, tau_max)
+    lb, ub = [ft(u) for u in lb64], [ft(u) for u in ub64]
+    x = [ft(u) for u in x64]
+    g = [ft(u) for u in np.asarray(g, dtype=np.float64)]
+    arr = lambda a: np.array(a, dtype=ft)                                                                # noqa: E731
+    if mode in ('init', 'radius'):
+        # 'radius': x is taken as it is (the float64 point strictly_feasible made: v = ub - x of a point 1e-10 ub below ub moves by
+        # 1e-6 relative when x moves by one ulp, so the radius of the long-double feasible point is another number)
+        if mode == 'init':
+            x = _strictly_feasible(ft, x, lb, ub, 1e-10)
+        v, dv = _cl_scaling(ft, x, g, lb, ub)
+        Delta = np.sqrt(_dot(ft, [a / np.sqrt(b) for a, b in zip(x, v)], [a / np.sqrt(b) for a, b in zip(x, v)]))
+        return dict(x=arr(x), v=arr(v), dv=arr(dv), Delta=ft(1) if Delta == 0 else Delta)
+    A64 = np.asarray(A, dtype=np.float64).reshape(n, n)
+    A = [[ft(A64[max(i, j), min(i, j)]) for j in range(n)] for i in range(n)]
+    Delta, alpha = ft(np.float64(Delta)), ft(np.float64(alpha_in))
+    marg = _Margins()
+    v, dv = _cl_scaling(ft, x, g, lb, ub)
+    g_norm = max(abs(a * b) for a, b in zip(g, v))
+    theta = max(ft(0.995), 1 - g_norm)
+    d = [np.sqrt(u) for u in v]
+    g_h = [a * b for a, b in zip(d, g)]
+    B = [[(A[i][j] * d[max(i, j)]) * d[min(i, j)] + (g[i] * dv[i] if i == j else ft(0)) for j in range(n)] for i in range(n)]
+    p_h, alpha, info = _solve_tr(ft, B, g_h, m, Delta, alpha, marg, inject)
+    p = [a * b for a, b in zip(d, p_h)]
+    step, step_h, predicted, branch = _select_step(ft, x, B, g_h, p, p_h, d, Delta, lb, ub, theta, marg, inject)
+    xn_raw = [a + b for a, b in zip(x, step)]
+    # strictly_feasible(., 0) acts on the float64 trial point
+    xn = _strictly_feasible(ft, xn_raw, lb, ub, 0.0)
+    return dict(v=arr(v), dv=arr(dv), g_norm=g_norm, theta=theta, d=arr(d), g_h=arr(g_h), B=arr(B), p_h=arr(p_h), alpha=alpha,
+                full_rank=int(info['full_rank']), iterations=info['iters'], pivot_failures=info['piv_fail'], step=arr(step),
+                step_h=arr(step_h), predicted=predicted, branch=branch, xn=arr(xn), xn_raw=arr(xn_raw),
+                step_h_norm=np.sqrt(_dot(ft, step_h, step_h)), step_norm=np.sqrt(_dot(ft, step, step)), margins=dict(marg),
+                events=sorted(marg.events), Delta_in=Delta)
+
+
+def trf_step_exact(x, A, g, tau_max, m, Delta, alpha_in, mode='step', inject=None):
+    """One trust-region step of the device fit (sr_expfit_step_probe_f64) in np.longdouble on the float64 inputs: what trf_solve
+    computes between a Jacobian and the trial evaluation.  Returns the probe's outputs plus `margins`: per decision the code takes
+    (in_bounds, phi_le_0, rank, pivot, alpha_clamp, phi_lt_0, phi_exit, root, r_stride_pos, r_stride_eq, r_l_le_u, value_cmp, hits,
+    to_bound2_lt_tr2, quad_interior, quad_value) the smallest relative distance between the two sides met on the way.  inject: one
+    of STEP_INJECT, a deliberate error (the tests' teeth)."""
+    return _trf_step(np.longdouble, x, A, g, tau_max, m, Delta, alpha_in, mode, inject)
+
+
+def step_cases(fixture):
+    """The cases of tests/golden/fit_step_cases.npz (or the dict it is saved from) as ((x, A, g, tau_max, m, Delta, alpha_in), class)
+    in the fixture's order: by model order, then by position."""
+    classes = [str(c) for c in fixture['classes']]
+    for P in [int(n) for n in fixture['orders']]:
+        par = fixture['par_%d' % P]
+        for i in range(par.shape[0]):
+            yield ((fixture['x_%d' % P][i], fixture['A_%d' % P][i], fixture['g_%d' % P][i], float(par[i, 0]), int(par[i, 1]),
+                    float(par[i, 2]), float(par[i, 3])), classes[int(fixture['cls_%d' % P][i])])
+
+
+def step_kappa(B, alpha):
+    """kappa_2(B + alpha I) from float64 eigenvalues, capped at 1 / u (below u * lambda_max the smallest one is rounding noise)."""
+    lam = np.linalg.eigvalsh(np.asarray(B, dtype=np.float64)) + float(alpha)
+    return float(lam[-1] / max(lam[0], 2.0 ** -53 * lam[-1]))
+
+
+def step_scales(ex):
+    """The scale of each output of a step that the conditioning bar multiplies: Delta for the scaled vectors p_h and step_h,
+    Delta * max d for step and xn (step = d step_h), |g_h| / Delta for alpha (its upper bound in solve_tr), |predicted|."""
+    D = float(ex['Delta_in'])
+    dm = float(np.max(np.asarray(ex['d'], dtype=np.float64)))
+    gn = float(np.sqrt(np.sum(np.asarray(ex['g_h'], dtype=np.float64) ** 2)))
+    return dict(alpha=gn / D, p_h=D, step_h=D, step=D * dm, xn=D * dm, predicted=abs(float(ex['predicted'])))
+
+
+def step_ratios(ex, other):
+    """|other - ex| of alpha, p_h, step, step_h, predicted and xn in units of kappa_2(B + alpha I) u scale (step_scales)."""
+    kap = step_kappa(ex['B'], ex['alpha'])
+    sc = step_scales(ex)
+    out = {}
+    for k, s in sc.items():
+        err = np.abs(np.asarray(other[k], dtype=np.longdouble) - np.asarray(ex[k], dtype=np.longdouble))
+        if k == 'xn':       # x + step is rounded at the size of x, whatever the size of the step
+            err = np.maximum(err - 2.0 ** -52 * np.abs(np.asarray(ex[k], dtype=np.longdouble)), 0)
+        err = np.max(err)
+        out[k] =float(err) / (kap * 2.0 ** -53 * s) if s > 0 else (0.0 if err == 0 else np.inf)
+    return out
+
+
+def step_svd(B, g_h):
+    """s, V, uf of a factor of the long-double B, each rounded to float64 from a 60-digit eigendecomposition (a float64 one knows
+    the small eigenvalues only to u lambda_max, which is all of them at kappa ~ 1 / u)."""
+    import mpmath as mp
+
+    def to_mp(a):
+        hi = np.float64(a)
+        return mp.mpf(float(hi)) + mp.mpf(float(np.longdouble(a) - np.longdouble(hi)))
+    n = len(g_h)
+    with mp.workdps(60):
+        M = mp.matrix(n, n)
+        for i in range(n):
+            for j in range(n):
+                M[i, j] = to_mp(B[max(i, j)][min(i, j)])
+        E, Q = mp.eigsy(M)
+        order = sorted(range(n), key=lambda k: -E[k])
+        gm = [to_mp(a) for a in g_h]
+        s, uf = [], []
+        for k in order:
+            sk = mp.sqrt(E[k]) if E[k] > 0 else mp.mpf(0)
+            s.append(float(sk))
+            uf.append(float(sum(Q[i, k] * gm[i] for i in range(n)) / sk) if sk > 0 else 0.0)
+        V = np.array([[float(Q[i, k]) for k in order] for i in range(n)])
+    return np.array(s), V, np.array(uf)
+
+
+def scipy_step(case, ex):
+    """scipy's own step for a case: solve_lsq_trust_region on the SVD of a factor of the case's B (step_svd), then
+    trf.select_step.  ex: trf_step_exact of the case (its v, d, g_h, B, theta are the inputs).  Returns p_h, alpha, iterations,
+    step, step_h, predicted."""
+    from scipy.optimize._lsq import common as C, trf
+    x, A, g, tau_max, m, Delta, alpha_in = case
+    n = len(x)
+    lb, ub = fit_bounds(n, tau_max)
+    s, V, uf = step_svd(ex['B'], ex['g_h'])
+    p_h, alpha, nit = C.solve_lsq_trust_region(n, m, uf, s, V, Delta, initial_alpha=alpha_in)
+    d, g_h = np.asarray(ex['d'], dtype=np.float64), np.asarray(ex['g_h'], dtype=np.float64)
+    step, step_h, pred = trf.select_step(np.asarray(x, dtype=np.float64), s[:, None] * V.T, np.zeros(n), g_h, d * p_h, p_h.copy(), d,
+                                         Delta, lb, ub, float(ex['theta']))
+    return dict(p_h=p_h, alpha=alpha, iterations=nit, step=step, step_h=step_h, predicted=pred)
+
+
+def trf_step_f64(x, A, g, tau_max, m, Delta, alpha_in, mode='step', inject=None):
+    """The same operations in float64 numpy scalars: the yardstick for how far a faithful float64 execution lies from
+    trf_step_exact."""
+    with np.errstate(all='ignore'):
+        return _trf_step(np.float64, x, A, g, tau_max, m, Delta, alpha_in, mode, inject)
+
+
 def calc_chiSq(t, y, dy, S2, C, tau, zeta=1.0):
     """fitting_Ct_functions.py:266-276: mean(resid^2 / sigma) -- sigma, not sigma^2."""
     model = zeta * (S2 + np.sum(np.asarray(C)[:, None] * np.exp(-1.0 * t[None, :] / np.asarray(tau)[:, None]), axis=0))

@@ -83,6 +83,9 @@ SIGNATURES = {
     # (ctx, t, C, sigma, x, nRes, L, P, tau_max, jac_mode, geo, cost, f, JtJ, Jtf, dx)
     'sr_expfit_probe_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (ctx, x, JtJ, Jtf, Delta, alpha, m, nRes, P, tau_max, mode, vec, B, sca, flags)
+    'sr_expfit_step_probe_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'sr_expfit_lm_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double,
                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'sr_expfit_lm_f64_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double,

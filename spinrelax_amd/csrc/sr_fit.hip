@@ -302,6 +302,49 @@ __device__ __forceinline__ void bwdN(const double *Lf, const double *inv, const 
     }
 }
 
+// p = (B + alpha I)^-1 g for a matrix that is NOT positive definite: L D L^T without pivoting (Lf: the strict lower triangle of the
+// unit triangular L; D may have either sign), then L z = g, z /= D, L^T p = z.  Only solve_tr's last solve uses it, when the update
+// of the last pass has left alpha negative -- scipy's SVD form evaluates V (s u_f / (s^2 + alpha)) for such an alpha all the same, and
+// this is that vector (tests/test_gpu_fit_step.py: within 1e-14 Delta of scipy's on the committed cases; the pivots there are
+// >= 2.7e-14 of the largest).  A pivot that is exactly 0 is replaced by 1.0, as cholN does.
+template <int N>
+__device__ __forceinline__ void ldl_solveN(const double *B, double alpha, double *Lf, const double *g, double *p)
+{
+    double dinv[N], z[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = B[tri(i, j)] + (i == j ? alpha : 0.0);
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = fma(-(Lf[tri(i, k)] * z[k]), Lf[tri(j, k)], s);     // z[k] = D_k until the solves
+            if (i == j) {
+                if (s == 0.0) s = 1.0;
+                z[i] = s;
+                dinv[i] = 1.0 / s;
+            } else {
+                Lf[tri(i, j)] = s * dinv[j];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double s = g[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s = fma(-Lf[tri(i, k)], p[k], s);
+        p[i] = s;                                                                              // p = L^-1 g
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+        double s = p[i] * dinv[i];
+#pragma unroll
+        for (int k = i + 1; k < N; ++k) s = fma(-Lf[tri(k, i)], z[k], s);
+        z[i] = s;
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) p[i] = z[i];
+}
+
 // phi(alpha) = ||p(alpha)|| - Delta, phi' = -(p^T (B+alpha I)^-1 p)/||p||, p = -(B+alpha I)^-1 g.
 // (common.py:phi_and_derivative expressed through the Cholesky factor: with L L^T = B + alpha I,
 //  z = L^-1 g, p = -L^-T z, q = L^-1 p:  p^T (B+alpha I)^-1 p = ||q||^2.)
@@ -320,9 +363,29 @@ __device__ __forceinline__ void phi_from_factor(const double *Lf, const double *
     phi_prime = -dotN<N>(q, q) / pn;
 }
 
+// What the step probe (k_step_probe) has solve_tr and select_step write down on their way.  The solver passes no note: the
+// parameter pack is empty there, and its instances have the signature and the code they had without it; the probe's are
+// instances of their own (Note = StepNote *), so the solver's keep their call sites.
+struct StepNote {
+    int full_rank;      // solve_tr took the full-rank path (Gauss-Newton step evaluated)
+    int iters;          // passes of More's iteration
+    int piv_fail;       // factorisations of B + alpha I inside the iteration that met a non-positive pivot (the probe adds the last one)
+    int branch;         // select_step: 0 in bounds, 1 theta * step to the bound, 2 reflected, 3 Cauchy
+};
+__device__ __forceinline__ void note_rank(StepNote *n, bool full_rank) { n->full_rank = full_rank; }
+__device__ __forceinline__ void note_factor(StepNote *n, bool ok, bool in_loop) { n->piv_fail += !ok; n->iters += in_loop; }
+__device__ __forceinline__ void note_branch(StepNote *n, int branch) { n->branch = branch; }
+
 // common.py:solve_lsq_trust_region
-template <int N>
-__device__ void solve_tr(const double *B, const double *g, int m, double Delta, double &alpha, double *p, double *lfbuf)
+// The update of the 10th pass can leave alpha negative (scipy's does too: same alpha, same 10 passes; about 1 step in 600 at 7
+// parameters and more).  B + alpha I is then indefinite and scipy's SVD form evaluates -(B + alpha I)^-1 g all the same; so does
+// the last solve here, by ldl_solveN when the Cholesky factorisation meets a non-positive pivot.  (Until that was tested one step
+// at a time -- tests/test_gpu_fit_step.py, the `breakdown` cases -- the factor with cholN's substituted pivots was used there: a
+// step up to one Delta away from scipy's, with predicted < 0 on some.)  Inside the iteration a failed factorisation is still used
+// as cholN leaves it; none of the committed cases meets one there (every one has exactly one failed factorisation, the last).
+template <int N, class... Note>
+__device__ void solve_tr(const double *B, const double *g, int m, double Delta, double &alpha, double *p, double *lfbuf,
+                         Note... note)
 {
     // rank test of scipy: s_min > EPS*m*s_max on the singular values of the augmented Jacobian.  Here:
     // B is accepted as full rank when its Cholesky factorisation succeeds with pivots above the
@@ -337,6 +400,7 @@ __device__ void solve_tr(const double *B, const double *g, int m, double Delta, 
         const double thr = kEPS * (double)m;
         if (!(lmin2 > thr * thr * dmax)) full_rank = false;
     }
+    if constexpr (sizeof...(Note) > 0) note_rank(note..., full_rank);
     double alpha_upper = normN<N>(g) / Delta;
     double alpha_lower = 0.0;
     if (full_rank) {
@@ -349,7 +413,9 @@ __device__ void solve_tr(const double *B, const double *g, int m, double Delta, 
     for (int it = 0; it < 10; ++it) {
         if (alpha < alpha_lower || alpha > alpha_upper) alpha = fmax(0.001 * alpha_upper, sqrt(alpha_lower * alpha_upper));
         double phi, phip;
-        cholN<N>(B, alpha, Lf, inv, lmin2);
+        const bool ok = cholN<N>(B, alpha, Lf, inv, lmin2);
+        if constexpr (sizeof...(Note) > 0) note_factor(note..., ok, true);
+        (void)ok;
         phi_from_factor<N>(Lf, inv, g, Delta, p, phi, phip);
         if (phi < 0) alpha_upper = alpha;
         const double ratio = phi / phip;
@@ -359,9 +425,12 @@ __device__ void solve_tr(const double *B, const double *g, int m, double Delta, 
     }
     {
         double z[N];
-        cholN<N>(B, alpha, Lf, inv, lmin2);
-        fwdN<N>(Lf, inv, g, z);
-        bwdN<N>(Lf, inv, z, p);
+        if (cholN<N>(B, alpha, Lf, inv, lmin2)) {      // (the probe repeats this factorisation for its count of failed pivots)
+            fwdN<N>(Lf, inv, g, z);
+            bwdN<N>(Lf, inv, z, p);
+        } else {
+            ldl_solveN<N>(B, alpha, Lf, g, p);         // alpha < 0 after the last pass: B + alpha I is indefinite
+        }
     }
     const double sc = -Delta / normN<N>(p);
 #pragma unroll
@@ -402,10 +471,10 @@ __device__ __forceinline__ void min_quad_1d(double a, double b, double lo, doubl
 }
 
 // trf.py:select_step.  B = J_h^T J_h + diag_h, so every quadratic form of the original is a form in B.
-template <int N>
+template <int N, class... Note>
 __device__ void select_step(const double *x, const double *B, const double *g_h, double *p, double *p_h,
                             const double *d, double Delta, const double *lb, const double *ub, double theta,
-                            double *step, double *step_h, double &predicted)
+                            double *step, double *step_h, double &predicted, Note... note)
 {
     bool inb = true;
 #pragma unroll
@@ -418,6 +487,7 @@ __device__ void select_step(const double *x, const double *B, const double *g_h,
 #pragma unroll
         for (int i = 0; i < N; ++i) { step[i] = p[i]; step_h[i] = p_h[i]; }
         predicted = -pv;
+        if constexpr (sizeof...(Note) > 0) note_branch(note..., 0);
         return;
     }
     int hits[N];
@@ -489,14 +559,17 @@ __device__ void select_step(const double *x, const double *B, const double *g_h,
 #pragma unroll
         for (int i = 0; i < N; ++i) { step[i] = p[i]; step_h[i] = p_h[i]; }
         predicted = -p_value;
+        if constexpr (sizeof...(Note) > 0) note_branch(note..., 1);
     } else if (r_value < p_value && r_value < ag_value) {
 #pragma unroll
         for (int i = 0; i < N; ++i) { step[i] = r[i]; step_h[i] = r_h[i]; }
         predicted = -r_value;
+        if constexpr (sizeof...(Note) > 0) note_branch(note..., 2);
     } else {
 #pragma unroll
         for (int i = 0; i < N; ++i) { step[i] = ag[i]; step_h[i] = ag_h[i]; }
         predicted = -ag_value;
+        if constexpr (sizeof...(Note) > 0) note_branch(note..., 3);
     }
 }
 
@@ -960,6 +1033,76 @@ struct SolveParams {
     double tau_max, ftol, xtol, gtol;
     int max_nfev, jac_mode;
 };
+
+// ---- the step probe's copy of the lines of one trust-region step that trf_solve has inline --------------------
+// RESTATED, not shared: with trf_solve calling these helpers (all forced inline) every k_trf / search_order instance came out
+// with another register allocation (scripts/dev/isa_diff.py: 120 of 156 functions differ), and the solver's code was not to
+// change for a test.  Each helper is the corresponding block of trf_solve, copied statement by statement; whoever edits one edits
+// the other.
+// common.py:CL_scaling_vector
+template <int N>
+__device__ __forceinline__ void cl_scaling_vector(const double *x, const double *g, const double *lb, const double *ub,
+                                                  double *v, double *dv)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        v[i] = 1.0; dv[i] = 0.0;
+        if (g[i] < 0) { v[i] = ub[i] - x[i]; dv[i] = -1.0; }
+        if (g[i] > 0) { v[i] = x[i] - lb[i]; dv[i] = 1.0; }
+    }
+}
+// the same at the head of an iteration: g, v and dv go to scalar registers (see below)
+template <int N>
+__device__ __forceinline__ void cl_scaling_vector_uni(const double *x, double *g, const double *lb, const double *ub,
+                                                      double *v, double *dv)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        g[i] = uni(g[i]);
+        v[i] = 1.0; dv[i] = 0.0;
+        if (g[i] < 0) { v[i] = ub[i] - x[i]; dv[i] = -1.0; }
+        if (g[i] > 0) { v[i] = x[i] - lb[i]; dv[i] = 1.0; }
+        v[i] = uni(v[i]);
+        dv[i] = uni(dv[i]);
+    }
+}
+// trf.py: Delta = norm(x0 * scale_inv / v**0.5), 1 when that is 0
+template <int N>
+__device__ __forceinline__ double initial_radius(const double *x, const double *v)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) { const double q = x[i] / sqrt(v[i]); s = fma(q, q, s); }
+    double Delta = sqrt(s);
+    if (Delta == 0) Delta = 1.0;
+    return Delta;
+}
+// norm(g * v, inf)
+template <int N>
+__device__ __forceinline__ double scaled_gradient_norm(const double *g, const double *v)
+{
+    double g_norm = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) g_norm = fmax(g_norm, fabs(g[i] * v[i]));
+    return g_norm;
+}
+// trf.py: theta = max(0.995, 1 - g_norm)
+__device__ __forceinline__ double step_theta(double g_norm) { return fmax(0.995, 1 - g_norm); }
+// d = v**0.5, g_h = d g and B = D A D + diag(g dv) (packed; stored by the thread `writer` is true for)
+template <int N>
+__device__ __forceinline__ void scaled_system(const double *A, const double *g, const double *v, const double *dv, double *d,
+                                              double *g_h, double *B, bool writer)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) { d[i] = uni(sqrt(v[i])); g_h[i] = uni(d[i] * g[i]); }
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            const double b = (A[tri(i, j)] * d[i]) * d[j] + (i == j ? g[i] * dv[i] : 0.0);
+            if (writer) B[tri(i, j)] = b;
+        }
+}
 
 // Workgroup-uniform n-vectors of the solver in SGPRs (round 4).  x, the gradient g, the Coleman-Li scaling v / dv, d = sqrt(v) and
 // g_h = d g are the same in every lane; the compiler cannot know that and keeps them in VGPRs -- 2 per double, ~110 registers at
@@ -1492,10 +1635,103 @@ __global__ __launch_bounds__(W * 64) void k_fit_probe(ProbeArgs a)
     }
 }
 
+// ---- step probe (test-facing) ---------------------------------------------------------------------------
+// What one pass of trf_solve's outer loop computes between the Jacobian and the trial evaluation, for a given iterate: x, A = J^T J,
+// g = J^T f, Delta and the alpha carried over, without any residue data.  mode 0 ("step"): the Coleman-Li scaling, B, solve_tr,
+// select_step, the trial point.  mode 1 ("init"): strictly_feasible(x, 1e-10), the scaling there and the initial radius.  The
+// shared pieces are the solver's own templates and helpers (cl_scaling_vector*, scaled_system, ...); solve_tr and select_step are
+// instantiated with a StepNote, which changes nothing in what they compute.  One workgroup per case, the leader wave does the work
+// as in trf_solve; A, B and the Cholesky factor live in the LDS areas the solver uses.
+struct StepArgs {
+    const double *x, *A, *g;          // (nRes, N), (nRes, N, N) symmetric (the lower triangle is read), (nRes, N)
+    const double *Delta, *alpha;      // (nRes)
+    const int *m;                     // (nRes) number of data points, for the rank threshold
+    double tau_max;
+    int nRes, L, mode;                // L = 0: nothing is staged
+    double *vec;                      // (nRes, 8, N): v, dv, d, g_h, p_h, step, step_h, xn (mode 1: v, dv and xn = the feasible x)
+    double *B;                        // (nRes, N, N)
+    double *sca;                      // (nRes, 8): g_norm, theta, alpha, predicted, |step_h|, |step|, initial Delta (mode 1), 0
+    int *flags;                       // (nRes, 4): StepNote
+};
+
+template <int N, int W, bool LDS>
+__global__ __launch_bounds__(W * 64) void k_step_probe(StepArgs a)
+{
+    constexpr int K = N / 2;
+    using R = Residue<W, false>;
+    const int res = blockIdx.x;
+    const int tid = threadIdx.x;
+    double *A = fit_smem + R::MA, *B = fit_smem + R::MB, *Lf = fit_smem + R::LF;
+    double x[N], g[N], lb[N], ub[N], v[N], dv[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        x[i] = a.x[(int64_t)res * N + i];
+        g[i] = a.g[(int64_t)res * N + i];
+        lb[i] = 0.0;
+        ub[i] = (i >= K && i < 2 * K) ? a.tau_max : 1.0;
+    }
+    double *vec = a.vec + (int64_t)res * 8 * N, *sca = a.sca + (int64_t)res * 8;
+    if (a.mode == 1) {
+        strictly_feasible<N>(x, lb, ub, 1e-10);
+        cl_scaling_vector<N>(x, g, lb, ub, v, dv);
+        const double Delta = initial_radius<N>(x, v);
+        if (tid == 0) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) { vec[i] = v[i]; vec[N + i] = dv[i]; vec[7 * N + i] = x[i]; }
+            sca[6] = Delta;
+        }
+        return;
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) A[tri(i, j)] = a.A[((int64_t)res * N + i) * N + j];
+    }
+    __syncthreads();
+    cl_scaling_vector_uni<N>(x, g, lb, ub, v, dv);
+    const double g_norm = scaled_gradient_norm<N>(g, v);
+    const double theta = step_theta(g_norm);
+    double d[N], g_h[N];
+    scaled_system<N>(A, g, v, dv, d, g_h, B, tid == 0);
+    __syncthreads();
+    if (tid >= 64) return;
+    const double Delta = a.Delta[res];
+    double alpha = a.alpha[res];
+    StepNote note = {0, 0, 0, -1};
+    double p_h[N], p_h0[N], p[N], step[N], step_h[N], xn[N], predicted;
+    solve_tr<N>(B, g_h, a.m[res], Delta, alpha, p_h, Lf, &note);
+    if (note.iters > 0) {     // solve_tr's last factorisation again (same B, same alpha, same code: the same pivots), for the count
+        double inv[N], lmin2;
+        note.piv_fail += !cholN<N>(B, alpha, Lf, inv, lmin2);
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) { p_h0[i] = p_h[i]; p[i] = d[i] * p_h[i]; }
+    select_step<N>(x, B, g_h, p, p_h, d, Delta, lb, ub, theta, step, step_h, predicted, &note);
+#pragma unroll
+    for (int i = 0; i < N; ++i) xn[i] = x[i] + step[i];
+    strictly_feasible<N>(xn, lb, ub, 0.0);
+    const double step_h_norm = normN<N>(step_h), step_norm = normN<N>(step);
+    if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            vec[i] = v[i]; vec[N + i] = dv[i]; vec[2 * N + i] = d[i]; vec[3 * N + i] = g_h[i]; vec[4 * N + i] = p_h0[i];
+            vec[5 * N + i] = step[i]; vec[6 * N + i] = step_h[i]; vec[7 * N + i] = xn[i];
+#pragma unroll
+            for (int j = 0; j < N; ++j) a.B[((int64_t)res * N + i) * N + j] = B[tri(i, j)];
+        }
+        sca[0] = g_norm; sca[1] = theta; sca[2] = alpha; sca[3] = predicted; sca[4] = step_h_norm; sca[5] = step_norm;
+        sca[6] = Delta;
+        int *fl = a.flags + (int64_t)res * 4;
+        fl[0] = note.full_rank; fl[1] = note.branch; fl[2] = note.piv_fail; fl[3] = note.iters;
+    }
+}
+
 // ---- the one launch ladder of the three fit kernel templates ----------------------------------------
 // A function template cannot be a template argument: one tag per kernel hands out its instances.
 struct TrfKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_trf<N, W, LDS>; } };
 struct ProbeKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_fit_probe<N, W, LDS>; } };
+struct StepProbeKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_step_probe<N, W, LDS>; } };
 struct SearchKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_order_search<N, W, LDS>; } };
 struct SearchSumsKernel { template <int N, int W, bool LDS> static constexpr auto fn() { return &k_order_search_sums<N, W, LDS>; } };
 
@@ -1767,6 +2003,39 @@ int sr_expfit_probe_f64(sr_ctx *ctx, const double *t, const double *C, const dou
     st.fetch(Jtf, a.g, nP);
     st.fetch(dx, a.dx, nP);
     st.fetch(geo, a.geo_out, nR);
+    return st.finish();
+}
+
+int sr_expfit_step_probe_f64(sr_ctx *ctx, const double *x, const double *JtJ, const double *Jtf, const double *Delta,
+                             const double *alpha, const int *m, int nRes, int P, double tau_max, int mode, double *vec, double *B,
+                             double *sca, int *flags)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(x && JtJ && Jtf && Delta && alpha && m && vec && B && sca && flags, -2, "sr_expfit_step_probe_f64: null pointer");
+    SR_REQUIRE(nRes >= 1 && P >= 2 && P <= kNmax, -3, "sr_expfit_step_probe_f64: bad sizes nRes=%d P=%d", nRes, P);
+    SR_REQUIRE(mode == 0 || mode == 1, -3, "sr_expfit_step_probe_f64: mode must be 0 (step) or 1 (init)");
+    const size_t nP = (size_t)nRes * P, nR = (size_t)nRes;
+    sr_stage st(ctx);
+    StepArgs a;
+    st.open(SR_WS_IN0, (nP * P + 2 * nP + 2 * nR) * sizeof(double));
+    a.x = st.put(x, nP); a.A = st.put(JtJ, nP * P); a.g = st.put(Jtf, nP); a.Delta = st.put(Delta, nR); a.alpha = st.put(alpha, nR);
+    a.m = st.open(SR_WS_OUT1, 5 * nR * sizeof(int)).put(m, nR);
+    a.flags = st.take<int>(4 * nR);
+    const size_t nOut = 8 * nP + nP * P + 8 * nR;
+    st.open(SR_WS_OUT0, nOut * sizeof(double));
+    a.vec = st.take<double>(8 * nP);
+    if (st.rc) return st.rc;
+    SR_HIP(hipMemsetAsync(a.vec, 0, nOut * sizeof(double), ctx->stream));
+    a.B = st.take<double>(nP * P); a.sca = st.take<double>(8 * nR);
+    if (st.rc) return st.rc;
+    SR_HIP(hipMemsetAsync(a.flags, 0, 4 * nR * sizeof(int), ctx->stream));
+    a.tau_max = tau_max; a.nRes = nRes; a.L = 0; a.mode = mode;
+    const int rc = dispatch_fit<StepProbeKernel>(ctx, "sr_expfit_step_probe_f64", P, false, a);
+    if (rc) return rc;
+    st.fetch(vec, a.vec, 8 * nP);
+    st.fetch(B, a.B, nP * P);
+    st.fetch(sca, a.sca, 8 * nR);
+    st.fetch(flags, a.flags, 4 * nR);
     return st.finish();
 }
 

@@ -602,6 +602,31 @@ class Context:
                                            _ptr(out['dx'])), 'sr_expfit_probe_f64')
         return out
 
+    def expfit_step_probe(self, x, JtJ, Jtf, Delta, alpha, m, tau_max, mode='step'):
+        """One trust-region step of the fit kernels per case (sr_expfit_step_probe_f64): x (n, P), JtJ (n, P, P), Jtf (n, P), Delta,
+        alpha, m (n).  mode 'step' returns a dict: v, dv, d, g_h, p_h, step, step_h, xn (n, P), B (n, P, P), g_norm, theta, alpha,
+        predicted, step_h_norm, step_norm (n), full_rank, branch, pivot_failures, iterations (n, int32).  mode 'init': x (after
+        strictly_feasible(., 1e-10)), v, dv (n, P) and Delta (n)."""
+        x = _f64(np.atleast_2d(x))
+        n, P = x.shape
+        A = _f64(np.asarray(JtJ).reshape(n, P, P))
+        g = _f64(np.asarray(Jtf).reshape(n, P))
+        De = _f64(np.broadcast_to(np.asarray(Delta, dtype=np.float64), (n,)))
+        al = _f64(np.broadcast_to(np.asarray(alpha, dtype=np.float64), (n,)))
+        mm = np.ascontiguousarray(np.broadcast_to(np.asarray(m), (n,)), dtype=np.int32)
+        vec, B, sca = np.empty((n, 8, P)), np.empty((n, P, P)), np.empty((n, 8))
+        flags = np.empty((n, 4), dtype=np.int32)
+        check(self.lib.sr_expfit_step_probe_f64(self.h, _ptr(x), _ptr(A), _ptr(g), _ptr(De), _ptr(al), _ptr(mm), n, P, float(tau_max),
+                                                {'step': 0, 'init': 1}[mode], _ptr(vec), _ptr(B), _ptr(sca), _ptr(flags)),
+              'sr_expfit_step_probe_f64')
+        if mode == 'init':
+            return dict(x=vec[:, 7].copy(), v=vec[:, 0].copy(), dv=vec[:, 1].copy(), Delta=sca[:, 6].copy())
+        out = {k: vec[:, i].copy() for i, k in enumerate(('v', 'dv', 'd', 'g_h', 'p_h', 'step', 'step_h', 'xn'))}
+        out.update({k: sca[:, i].copy() for i, k in enumerate(('g_norm', 'theta', 'alpha', 'predicted', 'step_h_norm', 'step_norm'))})
+        out.update({k: flags[:, i].copy() for i, k in enumerate(('full_rank', 'branch', 'pivot_failures', 'iterations'))})
+        out['B'] = B
+        return out
+
     def expfit(self, t, y, sigma, p0, tau_max, max_nfev=0, analytic_jac=False):
         """Batched bounded fit (scipy curve_fit/TRF semantics).  Returns popt, pcov, chisq, status, nfev."""
         y = _f64(np.atleast_2d(y))

@@ -37,7 +37,7 @@ extern "C" {
 
 typedef struct sr_ctx sr_ctx;
 
-#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long and sr_noe entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
+#define SR_ABI_VERSION 13   /* unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long, sr_noe and sr_noesy entry points: they only add symbols, and a binding that meets an older library fails at the missing symbol */
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
 int          sr_abi_version(void);
@@ -397,6 +397,45 @@ int sr_noe_pairs_check(sr_ctx *, int64_t nFrames, int64_t nAtoms, const int32_t 
                        const int64_t *block_len, int B, int mode);
 int sr_noe_tile(void);          /* T: atoms per tile side (tests aim at tile edges) */
 int sr_noe_frame_batch(void);   /* frames per LDS stage of k_noe_pairs */
+
+/* ---- NOESY intensities from the dipolar map: the full relaxation matrix (sr_noesy.hip; beyond the reference) -------------------------
+ * Macura & Ernst, Mol. Phys. 41, 95 (1980); Keepers & James, J. Magn. Reson. 57, 404 (1984); the model-free rates from <r^-6> and S2:
+ * Brueschweiler et al., JACS 114, 2289 (1992).  Isotropic tumbling, one kind of spin.  With A6 and S2 (P (P - 1) / 2 each) in the pair
+ * order of the map, k(i, j) = i (2 P - i - 1) / 2 + (j - i - 1):
+ *     J(w)     = S2 tau_c / (1 + w^2 tau_c^2) + (1 - S2) t' / (1 + w^2 t'^2),      1 / t' = 1 / tau_c + 1 / tau_e
+ *     R_ij     = sigma_ij = prefactor A6 [6 J(2 omega_H) - J(0)]                   (i != j; R_ji the same bits)
+ *     R_ii     = sum_j prefactor A6 [J(0) + 3 J(omega_H) + 6 J(2 omega_H)] + leak_i
+ * prefactor = 0.1 (mu0 / 4 pi)^2 hbar^2 gamma_H^4 / u^6, u = metres per unit of the coordinates that A6 was taken in.  tau_e_pair
+ * (one per pair) and leak_spin (one per spin) may be NULL: the scalars tau_e and leak then hold for all, and are ignored otherwise.
+ * S2 is clipped to [0, 1].  k_noesy_rates: one workgroup per row, the row sum in a fixed order, no atomics.
+ *   A6, S2, tau_e, leak: HOST arrays, checked before anything is queued and consumed on return; R_dev: DEVICE (P, P) float64.
+ * Refused with -3, before anything is queued: P < 2 or P > 32768, an A6 that is not finite and > 0, an S2 outside [-1e-6, 1 + 1e-6],
+ * tau_c <= 0, a tau_e <= 0, a negative leak, a prefactor <= 0, a negative omega_H, anything not finite. */
+int sr_noesy_rates_f64_dev(sr_ctx *, const double *A6_host, const double *S2_host, const double *tau_e_host, const double *leak_host,
+                           int64_t P, double omega_H, double tau_c, double tau_e, double leak, double prefactor, double *R_dev);
+/* the same with R on the HOST.  Blocks until R is there. */
+int sr_noesy_rates_f64(sr_ctx *, const double *A6, const double *S2, const double *tau_e_pair, const double *leak_spin, int64_t P,
+                       double omega_H, double tau_c, double tau_e, double leak, double prefactor, double *R);
+/* C = alpha A B + beta I for symmetric (P, P) float64 DEVICE matrices A and B that commute; C may be A or B.  Only the 64 x 64 tiles
+ * with tile row <= tile column are computed (k_symm_mul: v_mfma_f64_16x16x4_f64, both operands read as rows, k split over S
+ * workgroups, S a function of P alone) and k_symm_mul_finish writes C[i][j] and C[j][i] from one value: C == C^T bit for bit, equal
+ * input gives equal bits.  For symmetric input that does not commute the result is DEFINED as those tiles of alpha A B + beta I (of a
+ * diagonal tile the entries i <= j), mirrored below.  1 <= P <= 32768.  Asynchronous on the context's stream. */
+int sr_symm_mul_f64_dev(sr_ctx *, const double *A, const double *B, int64_t P, double alpha, double beta, double *C);
+/* out[k] = exp(-R tau[k]), k < n_tau, for a symmetric DEVICE matrix R (P, P) float64 and HOST mixing times tau, into the DEVICE array
+ * out (n_tau, P, P) float64, by scaling and squaring: s and the number of products as sr_symm_expm_plan gives them for |R|_1 (row
+ * sums on the device, their maximum on the host), Y = -R tau / 2^s, the Taylor polynomial of degree 12 by Horner, s squarings, every
+ * product by sr_symm_mul_f64_dev's kernels.  Each mixing time is computed from R on its own (equal bits alone and in a list).
+ * Refused with -3: P outside 1 .. 32768, n_tau < 1, a tau that is not finite or negative, results plus work area beyond the device's
+ * memory or a work area beyond what is free (both before anything is queued, the message names the sizes), an R that is not finite,
+ * more than 40 squarings.  Waits for the row sums, then asynchronous on the context's stream. */
+int sr_symm_expm_f64_dev(sr_ctx *, const double *R, int64_t P, const double *tau_host, int64_t n_tau, double *out);
+/* the arithmetic of the scaling alone (a host function, no context): s = the least integer >= 0 with norm1 tau / 2^s <= 0.5,
+ * products = 11 + s.  -3: norm1 or tau not finite or negative, s > 40. */
+int sr_symm_expm_plan(double norm1, double tau, int *s, int *products);
+/* What sr_symm_expm_f64_dev refuses for its sizes, with the results counted against the FREE memory as well: for a caller that has
+ * yet to allocate out.  Allocates and queues nothing. */
+int sr_symm_expm_check(sr_ctx *, int64_t P, int64_t n_tau);
 
 /* ---- time-lagged P2 cross-correlation between pairs of vectors (sr_ct_cross.hip; beyond the reference) ---------------------------
  * For pair p = (i, j) = (pair_i[p], pair_j[p]) on the Palmer chunk table of kernel 1 (R chunks of F frames, chunk_start_host as there):

@@ -6,7 +6,8 @@ files (<o>_Ctext.dat, <o>_Ctint.dat, <o>_vecHistogram.npz | _vecPhiTheta.npz|.da
 also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat; with the [extension] --crossCt --pairs FILE also <o>_crossCtint.dat
 and <o>_crossPairs.dat; with the [extension] --dipolarCt also <o>_dipolarCtint.dat and <o>_dipolarDist.dat; with the
 [extension] --dipolarCrossCt --pairs FILE also <o>_dipolarCrossCtint.dat and <o>_dipolarCrossPairs.dat; with the [extension] --noeMap
-also <o>_noeMap.dat and, with --binary, <o>_noeMap.npz).  C(t), the rotation into
+also <o>_noeMap.dat and, with --binary, <o>_noeMap.npz, and with --noesy on top of it <o>_noesy.dat and, with --binary,
+<o>_noesy.npz).  C(t), the rotation into
 the PAF, the spherical histogram, the mean vector and S2 are computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
 Several GPUs: run under torchrun (`torchrun --nproc-per-node N scripts/calculate-Ct-from-traj.py ...`): rank r computes the
@@ -122,7 +123,82 @@ def build_parser():
                         'of --dipolarCt.  Single process only.')
     p.add_argument('--noeCutoff', type=float, dest='noe_cutoff', default=None,
                    help='[extension] --noeMap lists only the pairs with reff6 <= this distance, in the units of the coordinates.')
+    p.add_argument('--noesy', dest='bDoNoesy', action='store_true', default=False,
+                   help='[extension] with --noeMap: NOESY cross-peak intensities of the map\'s spins by the full relaxation matrix '
+                        '(Macura & Ernst 1980; Keepers & James 1984; model-free rates from <r^-6> and S2, Brueschweiler et al. 1992), spin '
+                        'diffusion included: A(tau_m) = exp(-R tau_m) at the mixing times of --noesyMix.  <o>_noesy.dat with the columns '
+                        'i j name_i name_j sigma and one column per mixing time, the diagonal rows i = j included (--noeCutoff applies to '
+                        'the pairs); with --binary also <o>_noesy.npz.  Needs --noesyMix, --noesyField and --noesyTauC.  Isotropic tumbling, '
+                        'protons only, single process only.')
+    p.add_argument('--noesyMix', type=str, dest='noesy_mix', default=None, help='[extension] --noesy: the mixing times in seconds, e.g. "0.05 0.1 0.2".')
+    p.add_argument('--noesyField', type=float, dest='noesy_field', default=None, help='[extension] --noesy: the proton frequency of the spectrometer in MHz.')
+    p.add_argument('--noesyTauC', type=float, dest='noesy_tauc', default=None, help='[extension] --noesy: the overall correlation time tau_c in seconds.')
+    p.add_argument('--noesyTauE', type=float, dest='noesy_taue', default=None,
+                   help='[extension] --noesy: the correlation time of the internal motion tau_e in seconds (default 1e-10).')
+    p.add_argument('--noesyLeak', type=float, dest='noesy_leak', default=None,
+                   help='[extension] --noesy: a leakage rate in 1/s added to every diagonal element (default 0).')
+    p.add_argument('--noesyUnit', type=str, dest='noesy_unit', default=None, choices=('nm', 'A'),
+                   help='[extension] --noesy: the unit of the coordinates (default nm, MDTraj\'s).')
+    p.add_argument('--noesyGroups', type=str, dest='noesy_groups', default=None,
+                   help='[extension] --noesy: a file with one group of equivalent or unresolved spins per line (positions in the list of '
+                        'selected atoms); the intensities summed over the groups go to <o>_noesyGroups.dat.')
     return p
+
+
+def check_noesy_args(args):
+    """the --noesy* flags that do not fit together: an error message and exit, before any GPU work; returns the mixing times"""
+    given = [n for n, v in (('--noesyMix', args.noesy_mix), ('--noesyField', args.noesy_field), ('--noesyTauC', args.noesy_tauc),
+                            ('--noesyTauE', args.noesy_taue), ('--noesyLeak', args.noesy_leak), ('--noesyUnit', args.noesy_unit),
+                            ('--noesyGroups', args.noesy_groups)) if v is not None]
+    if not args.bDoNoesy:
+        if given:
+            print("= = = ERROR: %s belongs to --noesy; give both." % given[0], file=sys.stderr)
+            sys.exit(1)
+        return None
+    if not args.bDoNoeMap:
+        print("= = = ERROR: --noesy works on the map of --noeMap; give both.", file=sys.stderr)
+        sys.exit(1)
+    for name, v in (('--noesyMix', args.noesy_mix), ('--noesyField', args.noesy_field), ('--noesyTauC', args.noesy_tauc)):
+        if v is None:
+            print("= = = ERROR: --noesy needs %s." % name, file=sys.stderr)
+            sys.exit(1)
+    try:
+        mix = np.array([float(w) for w in args.noesy_mix.split()])
+    except ValueError:
+        mix = np.zeros(0)
+    if mix.size < 1 or not np.all(np.isfinite(mix)) or np.any(mix < 0):
+        print("= = = ERROR: --noesyMix must list mixing times in seconds, finite and >= 0; got '%s'." % args.noesy_mix, file=sys.stderr)
+        sys.exit(1)
+    if not args.noesy_field > 0 or not args.noesy_tauc > 0 or (args.noesy_taue is not None and not args.noesy_taue > 0) \
+            or (args.noesy_leak is not None and not args.noesy_leak >= 0):
+        print("= = = ERROR: --noesyField, --noesyTauC and --noesyTauE must be > 0 and --noesyLeak >= 0.", file=sys.stderr)
+        sys.exit(1)
+    if args.noesy_groups is not None and not os.path.isfile(args.noesy_groups):
+        print("= = = ERROR: --noesyGroups file %s does not exist." % args.noesy_groups, file=sys.stderr)
+        sys.exit(1)
+    return mix
+
+
+def run_noesy(args, out_pref, res, names):
+    """--noesy: the intensities of the map `res` at the mixing times of --noesyMix through spinrelax_amd.noesy"""
+    from spinrelax_amd import noesy
+    mix = check_noesy_args(args)
+    print("= = = Conducting the relaxation-matrix NOESY calculation of %i spins at %i mixing times." % (res['index'].size, mix.size))
+    try:
+        out = noesy.noesy(res, mix, args.noesy_field, args.noesy_tauc, tau_e=1e-10 if args.noesy_taue is None else args.noesy_taue,
+                          leak=0.0 if args.noesy_leak is None else args.noesy_leak, unit=args.noesy_unit or 'nm')
+        rows = noesy.write_noesy(out_pref + '_noesy.dat', out, names=names, reff6=res['reff6'], cutoff=args.noe_cutoff)
+        if args.noesy_groups is not None:
+            groups = noesy.read_groups(args.noesy_groups)
+            grp = dict(index=np.arange(len(groups)), R=noesy.sum_groups(out['R'], groups), A=noesy.sum_groups(out['A'], groups),
+                       mixing_times=out['mixing_times'])
+            noesy.write_noesy(out_pref + '_noesyGroups.dat', grp, names=['G%d' % g for g in range(len(groups))])
+    except (ValueError, hostct.hip.SpinRelaxHipError) as exc:
+        print("= = = ERROR: %s" % exc, file=sys.stderr)
+        sys.exit(1)
+    if args.binary:
+        np.savez(out_pref + '_noesy.npz', **{k: out[k] for k in ('R', 'sigma', 'rho', 'A', 'mixing_times', 'index', 'pairs')})
+    print("      ...%i rows written; complete." % rows)
 
 
 def run_noe_map(args, out_pref):
@@ -175,6 +251,8 @@ def run_noe_map(args, out_pref):
                 'reff6_b', 'reff3_b', 'S2_b', 'S2rad_b', 'block_len', 'sums')
         np.savez(out_pref + '_noeMap.npz', block_start=blocks[0], **{k: res[k] for k in keep})
     print("      ...%i of %i pairs written; complete." % (rows, res['reff6'].size))
+    if args.bDoNoesy:
+        run_noesy(args, out_pref, res, names)
     return all(('indexX' in np.load(fn, allow_pickle=True)) for fn in args.infn)
 
 
@@ -337,6 +415,7 @@ def main():
         print("= = = ERROR: --dipolarCt works on vector-file input (.npy/.npz), not on MDTraj input: the streaming front end keeps no "
               "distances.", file=sys.stderr)
         sys.exit(1)
+    check_noesy_args(args)
     time_start = time.time()
     rank, world = srdist.start()
     if args.bDoDipolarCt and world > 1:

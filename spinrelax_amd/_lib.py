@@ -204,6 +204,19 @@ SIGNATURES = {
     'sr_noe_pairs_check': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int]),
     'sr_noe_tile': (c_int, []),
     'sr_noe_frame_batch': (c_int, []),
+    # NOESY from the map (sr_noesy.hip): (ctx, A6_host, S2_host, tau_e_host | NULL, leak_host | NULL, P, omega_H, tau_c, tau_e, leak, prefactor, R),
+    # R on the device or on the host
+    'sr_noesy_rates_f64_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double, c_double,
+                                       c_void_p]),
+    'sr_noesy_rates_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double, c_double,
+                                   c_void_p]),
+    # (ctx, A, B, P, alpha, beta, C): device matrices
+    'sr_symm_mul_f64_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_void_p]),
+    # (ctx, R, P, tau_host, n_tau, out)
+    'sr_symm_expm_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    # (norm1, tau, &s, &products): host arithmetic
+    'sr_symm_expm_plan': (c_int, [c_double, c_double, POINTER(c_int), POINTER(c_int)]),
+    'sr_symm_expm_check': (c_int, [c_void_p, c_int64, c_int64]),
     'sr_counter': (c_int, [c_void_p, c_char_p, POINTER(ctypes.c_uint64)]),
     'sr_transpose_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'sr_transpose_batched_f64_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
@@ -214,7 +227,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long and sr_noe entry points, sr_vechist_plan and the sr_ct_palmer_sums_pack_* / sr_ct_pack_fused / sr_pack_reg_tiles group: they only add symbols, and load() fails at a missing one
+ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long, sr_noe and sr_noesy entry points, sr_vechist_plan and the sr_ct_palmer_sums_pack_* / sr_ct_pack_fused / sr_pack_reg_tiles group: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -69,6 +69,14 @@ def ct_pack_fused(formulation, F, series, tiles, aligned=True):
     return bool(_lib.load().sr_ct_pack_fused(int(formulation), int(F), int(series), int(tiles), 1 if aligned else 0))
 
 
+def symm_expm_plan(norm1, tau):
+    """(s, products) of the scaling and squaring of exp(-R tau) for |R|_1 = norm1: s the least integer >= 0 with norm1 tau / 2^s <= 0.5,
+    products = 11 + s (sr_symm_expm_plan: a host function, no Context and no GPU); SpinRelaxHipError for what symm_expm_dev refuses"""
+    s, products = ctypes.c_int(), ctypes.c_int()
+    check(_lib.load().sr_symm_expm_plan(float(norm1), float(tau), ctypes.byref(s), ctypes.byref(products)), 'sr_symm_expm_plan')
+    return s.value, products.value
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = _lib.load()
@@ -394,6 +402,69 @@ class Context:
     def noe_frame_batch(self):
         """frames per LDS stage of k_noe_pairs"""
         return int(self.lib.sr_noe_frame_batch())
+
+    # ---- NOESY from the dipolar map (sr_noesy.hip) ----
+    @staticmethod
+    def _noesy_args(A6, S2, P, tau_e, leak):
+        A6, S2 = _f64(A6), _f64(S2)
+        P = int(P)
+        npairs = P * (P - 1) // 2
+        if A6.shape != (npairs,) or S2.shape != (npairs,):
+            raise ValueError('A6 and S2 must hold the P (P - 1) / 2 = %d pairs of P = %d spins' % (npairs, P))
+        te_arr = lk_arr = None
+        te = lk = 0.0
+        if np.ndim(tau_e) == 0:
+            te = float(tau_e)
+        else:
+            te_arr = _f64(tau_e)
+            if te_arr.shape != (npairs,):
+                raise ValueError('tau_e must be a scalar or one value per pair')
+        if np.ndim(leak) == 0:
+            lk = float(leak)
+        else:
+            lk_arr = _f64(leak)
+            if lk_arr.shape != (P,):
+                raise ValueError('leak must be a scalar or one value per spin')
+        return A6, S2, P, te_arr, lk_arr, te, lk
+
+    def noesy_rates_dev(self, A6, S2, P, omega_H, tau_c, tau_e, leak, prefactor, R_ptr):
+        """The relaxation matrix of P spins from the map's host arrays A6 = <r^-6> and S2 (P (P - 1) / 2 each, pairs in the order of
+        noe.pair_index): R_ij = sigma_ij = prefactor A6 [6 J(2 omega_H) - J(0)], R_ii = sum_j prefactor A6 [J(0) + 3 J(omega_H) +
+        6 J(2 omega_H)] + leak_i with the model-free J of tau_c, S2 and tau_e, into the device array R_ptr (P, P) float64; tau_e a
+        scalar or one per pair, leak a scalar or one per spin (sr_noesy_rates_f64_dev); returns when the host arrays are consumed"""
+        A6, S2, P, te_arr, lk_arr, te, lk = self._noesy_args(A6, S2, P, tau_e, leak)
+        check(self.lib.sr_noesy_rates_f64_dev(self.h, _ptr(A6), _ptr(S2), _ptr(te_arr), _ptr(lk_arr), P, float(omega_H), float(tau_c), te, lk,
+                                              float(prefactor), R_ptr), 'sr_noesy_rates_f64_dev')
+
+    def noesy_rates(self, A6, S2, P, omega_H, tau_c, tau_e, leak, prefactor):
+        """The same with the result on the host: R (P, P) float64 (sr_noesy_rates_f64)"""
+        A6, S2, P, te_arr, lk_arr, te, lk = self._noesy_args(A6, S2, P, tau_e, leak)
+        R = np.empty((max(P, 0), max(P, 0)))
+        check(self.lib.sr_noesy_rates_f64(self.h, _ptr(A6), _ptr(S2), _ptr(te_arr), _ptr(lk_arr), P, float(omega_H), float(tau_c), te, lk,
+                                          float(prefactor), _ptr(R)), 'sr_noesy_rates_f64')
+        return R
+
+    def symm_mul_dev(self, A_ptr, B_ptr, P, C_ptr, alpha=1.0, beta=0.0):
+        """C = alpha A B + beta I of the symmetric device matrices A_ptr and B_ptr (P, P) float64 that commute, into the device array
+        C_ptr, which may be either of them; for symmetric matrices that do not commute the 64 x 64 tiles with tile row <= tile column
+        of that expression (of a diagonal tile i <= j), mirrored below (sr_symm_mul_f64_dev); asynchronous on the context's stream"""
+        check(self.lib.sr_symm_mul_f64_dev(self.h, A_ptr, B_ptr, int(P), float(alpha), float(beta), C_ptr), 'sr_symm_mul_f64_dev')
+
+    def symm_expm_dev(self, R_ptr, P, mixing_times, out_ptr):
+        """out[k] = exp(-R tau_k) of the symmetric device matrix R_ptr (P, P) float64 for the host list mixing_times, into the device
+        array out_ptr (n_tau, P, P) float64, each from R on its own by scaling and squaring (sr_symm_expm_f64_dev); waits for
+        |R|_1, then asynchronous on the context's stream"""
+        tau = np.ascontiguousarray(np.atleast_1d(mixing_times), dtype=np.float64)
+        if tau.ndim != 1:
+            raise ValueError('mixing_times must be 1-D')
+        check(self.lib.sr_symm_expm_f64_dev(self.h, R_ptr, int(P), _ptr(tau), tau.size, out_ptr), 'sr_symm_expm_f64_dev')
+
+    symm_expm_plan = staticmethod(symm_expm_plan)
+
+    def symm_expm_check(self, P, n_tau):
+        """raises what symm_expm_dev would refuse (-3) for these sizes, with the results counted against the free device memory too;
+        allocates and queues nothing (sr_symm_expm_check)"""
+        check(self.lib.sr_symm_expm_check(self.h, int(P), int(n_tau)), 'sr_symm_expm_check')
 
     def xh_quat_dev(self, xyz_ptr, nFrames, nAtoms, fit_indices, ref_xyz, quat_ptr):
         """The front end's superposition alone: the unit quaternions (w, x, y, z) that rotate every frame of the device coordinates

@@ -27,6 +27,7 @@
 // above sr_launch_ct_rfft32).  ct_long_min_frames defaults to SR_CT_LONG_MIN_FRAMES = 16384, above what fits: by default the
 // blocked form takes exactly the chunks the direct kernel cannot stage, and the option hands it shorter ones (from 5462 frames).
 #include "sr_internal.h"
+#include "sr_ct_shift.h"        // ct_Fp, kPad: the frames a staged series takes
 #include "sr_pack_tile.h"
 
 namespace {
@@ -195,6 +196,75 @@ int sr_ct_pack_fused(int formulation, int64_t F, int64_t series, int64_t tiles, 
 }
 
 }  // extern "C"
+
+// ---- the host path that the extensions of kernel 1 share: pair cross-correlation (sr_ct_cross*.hip), dipolar and dipolar pair function
+// (sr_ct_dipolar*.hip), from device planes or resident vectors (sr_vectors.hip) --------------------------------------------------------
+const sr_ct_form sr_ct_form_cross = {"two", 24, SR_CT_CROSS_LONG_FLOOR, "sr_ct_cross_long_f32_dev", true};
+const sr_ct_form sr_ct_form_dipolar = {"four", 16, SR_CT_DIPOLAR_LONG_FLOOR, "sr_ct_dipolar_long_f32_dev", false};
+const sr_ct_form sr_ct_form_dipolar_cross = {"eight", 32, SR_CT_DIPOLAR_CROSS_LONG_FLOOR, "sr_ct_dipolar_cross_long_f32_dev", true};
+
+size_t sr_ct_lds_bytes(int64_t F, int bytes_per_frame) { return (size_t)ct_Fp(F) * (size_t)bytes_per_frame; }
+
+int64_t sr_ct_lds_max_frames(int bytes_per_frame, size_t lds_limit)
+{
+    int64_t F = (int64_t)lds_limit / bytes_per_frame - kPad;       // an upper bound: ct_Fp(F) >= F + kPad
+    while (F >= 2 && sr_ct_lds_bytes(F, bytes_per_frame) > lds_limit) --F;
+    return F >= 2 ? F : 0;
+}
+
+int sr_ct_chunks_check(const char *who, int64_t frames, int64_t R, int64_t F, const int64_t *chunk_start_host)
+{
+    if (chunk_start_host) {
+        for (int64_t r = 0; r < R; ++r)
+            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= frames, -3, "%s: chunk %lld start %lld out of range", who,
+                       (long long)r, (long long)chunk_start_host[r]);
+    } else {
+        SR_REQUIRE(R * F <= frames, -3, "%s: R*F=%lld exceeds the %lld frames held", who, (long long)(R * F), (long long)frames);
+    }
+    return 0;
+}
+
+int sr_ct_rows_check(sr_ctx *ctx, const sr_ct_rows &w, const sr_ct_form &form)
+{
+    const char *who = w.who;
+    if (form.pairs) {
+        SR_REQUIRE(w.pair_i_host && w.pair_j_host, -2, "%s: null pointer", who);
+        SR_REQUIRE(w.R >= 1 && w.F >= 2 && w.nV >= 1 && w.nP >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld nP=%lld", who, (long long)w.R,
+                   (long long)w.F, (long long)w.nV, (long long)w.nP);
+        SR_REQUIRE((w.mode == 0 || w.mode == 1) && (w.sym == 0 || w.sym == 1), -3, "%s: mode and sym must be 0 or 1", who);
+    } else {
+        SR_REQUIRE(w.R >= 1 && w.F >= 2 && w.nV >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld", who, (long long)w.R, (long long)w.F,
+                   (long long)w.nV);
+        SR_REQUIRE(w.mode == 0 || w.mode == 1, -3, "%s: mode must be 0 or 1", who);
+    }
+    if (w.blocked) {
+        SR_REQUIRE(w.F <= SR_CT_LONG_MAX_FRAMES, -4, "%s: the blocked form takes chunks of at most %d frames, F=%lld", who, SR_CT_LONG_MAX_FRAMES,
+                   (long long)w.F);
+        SR_REQUIRE(w.F >= form.long_floor, -3, "%s: the blocked form takes chunks of at least %d frames, F=%lld", who, form.long_floor,
+                   (long long)w.F);
+    } else {
+        const size_t limit = sr_lds_limit(ctx);
+        SR_REQUIRE(sr_ct_lds_bytes(w.F, form.bytes_per_frame) <= limit, -4,
+                   "%s: the %s series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (longer chunks: the blocked form, %s)",
+                   who, form.series, (long long)w.F, sr_ct_lds_bytes(w.F, form.bytes_per_frame), limit,
+                   (long long)sr_ct_lds_max_frames(form.bytes_per_frame, limit), form.long_name);
+    }
+    const int64_t rows = form.pairs ? w.nP : w.nV;
+    SR_REQUIRE(w.R * rows < (int64_t)1 << 30, -3, "%s: too many series", who);
+    SR_REQUIRE((rows + kFinV - 1) / kFinV <= 65535, -3, "%s: too many %s in one call (%lld)", who, form.pairs ? "pairs" : "vectors",
+               (long long)rows);                                   // k_ct_finalize's grid
+    if (int rc = sr_ct_chunks_check(who, w.frames, w.R, w.F, w.chunk_start_host)) return rc;
+    for (int64_t p = 0; form.pairs && p < w.nP; ++p)
+        SR_REQUIRE(w.pair_i_host[p] >= 0 && w.pair_i_host[p] < w.nV && w.pair_j_host[p] >= 0 && w.pair_j_host[p] < w.nV, -3,
+                   "%s: pair %lld = (%d, %d) is outside the %lld vectors", who, (long long)p, (int)w.pair_i_host[p], (int)w.pair_j_host[p],
+                   (long long)w.nV);
+    return 0;
+}
+
+double *sr_ct_psum(sr_ctx *ctx, double *psum_ws, int64_t rows, int64_t R, int64_t F)
+{
+    return psum_ws ? psum_ws : (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(rows * R * sr_ct_psum_stride(F)) * sizeof(double));
+}
 
 namespace {
 

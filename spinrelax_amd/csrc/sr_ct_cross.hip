@@ -118,47 +118,7 @@ __global__ __launch_bounds__(256) void k_ct_cross_p0(const double *__restrict__ 
     dP0[p] = sqrt(v / (double)R) / (sqrt((double)R) - 1.0);
 }
 
-size_t cross_lds_bytes(int64_t F) { return 2 * sr_ct_direct_lds_bytes(F); }
-
-int64_t cross_max_frames(size_t lds_limit)
-{
-    int64_t F = (int64_t)lds_limit / 24 - kPad;         // an upper bound: ct_Fp(F) >= F + kPad
-    while (F >= 2 && cross_lds_bytes(F) > lds_limit) --F;
-    return F >= 2 ? F : 0;
-}
-
 }  // namespace
-
-int sr_ct_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                      const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, int blocked)
-{
-    SR_REQUIRE(pair_i && pair_j, -2, "%s: null pointer", who);
-    SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1 && nP >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld nP=%lld", who, (long long)R, (long long)F,
-               (long long)nV, (long long)nP);
-    SR_REQUIRE((mode == 0 || mode == 1) && (sym == 0 || sym == 1), -3, "%s: mode and sym must be 0 or 1", who);
-    if (blocked) {
-        SR_REQUIRE(F <= SR_CT_LONG_MAX_FRAMES, -4, "%s: the blocked form takes chunks of at most %d frames, F=%lld", who, SR_CT_LONG_MAX_FRAMES,
-                   (long long)F);
-        SR_REQUIRE(F >= SR_CT_CROSS_LONG_FLOOR, -3, "%s: the blocked form takes chunks of at least %d frames, F=%lld", who,
-                   SR_CT_CROSS_LONG_FLOOR, (long long)F);
-    } else {
-        SR_REQUIRE(cross_lds_bytes(F) <= sr_lds_limit(ctx), -4,
-                   "%s: the two series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (no blocked form for cross-correlations)",
-                   who, (long long)F, cross_lds_bytes(F), sr_lds_limit(ctx), (long long)cross_max_frames(sr_lds_limit(ctx)));
-    }
-    SR_REQUIRE(R * nP < (int64_t)1 << 30, -3, "%s: too many series", who);
-    if (chunk_start_host) {
-        for (int64_t r = 0; r < R; ++r)
-            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= frames, -3, "%s: chunk %lld start %lld out of range", who,
-                       (long long)r, (long long)chunk_start_host[r]);
-    } else {
-        SR_REQUIRE(R * F <= frames, -3, "%s: R*F=%lld exceeds the %lld frames held", who, (long long)(R * F), (long long)frames);
-    }
-    for (int64_t p = 0; p < nP; ++p)
-        SR_REQUIRE(pair_i[p] >= 0 && pair_i[p] < nV && pair_j[p] >= 0 && pair_j[p] < nV, -3, "%s: pair %lld = (%d, %d) is outside the %lld vectors",
-                   who, (long long)p, (int)pair_i[p], (int)pair_j[p], (long long)nV);
-    return 0;
-}
 
 int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nP, double *P0, double *dP0)
 {
@@ -173,7 +133,7 @@ extern "C" {
 int64_t sr_ct_cross_max_frames(sr_ctx *ctx)
 {
     if (!ctx) return -1;
-    return cross_max_frames(sr_lds_limit(ctx));
+    return sr_ct_lds_max_frames(sr_ct_form_cross.bytes_per_frame, sr_lds_limit(ctx));
 }
 
 static int cross_f32_dev(sr_ctx *ctx, const char *who, int blocked, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F,
@@ -182,28 +142,26 @@ static int cross_f32_dev(sr_ctx *ctx, const char *who, int blocked, const float 
 {
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(soa && P0 && Ct && dCt, -2, "%s: null pointer", who);
-    if (int rc = sr_ct_cross_check(ctx, who, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, blocked)) return rc;
-    const int64_t Lp = sr_ct_psum_stride(F);
-    double *psum = psum_ws;
-    if (!psum) {
-        psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(nP * R * Lp) * sizeof(double));
-        if (!psum) return -5;
-    }
+    const sr_ct_rows w = {who, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, blocked};
+    if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_cross)) return rc;
+    const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
+    double *psum = sr_ct_psum(ctx, psum_ws, nP, R, F);
+    if (!psum) return -5;
+    sr_stage st(ctx);
+    const sr_ct_tables t = sr_ct_stage_tables(st, w, blocked ? 2 * (size_t)nP * sizeof(int32_t) : 0);
     if (blocked) {
-        if (int rc = sr_launch_ct_cross_long(ctx, soa, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, psum, 3, 0)) return rc;
+        const sr_ct_pair_job job = {{soa, Npad, chunk_start_host, t.chunk_start, psum, (int)R, (int)F, (int)L, (int)Lp, R * nP},
+                                    nV, nP, pair_i_host, pair_j_host, t.pair_i, t.pair_j, sym, mode, &st};
+        if (int rc = sr_launch_ct_cross_long(ctx, job)) return rc;
     } else {
-        // ---- stage the chunk starts and the pair table ----
-        sr_stage st(ctx);
-        st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 2 * (size_t)nP * sizeof(int32_t));
-        CtCrossArgs a;
-        a.chunk_start = st.put(chunk_start_host, (size_t)R);
-        a.pair_i = st.put(pair_i_host, (size_t)nP);
-        a.pair_j = st.put(pair_j_host, (size_t)nP);
         if (int rc = st.finish()) return rc;            // small tables: the caller's arrays are free again when this returns
-        // ---- launch ----
+        CtCrossArgs a;
+        a.chunk_start = t.chunk_start; a.pair_i = t.pair_i; a.pair_j = t.pair_j;
         a.soa = soa; a.Npad = Npad; a.psum = psum;
-        a.R = (int)R; a.F = (int)F; a.Fp = (int)(sr_ct_direct_lds_bytes(F) / 12); a.L = (int)(F / 2); a.Lp = (int)Lp; a.sym = sym; a.mode = mode;
-        if (int rc = sr_launch(ctx, k_ct_cross, dim3((unsigned)(nP * R)), dim3(kCrossWaves * 64), cross_lds_bytes(F), a)) return rc;
+        a.R = (int)R; a.F = (int)F; a.Fp = (int)ct_Fp(F); a.L = (int)L; a.Lp = (int)Lp; a.sym = sym; a.mode = mode;
+        if (int rc = sr_launch(ctx, k_ct_cross, dim3((unsigned)(nP * R)), dim3(kCrossWaves * 64),
+                               sr_ct_lds_bytes(F, sr_ct_form_cross.bytes_per_frame), a))
+            return rc;
     }
     if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, P0, dP0)) return rc;
     return sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt);

@@ -297,25 +297,25 @@ struct CtlxTile {
 
 }  // namespace
 
-// what sr_ct_cross_f32_dev does behind its checks, for the chunks of sr_ct_cross_check(blocked = 1)
-int sr_launch_ct_cross_long(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                            const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *psum, int planes, int traceless)
+// what sr_ct_cross_f32_dev does behind its checks, for the chunks of sr_ct_rows_check(blocked = 1)
+int sr_launch_ct_cross_long(sr_ctx *ctx, const sr_ct_pair_job &job)
 {
-    SR_REQUIRE(!(traceless && mode == 1), -3, "blocked pair form: the traceless form has no float64 mode of its own");
-    const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
+    const float *soa = job.ct.soa;
+    const int64_t Npad = job.ct.Npad, nV = job.nV, nP = job.nP, R = job.ct.R, F = job.ct.F, L = job.ct.L, Lp = job.ct.Lp;
+    const int32_t *pair_i = job.pair_i_host, *pair_j = job.pair_j_host;
+    const int planes = job.ct.planes, traceless = job.ct.traceless;
+    double *psum = job.ct.psum;
+    sr_stage &st = *job.st;
     const int nb = (int)((F + kB - 1) / kB), nd = (int)(L / kB + 1);
     CtlxArgs x;
     x.soa = soa; x.Npad = Npad; x.psum = psum; x.nPR = nP * R;
-    x.R = (int)R; x.F = (int)F; x.L = (int)L; x.Lp = (int)Lp; x.nb = nb; x.nd = nd; x.sym = sym;
+    x.R = (int)R; x.F = (int)F; x.L = (int)L; x.Lp = (int)Lp; x.nb = nb; x.nd = nd; x.sym = job.sym;
     x.planes = planes; x.traceless = traceless;
     x.consts = x.pconsts = nullptr; x.spec = nullptr; x.Q = nullptr; x.slot_i = x.slot_j = nullptr; x.p0 = x.r0 = 0; x.nr = (int)R;
-    sr_stage st(ctx);
-    st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 4 * (size_t)nP * sizeof(int32_t));
-    x.chunk_start = st.put(chunk_start_host, (size_t)R);
-    x.pair_i = st.put(pair_i, (size_t)nP);
-    x.pair_j = st.put(pair_j, (size_t)nP);
-    if (mode == 1) {
+    x.chunk_start = job.ct.cs_dev; x.pair_i = job.pair_i_dev; x.pair_j = job.pair_j_dev;
+    if (job.mode == 1) {
         if (int rc = st.finish()) return rc;
+        SR_REQUIRE(!traceless, -3, "blocked pair form: the traceless form has no float64 mode of its own");
         hipLaunchKernelGGL(k_ctlx_f64, dim3((unsigned)(nP * R), (unsigned)((L + 256) / 256)), dim3(256), 0, ctx->stream, x);
         SR_HIP(hipGetLastError());
         return 0;

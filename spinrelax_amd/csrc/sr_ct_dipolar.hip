@@ -255,15 +255,6 @@ __global__ __launch_bounds__(256) void k_ct_dipolar_norm(const double *__restric
     }
 }
 
-size_t dip_lds_bytes(int64_t F) { return (size_t)ct_Fp(F) * 4 * sizeof(float); }
-
-int64_t dip_max_frames(size_t lds_limit)
-{
-    int64_t F = (int64_t)lds_limit / 16 - kPad;         // an upper bound: ct_Fp(F) >= F + kPad
-    while (F >= 2 && dip_lds_bytes(F) > lds_limit) --F;
-    return F >= 2 ? F : 0;
-}
-
 template <int W>
 int launch_dip(sr_ctx *ctx, const CtDipArgs &a, int64_t nblocks, size_t lds_bytes)
 {
@@ -271,33 +262,6 @@ int launch_dip(sr_ctx *ctx, const CtDipArgs &a, int64_t nblocks, size_t lds_byte
 }
 
 }  // namespace
-
-int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
-                        int blocked)
-{
-    SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1, -3, "%s: bad shape R=%lld F=%lld nV=%lld", who, (long long)R, (long long)F, (long long)nV);
-    SR_REQUIRE(mode == 0 || mode == 1, -3, "%s: mode must be 0 or 1", who);
-    if (blocked) {
-        SR_REQUIRE(F <= SR_CT_LONG_MAX_FRAMES, -4, "%s: the blocked form takes chunks of at most %d frames, F=%lld", who, SR_CT_LONG_MAX_FRAMES,
-                   (long long)F);
-        SR_REQUIRE(F >= SR_CT_DIPOLAR_LONG_FLOOR, -3, "%s: the blocked form takes chunks of at least %d frames, F=%lld", who,
-                   SR_CT_DIPOLAR_LONG_FLOOR, (long long)F);
-    } else {
-        SR_REQUIRE(dip_lds_bytes(F) <= sr_lds_limit(ctx), -4,
-                   "%s: the four series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (longer chunks: the blocked form, "
-                   "sr_ct_dipolar_long_f32_dev)",
-                   who, (long long)F, dip_lds_bytes(F), sr_lds_limit(ctx), (long long)dip_max_frames(sr_lds_limit(ctx)));
-    }
-    SR_REQUIRE(R * nV < (int64_t)1 << 30, -3, "%s: too many series", who);
-    if (chunk_start_host) {
-        for (int64_t r = 0; r < R; ++r)
-            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= frames, -3, "%s: chunk %lld start %lld out of range", who,
-                       (long long)r, (long long)chunk_start_host[r]);
-    } else {
-        SR_REQUIRE(R * F <= frames, -3, "%s: R*F=%lld exceeds the %lld frames held", who, (long long)(R * F), (long long)frames);
-    }
-    return 0;
-}
 
 int sr_ct_dipolar_norm_dev(sr_ctx *ctx, const double *wsum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt, double *wmean)
 {
@@ -313,7 +277,7 @@ extern "C" {
 int64_t sr_ct_dipolar_max_frames(sr_ctx *ctx)
 {
     if (!ctx) return -1;
-    return dip_max_frames(sr_lds_limit(ctx));
+    return sr_ct_lds_max_frames(sr_ct_form_dipolar.bytes_per_frame, sr_lds_limit(ctx));
 }
 
 int sr_pack_dipolar_f32_dev(sr_ctx *ctx, const float *vecs, const float *dist, int64_t N, int64_t Vtot, int64_t v0, int64_t nV, float *planes,
@@ -339,27 +303,21 @@ int sr_ct_dipolar_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, int64_
 {
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(planes && Ct && dCt && wmean, -2, "sr_ct_dipolar_f32_dev: null pointer");
-    if (int rc = sr_ct_dipolar_check(ctx, "sr_ct_dipolar_f32_dev", Npad, nV, R, F, chunk_start_host, mode, 0)) return rc;
+    const sr_ct_rows w = {"sr_ct_dipolar_f32_dev", Npad, nV, R, F, chunk_start_host, nullptr, nullptr, 0, 0, mode, 0};
+    if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_dipolar)) return rc;
     const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
-    SR_REQUIRE((nV + 15) / 16 <= 65535, -3, "sr_ct_dipolar_f32_dev: too many vectors in one call (%lld)", (long long)nV);   // k_ct_finalize's grid
-    double *psum = psum_ws;
-    if (!psum) {
-        psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(nV * R * Lp) * sizeof(double));
-        if (!psum) return -5;
-    }
+    double *psum = sr_ct_psum(ctx, psum_ws, nV, R, F);
+    if (!psum) return -5;
     // ---- stage the chunk starts; the chunk sums of w and w^2 live behind them ----
     sr_stage st(ctx);
-    st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 2 * (size_t)(nV * R) * sizeof(double));
     CtDipArgs a;
-    a.chunk_start = st.put(chunk_start_host, (size_t)R);
+    a.chunk_start = sr_ct_stage_tables(st, w, 2 * (size_t)(nV * R) * sizeof(double)).chunk_start;
     a.wsum = st.take<double>(2 * (size_t)(nV * R));
-    if (st.rc) return st.rc;
-    if (chunk_start_host)
-        if (int rc = st.finish()) return rc;            // tiny table: the caller's array is free again when this returns
+    if (int rc = chunk_start_host ? st.finish() : st.rc) return rc;     // tiny table: the caller's array is free again when this returns
     // ---- launch: the dispatch of sr_launch_ct_direct ----
     a.soa = planes; a.Npad = Npad; a.psum = psum;
     a.R = (int)R; a.F = (int)F; a.Fp = (int)ct_Fp(F); a.L = (int)L; a.Lp = (int)Lp; a.mode = mode;
-    const size_t lds_bytes = dip_lds_bytes(F);
+    const size_t lds_bytes = sr_ct_lds_bytes(F, sr_ct_form_dipolar.bytes_per_frame);
     const int nb = mode == 0 ? (int)((L + 1) / kLagBlock) : 0;
     const int64_t series = R * nV;
     int rc;

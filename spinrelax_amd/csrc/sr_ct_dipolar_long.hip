@@ -137,23 +137,17 @@ int sr_ct_dipolar_long_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, i
     const char *who = "sr_ct_dipolar_long_f32_dev";
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(planes && Ct && dCt && wmean, -2, "%s: null pointer", who);
-    if (int rc = sr_ct_dipolar_check(ctx, who, Npad, nV, R, F, chunk_start_host, mode, 1)) return rc;
-    SR_REQUIRE((nV + 15) / 16 <= 65535, -3, "%s: too many vectors in one call (%lld)", who, (long long)nV);     // k_ct_finalize's grid
+    const sr_ct_rows w = {who, Npad, nV, R, F, chunk_start_host, nullptr, nullptr, 0, 0, mode, 1};
+    if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_dipolar)) return rc;
     const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
-    double *psum = psum_ws;
-    if (!psum) {
-        psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(nV * R * Lp) * sizeof(double));
-        if (!psum) return -5;
-    }
+    double *psum = sr_ct_psum(ctx, psum_ws, nV, R, F);
+    if (!psum) return -5;
     // ---- stage the chunk starts; the chunk sums of w and w^2 live behind them ----
     sr_stage st(ctx);
-    st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 2 * (size_t)(nV * R) * sizeof(double));
     DiplArgs a;
-    a.chunk_start = st.put(chunk_start_host, (size_t)R);
+    a.chunk_start = sr_ct_stage_tables(st, w, 2 * (size_t)(nV * R) * sizeof(double)).chunk_start;
     a.wsum = st.take<double>(2 * (size_t)(nV * R));
-    if (st.rc) return st.rc;
-    if (chunk_start_host)
-        if (int rc = st.finish()) return rc;            // tiny table: the caller's array is free again when this returns
+    if (int rc = chunk_start_host ? st.finish() : st.rc) return rc;     // tiny table: the caller's array is free again when this returns
     a.soa = planes; a.Npad = Npad; a.pair_i = a.pair_j = nullptr; a.psum = psum;
     a.R = (int)R; a.F = (int)F; a.L = (int)L; a.Lp = (int)Lp; a.sym = 0;
     if (int rc = launch_wsums(ctx, a, nV)) return rc;
@@ -176,32 +170,32 @@ int sr_ct_dipolar_cross_long_f32_dev(sr_ctx *ctx, const float *planes, int64_t N
     const char *who = "sr_ct_dipolar_cross_long_f32_dev";
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(planes && P0 && Ct && dCt && wsum2, -2, "%s: null pointer", who);
-    if (int rc = sr_ct_dipolar_cross_check(ctx, who, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, 1)) return rc;
+    const sr_ct_rows w = {who, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, 1};
+    if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_dipolar_cross)) return rc;
     const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
-    double *psum = psum_ws;
-    if (!psum) {
-        psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(nP * R * Lp) * sizeof(double));
-        if (!psum) return -5;
+    double *psum = sr_ct_psum(ctx, psum_ws, nP, R, F);
+    if (!psum) return -5;
+    // ---- the tables go up once: the chunk sums (and mode 1) read them behind the copies in stream order, and sr_launch_ct_cross_long
+    // puts its slot tables in the room behind them ----
+    sr_stage st(ctx);
+    const sr_ct_tables t = sr_ct_stage_tables(st, w, 2 * (size_t)nP * sizeof(int32_t));
+    DiplArgs a;
+    a.chunk_start = t.chunk_start; a.pair_i = t.pair_i; a.pair_j = t.pair_j;
+    a.soa = planes; a.Npad = Npad; a.psum = psum; a.wsum = wsum2;
+    a.R = (int)R; a.F = (int)F; a.L = (int)L; a.Lp = (int)Lp; a.sym = sym;
+    int err = st.rc;
+    if (!err) err = launch_wsums(ctx, a, nP);
+    if (!err && mode == 1) err = launch_f64(ctx, a, nP);
+    if (!err && mode == 0) {
+        sr_ct_pair_job job = {{planes, Npad, chunk_start_host, t.chunk_start, psum, (int)R, (int)F, (int)L, (int)Lp, R * nP},
+                              nV, nP, pair_i_host, pair_j_host, t.pair_i, t.pair_j, sym, 0, &st};
+        job.ct.planes = 4;
+        job.ct.traceless = 1;
+        if (int rc = sr_launch_ct_cross_long(ctx, job)) return rc;
+    } else {                                            // no transforms follow, or a failure: the caller's arrays are free again behind finish()
+        const int rc = st.finish();
+        if (err || rc) return err ? err : rc;
     }
-    {
-        // ---- the chunk sums (and mode 1) on tables of their own: sr_launch_ct_cross_long stages its tables in the same slot afterwards,
-        // in stream order behind these kernels ----
-        sr_stage st(ctx);
-        st.open(SR_WS_MISC, (size_t)R * sizeof(int64_t) + 2 * (size_t)nP * sizeof(int32_t));
-        DiplArgs a;
-        a.chunk_start = st.put(chunk_start_host, (size_t)R);
-        a.pair_i = st.put(pair_i_host, (size_t)nP);
-        a.pair_j = st.put(pair_j_host, (size_t)nP);
-        if (int rc = st.finish()) return rc;            // small tables: the caller's arrays are free again when this returns
-        a.soa = planes; a.Npad = Npad; a.psum = psum; a.wsum = wsum2;
-        a.R = (int)R; a.F = (int)F; a.L = (int)L; a.Lp = (int)Lp; a.sym = sym;
-        if (int rc = launch_wsums(ctx, a, nP)) return rc;
-        if (mode == 1)
-            if (int rc = launch_f64(ctx, a, nP)) return rc;
-    }
-    if (mode == 0)
-        if (int rc = sr_launch_ct_cross_long(ctx, planes, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, 0, psum, 4, 1))
-            return rc;
     if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, P0, dP0)) return rc;
     if (int rc = sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt)) return rc;
     return sr_ct_dipolar_cross_norm_dev(ctx, wsum2, R, F, nP, Ct, dCt, P0, dP0);

@@ -129,37 +129,58 @@ int64_t sr_ct_direct_max_frames(size_t lds_limit);
 int sr_launch_ct_fft64(sr_ctx *ctx, const sr_ct_job &job);
 int sr_launch_ct_rfft64(sr_ctx *ctx, const sr_ct_job &job);
 
-// sr_ct_cross.hip: what the entry points of the pair cross-correlation refuse, before anything is queued: shapes, a chunk whose two
-// series do not fit the LDS (-4; blocked = 1: a chunk of more than SR_CT_LONG_MAX_FRAMES frames, and -3 below SR_CT_CROSS_LONG_FLOOR),
-// chunk starts and pair indices outside the `frames` frames / nV vectors held (-3)
-int sr_ct_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                      const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, int blocked);
+// ---- the extensions of kernel 1: pair cross-correlation, dipolar and dipolar pair function, each staged (LDS) and blocked.  Their
+// entry points share one host path (sr_ct.hip): null checks, sr_ct_rows_check, sr_ct_psum, sr_ct_stage_tables, launch, epilogue ----
+// what an entry point is asked for: R chunks of F frames out of the `frames` held, of nV vectors or of nP pairs of them
+struct sr_ct_rows {
+    const char *who;                            // the entry point, for messages
+    int64_t frames, nV, R, F;
+    const int64_t *chunk_start_host;            // null: chunk r starts at r F
+    const int32_t *pair_i_host, *pair_j_host;   // [nP]; the autocorrelation form has none (nP = 0): its rows are the nV vectors
+    int64_t nP;
+    int sym, mode, blocked;
+};
+// what tells the three functions apart on the host
+struct sr_ct_form {
+    const char *series;                         // "two", "four", "eight": the series a workgroup of the staged form holds in LDS,
+    int bytes_per_frame;                        // and their bytes per staged frame
+    int long_floor;                             // the shortest chunk of the blocked form
+    const char *long_name;                      // and its entry point, for the staged form's -4 message
+    bool pairs;                                 // rows are pairs (a pair table is required) or the vectors themselves
+};
+extern const sr_ct_form sr_ct_form_cross, sr_ct_form_dipolar, sr_ct_form_dipolar_cross;
+// LDS of a staged chunk of F frames, and the longest chunk that a limit admits (0: none)
+size_t sr_ct_lds_bytes(int64_t F, int bytes_per_frame);
+int64_t sr_ct_lds_max_frames(int bytes_per_frame, size_t lds_limit);
+// what the entry points refuse, before any workspace is requested or anything is queued: a missing pair table (-2), shapes, mode and
+// sym (-3), a chunk whose series do not fit the LDS (-4; blocked: a chunk of more than SR_CT_LONG_MAX_FRAMES frames, and -3 below the
+// form's floor), too many rows for one call, chunk starts and pair indices outside the frames / vectors held (-3)
+int sr_ct_rows_check(sr_ctx *ctx, const sr_ct_rows &w, const sr_ct_form &form);
+int sr_ct_chunks_check(const char *who, int64_t frames, int64_t R, int64_t F, const int64_t *chunk_start_host);
+// raw sums (rows, R, sr_ct_psum_stride(F)): the caller's work area, or the context's when there is none; NULL (error set) on failure
+double *sr_ct_psum(sr_ctx *ctx, double *psum_ws, int64_t rows, int64_t R, int64_t F);
 
 // sr_ct_cross.hip: k_ct_cross_p0 on raw sums (nP, R, sr_ct_psum_stride(F)) whose slot 0 holds lag 0: P0 (nP) the chunk mean of
 // 1.5 S / F - 0.5 and, when dP0 is not null, its std / (sqrt(R) - 1); device arrays, asynchronous on ctx->stream
 int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nP, double *P0, double *dP0);
 
 // sr_ct_cross_long.hip: the blocked form of the pair cross-correlation (raw sums in kernel 1's layout, lag 0 in slot 0), for what
-// sr_ct_cross_check(blocked = 1) admits: the range in which the kernels it shares with sr_ct_long.hip are tested
+// sr_ct_rows_check(blocked = 1) admits: the range in which the kernels it shares with sr_ct_long.hip are tested
 #define SR_CT_CROSS_LONG_FLOOR 5462
 #define SR_CT_CROSS_LONG_MIN_FRAMES 6625   /* default of "ct_cross_long_min_frames": the first length k_ct_cross cannot stage */
-// planes = 3, traceless = 0: unit-vector planes (sr_ct_cross.hip).  planes = 4, traceless = 1: the dipolar pack, five traceless signals
-// and S_a - S_w / 3 + F / 3 in slot 0 (sr_ct_dipolar_long.hip, mode 0 only)
-int sr_launch_ct_cross_long(sr_ctx *ctx, const float *soa, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                            const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *psum, int planes,
-                            int traceless);
-
-// sr_ct_dipolar.hip: what the entry points of the dipolar correlation function refuse, before anything is queued: shapes and mode (-3), a
-// chunk whose four series do not fit the LDS (-4; blocked = 1: a chunk of more than SR_CT_LONG_MAX_FRAMES frames, and -3 below
-// SR_CT_DIPOLAR_LONG_FLOOR), chunk starts outside the `frames` frames held (-3)
-int sr_ct_dipolar_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host, int mode,
-                        int blocked);
-
-// sr_ct_dipolar_cross.hip: what the entry points of the dipolar cross-correlation function refuse, before anything is queued: shapes, mode
-// and sym (-3), a chunk whose eight series do not fit the LDS (-4; blocked = 1: a chunk of more than SR_CT_LONG_MAX_FRAMES frames, and -3
-// below SR_CT_DIPOLAR_CROSS_LONG_FLOOR), chunk starts and pair indices outside the `frames` frames / nV vectors held (-3)
-int sr_ct_dipolar_cross_check(sr_ctx *ctx, const char *who, int64_t frames, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
-                              const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, int blocked);
+// A checked job whose tables the caller has put on `st` (sr_ct_stage_tables with room for 2 nP more int32 behind them): the launcher
+// appends its two slot tables and calls st->finish(), on every path.  ct: psum (nP, R, Lp), series = R nP, and planes = 3,
+// traceless = 0 for unit-vector planes (sr_ct_cross.hip) or planes = 4, traceless = 1 for the dipolar pack: five traceless signals and
+// S_a - S_w / 3 + F / 3 in slot 0 (sr_ct_dipolar_long.hip, mode 0 only)
+struct sr_stage;
+struct sr_ct_pair_job {
+    sr_ct_job ct;
+    int64_t nV, nP;
+    const int32_t *pair_i_host, *pair_j_host, *pair_i_dev, *pair_j_dev;
+    int sym, mode;
+    sr_stage *st;
+};
+int sr_launch_ct_cross_long(sr_ctx *ctx, const sr_ct_pair_job &job);
 
 // sr_ct_dipolar_long.hip: the blocked forms of both, on planes from sr_pack_dipolar_f32_dev.  The floors are the shortest chunks at
 // which the shared kernels keep a block structure they are tested at (5462: F + L > 8192; 4097: two blocks, one offset)
@@ -267,6 +288,23 @@ struct sr_stage {
         return nullptr;
     }
 };
+
+// the tables of a C(t) extension on the device: chunk starts (null: regular chunks) and, in the pair forms, the pair table
+struct sr_ct_tables {
+    const int64_t *chunk_start;
+    const int32_t *pair_i, *pair_j;
+};
+// opens SR_WS_MISC for them with `room` bytes behind for the caller to take() and queues the copies; the caller tests st.rc or calls
+// st.finish(), which also frees the caller's arrays again
+inline sr_ct_tables sr_ct_stage_tables(sr_stage &st, const sr_ct_rows &w, size_t room)
+{
+    st.open(SR_WS_MISC, (size_t)w.R * sizeof(int64_t) + 2 * (size_t)w.nP * sizeof(int32_t) + room);
+    sr_ct_tables t;
+    t.chunk_start = st.put(w.chunk_start_host, (size_t)w.R);
+    t.pair_i = st.put(w.pair_i_host, (size_t)w.nP);
+    t.pair_j = st.put(w.pair_j_host, (size_t)w.nP);
+    return t;
+}
 
 #ifdef __HIPCC__
 // ---- wave-level float64 sum on the VALU only (DPP + readlane), no LDS round trips -----------------

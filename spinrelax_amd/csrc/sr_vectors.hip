@@ -12,6 +12,7 @@
 #include "sr_internal.h"
 #include <cmath>
 #include <cstdlib>
+#include <vector>
 
 struct sr_vectors {
     int64_t nV;            // vectors of this shard
@@ -157,6 +158,34 @@ int check_dist(const char *who, const sr_vectors *h, const float *dist_host)
             SR_REQUIRE(dist_host[i] > 0.f && std::isfinite(dist_host[i]), -3,
                        "%s: the distance of frame %lld, vector %lld is %g: distances must be positive and finite", who, (long long)(i / h->nV),
                        (long long)(i % h->nV), (double)dist_host[i]);
+    return 0;
+}
+
+/* one download of a result: host[k] = (device buffer `buf`)[off + k stride], k < n; a null host array is an output not asked for */
+struct CtDown {
+    double *host;
+    int buf;
+    size_t off, n, stride;
+};
+
+/* the results of a pair / dipolar C(t) of resident vectors: device buffers of n[k] doubles in SR_WS_OUT0 + k, `run` on them, the
+ * downloads, and the stream synchronised */
+template <size_t K, size_t D, class Run>
+int ct_results(sr_ctx *ctx, const size_t (&n)[K], const CtDown (&down)[D], Run run)
+{
+    double *dev[K];
+    for (size_t k = 0; k < K; ++k)
+        if (!(dev[k] = (double *)sr_workspace(ctx, SR_WS_OUT0 + (int)k, n[k] * sizeof(double)))) return -5;
+    if (int rc = run(dev)) return rc;
+    for (const CtDown &d : down) {
+        if (!d.host) continue;
+        if (d.stride == 1)
+            SR_HIP(hipMemcpyAsync(d.host, dev[d.buf] + d.off, d.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        else
+            SR_HIP(hipMemcpy2DAsync(d.host, sizeof(double), dev[d.buf] + d.off, d.stride * sizeof(double), sizeof(double), d.n,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SR_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
@@ -342,10 +371,7 @@ int sr_vectors_ct_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, const in
     double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * h->nV) * sizeof(double));
     double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * h->nV) * sizeof(double));
     if (!Ct_d || !dCt_d) return -5;
-    if (!chunk_start_host) SR_REQUIRE(R * F <= h->N, -3, "sr_vectors_ct_f32: R*F=%lld exceeds the %lld frames held", (long long)(R * F), (long long)h->N);
-    else
-        for (int64_t r = 0; r < R; ++r)
-            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= h->N, -3, "sr_vectors_ct_f32: chunk %lld out of range", (long long)r);
+    if (int rc = sr_ct_chunks_check("sr_vectors_ct_f32", h->N, R, F, chunk_start_host)) return rc;
     int rc = sr_ct_palmer_f32_dev(ctx, h->soa, h->Npad, R, F, h->nV, chunk_start_host, mode, nullptr, Ct_d, dCt_d);
     if (rc) return rc;
     SR_HIP(hipMemcpyAsync(Ct, Ct_d, (size_t)(L * h->nV) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -361,22 +387,16 @@ static int vectors_ct_cross(sr_ctx *ctx, const char *who, int blocked, sr_vector
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(h && P0 && Ct && dCt, -2, "%s: null pointer", who);
     // refusals come before kernel 0: a bad pair table or a chunk that does not fit launches nothing
-    if (int rc = sr_ct_cross_check(ctx, who, h->N, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, blocked)) return rc;
+    const sr_ct_rows w = {who, h->N, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, blocked};
+    if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_cross)) return rc;
     if (int rc = pack(ctx, h)) return rc;
-    const int64_t L = F / 2;
-    double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nP) * sizeof(double));
-    double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * nP) * sizeof(double));
-    double *P0_d = (double *)sr_workspace(ctx, SR_WS_OUT2, 2 * (size_t)nP * sizeof(double));        // P0 | dP0
-    if (!Ct_d || !dCt_d || !P0_d) return -5;
-    int rc = (blocked ? sr_ct_cross_long_f32_dev : sr_ct_cross_f32_dev)(ctx, h->soa, h->Npad, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym,
-                                                                        mode, nullptr, P0_d, dP0 ? P0_d + nP : nullptr, Ct_d, dCt_d);
-    if (rc) return rc;
-    SR_HIP(hipMemcpyAsync(P0, P0_d, (size_t)nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (dP0) SR_HIP(hipMemcpyAsync(dP0, P0_d + nP, (size_t)nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(Ct, Ct_d, (size_t)(L * nP) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(dCt, dCt_d, (size_t)(L * nP) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    const size_t LP = (size_t)(F / 2 * nP), P = (size_t)nP;
+    const size_t n[] = {LP, LP, 2 * P};                                                             // Ct, dCt, P0 | dP0
+    const CtDown down[] = {{P0, 2, 0, P, 1}, {dP0, 2, P, P, 1}, {Ct, 0, 0, LP, 1}, {dCt, 1, 0, LP, 1}};
+    return ct_results(ctx, n, down, [&](double *const *d) {
+        return (blocked ? sr_ct_cross_long_f32_dev : sr_ct_cross_f32_dev)(ctx, h->soa, h->Npad, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym,
+                                                                            mode, nullptr, d[2], dP0 ? d[2] + nP : nullptr, d[0], d[1]);
+    });
 }
 
 int sr_vectors_ct_cross_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, const int64_t *chunk_start_host, const int32_t *pair_i,
@@ -409,23 +429,20 @@ static int vectors_ct_dipolar(sr_ctx *ctx, const char *who, int blocked, sr_vect
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(h && Ct && dCt && reff6 && reff3 && S2rad, -2, "%s: null pointer", who);
     // refusals come before the pack: a chunk that does not fit or a bad distance launches nothing
-    if (int rc = sr_ct_dipolar_check(ctx, who, h->N, h->nV, R, F, chunk_start_host, mode, blocked)) return rc;
+    const sr_ct_rows w = {who, h->N, h->nV, R, F, chunk_start_host, nullptr, nullptr, 0, 0, mode, blocked};
+    if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_dipolar)) return rc;
     if (int rc = check_dist(who, h, dist_host)) return rc;
     if (int rc = pack_dipolar(ctx, who, h, dist_host)) return rc;
-    const int64_t L = F / 2, nV = h->nV;
-    double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nV) * sizeof(double));
-    double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * nV) * sizeof(double));
-    double *wm_d = (double *)sr_workspace(ctx, SR_WS_OUT2, 2 * (size_t)nV * sizeof(double));
-    if (!Ct_d || !dCt_d || !wm_d) return -5;
-    int rc = (blocked ? sr_ct_dipolar_long_f32_dev : sr_ct_dipolar_f32_dev)(ctx, h->soa4, h->Npad4, nV, R, F, chunk_start_host, mode, nullptr, Ct_d,
-                                                                            dCt_d, wm_d);
-    if (rc) return rc;
-    SR_HIP(hipMemcpyAsync(Ct, Ct_d, (size_t)(L * nV) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpyAsync(dCt, dCt_d, (size_t)(L * nV) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const int64_t nV = h->nV;
+    const size_t LV = (size_t)(F / 2 * nV), V = (size_t)nV;
+    const size_t n[] = {LV, LV, 2 * V};                                                             // Ct, dCt, (<w>, <w^2>) per vector
     // <w> and <w^2> arrive as two strided columns in the caller's arrays and are turned into the three results in place
-    SR_HIP(hipMemcpy2DAsync(reff3, sizeof(double), wm_d, 2 * sizeof(double), sizeof(double), (size_t)nV, hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipMemcpy2DAsync(reff6, sizeof(double), wm_d + 1, 2 * sizeof(double), sizeof(double), (size_t)nV, hipMemcpyDeviceToHost, ctx->stream));
-    SR_HIP(hipStreamSynchronize(ctx->stream));
+    const CtDown down[] = {{Ct, 0, 0, LV, 1}, {dCt, 1, 0, LV, 1}, {reff3, 2, 0, V, 2}, {reff6, 2, 1, V, 2}};
+    int rc = ct_results(ctx, n, down, [&](double *const *d) {
+        return (blocked ? sr_ct_dipolar_long_f32_dev : sr_ct_dipolar_f32_dev)(ctx, h->soa4, h->Npad4, nV, R, F, chunk_start_host, mode, nullptr, d[0],
+                                                                                d[1], d[2]);
+    });
+    if (rc) return rc;
     for (int64_t v = 0; v < nV; ++v) {
         const double w1 = reff3[v], w2 = reff6[v];
         reff6[v] = h->rref[v] * pow(w2, -1.0 / 6.0);
@@ -454,41 +471,27 @@ static int vectors_ct_dipolar_cross(sr_ctx *ctx, const char *who, int blocked, s
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(h && P0 && dP0 && Ct && dCt && reff6, -2, "%s: null pointer", who);
     // refusals come before the pack: a bad pair table, a chunk that does not fit or a bad distance launches nothing
-    if (int rc = sr_ct_dipolar_cross_check(ctx, who, h->N, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, blocked)) return rc;
+    const sr_ct_rows w = {who, h->N, h->nV, R, F, chunk_start_host, pair_i, pair_j, nP, sym, mode, blocked};
+    if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_dipolar_cross)) return rc;
     if (int rc = check_dist(who, h, dist_host)) return rc;
     if (int rc = pack_dipolar(ctx, who, h, dist_host)) return rc;
-    const int64_t L = F / 2;
-    double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nP) * sizeof(double));
-    double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * nP) * sizeof(double));
-    double *P0_d = (double *)sr_workspace(ctx, SR_WS_OUT2, 2 * (size_t)nP * sizeof(double));        // P0 | dP0
-    double *ws_d = (double *)sr_workspace(ctx, SR_WS_OUT3, 2 * (size_t)(nP * R) * sizeof(double));  // sum w_i^2, sum w_j^2 per (pair, chunk)
-    if (!Ct_d || !dCt_d || !P0_d || !ws_d) return -5;
-    double *ws = (double *)malloc(2 * (size_t)(nP * R) * sizeof(double));
-    SR_REQUIRE(ws != nullptr, -5, "%s: out of host memory", who);
-    int rc = (blocked ? sr_ct_dipolar_cross_long_f32_dev : sr_ct_dipolar_cross_f32_dev)(ctx, h->soa4, h->Npad4, h->nV, R, F, chunk_start_host, pair_i,
-                                                                                        pair_j, nP, sym, mode, nullptr, P0_d, P0_d + nP, Ct_d,
-                                                                                        dCt_d, ws_d);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        e = hipMemcpyAsync(P0, P0_d, (size_t)nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dP0, P0_d + nP, (size_t)nP * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(Ct, Ct_d, (size_t)(L * nP) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dCt, dCt_d, (size_t)(L * nP) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ws, ws_d, 2 * (size_t)(nP * R) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    if (!rc && e == hipSuccess) {
-        // <r^-6>^(-1/6) = r_ref <w^2>^(-1/6), <w^2> over the frames of all chunks, the chunk sums added in chunk order
-        for (int64_t p = 0; p < nP; ++p)
-            for (int c = 0; c < 2; ++c) {
-                double m2 = 0.0;
-                for (int64_t r = 0; r < R; ++r) m2 += ws[(p * R + r) * 2 + c];
-                reff6[2 * p + c] = h->rref[c ? pair_j[p] : pair_i[p]] * pow(m2 / ((double)R * (double)F), -1.0 / 6.0);
-            }
-    }
-    free(ws);
+    const size_t LP = (size_t)(F / 2 * nP), P = (size_t)nP, PR2 = 2 * (size_t)(nP * R);
+    std::vector<double> ws(PR2);                                           // sum w_i^2, sum w_j^2 per (pair, chunk)
+    const size_t n[] = {LP, LP, 2 * P, PR2};                               // Ct, dCt, P0 | dP0, the chunk sums
+    const CtDown down[] = {{P0, 2, 0, P, 1}, {dP0, 2, P, P, 1}, {Ct, 0, 0, LP, 1}, {dCt, 1, 0, LP, 1}, {ws.data(), 3, 0, PR2, 1}};
+    int rc = ct_results(ctx, n, down, [&](double *const *d) {
+        return (blocked ? sr_ct_dipolar_cross_long_f32_dev : sr_ct_dipolar_cross_f32_dev)(ctx, h->soa4, h->Npad4, h->nV, R, F, chunk_start_host,
+                                                                                            pair_i, pair_j, nP, sym, mode, nullptr, d[2], d[2] + nP,
+                                                                                            d[0], d[1], d[3]);
+    });
     if (rc) return rc;
-    SR_HIP(e);
+    // <r^-6>^(-1/6) = r_ref <w^2>^(-1/6), <w^2> over the frames of all chunks, the chunk sums added in chunk order
+    for (int64_t p = 0; p < nP; ++p)
+        for (int c = 0; c < 2; ++c) {
+            double m2 = 0.0;
+            for (int64_t r = 0; r < R; ++r) m2 += ws[(p * R + r) * 2 + c];
+            reff6[2 * p + c] = h->rref[c ? pair_j[p] : pair_i[p]] * pow(m2 / ((double)R * (double)F), -1.0 / 6.0);
+        }
     return 0;
 }
 
@@ -517,12 +520,9 @@ int sr_vectors_ct_sums_f32(sr_ctx *ctx, sr_vectors *h, int64_t R, int64_t F, con
     SR_REQUIRE(R >= 1 && F >= 2, -3, "sr_vectors_ct_sums_f32: bad shape R=%lld F=%lld", (long long)R, (long long)F);
     if (int rc = pack(ctx, h)) return rc;
     const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
-    double *psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(h->nV * R * Lp) * sizeof(double));
+    double *psum = sr_ct_psum(ctx, nullptr, h->nV, R, F);
     if (!psum) return -5;
-    if (!chunk_start_host) SR_REQUIRE(R * F <= h->N, -3, "sr_vectors_ct_sums_f32: R*F=%lld exceeds the %lld frames held", (long long)(R * F), (long long)h->N);
-    else
-        for (int64_t r = 0; r < R; ++r)
-            SR_REQUIRE(chunk_start_host[r] >= 0 && chunk_start_host[r] + F <= h->N, -3, "sr_vectors_ct_sums_f32: chunk %lld out of range", (long long)r);
+    if (int rc = sr_ct_chunks_check("sr_vectors_ct_sums_f32", h->N, R, F, chunk_start_host)) return rc;
     int rc = sr_ct_palmer_sums_f32_dev(ctx, h->soa, h->Npad, R, F, h->nV, chunk_start_host, mode, psum);
     if (rc) return rc;
     SR_HIP(hipMemcpy2DAsync(sums, (size_t)L * sizeof(double), psum + 1, (size_t)Lp * sizeof(double), (size_t)L * sizeof(double),
@@ -539,8 +539,8 @@ int sr_ct_finalize_sums_f64(sr_ctx *ctx, const double *sums, int64_t R, int64_t 
     SR_REQUIRE(sums && Ct && dCt, -2, "sr_ct_finalize_sums_f64: null pointer");
     SR_REQUIRE(R >= 1 && F >= 2 && nV >= 1, -3, "sr_ct_finalize_sums_f64: bad shape");
     const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
-    double *psum = (double *)sr_workspace(ctx, SR_WS_PSUM, (size_t)(nV * R * Lp) * sizeof(double));
-    double *Ct_d = (double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nV) * sizeof(double));
+    double *psum = sr_ct_psum(ctx, nullptr, nV, R, F);
+    double *Ct_d =(double *)sr_workspace(ctx, SR_WS_OUT0, (size_t)(L * nV) * sizeof(double));
     double *dCt_d = (double *)sr_workspace(ctx, SR_WS_OUT1, (size_t)(L * nV) * sizeof(double));
     if (!psum || !Ct_d || !dCt_d) return -5;
     SR_HIP(hipMemcpy2DAsync(psum + 1, (size_t)Lp * sizeof(double), sums, (size_t)L * sizeof(double), (size_t)L * sizeof(double),

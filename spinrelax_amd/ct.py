@@ -123,17 +123,22 @@ def _check_pairs(pairs, nV):
     return np.stack(hip.pair_columns(pairs, nV), axis=1)
 
 
-def _ct_cross(rv, R, F, pairs, **kw):
-    """The dispatch of the pair cross-correlation: chunks that k_ct_cross can stage go to it (rv.ct_cross), longer ones -- and, under
-    sr_set_option("ct_cross_long_min_frames", n), every chunk of at least n frames -- to the blocked form (rv.ct_cross_long)."""
+def _dispatch(rv, stem, label, F, *args, **kw):
+    """The dispatch of the three extensions of C(t), stem = 'cross', 'dipolar' or 'dipolar_cross': chunks that the staged kernel can hold
+    go to it (rv.ct_<stem>), longer ones -- and, under sr_set_option("ct_<stem>_long_min_frames", n), every chunk of at least n frames --
+    to the blocked form (rv.ct_<stem>_long); args and kw are handed on to either."""
     c = rv.ctx
-    direct_max, long_max = c.ct_cross_max_frames(), c.ct_cross_long_max_frames()
+    direct_max = getattr(c, 'ct_%s_max_frames' % stem)()
+    long_max = getattr(c, 'ct_%s_long_max_frames' % stem)()
     if F > long_max:
-        raise ValueError('cross-correlation functions: a chunk of %d frames is beyond both forms (the staged kernel takes %d frames, the '
-                         'blocked transforms %d)' % (F, direct_max, long_max))
-    if F > direct_max or F >= c.ct_cross_long_min_frames:
-        return rv.ct_cross_long(R, F, pairs, **kw)
-    return rv.ct_cross(R, F, pairs, **kw)
+        raise ValueError('%s: a chunk of %d frames is beyond both forms (the staged kernel takes %d frames, the blocked transforms %d)'
+                         % (label, F, direct_max, long_max))
+    blocked = F > direct_max or F >= getattr(c, 'ct_%s_long_min_frames' % stem)
+    return getattr(rv, 'ct_%s_long' % stem if blocked else 'ct_%s' % stem)(*args, **kw)
+
+
+def _ct_cross(rv, R, F, pairs, **kw):
+    return _dispatch(rv, 'cross', 'cross-correlation functions', F, R, F, pairs, **kw)
 
 
 def calculate_Ct_cross(vecs, pairs, symmetric=True, ctx=None, mode=0):
@@ -185,29 +190,11 @@ def _check_dist(dist, shape):
 
 
 def _ct_dipolar(rv, R, F, **kw):
-    """The dispatch of the dipolar correlation function: chunks that k_ct_dipolar can stage go to it (rv.ct_dipolar), longer ones -- and,
-    under sr_set_option("ct_dipolar_long_min_frames", n), every chunk of at least n frames -- to the blocked form (rv.ct_dipolar_long)."""
-    c = rv.ctx
-    direct_max, long_max = c.ct_dipolar_max_frames(), c.ct_dipolar_long_max_frames()
-    if F > long_max:
-        raise ValueError('dipolar correlation function: a chunk of %d frames is beyond both forms (the staged kernel takes %d frames, the '
-                         'blocked transforms %d)' % (F, direct_max, long_max))
-    if F > direct_max or F >= c.ct_dipolar_long_min_frames:
-        return rv.ct_dipolar_long(R, F, **kw)
-    return rv.ct_dipolar(R, F, **kw)
+    return _dispatch(rv, 'dipolar', 'dipolar correlation function', F, R, F, **kw)
 
 
 def _ct_dipolar_cross(rv, R, F, pairs, **kw):
-    """The same for the dipolar pair cross-correlation: rv.ct_dipolar_cross, or rv.ct_dipolar_cross_long beyond what k_ct_dipolar_cross can
-    stage and from sr_set_option("ct_dipolar_cross_long_min_frames", n) frames on."""
-    c = rv.ctx
-    direct_max, long_max = c.ct_dipolar_cross_max_frames(), c.ct_dipolar_cross_long_max_frames()
-    if F > long_max:
-        raise ValueError('dipolar cross-correlation functions: a chunk of %d frames is beyond both forms (the staged kernel takes %d frames, '
-                         'the blocked transforms %d)' % (F, direct_max, long_max))
-    if F > direct_max or F >= c.ct_dipolar_cross_long_min_frames:
-        return rv.ct_dipolar_cross_long(R, F, pairs, **kw)
-    return rv.ct_dipolar_cross(R, F, pairs, **kw)
+    return _dispatch(rv, 'dipolar_cross', 'dipolar cross-correlation functions', F, R, F, pairs, **kw)
 
 
 def calculate_Ct_dipolar(vecs, dist=None, ctx=None, mode=0):

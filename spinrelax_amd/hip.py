@@ -26,6 +26,16 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _chunk_starts(chunk_start, R=None):
+    """the chunk table as the C ABI takes it: None (regular chunks) or contiguous int64; with R, a table of another length raises"""
+    if chunk_start is None:
+        return None
+    cs = np.ascontiguousarray(chunk_start, dtype=np.int64)
+    if R is not None and cs.shape != (R,):
+        raise ValueError('chunk_start must have R entries')
+    return cs
+
+
 def pair_columns(pairs, nV=None):
     """(nP, 2) vector indices -> the two contiguous int32 columns the C ABI takes; with nV, indices outside [0, nV) raise
     ValueError here (otherwise the library refuses them)"""
@@ -185,9 +195,7 @@ class Context:
         L = F // 2
         Ct = np.empty((L, nV))
         dCt = np.empty((L, nV))
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        if cs is not None and cs.shape != (R,):
-            raise ValueError('chunk_start must have R entries')
+        cs = _chunk_starts(chunk_start, R)
         check(self.lib.sr_ct_palmer_f32(self.h, _ptr(vecs), N, Vtot, v0, nV, R, F, _ptr(cs), int(mode), _ptr(Ct), _ptr(dCt)),
               'sr_ct_palmer_f32')
         return Ct, dCt
@@ -199,21 +207,21 @@ class Context:
         check(self.lib.sr_pack_soa_rot_f32_dev(self.h, vecs_ptr, N, Vtot, v0, nV, quat_ptr, soa_ptr, Npad), 'sr_pack_soa_rot_f32_dev')
 
     def ct_palmer_dev(self, soa_ptr, Npad, R, F, nV, Ct_ptr, dCt_ptr, chunk_start=None, mode=0, psum_ptr=None):
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        cs = _chunk_starts(chunk_start)
         check(self.lib.sr_ct_palmer_f32_dev(self.h, soa_ptr, Npad, R, F, nV, _ptr(cs), int(mode), psum_ptr, Ct_ptr, dCt_ptr),
               'sr_ct_palmer_f32_dev')
 
     def ct_sums_dev(self, soa_ptr, Npad, R, F, nV, psum_ptr, chunk_start=None, mode=0):
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        check(self.lib.sr_ct_palmer_sums_f32_dev(self.h, soa_ptr, Npad, R, F, nV, None if cs is None else _ptr(cs), mode, psum_ptr),
+        cs = _chunk_starts(chunk_start)
+        check(self.lib.sr_ct_palmer_sums_f32_dev(self.h, soa_ptr, Npad, R, F, nV, _ptr(cs), mode, psum_ptr),
               'sr_ct_palmer_sums_f32_dev')
 
     def ct_sums_pack_dev(self, soa_ptr, Npad, R, F, nV, psum_ptr, next_vecs_ptr, next_N, next_Vtot, next_v0, next_nV, next_soa_ptr,
                          next_Npad, chunk_start=None, mode=0):
         """ct_sums_dev, and pack_soa_dev of the next batch (another plane buffer) with it: one launch when the library can carry
         the pack inside the C(t) kernel (ct_pack_fused), else the pack in front of the C(t) kernel on the same stream"""
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        check(self.lib.sr_ct_palmer_sums_pack_f32_dev(self.h, soa_ptr, Npad, R, F, nV, None if cs is None else _ptr(cs), mode, psum_ptr,
+        cs = _chunk_starts(chunk_start)
+        check(self.lib.sr_ct_palmer_sums_pack_f32_dev(self.h, soa_ptr, Npad, R, F, nV, _ptr(cs), mode, psum_ptr,
                                                       next_vecs_ptr, next_N, next_Vtot, next_v0, next_nV, next_soa_ptr, next_Npad),
               'sr_ct_palmer_sums_pack_f32_dev')
 
@@ -221,8 +229,8 @@ class Context:
                           next_Npad, chunk_start=None, mode=0):
         """what ct_sums_pack_dev would do with these arguments, nothing queued: True = one launch carries the pack, False = the pack
         in front of the C(t) kernel; a refusal raises"""
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        rc = self.lib.sr_ct_palmer_sums_pack_plan(self.h, soa_ptr, Npad, R, F, nV, None if cs is None else _ptr(cs), mode, psum_ptr,
+        cs = _chunk_starts(chunk_start)
+        rc = self.lib.sr_ct_palmer_sums_pack_plan(self.h, soa_ptr, Npad, R, F, nV, _ptr(cs), mode, psum_ptr,
                                                   next_vecs_ptr, next_N, next_Vtot, next_v0, next_nV, next_soa_ptr, next_Npad)
         if rc < 0:
             check(rc, 'sr_ct_palmer_sums_pack_plan')
@@ -248,10 +256,20 @@ class Context:
                      dP0_ptr=None):
         """P0 (nP) (and its error dP0 when dP0_ptr is given), C(t) and dC(t) (F//2, nP) of the pairs (nP, 2) from packed planes into
         device arrays (sr_ct_cross_f32_dev); asynchronous on the context's stream"""
+        self._pairs_dev('sr_ct_cross_f32_dev', soa_ptr, Npad, nV, R, F, pairs, chunk_start, sym, mode, psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr)
+
+    def _pairs_dev(self, name, planes_ptr, Npad, nV, R, F, pairs, chunk_start, sym, mode, psum_ptr, *out_ptrs):
+        """a pair entry point of the library by name: staged or blocked, unit-vector planes or the dipolar pack (whose wsum2 follows dCt)"""
         pi, pj = pair_columns(pairs)
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        check(self.lib.sr_ct_cross_f32_dev(self.h, soa_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
-                                           int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr), 'sr_ct_cross_f32_dev')
+        cs = _chunk_starts(chunk_start)
+        check(getattr(self.lib, name)(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
+                                      int(mode), psum_ptr, *out_ptrs), name)
+
+    def _dipolar_dev(self, name, planes_ptr, Npad, nV, R, F, chunk_start, mode, psum_ptr, Ct_ptr, dCt_ptr, wmean_ptr):
+        """sr_ct_dipolar_f32_dev or its blocked counterpart, by name"""
+        cs = _chunk_starts(chunk_start)
+        check(getattr(self.lib, name)(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), int(mode), psum_ptr, Ct_ptr, dCt_ptr,
+                                      wmean_ptr), name)
 
     ct_cross_long_min_frames = 6625     # the library's default of the option: the first length ct_cross refuses
 
@@ -262,10 +280,8 @@ class Context:
     def ct_cross_long_dev(self, soa_ptr, Npad, nV, R, F, pairs, P0_ptr, Ct_ptr, dCt_ptr, chunk_start=None, sym=1, mode=0, psum_ptr=None,
                           dP0_ptr=None):
         """ct_cross_dev for chunks of 5462 .. ct_cross_long_max_frames() frames, by blocked transforms (sr_ct_cross_long_f32_dev)"""
-        pi, pj = pair_columns(pairs)
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        check(self.lib.sr_ct_cross_long_f32_dev(self.h, soa_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
-                                                int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr), 'sr_ct_cross_long_f32_dev')
+        self._pairs_dev('sr_ct_cross_long_f32_dev', soa_ptr, Npad, nV, R, F, pairs, chunk_start, sym, mode, psum_ptr, P0_ptr, dP0_ptr, Ct_ptr,
+                        dCt_ptr)
 
     # ---- distance-weighted dipolar correlation function (sr_ct_dipolar.hip) ----
     def ct_dipolar_max_frames(self):
@@ -282,9 +298,7 @@ class Context:
     def ct_dipolar_dev(self, planes_ptr, Npad, nV, R, F, Ct_ptr, dCt_ptr, wmean_ptr, chunk_start=None, mode=0, psum_ptr=None):
         """C_dd(t) and dC_dd(t) (F//2, nV) and wmean (nV, 2) = <w>, <w^2> from the four planes of pack_dipolar_dev into device arrays
         (sr_ct_dipolar_f32_dev); asynchronous on the context's stream"""
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        check(self.lib.sr_ct_dipolar_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), int(mode), psum_ptr, Ct_ptr,
-                                             dCt_ptr, wmean_ptr), 'sr_ct_dipolar_f32_dev')
+        self._dipolar_dev('sr_ct_dipolar_f32_dev', planes_ptr, Npad, nV, R, F, chunk_start, mode, psum_ptr, Ct_ptr, dCt_ptr, wmean_ptr)
 
     # ---- distance-weighted pair cross-correlation functions (sr_ct_dipolar_cross.hip) ----
     def ct_dipolar_cross_max_frames(self):
@@ -297,11 +311,8 @@ class Context:
         """P0 (nP) (and its error dP0 when dP0_ptr is given), C(t) and dC(t) (F//2, nP) of the pairs (nP, 2) and wsum2 (nP, R, 2), the sums
         of w_i^2 and w_j^2 over every chunk, from the four planes of pack_dipolar_dev into device arrays (sr_ct_dipolar_cross_f32_dev);
         asynchronous on the context's stream"""
-        pi, pj = pair_columns(pairs)
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        check(self.lib.sr_ct_dipolar_cross_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size,
-                                                   int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr, wsum2_ptr),
-              'sr_ct_dipolar_cross_f32_dev')
+        self._pairs_dev('sr_ct_dipolar_cross_f32_dev', planes_ptr, Npad, nV, R, F, pairs, chunk_start, sym, mode, psum_ptr, P0_ptr, dP0_ptr, Ct_ptr,
+                        dCt_ptr, wsum2_ptr)
 
     # ---- both for long chunks: blocked transforms (sr_ct_dipolar_long.hip) ----
     ct_dipolar_long_min_frames = 10017          # the library's defaults of the two options: the first lengths that ct_dipolar and
@@ -318,19 +329,14 @@ class Context:
     def ct_dipolar_long_dev(self, planes_ptr, Npad, nV, R, F, Ct_ptr, dCt_ptr, wmean_ptr, chunk_start=None, mode=0, psum_ptr=None):
         """ct_dipolar_dev for chunks of 5462 .. ct_dipolar_long_max_frames() frames, by blocked transforms (sr_ct_dipolar_long_f32_dev); the
         planes must come from pack_dipolar_dev"""
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        check(self.lib.sr_ct_dipolar_long_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), int(mode), psum_ptr, Ct_ptr,
-                                                  dCt_ptr, wmean_ptr), 'sr_ct_dipolar_long_f32_dev')
+        self._dipolar_dev('sr_ct_dipolar_long_f32_dev', planes_ptr, Npad, nV, R, F, chunk_start, mode, psum_ptr, Ct_ptr, dCt_ptr, wmean_ptr)
 
     def ct_dipolar_cross_long_dev(self, planes_ptr, Npad, nV, R, F, pairs, P0_ptr, Ct_ptr, dCt_ptr, wsum2_ptr, chunk_start=None, sym=1, mode=0,
                                   psum_ptr=None, dP0_ptr=None):
         """ct_dipolar_cross_dev for chunks of 4097 .. ct_dipolar_cross_long_max_frames() frames, by blocked transforms
         (sr_ct_dipolar_cross_long_f32_dev); the planes must come from pack_dipolar_dev"""
-        pi, pj = pair_columns(pairs)
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        check(self.lib.sr_ct_dipolar_cross_long_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj),
-                                                        pi.size, int(sym), int(mode), psum_ptr, P0_ptr, dP0_ptr, Ct_ptr, dCt_ptr, wsum2_ptr),
-              'sr_ct_dipolar_cross_long_f32_dev')
+        self._pairs_dev('sr_ct_dipolar_cross_long_f32_dev', planes_ptr, Npad, nV, R, F, pairs, chunk_start, sym, mode, psum_ptr, P0_ptr, dP0_ptr,
+                        Ct_ptr, dCt_ptr, wsum2_ptr)
 
     # ---- iRED matrix (sr_ired.hip) ----
     def ired_matrix_dev(self, soa_ptr, Npad, nV, win_start, win_len, M_ptr):
@@ -981,9 +987,7 @@ class ResidentVectors:
         L = F // 2
         Ct = np.empty((L, self.nV))
         dCt = np.empty((L, self.nV))
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        if cs is not None and cs.shape != (R,):
-            raise ValueError('chunk_start must have R entries')
+        cs = _chunk_starts(chunk_start, R)
         check(self.ctx.lib.sr_vectors_ct_f32(self.ctx.h, self.h, int(R), int(F), _ptr(cs), int(mode), _ptr(Ct), _ptr(dCt)),
               'sr_vectors_ct_f32')
         return Ct, dCt
@@ -1005,17 +1009,12 @@ class ResidentVectors:
         P0 = np.empty(pi.size)
         Ct = np.empty((L, pi.size))
         dCt = np.empty((L, pi.size))
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        if cs is not None and cs.shape != (R,):
-            raise ValueError('chunk_start must have R entries')
-        if want_dP0:
-            dP0 = np.empty(pi.size)
-            check(getattr(self.ctx.lib, stem + '_err_f32')(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
-                                                           int(mode), _ptr(P0), _ptr(dP0), _ptr(Ct), _ptr(dCt)), stem + '_err_f32')
-            return P0, dP0, Ct, dCt
-        check(getattr(self.ctx.lib, stem + '_f32')(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym),
-                                                   int(mode), _ptr(P0), _ptr(Ct), _ptr(dCt)), stem + '_f32')
-        return P0, Ct, dCt
+        cs = _chunk_starts(chunk_start, R)
+        out = (P0, np.empty(pi.size), Ct, dCt) if want_dP0 else (P0, Ct, dCt)
+        name = stem + ('_err_f32' if want_dP0 else '_f32')
+        check(getattr(self.ctx.lib, name)(self.ctx.h, self.h, int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym), int(mode),
+                                          *[_ptr(a) for a in out]), name)
+        return out
 
     def ct_dipolar(self, R, F, dist=None, chunk_start=None, mode=0):
         """distance-weighted dipolar correlation function of the resident vectors (sr_vectors_ct_dipolar_f32):
@@ -1029,19 +1028,22 @@ class ResidentVectors:
         (sr_vectors_ct_dipolar_long_f32): the same arguments and results"""
         return self._ct_dipolar('sr_vectors_ct_dipolar_long_f32', R, F, dist, chunk_start, mode)
 
+    def _held_dist(self, dist):
+        """a distance array as the library takes it: None, or float32 of the shape (frames held, vectors)"""
+        if dist is None:
+            return None
+        d = _f32(dist)
+        if d.shape != (self.frames, self.nV):
+            raise ValueError('dist must be (frames held, vectors) = (%d, %d), got %s' % (self.frames, self.nV, d.shape))
+        return d
+
     def _ct_dipolar(self, name, R, F, dist, chunk_start, mode):
         L = F // 2
-        d = None
-        if dist is not None:
-            d = _f32(dist)
-            if d.shape != (self.frames, self.nV):
-                raise ValueError('dist must be (frames held, vectors) = (%d, %d), got %s' % (self.frames, self.nV, d.shape))
+        d = self._held_dist(dist)
         Ct = np.empty((L, self.nV))
         dCt = np.empty((L, self.nV))
         reff6, reff3, S2rad = np.empty(self.nV), np.empty(self.nV), np.empty(self.nV)
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        if cs is not None and cs.shape != (R,):
-            raise ValueError('chunk_start must have R entries')
+        cs = _chunk_starts(chunk_start, R)
         check(getattr(self.ctx.lib, name)(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), int(mode), _ptr(Ct), _ptr(dCt), _ptr(reff6),
                                           _ptr(reff3), _ptr(S2rad)), name)
         return Ct, dCt, reff6, reff3, S2rad
@@ -1061,18 +1063,12 @@ class ResidentVectors:
     def _ct_dipolar_cross(self, name, R, F, pairs, dist, chunk_start, sym, mode):
         pi, pj = pair_columns(pairs)
         L = F // 2
-        d = None
-        if dist is not None:
-            d = _f32(dist)
-            if d.shape != (self.frames, self.nV):
-                raise ValueError('dist must be (frames held, vectors) = (%d, %d), got %s' % (self.frames, self.nV, d.shape))
+        d = self._held_dist(dist)
         P0, dP0 = np.empty(pi.size), np.empty(pi.size)
         Ct = np.empty((L, pi.size))
         dCt = np.empty((L, pi.size))
         reff6 = np.empty((pi.size, 2))
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
-        if cs is not None and cs.shape != (R,):
-            raise ValueError('chunk_start must have R entries')
+        cs = _chunk_starts(chunk_start, R)
         check(getattr(self.ctx.lib, name)(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), _ptr(pi), _ptr(pj), pi.size, int(sym), int(mode),
                                           _ptr(P0), _ptr(dP0), _ptr(Ct), _ptr(dCt), _ptr(reff6)), name)
         return P0, dP0, Ct, dCt, reff6
@@ -1080,7 +1076,7 @@ class ResidentVectors:
     def ct_sums(self, R, F, chunk_start=None, mode=0):
         """raw sums S[v, r, d-1] = sum_j (u_j . u_{j+d})^2 of the R chunks held, (nV, R, F//2) float64 (replicate sharding)"""
         sums = np.empty((self.nV, R, F // 2))
-        cs = None if chunk_start is None else np.ascontiguousarray(chunk_start, dtype=np.int64)
+        cs = _chunk_starts(chunk_start)
         check(self.ctx.lib.sr_vectors_ct_sums_f32(self.ctx.h, self.h, int(R), int(F), _ptr(cs), int(mode), _ptr(sums)),
               'sr_vectors_ct_sums_f32')
         return sums

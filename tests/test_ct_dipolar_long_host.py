@@ -183,10 +183,17 @@ def test_library_exports_the_new_entry_points():
 
 # ---- dispatch ----------------------------------------------------------------------------------------------------------------------------
 class StubContext:
-    """what ct._ct_dipolar and ct._ct_dipolar_cross ask of a context: the limits of both forms and the two options, kept as hip.Context
+    """what ct._dispatch asks of a context for its three stems: the limits of both forms and the three options, kept as hip.Context
     keeps them"""
+    ct_cross_long_min_frames = 6625
     ct_dipolar_long_min_frames = 10017
     ct_dipolar_cross_long_min_frames = 4897
+
+    def ct_cross_max_frames(self):
+        return 6624
+
+    def ct_cross_long_max_frames(self):
+        return 262144
 
     def ct_dipolar_max_frames(self):
         return 10016
@@ -204,6 +211,14 @@ class StubContext:
 class StubVectors:
     def __init__(self, nV=3, frames=1 << 20):
         self.ctx, self.nV, self.frames, self.calls = StubContext(), nV, frames, []
+
+    def ct_cross(self, R, F, pairs, **kw):
+        self.calls.append(('direct', R, F, kw))
+        return 'udirect'
+
+    def ct_cross_long(self, R, F, pairs, **kw):
+        self.calls.append(('blocked', R, F, kw))
+        return 'ublocked'
 
     def ct_dipolar(self, R, F, **kw):
         self.calls.append(('direct', R, F, kw))
@@ -251,6 +266,56 @@ def test_dispatch_of_the_dipolar_pair_cross_correlation():
     assert hostct.calculate_Ct_dipolar_cross_resident(rv, pairs, 2, 4096) == 'xdirect'
     assert hostct.calculate_Ct_dipolar_cross_resident(rv, pairs, 2, 4097) == 'xblocked'
     assert hostct.calculate_Ct_dipolar_cross_resident(rv, pairs, 2, 4896) == 'xblocked'
+
+
+def test_dispatch_of_the_pair_cross_correlation():
+    rv = StubVectors()
+    pairs = [(0, 1), (2, 2)]
+    assert hostct.calculate_Ct_cross_resident(rv, pairs, 2, 6624) == 'udirect'
+    assert hostct.calculate_Ct_cross_resident(rv, pairs, 2, 6625, symmetric=False, want_dP0=True) == 'ublocked'
+    assert rv.calls[-1] == ('blocked', 2, 6625, {'chunk_start': None, 'sym': 0, 'mode': 0, 'want_dP0': True})
+    assert hostct.calculate_Ct_cross_resident(rv, pairs, 1, 262144) == 'ublocked'
+    with pytest.raises(ValueError) as exc:
+        hostct.calculate_Ct_cross_resident(rv, pairs, 1, 262145)
+    assert '6624' in str(exc.value) and '262144' in str(exc.value)
+    rv.ctx.ct_cross_long_min_frames = 5462
+    assert hostct.calculate_Ct_cross_resident(rv, pairs, 2, 5461) == 'udirect'
+    assert hostct.calculate_Ct_cross_resident(rv, pairs, 2, 5462) == 'ublocked'
+    assert hostct.calculate_Ct_cross_resident(rv, pairs, 2, 6624) == 'ublocked'
+
+
+# stem, label of the error text, staged limit, floor of the blocked form, extra positional arguments, names of the two forms' results
+STEMS = [('cross', 'cross-correlation functions', 6624, 5462, ([(0, 1)],), ('udirect', 'ublocked')),
+         ('dipolar', 'dipolar correlation function', 10016, 5462, (), ('direct', 'blocked')),
+         ('dipolar_cross', 'dipolar cross-correlation functions', 4896, 4097, ([(0, 1)],), ('xdirect', 'xblocked'))]
+
+
+@pytest.mark.parametrize('stem,label,staged,floor,extra,names', STEMS)
+def test_one_dispatch_rule_for_the_three_stems(stem, label, staged, floor, extra, names):
+    """ct._dispatch at the staged limit, one beyond it, the floor the option may be set to, the blocked limit and one beyond it: the
+    decisions of the three functions it replaced (beyond the staged limit or from the option on: blocked; beyond both: ValueError with the
+    text of that function, word for word)"""
+    rv = StubVectors()
+    go = lambda F: hostct._dispatch(rv, stem, label, F, 2, F, *extra, mode=1)
+    assert go(staged) == names[0] and rv.calls[-1] == ('direct', 2, staged, {'mode': 1})
+    assert go(staged + 1) == names[1] and rv.calls[-1] == ('blocked', 2, staged + 1, {'mode': 1})
+    assert go(262144) == names[1]
+    with pytest.raises(ValueError) as exc:
+        go(262145)
+    assert str(exc.value) == ('%s: a chunk of 262145 frames is beyond both forms (the staged kernel takes %d frames, the blocked transforms '
+                              '262144)' % (label, staged))
+    assert len(rv.calls) == 3                                             # the refusal called neither form
+    setattr(rv.ctx, 'ct_%s_long_min_frames' % stem, floor)
+    assert go(floor - 1) == names[0] and go(floor) == names[1] and go(staged) == names[1]
+
+
+def test_no_source_claims_that_a_blocked_form_is_missing():
+    """every staged form names its blocked counterpart in its -4 message (tests/test_gpu_ct_cross.py holds the library to it)"""
+    for sub in (os.path.join('spinrelax_amd', 'csrc'), 'include'):
+        for name in sorted(os.listdir(os.path.join(ROOT, sub))):
+            if name.endswith(('.hip', '.h')):
+                with open(os.path.join(ROOT, sub, name)) as fp:
+                    assert 'no blocked form' not in fp.read(), name
 
 
 def test_context_keeps_the_defaults_of_the_two_options():

@@ -241,6 +241,27 @@ def test_capacity(ctx):
         assert '(-3)' in str(exc.value)
 
 
+def test_too_many_pairs_are_refused_by_the_check(ctx):
+    """one pair more than k_ct_finalize's grid takes (16 x 65535): refused with the other shapes, before anything is queued"""
+    pairs = np.zeros((16 * 65535 + 1, 2), dtype=np.int32)
+    with ctx.vectors(1, 2) as rv:
+        rv.append(make_vectors(2, seed=3, nV=1))
+        with pytest.raises(SpinRelaxHipError) as exc:
+            rv.ct_cross(1, 2, pairs)
+        assert '(-3)' in str(exc.value) and 'too many pairs' in str(exc.value)
+
+
+def test_the_staged_form_names_the_blocked_one(ctx):
+    """one frame beyond the staged limit: the refusal states the limit and where longer chunks go"""
+    pairs = np.array([(0, 1)], dtype=np.int32)
+    with ctx.vectors(2, 6625) as rv:
+        rv.append(make_vectors(6625, seed=9, nV=2))
+        with pytest.raises(SpinRelaxHipError) as exc:
+            rv.ct_cross(1, 6625, pairs)
+        text = str(exc.value)
+        assert '(-4)' in text and '6624' in text and 'sr_ct_cross_long_f32_dev' in text and 'no blocked form' not in text
+
+
 def run(script, *args):
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', script)] + [str(a) for a in args], stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, timeout=600)

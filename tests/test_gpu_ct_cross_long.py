@@ -270,6 +270,17 @@ def test_refusals(ctx):
         rv.ct_cross_long(1, 7000, pairs)                                       # and the object still works
 
 
+def test_too_many_pairs_are_refused_by_the_check(ctx):
+    """one pair more than k_ct_finalize's grid takes (16 x 65535) at the shortest blocked chunk: refused with the other shapes, before
+    the work area for the raw sums of a million pairs is asked for"""
+    pairs = np.zeros((16 * 65535 + 1, 2), dtype=np.int32)
+    with ctx.vectors(1, 5462) as rv:
+        rv.append(make_vectors(5462, seed=3, nV=1))
+        with pytest.raises(SpinRelaxHipError) as exc:
+            rv.ct_cross_long(1, 5462, pairs)
+        assert '(-3)' in str(exc.value) and 'too many pairs' in str(exc.value)
+
+
 def run(script, *args):
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', script)] + [str(a) for a in args], stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, timeout=600)

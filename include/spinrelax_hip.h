@@ -398,6 +398,37 @@ int sr_noe_pairs_check(sr_ctx *, int64_t nFrames, int64_t nAtoms, const int32_t 
 int sr_noe_tile(void);          /* T: atoms per tile side (tests aim at tile edges) */
 int sr_noe_frame_batch(void);   /* frames per LDS stage of k_noe_pairs */
 
+/* ---- the all-pairs dipolar map at a few chosen lags (sr_noe_lagged.hip; beyond the reference) ----------------------------------------
+ * For the same atoms, blocks and pair order, and K lags k = lags[0] < lags[1] < ...:
+ *     G[b][q][k(i, j)] = sum over the origins t of block b with t + k inside the block of
+ *                        [1.5 (d'(t) . d'(t + k))^2 / (r(t)^2 r(t + k)^2) - 0.5] r(t)^-3 r(t + k)^-3,      d'(t) = R(quat[t]) d(t)
+ * the unnormalised dipolar correlation function of every pair at lag k; G at lag 0 is the map's r^-6 sum.  C_dd(k) and the per-pair
+ * internal correlation time are host work (spinrelax_amd/noe.py).
+ *   mode 0: float32 per pair, frame and lag: d, e the differences at t and t + k; r2, s2 by the map's two-fma chain; v_rsq_f32 of
+ *           both; d', e' by three fmas per component, R rounded to float32; c = fma(d'z, e'z, fma(d'y, e'y, d'x e'x)); g = ri si;
+ *           x = c g; g3 = (g g) g; p = fma(1.5 x, x, -0.5); term = p g3; float32 partial sums of at most 8 origins, then float64.
+ *   mode 1: the same sequence in float64 with 1 / sqrt.
+ * k_noe_lagged: one workgroup per (block, lag, frame split, tile pair), tiles and threads as in k_noe_pairs, two windows of
+ * sr_noe_frame_batch() frames in LDS (the origins and the frames one lag later).  A frame split owns a range of origins, runs of
+ * ceil((n_b - k) / S); k_noe_lagged_finish adds the S partial tiles in the order s = 0 .. S-1.  No atomics: equal input gives
+ * bit-equal G.  S = sr_noe_lagged_splits(P, longest block, B) is the map's split count and does not depend on the lags: a lag has the
+ * same bits alone and in any list.  With S > 1 the partial tiles are a work area of about S times the bytes of G.
+ *   lags_host (K) int32: HOST array, like the index and the block tables; G: DEVICE (B, K, P (P - 1) / 2) float64.  Asynchronous on
+ *   the context's stream.
+ * Refused with -3, before anything is queued: everything sr_noe_pairs_check refuses; K < 1 or K > 64; a negative lag; lags that are
+ * not strictly increasing; a largest lag >= the shortest block (every (block, lag) has at least one term); G plus the partial tiles
+ * beyond the device's memory; B K S tile pairs >= 2^31 workgroups. */
+int sr_noe_lagged_f32_dev(sr_ctx *, const float *xyz, int64_t nFrames, int64_t nAtoms, const int32_t *index_host, int64_t P,
+                          const double *quat, const int64_t *block_start_host, const int64_t *block_len_host, int B,
+                          const int32_t *lags_host, int K, int mode, double *G);
+/* the same with xyz, quat (may be NULL) and G on the HOST.  Blocks until G is there. */
+int sr_noe_lagged_f32(sr_ctx *, const float *xyz, int64_t nFrames, int64_t nAtoms, const int32_t *index, int64_t P, const double *quat,
+                      const int64_t *block_start, const int64_t *block_len, int B, const int32_t *lags, int K, int mode, double *G);
+/* What the two calls above refuse with -3, with their message, and nothing else: all host work, nothing allocated or queued. */
+int sr_noe_lagged_check(sr_ctx *, int64_t nFrames, int64_t nAtoms, const int32_t *index, int64_t P, const int64_t *block_start,
+                        const int64_t *block_len, int B, const int32_t *lags, int K, int mode);
+int sr_noe_lagged_splits(int64_t P, int64_t longest_block, int B);   /* S of such a call (tests aim at S > 1); 0 for a bad shape */
+
 /* ---- NOESY intensities from the dipolar map: the full relaxation matrix (sr_noesy.hip; beyond the reference) -------------------------
  * Macura & Ernst, Mol. Phys. 41, 95 (1980); Keepers & James, J. Magn. Reson. 57, 404 (1984); the model-free rates from <r^-6> and S2:
  * Brueschweiler et al., JACS 114, 2289 (1992).  Isotropic tumbling, one kind of spin.  With A6 and S2 (P (P - 1) / 2 each) in the pair

@@ -6,7 +6,7 @@ files (<o>_Ctext.dat, <o>_Ctint.dat, <o>_vecHistogram.npz | _vecPhiTheta.npz|.da
 also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat; with the [extension] --crossCt --pairs FILE also <o>_crossCtint.dat
 and <o>_crossPairs.dat; with the [extension] --dipolarCt also <o>_dipolarCtint.dat and <o>_dipolarDist.dat; with the
 [extension] --dipolarCrossCt --pairs FILE also <o>_dipolarCrossCtint.dat and <o>_dipolarCrossPairs.dat; with the [extension] --noeMap
-also <o>_noeMap.dat and, with --binary, <o>_noeMap.npz, and with --noesy on top of it <o>_noesy.dat and, with --binary,
+also <o>_noeMap.dat and, with --binary, <o>_noeMap.npz, with --noeLags / --noeLagMax on top of it <o>_noeMapCt.dat, and with --noesy on top of it <o>_noesy.dat and, with --binary,
 <o>_noesy.npz).  C(t), the rotation into
 the PAF, the spherical histogram, the mean vector and S2 are computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
@@ -123,6 +123,16 @@ def build_parser():
                         'of --dipolarCt.  Single process only.')
     p.add_argument('--noeCutoff', type=float, dest='noe_cutoff', default=None,
                    help='[extension] --noeMap lists only the pairs with reff6 <= this distance, in the units of the coordinates.')
+    p.add_argument('--noeLags', type=str, dest='noe_lags', default=None,
+                   help='[extension] with --noeMap: the dipolar correlation function C_dd(k) of EVERY pair at these lags, in frames, e.g. '
+                        '"1 2 4 8 16" (integers >= 0, strictly increasing, at most 64, the largest below the frames of a --tau block), and '
+                        'from them the internal correlation time tau_e of every pair (the Lipari-Szabo integral of (C_dd - S2) / (1 - S2) by '
+                        'the trapezoid rule): <o>_noeMapCt.dat with the columns i j name_i name_j tau_e dtau_e and one C_dd column per lag, '
+                        'times in ps; with --binary lags, G, Cdd, dCdd, tau_e and dtau_e also go into <o>_noeMap.npz.')
+    p.add_argument('--noeLagMax', type=int, dest='noe_lag_max', default=None,
+                   help='[extension] with --noeMap, in the place of --noeLags: about --noeLagCount log-spaced lags from 1 to this many frames.')
+    p.add_argument('--noeLagCount', type=int, dest='noe_lag_count', default=None,
+                   help='[extension] --noeLagMax: the number of lags (default 12; neighbours that round to the same frame are merged).')
     p.add_argument('--noesy', dest='bDoNoesy', action='store_true', default=False,
                    help='[extension] with --noeMap: NOESY cross-peak intensities of the map\'s spins by the full relaxation matrix '
                         '(Macura & Ernst 1980; Keepers & James 1984; model-free rates from <r^-6> and S2, Brueschweiler et al. 1992), spin '
@@ -135,6 +145,9 @@ def build_parser():
     p.add_argument('--noesyTauC', type=float, dest='noesy_tauc', default=None, help='[extension] --noesy: the overall correlation time tau_c in seconds.')
     p.add_argument('--noesyTauE', type=float, dest='noesy_taue', default=None,
                    help='[extension] --noesy: the correlation time of the internal motion tau_e in seconds (default 1e-10).')
+    p.add_argument('--noesyTauEMap', dest='noesy_taue_map', action='store_true', default=False,
+                   help='[extension] --noesy: every pair with its own tau_e, the one --noeLags / --noeLagMax give (ps, converted to '
+                        'seconds; floored at 1e-12 s), in the place of one --noesyTauE for all pairs.')
     p.add_argument('--noesyLeak', type=float, dest='noesy_leak', default=None,
                    help='[extension] --noesy: a leakage rate in 1/s added to every diagonal element (default 0).')
     p.add_argument('--noesyUnit', type=str, dest='noesy_unit', default=None, choices=('nm', 'A'),
@@ -145,11 +158,45 @@ def build_parser():
     return p
 
 
+TIME_UNIT_S = 1e-12       # the times of a run (dt of the input, --dt, --tau) are in ps
+
+
+def check_noe_lag_args(args):
+    """the --noeLag* flags that do not fit together or give no lag list: an error message and exit, before any GPU work; returns the
+    lags in frames (int64), None without them"""
+    def fail(msg):
+        print("= = = ERROR: %s" % msg, file=sys.stderr)
+        sys.exit(1)
+    given = [n for n, v in (('--noeLags', args.noe_lags), ('--noeLagMax', args.noe_lag_max), ('--noeLagCount', args.noe_lag_count))
+             if v is not None]
+    if not given:
+        return None
+    if not args.bDoNoeMap:
+        fail("%s belongs to --noeMap; give both." % given[0])
+    if args.noe_lags is not None and args.noe_lag_max is not None:
+        fail("--noeLags and --noeLagMax both give the lags; give one of them.")
+    if args.noe_lag_count is not None and args.noe_lag_max is None:
+        fail("--noeLagCount belongs to --noeLagMax; give both.")
+    if args.noe_lag_max is not None:
+        n = 12 if args.noe_lag_count is None else args.noe_lag_count
+        if args.noe_lag_max < 1 or n < 2 or n > 64:
+            fail("--noeLagMax must be >= 1 and --noeLagCount 2 .. 64; got %d and %d." % (args.noe_lag_max, n))
+        from spinrelax_amd.noe import log_lags
+        return log_lags(args.noe_lag_max, n)
+    try:
+        lags = np.array([int(w) for w in args.noe_lags.split()], dtype=np.int64)
+    except ValueError:
+        lags = np.zeros(0, dtype=np.int64)
+    if lags.size < 1 or lags.size > 64 or lags[0] < 0 or np.any(np.diff(lags) <= 0) or lags[-1] >= 2 ** 31:
+        fail("--noeLags must list 1 .. 64 lags in frames, integers >= 0 and strictly increasing; got '%s'." % args.noe_lags)
+    return lags
+
+
 def check_noesy_args(args):
     """the --noesy* flags that do not fit together: an error message and exit, before any GPU work; returns the mixing times"""
     given = [n for n, v in (('--noesyMix', args.noesy_mix), ('--noesyField', args.noesy_field), ('--noesyTauC', args.noesy_tauc),
                             ('--noesyTauE', args.noesy_taue), ('--noesyLeak', args.noesy_leak), ('--noesyUnit', args.noesy_unit),
-                            ('--noesyGroups', args.noesy_groups)) if v is not None]
+                            ('--noesyGroups', args.noesy_groups), ('--noesyTauEMap', args.noesy_taue_map or None)) if v is not None]
     if not args.bDoNoesy:
         if given:
             print("= = = ERROR: %s belongs to --noesy; give both." % given[0], file=sys.stderr)
@@ -176,6 +223,13 @@ def check_noesy_args(args):
     if args.noesy_groups is not None and not os.path.isfile(args.noesy_groups):
         print("= = = ERROR: --noesyGroups file %s does not exist." % args.noesy_groups, file=sys.stderr)
         sys.exit(1)
+    if args.noesy_taue_map:
+        if args.noesy_taue is not None:
+            print("= = = ERROR: --noesyTauEMap and --noesyTauE both give tau_e; give one of them.", file=sys.stderr)
+            sys.exit(1)
+        if args.noe_lags is None and args.noe_lag_max is None:
+            print("= = = ERROR: --noesyTauEMap takes tau_e from the lagged map; give --noeLags or --noeLagMax.", file=sys.stderr)
+            sys.exit(1)
     return mix
 
 
@@ -184,8 +238,13 @@ def run_noesy(args, out_pref, res, names):
     from spinrelax_amd import noesy
     mix = check_noesy_args(args)
     print("= = = Conducting the relaxation-matrix NOESY calculation of %i spins at %i mixing times." % (res['index'].size, mix.size))
+    tau_e = 1e-10 if args.noesy_taue is None else args.noesy_taue
+    if args.noesy_taue_map:
+        # the map's tau_e is in the time unit of the run
+        res = dict(res, tau_e=res['tau_e'] * TIME_UNIT_S)
+        tau_e = 'map'
     try:
-        out = noesy.noesy(res, mix, args.noesy_field, args.noesy_tauc, tau_e=1e-10 if args.noesy_taue is None else args.noesy_taue,
+        out = noesy.noesy(res, mix, args.noesy_field, args.noesy_tauc, tau_e=tau_e,
                           leak=0.0 if args.noesy_leak is None else args.noesy_leak, unit=args.noesy_unit or 'nm')
         rows = noesy.write_noesy(out_pref + '_noesy.dat', out, names=names, reff6=res['reff6'], cutoff=args.noe_cutoff)
         if args.noesy_groups is not None:
@@ -203,8 +262,10 @@ def run_noesy(args, out_pref, res, names):
 
 def run_noe_map(args, out_pref):
     """--noeMap: the coordinates of all files, one after the other, through spinrelax_amd.noe; the blocks are the --tau chunks of
-    every file (a tail that does not fill one is dropped), without --tau every file as a whole"""
+    every file (a tail that does not fill one is dropped), without --tau every file as a whole; with --noeLags / --noeLagMax also the
+    correlation functions and tau_e of every pair"""
     from spinrelax_amd import ired, noe
+    lags = check_noe_lag_args(args)
     xyz, frames, first = [], [], None
     for fn in args.infn:
         z = np.load(fn, allow_pickle=True) if fn.endswith('.npz') else {}
@@ -237,18 +298,22 @@ def run_noe_map(args, out_pref):
     print("= = = Conducting the all-pairs dipolar map of %i atoms (%i pairs) over %i blocks." % (index.size, noe.n_pairs(index.size), blocks[0].size))
     try:
         if 'ref_xyz' in z and 'fit_indices' in z:
-            res = noe.dipolar_map_superposed(allxyz, z['ref_xyz'], z['fit_indices'], index, blocks=blocks, mode=mode)
+            res = noe.dipolar_map_superposed(allxyz, z['ref_xyz'], z['fit_indices'], index, blocks=blocks, mode=mode, lags=lags, dt=dt)
         else:
             print("= = = WARNING: no `ref_xyz` / `fit_indices` in the input: the map is computed in the lab frame and its S2 includes "
                   "overall tumbling.", file=sys.stderr)
-            res = noe.dipolar_map(allxyz, index, blocks=blocks, mode=mode)
+            res = noe.dipolar_map(allxyz, index, blocks=blocks, mode=mode, lags=lags, dt=dt)
         rows = noe.write_map(out_pref + '_noeMap.dat', res, names=names, cutoff=args.noe_cutoff)
+        if lags is not None:
+            noe.write_map_ct(out_pref + '_noeMapCt.dat', res, names=names, cutoff=args.noe_cutoff)
     except (ValueError, hostct.hip.SpinRelaxHipError) as exc:        # coinciding atoms, a bad index list, a map beyond the device
         print("= = = ERROR: %s" % exc, file=sys.stderr)
         sys.exit(1)
     if args.binary:
         keep = ('pairs', 'index', 'A6', 'A3', 'T', 'reff6', 'reff3', 'S2', 'S2rad', 'dS2', 'dreff6', 'dreff3', 'A6_b', 'A3_b', 'T_b',
                 'reff6_b', 'reff3_b', 'S2_b', 'S2rad_b', 'block_len', 'sums')
+        if lags is not None:
+            keep += ('lags', 'G', 'Cdd', 'dCdd', 'tau_e', 'dtau_e')
         np.savez(out_pref + '_noeMap.npz', block_start=blocks[0], **{k: res[k] for k in keep})
     print("      ...%i of %i pairs written; complete." % (rows, res['reff6'].size))
     if args.bDoNoesy:
@@ -415,6 +480,7 @@ def main():
         print("= = = ERROR: --dipolarCt works on vector-file input (.npy/.npz), not on MDTraj input: the streaming front end keeps no "
               "distances.", file=sys.stderr)
         sys.exit(1)
+    check_noe_lag_args(args)
     check_noesy_args(args)
     time_start = time.time()
     rank, world = srdist.start()

@@ -1,0 +1,108 @@
+// Developer tool: sweeps the pure host helpers of the lagged dipolar map (spinrelax_amd/csrc/sr_noe_host.h: split rule, lag list check,
+// origin ranges, byte counts, grid sizes) against plain restatements of their definitions, under the sanitizers.  No HIP, no GPU:
+//
+//     c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I spinrelax_amd/csrc \
+//         scripts/dev/noe_lagged_host_sweep.cpp -o /tmp/noe_lagged_host_sweep && /tmp/noe_lagged_host_sweep
+//
+// Prints the number of comparisons and exits 0, or names the first disagreement and exits 1.
+#include "sr_noe_host.h"
+
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <vector>
+
+static long checks = 0;
+#define EXPECT(cond, ...)                                  \
+    do {                                                   \
+        ++checks;                                          \
+        if (!(cond)) {                                     \
+            fprintf(stderr, "FAILED %s: ", #cond);         \
+            fprintf(stderr, __VA_ARGS__);                  \
+            fprintf(stderr, "\n");                         \
+            exit(1);                                       \
+        }                                                  \
+    } while (0)
+
+int main()
+{
+    // ---- the split rule: min(256, max(1, Fmax / 128), ceil(4096 / (NP B))), never below 1 ----
+    for (int64_t NP : std::initializer_list<int64_t>{1, 2, 3, 10, 136, 4095, 4096, 4097, (int64_t)1 << 28})
+        for (int64_t F : std::initializer_list<int64_t>{1, 2, 127, 128, 255, 256, 300, 1000, 32768, 100000, (int64_t)1 << 40})
+            for (int B : {1, 2, 3, 24, 65535}) {
+                const int S = noe_ksplit(NP, F, B);
+                int64_t want = (4096 + NP * B - 1) / (NP * B);
+                if (want > (F / 128 > 1 ? F / 128 : 1)) want = F / 128 > 1 ? F / 128 : 1;
+                if (want > 256) want = 256;
+                EXPECT(S == want && S >= 1 && S <= 256, "noe_ksplit(%lld, %lld, %d) = %d", (long long)NP, (long long)F, B, S);
+            }
+
+    // ---- origin ranges: the S ranges tile [0, len - k) in order, none longer than ceil((len - k) / S), hi + k <= len ----
+    for (int64_t len = 1; len <= 700; len += (len < 70 ? 1 : 37))
+        for (int64_t k = 0; k < len; k += (k < 40 ? 1 : 29))
+            for (int S : {1, 2, 3, 5, 7, 16, 255, 256}) {
+                const int64_t no = len - k, per = (no + S - 1) / S;
+                int64_t next = 0;
+                for (int s = 0; s < S; ++s) {
+                    int64_t lo, hi;
+                    noe_lag_origins(len, k, S, s, lo, hi);
+                    EXPECT(lo == next && hi >= lo && hi - lo <= per && hi + k <= len, "origins(len %lld, k %lld, S %d, s %d) = [%lld, %lld)",
+                           (long long)len, (long long)k, S, s, (long long)lo, (long long)hi);
+                    next = hi;
+                }
+                EXPECT(next == no, "origins(len %lld, k %lld, S %d) end at %lld", (long long)len, (long long)k, S, (long long)next);
+            }
+    {   // at the largest values a call can carry
+        int64_t lo, hi;
+        noe_lag_origins(INT64_MAX / 512, 0, 256, 255, lo, hi);
+        EXPECT(hi == INT64_MAX / 512 && lo <= hi, "origins at the largest block");
+    }
+
+    // ---- the lag list ----
+    char msg[160];
+    std::vector<int32_t> lags;
+    EXPECT(noe_lag_check(nullptr, 0, 10, msg, sizeof msg) == -3 && strstr(msg, "K=0"), "K = 0: %s", msg);
+    EXPECT(noe_lag_check(nullptr, -1, 10, msg, sizeof msg) == -3, "K = -1");
+    lags.assign(kNoeMaxLags + 1, 0);
+    for (size_t q = 0; q < lags.size(); ++q) lags[q] = (int32_t)q;
+    EXPECT(noe_lag_check(lags.data(), kNoeMaxLags + 1, 1000, msg, sizeof msg) == -3 && strstr(msg, "K=65"), "K = 65: %s", msg);
+    EXPECT(noe_lag_check(lags.data(), kNoeMaxLags, 1000, msg, sizeof msg) == 0, "K = 64");
+    EXPECT(noe_lag_check(lags.data(), kNoeMaxLags, 64, msg, sizeof msg) == 0, "largest lag 63 in a block of 64");
+    EXPECT(noe_lag_check(lags.data(), kNoeMaxLags, 63, msg, sizeof msg) == -3 && strstr(msg, "leaves no term"), "lag 63 in a block of 63: %s", msg);
+    for (int K = 1; K <= 6; ++K)
+        for (int bad = 0; bad < K; ++bad)
+            for (int kind = 0; kind < 3; ++kind) {        // 0: a repeat, 1: a decrease, 2: a negative value
+                lags.assign(K, 0);
+                for (int q = 0; q < K; ++q) lags[q] = 3 * q + 1;
+                if (kind == 0 && bad > 0) lags[bad] = lags[bad - 1];
+                else if (kind == 1 && bad > 0) lags[bad] = lags[bad - 1] - 1;
+                else if (kind == 2) lags[bad] = -1 - bad;
+                const bool broken = kind == 2 || bad > 0;
+                const int rc = noe_lag_check(lags.data(), K, 100, msg, sizeof msg);
+                EXPECT(rc == (broken ? -3 : 0), "K %d bad %d kind %d: rc %d (%s)", K, bad, kind, rc, msg);
+                if (broken) EXPECT(strstr(msg, kind == 2 ? "negative" : "strictly increasing"), "K %d bad %d kind %d: %s", K, bad, kind, msg);
+            }
+    lags = {0, INT32_MAX};
+    EXPECT(noe_lag_check(lags.data(), 2, (int64_t)INT32_MAX + 1, msg, sizeof msg) == 0, "the largest lag");
+    EXPECT(noe_lag_check(lags.data(), 2, INT32_MAX, msg, sizeof msg) == -3, "the largest lag in a block of its length");
+
+    // ---- byte counts and grid sizes, against 128-bit restatements, up to the largest admitted shape ----
+    for (int B : {1, 3, 65535, INT32_MAX})
+        for (int K : {1, 12, 64})
+            for (int64_t P : {(int64_t)2, (int64_t)33, (int64_t)512, (int64_t)40000, (int64_t)1 << 20})
+                for (int S : {1, 2, 256}) {
+                    const int64_t nT = (P + kNoeTile - 1) / kNoeTile, NP = nT * (nT + 1) / 2, npairs = P * (P - 1) / 2;
+                    unsigned __int128 out, part;
+                    noe_lagged_bytes(B, K, npairs, S, NP, out, part);
+                    unsigned __int128 want_out = 8, want_part = S > 1 ? 8 * 1024 : 0;
+                    want_out *= (unsigned __int128)B; want_out *= (unsigned __int128)K; want_out *= (unsigned __int128)npairs;
+                    want_part *= (unsigned __int128)B; want_part *= (unsigned __int128)K; want_part *= (unsigned __int128)S;
+                    want_part *= (unsigned __int128)NP;
+                    EXPECT(out == want_out && part == want_part, "bytes(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
+                    const unsigned __int128 wg = (unsigned __int128)B * K * S * NP, fin = (unsigned __int128)B * K * NP * 4;
+                    const bool ok = wg < ((unsigned __int128)1 << 31) && fin < ((unsigned __int128)1 << 31);
+                    EXPECT(noe_lagged_grid_ok(B, K, S, NP) == ok, "grid(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
+                }
+    printf("noe_lagged_host_sweep: %ld comparisons, no disagreement\n", checks);
+    return 0;
+}

@@ -33,30 +33,17 @@
 //   large map) there are no partial tiles: k_noe_pairs writes its pairs i < j < P into sums itself, and the call needs no memory
 //   beside its result.
 // No atomics anywhere: equal input gives bit-equal sums.
-#include "sr_internal.h"
+#include "sr_noe_common.h"
 #include <vector>
 
 namespace {
 
-constexpr int kTile = 32;                   // atoms per tile side
+constexpr int kTile = kNoeTile;             // atoms per tile side (sr_noe_host.h)
 constexpr int kFB = 16;                     // frames per LDS stage
 constexpr int kFlush = 8;                   // mode 0: frames per float32 partial sum
 constexpr int kRows = 2 * kTile * 3;        // staged series per frame: (side, atom, component) = 192, one thread each
 constexpr int kPart = kTile * kTile * 7;    // float64 values of one partial tile
 static_assert(kRows + kFB <= 256 && kFB % kFlush == 0 && kPart % 256 == 0, "stage shape");
-
-// tile pair p = 0 .. nT (nT + 1) / 2 - 1, row-major over ti <= tj
-__device__ __forceinline__ void noe_tile_pair(int p, int nT, int &ti, int &tj)
-{
-    ti = 0;
-    while (p >= nT - ti) { p -= nT - ti; ++ti; }
-    tj = ti + p;
-}
-
-__device__ __forceinline__ float noe_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double noe_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ __forceinline__ float noe_rsqrt(float x) { return __builtin_amdgcn_rsqf(x); }
-__device__ __forceinline__ double noe_rsqrt(double x) { return 1.0 / sqrt(x); }
 
 template <typename Real, bool ROT>
 __global__ __launch_bounds__(256) void k_noe_pairs(const float *__restrict__ xyz, int64_t nAtoms, const int *__restrict__ index, int P,
@@ -207,21 +194,7 @@ __global__ __launch_bounds__(256) void k_noe_finish(const double *__restrict__ p
     dst[(i * (2 * (int64_t)P - i - 1) / 2 + (j - i - 1)) * 7 + k] = sum;
 }
 
-// the split rule: a function of the shape alone: about sixteen workgroups per CU of a 256-CU part (three fit a SIMD at a time: several
-// rounds of them keep the last round short), each with at least 128 frames, at most 256 partial tiles to add
-int noe_ksplit(int64_t NP, int64_t Fmax, int B)
-{
-    int64_t S = (4096 + NP * B - 1) / (NP * B);
-    const int64_t by_frames = Fmax / 128 > 1 ? Fmax / 128 : 1;
-    if (S > by_frames) S = by_frames;
-    if (S > 256) S = 256;
-    return (int)S;
-}
-
-struct NoeShape {
-    int64_t nT, NP, npairs, Fmax;
-    int S;
-};
+}  // namespace
 
 // everything that is refused, before anything is queued
 int noe_check(sr_ctx *ctx, const char *who, int64_t nFrames, int64_t nAtoms, const int32_t *index, int64_t P, const int64_t *bs,
@@ -263,8 +236,6 @@ int noe_check(sr_ctx *ctx, const char *who, int64_t nFrames, int64_t nAtoms, con
                "%s: %lld tile pairs x %d splits x %d blocks are too many for one call", who, (long long)sh.NP, sh.S, B);
     return 0;
 }
-
-}  // namespace
 
 extern "C" {
 

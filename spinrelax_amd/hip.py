@@ -409,6 +409,72 @@ class Context:
         """frames per LDS stage of k_noe_pairs"""
         return int(self.lib.sr_noe_frame_batch())
 
+    # ---- the dipolar map at chosen lags (sr_noe_lagged.hip) ----
+    @staticmethod
+    def _lags(lags):
+        lg = np.ascontiguousarray(np.atleast_1d(lags))
+        if lg.size == 0:                                   # an empty list is the library's to refuse
+            lg = lg.astype(np.int32)
+        if lg.ndim != 1 or lg.dtype.kind not in 'iu':
+            raise ValueError('lags must be a 1-D list of integers')
+        if lg.size and (lg.min() < -2 ** 31 or lg.max() >= 2 ** 31):
+            raise ValueError('lags must fit 32 bits')
+        return np.ascontiguousarray(lg, dtype=np.int32)
+
+    def noe_lagged_dev(self, xyz_ptr, nFrames, nAtoms, index, quat_ptr, block_start, block_len, lags, G_ptr, mode=0):
+        """G[b][q][pair] = sum over the origins t of block b of [1.5 cos^2 - 0.5] r(t)^-3 r(t + k)^-3 at the lags k = lags[q] (strictly
+        increasing, >= 0, below the shortest block; at most 64), cos the angle between d'(t) and d'(t + k), of every pair i < j of the
+        atoms `index` from the device coordinates xyz_ptr (nFrames, nAtoms, 3) float32 and the device quaternions quat_ptr (nFrames,
+        4) float64 (None: identity), into the device array G_ptr (B, K, P (P - 1) / 2) float64, pairs in the order of noe.pair_index
+        (sr_noe_lagged_f32_dev); asynchronous on the context's stream"""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError('index must be 1-D')
+        bs, bl = _windows(block_start, block_len)
+        lg = self._lags(lags)
+        check(self.lib.sr_noe_lagged_f32_dev(self.h, xyz_ptr, int(nFrames), int(nAtoms), _ptr(idx), idx.size, quat_ptr, _ptr(bs), _ptr(bl),
+                                             bs.size, _ptr(lg), lg.size, int(mode), G_ptr), 'sr_noe_lagged_f32_dev')
+
+    def noe_lagged(self, xyz, index, lags, quat=None, block_start=None, block_len=None, mode=0):
+        """The same of host arrays: xyz (nFrames, nAtoms, 3) float32, quat (nFrames, 4) float64 or None -> G (B, K, P (P - 1) / 2)
+        float64; without block tables one block of all frames (sr_noe_lagged_f32)"""
+        xyz = _f32(xyz)
+        if xyz.ndim != 3 or xyz.shape[2] != 3:
+            raise ValueError('xyz must be (frames, atoms, 3)')
+        nF, nA, _ = xyz.shape
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError('index must be 1-D')
+        qq = None if quat is None else _f64(quat)
+        if qq is not None and qq.shape != (nF, 4):
+            raise ValueError('quat must be (frames, 4)')
+        if block_start is None:
+            block_start, block_len = [0], [nF]
+        bs, bl = _windows(block_start, block_len)
+        lg = self._lags(lags)
+        P = idx.size
+        self.noe_lagged_check(nF, nA, idx, bs, bl, lg, mode)    # a result beyond the device's memory is refused before its host array exists
+        G = np.empty((bs.size, lg.size, P * (P - 1) // 2))
+        check(self.lib.sr_noe_lagged_f32(self.h, _ptr(xyz), nF, nA, _ptr(idx), P, _ptr(qq), _ptr(bs), _ptr(bl), bs.size, _ptr(lg), lg.size,
+                                         int(mode), _ptr(G)), 'sr_noe_lagged_f32')
+        return G
+
+    def noe_lagged_check(self, nFrames, nAtoms, index, block_start, block_len, lags, mode=0):
+        """raises what noe_lagged / noe_lagged_dev would refuse (-3) for these arguments, the size of the result included; allocates and
+        queues nothing (sr_noe_lagged_check)"""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError('index must be 1-D')
+        bs, bl = _windows(block_start, block_len)
+        lg = self._lags(lags)
+        check(self.lib.sr_noe_lagged_check(self.h, int(nFrames), int(nAtoms), _ptr(idx), idx.size, _ptr(bs), _ptr(bl), bs.size, _ptr(lg), lg.size,
+                                           int(mode)), 'sr_noe_lagged_check')
+
+    def noe_lagged_splits(self, P, longest_block, B=1):
+        """frame splits S of a lagged map of P atoms over B blocks, the longest of longest_block frames: the map's own rule, whatever
+        the lags"""
+        return int(self.lib.sr_noe_lagged_splits(int(P), int(longest_block), int(B)))
+
     # ---- NOESY from the dipolar map (sr_noesy.hip) ----
     @staticmethod
     def _noesy_args(A6, S2, P, tau_e, leak):

@@ -15,6 +15,13 @@ Peter, Daura & van Gunsteren, J. Biomol. NMR 20, 297 (2001)):
 The block sums of r^-6 and d_a d_b r^-5, the loop that is quadratic in the number of spins, are computed on the MI355X
 (csrc/sr_noe.hip) and nowhere else: without a GPU dipolar_map raises SpinRelaxHipError.  Everything after the sums is finalize(),
 pure numpy.
+
+With lags (dipolar_map(..., lags=...)) the map also holds the dipolar correlation function of every pair at those lags,
+
+    Cdd(k) = <P2(u(t) . u(t + k)) r(t)^-3 r(t + k)^-3> / A6       (calculate_Ct_dipolar's normalisation: Cdd(0) = 1, plateau S2)
+
+from the block sums G_b(k) of csrc/sr_noe_lagged.hip, and from it the internal correlation time of the pair, the Lipari-Szabo integral
+tau_e = int (Cdd - S2) / (1 - S2) dt (tau_e_from_Cdd): what noesy.rate_matrix(..., tau_e='map') takes.  finalize_lagged() is pure numpy.
 """
 import warnings
 
@@ -114,31 +121,116 @@ def _blocks(blocks, n_frames):
     return np.ascontiguousarray(np.atleast_1d(bs), dtype=np.int64), np.ascontiguousarray(np.atleast_1d(bl), dtype=np.int64)
 
 
-def _result(sums, bl, index):
+def log_lags(max_lag, n):
+    """about n integer lags from 1 to max_lag, log-spaced, rounded and deduplicated: strictly increasing int64, the first 1, the last
+    max_lag (fewer than n where the rounding merges neighbours, all of 1 .. max_lag when n >= max_lag)"""
+    max_lag, n = int(max_lag), int(n)
+    if max_lag < 1 or n < 1 or (n < 2 and max_lag > 1):
+        raise ValueError('log_lags needs max_lag >= 1 and n >= 2 lags (one lag only for max_lag = 1)')
+    lags = np.unique(np.rint(np.geomspace(1.0, float(max_lag), n)).astype(np.int64))
+    lags[0], lags[-1] = 1, max_lag
+    return np.unique(lags)
+
+
+def _lag_array(lags):
+    lg = np.atleast_1d(np.asarray(lags))
+    if lg.ndim != 1 or lg.size < 1 or lg.dtype.kind not in 'iu':
+        raise ValueError('lags must be a non-empty 1-D list of integers')
+    return lg.astype(np.int64)
+
+
+def tau_e_from_Cdd(Cdd, S2, lags, dt=1.0):
+    """The internal correlation time of Lipari & Szabo, tau_e = int_0^inf (C(t) - S2) / (1 - S2) dt, from C at a few lags: Cdd (K, n)
+    (or (K) for one series), S2 (n), lags (K) strictly increasing, in frames of dt -> tau_e (n) in the units of dt.  The trapezoid rule
+    through (0, 1) and the given points (a given lag 0 is replaced by that point); the integral stops at the first point with
+    C <= S2, the crossing located by linear interpolation; 0 where 1 - S2 < 1e-6 (a rigid pair has no internal term)."""
+    lg = _lag_array(lags)
+    C = np.asarray(Cdd, dtype=np.float64)
+    one = C.ndim == 1
+    C = C.reshape(lg.size, -1) if one else C
+    S2 = np.atleast_1d(np.asarray(S2, dtype=np.float64))
+    if C.ndim != 2 or C.shape[0] != lg.size or S2.shape != (C.shape[1],):
+        raise ValueError('tau_e_from_Cdd needs Cdd (lags, n) and S2 (n)')
+    if np.any(lg < 0) or np.any(np.diff(lg) <= 0):
+        raise ValueError('lags must be >= 0 and strictly increasing')
+    if lg[0] == 0:
+        lg, C = lg[1:], C[1:]
+    flex = (1.0 - S2) >= 1e-6
+    den = np.where(flex, 1.0 - S2, 1.0)
+    t = np.concatenate([[0.0], lg.astype(np.float64)])          # in frames: dt multiplies the finished integral, exactly linear in it
+    Y = np.concatenate([np.ones((1, C.shape[1])), (C - S2[None]) / den[None]], axis=0)
+    alive = np.logical_and.accumulate(Y > 0, axis=0)           # up to and including this point the series stayed above S2
+    tau = np.zeros(C.shape[1])
+    for k in range(1, t.size):
+        h = t[k] - t[k - 1]
+        y0, y1 = Y[k - 1], Y[k]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            cross = 0.5 * y0 * y0 / (y0 - y1) * h              # the triangle up to the crossing at t[k-1] + h y0 / (y0 - y1)
+        tau += np.where(alive[k], 0.5 * (y0 + y1) * h, np.where(alive[k - 1], cross, 0.0))
+    tau = np.where(flex, tau, 0.0) * float(dt)
+    return float(tau[0]) if one else tau
+
+
+def finalize_lagged(G, block_len, lags, fin, dt=1.0):
+    """G (B, K, npairs) float64 as the library writes it, block_len (B), lags (K) and fin = finalize()'s dict of the same blocks ->
+    dict: lags (K) int64, G, Cdd (K, npairs) = [sum_b G_b(k) / sum_b (n_b - k)] / A6 (for blocks of equal length
+    calculate_Ct_dipolar's normalisation), dCdd (K, npairs) from the per-block values G_b(k) / (n_b - k) / A6_b by the convention of
+    ired.ired_reduce, tau_e (npairs) = tau_e_from_Cdd(Cdd, S2, lags, dt) in the units of dt, dtau_e from the per-block values, each
+    with its block's own S2_b; Cdd_b (B, K, npairs), tau_e_b (B, npairs) and dt."""
+    G = np.asarray(G, dtype=np.float64)
+    lg = _lag_array(lags)
+    bl = np.atleast_1d(np.asarray(block_len, dtype=np.int64))
+    if G.ndim != 3 or G.shape[:2] != (bl.size, lg.size) or G.shape[2] != fin['A6'].size:
+        raise ValueError('G must be (blocks, lags, pairs), got %s' % (G.shape,))
+    terms = bl[:, None] - lg[None, :]                           # (B, K) origins per block and lag
+    if np.any(terms < 1):
+        raise ValueError('every lag must leave a term in every block')
+    Cdd = G.sum(axis=0) / terms.sum(axis=0)[:, None].astype(np.float64) / fin['A6'][None]
+    Cdd_b = G / terms[:, :, None].astype(np.float64) / fin['A6_b'][:, None, :]
+    tau_e = tau_e_from_Cdd(Cdd, fin['S2'], lg, dt)
+    tau_e_b = np.stack([tau_e_from_Cdd(Cdd_b[b], fin['S2_b'][b], lg, dt) for b in range(bl.size)])
+    return dict(lags=lg, dt=float(dt), G=G, Cdd=Cdd, dCdd=_error(Cdd_b.reshape(bl.size, -1)).reshape(Cdd.shape), tau_e=tau_e, dtau_e=_error(tau_e_b),
+                Cdd_b=Cdd_b, tau_e_b=tau_e_b)
+
+
+def _result(sums, bl, index, G=None, lags=None, dt=1.0):
     index = np.asarray(index)
     out = finalize(sums, bl)
     out['pairs'] = pair_list(index.size)
     out['index'] = index.astype(np.int64)
     out['sums'] = sums
+    if G is not None:
+        out.update(finalize_lagged(G, bl, lags, out, dt))
     return out
 
 
-def dipolar_map(xyz, index, quat=None, blocks=None, mode=0, ctx=None):
+def dipolar_map(xyz, index, quat=None, blocks=None, mode=0, ctx=None, lags=None, dt=1.0):
     """The map of every pair of the atoms `index` of the coordinates xyz (frames, atoms, 3) float32.  quat (frames, 4) float64: the
     unit quaternion (w, x, y, z) that takes each frame into the molecule-fixed frame (what ct.superpose_XHvecs(..., want_quat=True)
     returns); None: the lab frame, S2 then includes overall tumbling.  blocks = (block_start, block_len) in frames (ragged lengths
     allowed), None: one block.  mode 0: float32 per pair and frame, 1: float64 throughout.
-    Returns finalize()'s dict and pairs (npairs, 2) positions in `index`, index, sums (B, npairs, 7)."""
+    Returns finalize()'s dict and pairs (npairs, 2) positions in `index`, index, sums (B, npairs, 7).
+    lags: integer lags in frames (strictly increasing, >= 0, below the shortest block, at most 64; log_lags makes such a list), dt the
+    time between frames: the dict then also holds finalize_lagged()'s lags, G, Cdd, dCdd, tau_e, dtau_e (tau_e in the units of dt).
+    None: the map alone, as ever."""
     xyz = np.ascontiguousarray(xyz, dtype=np.float32)
     bs, bl = _blocks(blocks, xyz.shape[0])
-    sums = _ctx(ctx).noe_pairs(xyz, index, quat=quat, block_start=bs, block_len=bl, mode=mode)
-    return _result(sums, bl, index)
+    c = _ctx(ctx)
+    if lags is None:
+        return _result(c.noe_pairs(xyz, index, quat=quat, block_start=bs, block_len=bl, mode=mode), bl, index)
+    lg = _lag_array(lags)
+    if xyz.ndim == 3:
+        c.noe_lagged_check(xyz.shape[0], xyz.shape[1], index, bs, bl, lg, mode)     # the lags' refusals before the map is computed
+    sums = c.noe_pairs(xyz, index, quat=quat, block_start=bs, block_len=bl, mode=mode)
+    G = c.noe_lagged(xyz, index, lg, quat=quat, block_start=bs, block_len=bl, mode=mode)
+    return _result(sums, bl, index, G, lg, dt)
 
 
-def dipolar_map_superposed(xyz, ref_xyz, fit_indices, index, blocks=None, mode=0, ctx=None):
+def dipolar_map_superposed(xyz, ref_xyz, fit_indices, index, blocks=None, mode=0, ctx=None, lags=None, dt=1.0):
     """dipolar_map in the frame of the per-frame least-squares superposition onto ref_xyz (atoms, 3) over fit_indices, the front end's
     (Context.xh_vectors / ct.superpose_XHvecs): the coordinates are uploaded once, the front end's kernel leaves its quaternions on
-    the device and the map reads them there.  The result also holds quat (frames, 4)."""
+    the device and the map reads them there.  The result also holds quat (frames, 4).  lags, dt: as in dipolar_map; the lagged sums
+    read the same device coordinates and quaternions."""
     import torch
     c = _ctx(ctx)
     xyz = np.ascontiguousarray(xyz, dtype=np.float32)
@@ -148,6 +240,9 @@ def dipolar_map_superposed(xyz, ref_xyz, fit_indices, index, blocks=None, mode=0
     index = np.asarray(index)
     bs, bl = _blocks(blocks, nF)
     c.noe_pairs_check(nF, nA, index, bs, bl, mode)  # the library's refusals, a map beyond the device's memory among them, before torch allocates
+    lg = None if lags is None else _lag_array(lags)
+    if lg is not None:
+        c.noe_lagged_check(nF, nA, index, bs, bl, lg, mode)
     dev = torch.device('cuda', c.device)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore', UserWarning)    # a read-only array: it is only read
@@ -157,8 +252,13 @@ def dipolar_map_superposed(xyz, ref_xyz, fit_indices, index, blocks=None, mode=0
     torch.cuda.synchronize(dev)                     # the upload is torch's, the kernels run on the context's stream
     c.xh_quat_dev(xyz_d.data_ptr(), nF, nA, fit_indices, ref_xyz, quat_d.data_ptr())
     c.noe_pairs_dev(xyz_d.data_ptr(), nF, nA, index, quat_d.data_ptr(), bs, bl, sums_d.data_ptr(), mode=mode)
+    G_d = None
+    if lg is not None:
+        G_d = torch.empty((bs.size, lg.size, n_pairs(index.size)), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        c.noe_lagged_dev(xyz_d.data_ptr(), nF, nA, index, quat_d.data_ptr(), bs, bl, lg, G_d.data_ptr(), mode=mode)
     c.sync()
-    out = _result(sums_d.cpu().numpy(), bl, index)
+    out = _result(sums_d.cpu().numpy(), bl, index, None if G_d is None else G_d.cpu().numpy(), lg, dt)
     out['quat'] = quat_d.cpu().numpy()
     return out
 
@@ -175,10 +275,8 @@ def select_pairs(result, cutoff):
 COLUMNS = ('i', 'j', 'name_i', 'name_j', 'reff6', 'dreff6', 'reff3', 'S2', 'dS2', 'S2rad')
 
 
-def write_map(path, result, names=None, cutoff=None):
-    """<o>_noeMap.dat: one row per pair, columns i j name_i name_j reff6 dreff6 reff3 S2 dS2 S2rad (i, j atom indices, the numbers
-    as %.8g); cutoff keeps the pairs with reff6 <= cutoff.  names: one per entry of the index list, default the atom index.
-    Returns the number of rows."""
+def _rows(result, names, cutoff):
+    """what write_map and write_map_ct share: the atom indices, one checked name per atom, the pairs the cutoff keeps"""
     idx = np.asarray(result['index'], dtype=np.int64)
     names = [str(a) for a in idx] if names is None else [str(n) for n in names]
     if len(names) != idx.size:
@@ -186,6 +284,14 @@ def write_map(path, result, names=None, cutoff=None):
     if any((not n) or any(ch.isspace() for ch in n) for n in names):
         raise ValueError('names must be non-empty and free of white space')
     keep = np.arange(result['reff6'].size) if cutoff is None else np.nonzero(result['reff6'] <= cutoff)[0]
+    return idx, names, keep
+
+
+def write_map(path, result, names=None, cutoff=None):
+    """<o>_noeMap.dat: one row per pair, columns i j name_i name_j reff6 dreff6 reff3 S2 dS2 S2rad (i, j atom indices, the numbers
+    as %.8g); cutoff keeps the pairs with reff6 <= cutoff.  names: one per entry of the index list, default the atom index.
+    Returns the number of rows."""
+    idx, names, keep = _rows(result, names, cutoff)
     with open(path, 'w') as fp:
         fp.write('# ' + ' '.join(COLUMNS) + '\n')
         for k in keep:
@@ -216,3 +322,47 @@ def read_map(path):
         else:
             out[c] = np.array(cols[c], dtype=np.float64)
     return out
+
+
+def _ct_columns(lags, dt):
+    return ['i', 'j', 'name_i', 'name_j', 'tau_e', 'dtau_e'] + ['Cdd(%.8g)' % (k * dt) for k in lags]
+
+
+def write_map_ct(path, result, names=None, cutoff=None):
+    """<o>_noeMapCt.dat of a map with lags: a header '# i j name_i name_j tau_e dtau_e Cdd(t0) Cdd(t1) ...', a line '# lags t0 t1 ...'
+    (the lags in time units, lag x the map's dt, %.8g), then one row per pair: the atom indices, the names, tau_e and dtau_e (in the units the
+    map was made with) and one Cdd column per lag, %.8g.  names and cutoff as in write_map.  Returns the number of rows."""
+    if 'Cdd' not in result:
+        raise ValueError('write_map_ct needs a map with lags (dipolar_map(..., lags=...))')
+    idx, names, keep = _rows(result, names, cutoff)
+    lags, dt = np.asarray(result['lags'], dtype=np.int64), float(result.get('dt', 1.0))
+    with open(path, 'w') as fp:
+        fp.write('# ' + ' '.join(_ct_columns(lags, dt)) + '\n')
+        fp.write('# lags ' + ' '.join('%.8g' % (k * dt) for k in lags) + '\n')
+        for k in keep:
+            i, j = result['pairs'][k]
+            fp.write('%d %d %s %s %.8g %.8g %s\n' % (idx[i], idx[j], names[i], names[j], result['tau_e'][k], result['dtau_e'][k],
+                                                     ' '.join('%.8g' % v for v in result['Cdd'][:, k])))
+    return int(keep.size)
+
+
+def read_map_ct(path):
+    """parse write_map_ct's file back: dict(i, j int64, name_i, name_j lists of str, tau_e, dtau_e (rows) float64, Cdd (rows, K)
+    float64, lags (K) float64 in time units)"""
+    lags = None
+    i, j, ni, nj, te, dte, C = [], [], [], [], [], [], []
+    with open(path) as fp:
+        for line in fp:
+            if line.startswith('# lags'):
+                lags = np.array(line.split()[2:], dtype=np.float64)
+                continue
+            if line.startswith('#') or not line.strip():
+                continue
+            w = line.split()
+            if lags is None or len(w) != 6 + lags.size:
+                raise ValueError('%s: a row with %d columns, expected %s' % (path, len(w), 'a lags line first' if lags is None else 6 + lags.size))
+            i.append(w[0]); j.append(w[1]); ni.append(w[2]); nj.append(w[3]); te.append(w[4]); dte.append(w[5]); C.append(w[6:])
+    if lags is None:
+        raise ValueError('%s: no lags line' % path)
+    return dict(i=np.array(i, dtype=np.int64), j=np.array(j, dtype=np.int64), name_i=ni, name_j=nj, tau_e=np.array(te, dtype=np.float64),
+                dtau_e=np.array(dte, dtype=np.float64), Cdd=np.array(C, dtype=np.float64).reshape(len(i), lags.size), lags=lags)

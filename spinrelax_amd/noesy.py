@@ -15,8 +15,10 @@ q = 0.1 (mu0 / 4 pi)^2 hbar^2 gamma_H^4 / u^6 with u the length of one coordinat
 are computed on the MI355X (csrc/sr_noesy.hip) and nowhere else: without a GPU every function that needs them raises SpinRelaxHipError.
 sum_groups, write_noesy and read_noesy are host numpy.
 
-Not done: anisotropic tumbling (the map keeps no pair orientation in the diffusion frame), other nuclei than protons, more than one GPU;
-a per-pair tau_e (say from fitted dipolar C(t)) is taken as an array but nothing here produces it.
+A per-pair tau_e comes from the map itself when it was made with lags (noe.dipolar_map(..., lags=...), csrc/sr_noe_lagged.hip):
+tau_e='map' takes map_result['tau_e'], in seconds, floored at TAU_E_FLOOR.
+
+Not done: anisotropic tumbling (the map keeps no pair orientation in the diffusion frame), other nuclei than protons, more than one GPU.
 """
 import numpy as np
 
@@ -27,6 +29,10 @@ from .spectral_densities import GAMMA
 # 0.1 (mu0 / 4 pi)^2 hbar^2 gamma_H^4 in SI units (m^6 s^-2): the constant of relaxationExperiment.get_f_DD with both spins 1H
 Q_HH = 0.10 * 1.1121216813552401e-82 * GAMMA['1H'] ** 4.0
 UNITS = {'nm': 1e-9, 'A': 1e-10}
+# tau_e='map': the smallest internal correlation time handed to the library, in seconds.  The library needs tau_e > 0, the map gives 0
+# for a rigid pair and for one whose C_dd is at its plateau by the first lag; at 1 ps the internal term (1 - S2) t' is negligible
+# beside S2 tau_c of any molecule that gives a NOESY spectrum (tau_c of nanoseconds).
+TAU_E_FLOOR = 1e-12
 
 
 def _ctx(ctx):
@@ -53,9 +59,27 @@ def _torch_dev(c):
     return torch, torch.device('cuda', c.device)
 
 
+def map_tau_e(map_result):
+    """the per-pair tau_e of a map made with lags as the rate matrix takes it: map_result['tau_e'], which must be in seconds
+    (noe.dipolar_map(..., lags=..., dt=<seconds per frame>)), floored at TAU_E_FLOOR; ValueError for a map without tau_e"""
+    if 'tau_e' not in map_result:
+        raise ValueError("tau_e='map' needs a map made with lags (noe.dipolar_map(..., lags=...)): this one holds no tau_e")
+    return np.maximum(np.asarray(map_result['tau_e'], dtype=np.float64), TAU_E_FLOOR)
+
+
+def _tau_e(map_result, tau_e):
+    """tau_e as the library takes it: a scalar or one value per pair in seconds; 'map': map_tau_e(map_result)"""
+    if not isinstance(tau_e, str):
+        return tau_e
+    if tau_e != 'map':
+        raise ValueError("tau_e must be a time in seconds, one per pair, or 'map'")
+    return map_tau_e(map_result)
+
+
 def _rates_dev(c, map_result, field_MHz, tau_c, tau_e, leak, unit):
     """R as a torch tensor on the context's device"""
     P = _n_spins(map_result)
+    tau_e = _tau_e(map_result, tau_e)
     torch, dev = _torch_dev(c)
     R_d = torch.empty((P, P), dtype=torch.float64, device=dev)
     torch.cuda.synchronize(dev)
@@ -66,8 +90,10 @@ def _rates_dev(c, map_result, field_MHz, tau_c, tau_e, leak, unit):
 def rate_matrix(map_result, field_MHz, tau_c, tau_e=1e-10, leak=0.0, unit='nm', ctx=None):
     """R (P, P) float64 of the P spins of a map: noe.dipolar_map's dict, or anything that holds A6, S2 (P (P - 1) / 2 each, pairs in
     the order of noe.pair_index) and index (P).  field_MHz: the proton frequency; tau_c, tau_e in seconds, tau_e a scalar or one value
-    per pair; leak in 1 / s, a scalar or one value per spin; unit: the unit of the coordinates the map was taken from, 'nm' (MDTraj's,
+    per pair, or 'map': the map's own tau_e (a map made with lags and dt in seconds per frame), floored at TAU_E_FLOOR; leak in 1 / s, a
+    scalar or one value per spin; unit: the unit of the coordinates the map was taken from, 'nm' (MDTraj's,
     the default), 'A', or metres per unit.  R_ij = sigma_ij, R_ii = sum_j rho_ij + leak_i, exactly symmetric."""
+    tau_e = _tau_e(map_result, tau_e)           # a map without tau_e is refused before a context is asked for
     return _ctx(ctx).noesy_rates(map_result['A6'], map_result['S2'], _n_spins(map_result), omega_H(field_MHz), tau_c, tau_e, leak,
                                  prefactor(unit))
 
@@ -107,6 +133,7 @@ def noesy(map_result, mixing_times, field_MHz, tau_c, tau_e=1e-10, leak=0.0, uni
     """rate_matrix and intensities in one go, R staying on the device between the two.  Returns dict(R (P, P), sigma (npairs) the
     cross-relaxation rates in the map's pair order, rho (P) the auto-relaxation rates R_ii (leak included), A (n_tau, P, P),
     mixing_times, index, pairs)."""
+    tau_e = _tau_e(map_result, tau_e)           # a map without tau_e is refused before a context is asked for
     c = _ctx(ctx)
     tau = _mixing(mixing_times)
     R_d = _rates_dev(c, map_result, field_MHz, tau_c, tau_e, leak, unit)

@@ -1,0 +1,337 @@
+"""
+GPU tests of the lagged all-pairs dipolar map (csrc/sr_noe_lagged.hip) and of everything above it: hip.Context.noe_lagged,
+noe.dipolar_map(..., lags=...), noesy's tau_e='map' and the --noeLags / --noesyTauEMap flags of scripts/calculate-Ct-from-traj.py.
+
+Oracle (in this file): the definition in float64 numpy on the same float32 coordinates and the same float64 quaternions:
+d = x_j - x_i of the coordinates converted to float64, r = |d|, d' = R(q) d,
+
+    G_b(k) = sum_t [1.5 (d'(t) . d'(t + k))^2 / (r(t)^2 r(t + k)^2) - 0.5] r(t)^-3 r(t + k)^-3,     W_b(k) = sum_t r(t)^-3 r(t + k)^-3
+
+over the origins t of block b with t + k inside the block.  Inputs: make_body of tests/test_gpu_noe.py (a wobbling, tumbling body 40
+units from the origin; the oracle asserts a minimum pair distance of 0.05).
+
+Bars, u = 2^-24, absolute on G, first order in u.
+Mode 1 (float64 throughout): both sides add n <= 1000 float64 terms of magnitude <= r^-3 s^-3 in different orders, each term after
+  some twenty float64 roundings: by the argument of tests/test_gpu_noe.py below 2 * 1020 * 1.1e-16 = 2.3e-13 of W.  BAR1 = 1e-12 W.
+Mode 0 (float32 per pair, frame and lag), the sequence of csrc/sr_noe_lagged.hip; r, s the two distances, |x| <= 1, |p| <= 1:
+  d_a, e_a = differences of float32 coordinates                       u each (relative)
+  r2 = fma(dz, dz, fma(dy, dy, dx dx)), s2 likewise                    2u from d, 3 roundings: 5u
+  ri = v_rsq_f32(r2), si                                               2.5u from r2, 1 ulp <= 2u: 4.5u
+  d'_a = fma(Ra0, dx, fma(Ra1, dy, Ra2 dz)), R rounded to float32      every product 2u from its inputs, 3 roundings, a row of R of unit
+                                                                       length: |err d'_a| <= 5u r; e'_a likewise 5u s
+  c = fma(d'z, e'z, fma(d'y, e'y, d'x e'x))                            |d'| <= r, |e'| <= s: 5u r s from each side, 3 roundings of
+                                                                       partial sums <= r s: 13u r s absolute
+  g = ri si                                                            4.5u + 4.5u + 1 rounding: 10u relative
+  x = c g                                                              13u from c, 10u |x| from g, 1 rounding: 24u absolute
+  g3 = (g g) g                                                         3 * 10u + 2 roundings: 32u relative
+  p = fma(1.5 x, x, -0.5)                                              dp/dx = 3x: 72u; 1.5 x rounded: 1.5u; the fma: u: <= 76u absolute
+  term = p g3                                                          76u g3 + 32u |p| g3 + 1 rounding: 109u r^-3 s^-3
+  float32 partial sums of at most 8 terms, 7 roundings, each <= u sum |term| <= u W': 7u W;  then float64.
+  BAR0 = 116u W.  (A numpy emulation of this sequence with a correctly rounded rsq stayed below 6u W on make_body(33, 300),
+  (65, 120) and the rigid (33, 120); the worst values measured on the device are in docs/EXPERIMENTS.md.)
+G at lag 0 against the map's r^-6 sums: there x = 1 up to 24u, p = 1 up to 76u, g3 = r^-6: both kernels are inside their own bars of
+  the exact sum, 2 * 39u relative in mode 0 (test_gpu_noe.py: BAR0_A6 = 39u; a lag-0 term is within 109u, but the issue's bar is the
+  tighter 2 * 39u and the test keeps it), 2e-12 in mode 1.
+"""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from spinrelax_amd import ct as hostct
+from spinrelax_amd import hip, noe, noesy
+from spinrelax_amd._lib import SpinRelaxHipError
+from test_gpu_noe import MIN_DIST, make_body, rotmat
+
+pytestmark = pytest.mark.gpu
+
+U = 2.0 ** -24
+BAR1 = 1e-12
+BAR0 = 116 * U
+BAR_LAG0 = {0: 2 * 39 * U, 1: 2e-12}
+LAGS_120 = [0, 1, 3, 16, 17, 31]                 # the stage boundary (16 frames), lags >= one stage, a short last stage
+RAGGED = [(0, 37), (37, 20), (60, 40)]
+LAGS_RAGGED = [0, 1, 3, 16, 19]
+
+
+@pytest.fixture(scope='module')
+def ctx():
+    c = hip.Context()
+    yield c
+    c.close()
+
+
+def oracle_G(xyz, index, quat, blocks, lags):
+    """G and W (B, K, npairs) by the definition; asserts the minimum distance"""
+    x = np.asarray(xyz[:, index], dtype=np.float64)
+    iu, ju = np.triu_indices(len(index), k=1)
+    d = x[:, ju] - x[:, iu]
+    r = np.sqrt((d * d).sum(axis=-1))
+    assert r.min() >= MIN_DIST, 'oracle: a pair comes as close as %.3g' % r.min()
+    dp = d if quat is None else np.einsum('tab,tpb->tpa', rotmat(np.asarray(quat, dtype=np.float64)), d)
+    w = r ** -3
+    G = np.empty((len(blocks), len(lags), iu.size))
+    W = np.empty_like(G)
+    for b, (s, n) in enumerate(blocks):
+        for q, k in enumerate(lags):
+            a, c = slice(s, s + n - k), slice(s + k, s + n)
+            cos2 = (dp[a] * dp[c]).sum(axis=-1) ** 2 / (r[a] ** 2 * r[c] ** 2)
+            ww = w[a] * w[c]
+            G[b, q] = ((1.5 * cos2 - 0.5) * ww).sum(axis=0)
+            W[b, q] = ww.sum(axis=0)
+    return G, W
+
+
+def scrambled(P, F, wobble=True):
+    """make_body's atoms in a scrambled order among twice as many: the gather by a permuted subset is part of the kernel"""
+    _, xyz, quat = make_body(P, F, wobble)
+    rng = np.random.default_rng(P + F)
+    big = np.zeros((F, 2 * P + 1, 3), dtype=np.float32)
+    index = rng.permutation(2 * P + 1)[:P]
+    big[:, index] = xyz
+    return big, index, quat
+
+
+def check_G(tag, got, ref, W, bar):
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    e = np.max(np.abs(got - ref) / W)
+    print('%s: |G - oracle| / W %.3g = %.2f u (bar %.3g)' % (tag, e, e / U, bar))
+    assert e <= bar, tag
+
+
+def run_case(ctx, P, F, blocks, lags, mode):
+    big, index, quat = scrambled(P, F)
+    bs, bl = [b[0] for b in blocks], [b[1] for b in blocks]
+    for q in (quat, None):
+        ref, W = oracle_G(big, index, q, blocks, lags)
+        got = ctx.noe_lagged(big, index, lags, quat=q, block_start=bs, block_len=bl, mode=mode)
+        check_G('mode %d P=%d F=%d B=%d %s' % (mode, P, F, len(blocks), 'quat' if q is not None else 'lab'), got, ref, W,
+                BAR1 if mode else BAR0)
+    return got
+
+
+@pytest.mark.parametrize('mode', (0, 1))
+@pytest.mark.parametrize('P', (2, 33, 65))
+def test_against_the_oracle(ctx, P, mode):
+    """P = 2 (one diagonal tile, one pair), 33 (a partial second tile: diagonal and off-diagonal tiles), 65 (three tiles, the last
+    of one atom); 120 frames as one block at the lags 0, 1, 3, 16, 17, 31 and as three ragged blocks (the frames 57 .. 59 in none) at
+    lags up to 19 = the shortest block - 1, with the quaternions and without, the atoms a permuted subset of twice as many"""
+    run_case(ctx, P, 120, [(0, 120)], LAGS_120, mode)
+    run_case(ctx, P, 120, RAGGED, LAGS_RAGGED, mode)
+
+
+@pytest.mark.parametrize('mode', (0, 1))
+def test_frame_splits(ctx, mode):
+    """P = 5, 300 frames: two frame splits (asserted: otherwise the case is vacuous).  At lag 129 split 0 owns the origins 0 .. 85 and
+    reads the frames 129 .. 214, which hold split 1's origins 86 .. 170; at lag 200 the 100 origins are 50 and 50; three blocks of
+    300, 140 and 260 frames share the split count but not the ranges"""
+    S = ctx.noe_lagged_splits(5, 300, 1)
+    assert S == 2 and ctx.noe_lagged_splits(5, 300, 3) == 2
+    run_case(ctx, 5, 300, [(0, 300)], [1, 129, 200], mode)
+    _, xyz, quat = make_body(5, 700)
+    blocks = [(0, 300), (300, 140), (440, 260)]
+    lags = [0, 7, 128, 139]
+    ref, W = oracle_G(xyz, np.arange(5), quat, blocks, lags)
+    got = ctx.noe_lagged(xyz, np.arange(5), lags, quat=quat, block_start=[b[0] for b in blocks], block_len=[b[1] for b in blocks], mode=mode)
+    check_G('mode %d, three blocks in two splits' % mode, got, ref, W, BAR1 if mode else BAR0)
+
+
+@pytest.mark.parametrize('mode', (0, 1))
+def test_lag_zero_is_the_maps_r6_sum(ctx, mode):
+    for P, F, blocks in ((33, 120, RAGGED), (5, 300, [(0, 300)])):
+        _, xyz, quat = make_body(P, F)
+        bs, bl = [b[0] for b in blocks], [b[1] for b in blocks]
+        sums = ctx.noe_pairs(xyz, np.arange(P), quat=quat, block_start=bs, block_len=bl, mode=mode)
+        G = ctx.noe_lagged(xyz, np.arange(P), [0, 2], quat=quat, block_start=bs, block_len=bl, mode=mode)
+        e = np.max(np.abs(G[:, 0] / sums[:, :, 0] - 1))
+        print('mode %d P=%d: G(0) against the r^-6 sums %.3g (bar %.3g)' % (mode, P, e, BAR_LAG0[mode]))
+        assert e <= BAR_LAG0[mode]
+
+
+def test_equal_bits_from_call_to_call_and_alone_or_in_a_list(ctx):
+    """two calls give the same bits; a lag computed alone has the bits it has in a list -- also where the frames are split"""
+    for P, F, blocks, lags in ((65, 120, RAGGED, LAGS_RAGGED), (5, 300, [(0, 300)], [1, 129, 200]), (33, 300, [(0, 300)], [0, 5, 64])):
+        _, xyz, quat = make_body(P, F)
+        bs, bl = [b[0] for b in blocks], [b[1] for b in blocks]
+        for mode in (0, 1):
+            a = ctx.noe_lagged(xyz, np.arange(P), lags, quat=quat, block_start=bs, block_len=bl, mode=mode)
+            b = ctx.noe_lagged(xyz, np.arange(P), lags, quat=quat, block_start=bs, block_len=bl, mode=mode)
+            assert np.isfinite(a).all() and a.tobytes() == b.tobytes()
+            for q, k in enumerate(lags):
+                one = ctx.noe_lagged(xyz, np.arange(P), [k], quat=quat, block_start=bs, block_len=bl, mode=mode)
+                assert one.shape == (len(bs), 1, noe.n_pairs(P)) and one[:, 0].tobytes() == a[:, q].tobytes(), (P, mode, k)
+
+
+def test_rigid_body(ctx):
+    """A rigid body (no wobble), tumbled.  With its quaternions every pair vector stands still in the body's frame: Cdd = 1 at every
+    lag up to the float32 rounding of the coordinates (the oracle gives 1 - Cdd <= 1.7e-6 here): |Cdd - 1| <= 1e-4, tau_e = 0 or
+    next to it.  A kernel that rotated both windows with the origin's quaternion, or swapped the two, fails this by orders of
+    magnitude: the body turns by ~0.15 rad per frame.  Without quaternions the tumbling is in Cdd, which falls well below 1 --
+    asserted on the oracle first."""
+    P, F = 33, 120
+    _, xyz, quat = make_body(P, F, False)
+    index = np.arange(P)
+    lags = LAGS_120[1:]
+    ref, W = oracle_G(xyz, index, quat, [(0, F)], lags)
+    ref_lab, W_lab = oracle_G(xyz, index, None, [(0, F)], lags)
+    assert np.max(np.abs(ref / W - 1)) <= 1e-5 and (ref_lab / W_lab)[0, -1].max() < 0.9
+    for mode in (0, 1):
+        res = noe.dipolar_map(xyz, index, quat=quat, mode=mode, ctx=ctx, lags=lags)
+        e = np.max(np.abs(res['Cdd'] - 1))
+        print('rigid, mode %d: |Cdd - 1| %.3g' % (mode, e))
+        assert res['Cdd'].shape == (len(lags), noe.n_pairs(P)) and e <= 1e-4
+        lab = noe.dipolar_map(xyz, index, mode=mode, ctx=ctx, lags=lags)
+        assert lab['Cdd'][-1].max() < 0.9 and np.max(np.abs(lab['G'] - ref_lab) / W_lab) <= (BAR1 if mode else BAR0)
+
+
+def test_map_with_lags_keeps_the_map_and_adds_the_functions(ctx):
+    """dipolar_map(..., lags=...) holds, bit for bit, the map without lags, and lags, G, Cdd, dCdd, tau_e, dtau_e from the library's G
+    by finalize_lagged; the superposed form gives the same from the coordinates it uploaded once"""
+    P, F = 33, 120
+    body, xyz, quat = make_body(P, F)
+    index = np.arange(P)
+    blocks = ([0, 40, 80], [40, 40, 40])
+    lags = [1, 2, 4, 8, 16]
+    plain = noe.dipolar_map(xyz, index, quat=quat, blocks=blocks, ctx=ctx)
+    res = noe.dipolar_map(xyz, index, quat=quat, blocks=blocks, ctx=ctx, lags=lags, dt=2.0)
+    for k, v in plain.items():
+        assert np.asarray(v).tobytes() == np.asarray(res[k]).tobytes(), k
+    assert set(res) - set(plain) >= {'lags', 'G', 'Cdd', 'dCdd', 'tau_e', 'dtau_e'}
+    G = ctx.noe_lagged(xyz, index, lags, quat=quat, block_start=blocks[0], block_len=blocks[1])
+    want = noe.finalize_lagged(G, blocks[1], lags, plain, dt=2.0)
+    for k in ('lags', 'G', 'Cdd', 'dCdd', 'tau_e', 'dtau_e'):
+        assert np.asarray(res[k]).tobytes() == np.asarray(want[k]).tobytes(), k
+    # the wobble is an AR(1) process of coefficient 0.9: its correlation time is 1 / -ln 0.9 = 9.5 frames = 19 units of dt, the
+    # pair vector's of that order; the functions decay and the errors over three blocks are there
+    assert np.median(res['Cdd'][0] - res['Cdd'][-1]) > 0 and 0 < np.median(res['tau_e']) < 40.0 and res['dtau_e'].min() >= 0 and res['dCdd'].max() > 0
+    sup = noe.dipolar_map_superposed(xyz, body.astype(np.float32), index, index, blocks=blocks, ctx=ctx, lags=lags, dt=2.0)
+    Gs = ctx.noe_lagged(xyz, index, lags, quat=sup['quat'], block_start=blocks[0], block_len=blocks[1])
+    assert sup['G'].tobytes() == Gs.tobytes() and sup['tau_e'].shape == (noe.n_pairs(P),)
+
+
+def test_agrees_with_calculate_Ct_dipolar(ctx):
+    """the rotated difference vectors of three pairs, cast to float32, through ct.calculate_Ct_dipolar with the chunk = the block,
+    both sides in mode 1: the same normalisation, so Cdd agrees to the float32 rounding of the vectors handed over (1e-7): 1e-5"""
+    P, F = 33, 120
+    _, xyz, quat = make_body(P, F)
+    index = np.arange(P)
+    lags = LAGS_120[1:]
+    res = noe.dipolar_map(xyz, index, quat=quat, mode=1, ctx=ctx, lags=lags)
+    pick = np.array([0, 100, noe.n_pairs(P) - 1])
+    x = xyz.astype(np.float64)
+    pr = res['pairs'][pick]
+    d = np.einsum('tab,tpb->tpa', rotmat(quat), x[:, pr[:, 1]] - x[:, pr[:, 0]])
+    Ct = hostct.calculate_Ct_dipolar(d.astype(np.float32)[None], ctx=ctx, mode=1)[0]
+    want = Ct[np.array(lags) - 1]                                 # Ct holds the lags 1 .. F // 2
+    e = np.max(np.abs(res['Cdd'][:, pick] - want))
+    print('Cdd against calculate_Ct_dipolar: %.3g' % e)
+    assert e <= 1e-5
+
+
+def test_refusals_leave_the_context_usable(ctx):
+    _, xyz, quat = make_body(5, 17)
+    good = ctx.noe_lagged(xyz, np.arange(5), [0, 1, 5], quat=quat)
+
+    def refused(pattern, index=np.arange(5), bs=(0,), bl=(17,), lags=(0, 1, 5), mode=0, x=xyz):
+        with pytest.raises(SpinRelaxHipError, match=r'\(-3\): sr_noe_lagged_check: .*' + pattern):
+            ctx.noe_lagged(x, index, list(lags), block_start=list(bs), block_len=list(bl), mode=mode)
+        again = ctx.noe_lagged(xyz, np.arange(5), [0, 1, 5], quat=quat)        # nothing was queued: the context works, the same bits
+        assert again.tobytes() == good.tobytes()
+
+    # everything the map refuses
+    refused('a pair needs two', index=[3])
+    refused(r'index\[2\] = 5 is outside the 5 atoms', index=[0, 1, 5])
+    refused(r'index\[3\] = 1 is listed twice', index=[0, 1, 2, 1])
+    refused(r'block 1 = frames \[10, 18\) is outside the 17 held', bs=(0, 10), bl=(10, 8))
+    refused('block 0 has length 0', bl=(0,))
+    refused('mode 2', mode=2)
+    # the lags
+    refused(r'K=0 lags', lags=())
+    refused(r'K=65 lags', lags=range(65), bl=(17,))
+    refused(r'lag\[0\] = -1 is negative', lags=(-1, 2))
+    refused(r'strictly increasing: lag\[2\] = 3 after 3', lags=(1, 3, 3))
+    refused(r'strictly increasing: lag\[1\] = 2 after 4', lags=(4, 2))
+    refused('lag 17 leaves no term in a block of 17 frames', lags=(1, 17))
+    refused('lag 8 leaves no term in a block of 8 frames', bs=(0, 9), bl=(9, 8), lags=(1, 8))
+    # a result beyond the device's memory: 40000 atoms are 8e8 pairs; the map's own check passes at one block (45 GB), 64 lags of
+    # 8 bytes do not (410 GB)
+    big = np.zeros((70, 40000, 3), dtype=np.float32)
+    refused('64 lags x 799980000 pairs x 8 bytes = .* do not fit the device', index=np.arange(40000), bs=(0,), bl=(70,), lags=range(64), x=big)
+    # (a grid of 2^31 workgroups cannot be reached on a device of this memory: a workgroup stands for a tile of results or a partial
+    # tile, 2^31 of them for terabytes, and the memory refuses first; that guard is swept on the host, noe_lagged_host_sweep.cpp)
+    assert ctx.noe_lagged(xyz, np.arange(5), [0, 1, 5], quat=quat).tobytes() == good.tobytes()
+    # through the module: the lags are refused before the map is computed
+    with pytest.raises(SpinRelaxHipError, match=r'\(-3\): sr_noe_lagged_check: .*leaves no term'):
+        noe.dipolar_map(xyz, np.arange(5), quat=quat, lags=[1, 20], ctx=ctx)
+    with pytest.raises(SpinRelaxHipError, match=r'\(-3\): sr_noe_lagged_check: .*leaves no term'):
+        noe.dipolar_map_superposed(xyz, xyz[0], np.arange(5), np.arange(5), lags=[1, 20], ctx=ctx)
+
+
+def test_noesy_with_the_maps_tau_e(ctx):
+    """tau_e='map' is, bit for bit, the call with max(tau_e in frames x seconds per frame, TAU_E_FLOOR) as the array, and differs
+    from the call with one tau_e of 100 ps for all pairs"""
+    P, F = 12, 300
+    _, xyz, quat = make_body(P, F)
+    index = np.arange(P)
+    lags = noe.log_lags(64, 8)
+    dt_seconds = 2e-12
+    frames = noe.dipolar_map(xyz, index, quat=quat, ctx=ctx, lags=lags)                       # tau_e in frames
+    res = noe.dipolar_map(xyz, index, quat=quat, ctx=ctx, lags=lags, dt=dt_seconds)           # in seconds
+    arr = np.maximum(frames['tau_e'] * dt_seconds, noesy.TAU_E_FLOOR)
+    assert arr.max() > 5 * noesy.TAU_E_FLOOR                      # the floor is not all there is
+    args = ([0.05, 0.2], 600.0, 5e-9)
+    a = noesy.noesy(res, *args, tau_e='map', ctx=ctx)
+    b = noesy.noesy(res, *args, tau_e=arr, ctx=ctx)
+    c = noesy.noesy(res, *args, tau_e=1e-10, ctx=ctx)
+    for k in ('R', 'sigma', 'rho', 'A'):
+        assert a[k].tobytes() == b[k].tobytes(), k
+    assert np.max(np.abs(a['R'] - c['R'])) > 1e-6 * np.max(np.abs(c['R'])) and not np.array_equal(a['A'], c['A'])
+    assert noesy.rate_matrix(res, 600.0, 5e-9, tau_e='map', ctx=ctx).tobytes() == noesy.rate_matrix(res, 600.0, 5e-9, tau_e=arr, ctx=ctx).tobytes()
+
+
+def test_cli_noeLags_and_noesyTauEMap(tmp_path, ctx):
+    """one run of the script with --noeMap --noeLags --noesy --noesyTauEMap on a generated .npz: the files it writes against the
+    library called directly (4 blocks of 50 frames, dt = 10 ps)"""
+    P, F, nA = 12, 200, 20
+    body, xyz, _ = make_body(nA, F)
+    indexP = np.array([1, 4, 5, 7, 8, 10, 11, 13, 14, 16, 17, 19])
+    names = ['H%d' % a for a in indexP]
+    fit = np.arange(nA)
+    ref32 = body.astype(np.float32)
+    fn = str(tmp_path / 'traj.npz')
+    np.savez(fn, xyz=xyz, indexP=indexP, ref_xyz=ref32, fit_indices=fit, namesP=np.array(names), dt=np.float32(10.0))
+    script = os.path.join(ROOT, 'scripts', 'calculate-Ct-from-traj.py')
+    d = tmp_path / 'out'
+    d.mkdir()
+    p = subprocess.run([sys.executable, script, '-s', 'none.pdb', '-f', fn, '--tau', '500', '-o', str(d / 'o'), '--noeMap', '--noeLags',
+                        '1 2 4 8 16', '--noeCutoff', '0.7', '--binary', '--noesy', '--noesyMix', '0.05 0.2', '--noesyField', '600',
+                        '--noesyTauC', '5e-9', '--noesyTauEMap'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    assert p.returncode == 0, p.stdout.decode()[-3000:]
+    assert sorted(os.listdir(str(d))) == ['o_noeMap.dat', 'o_noeMap.npz', 'o_noeMapCt.dat', 'o_noesy.dat', 'o_noesy.npz']
+    lags = [1, 2, 4, 8, 16]
+    res = noe.dipolar_map_superposed(xyz, ref32, fit, indexP, blocks=([0, 50, 100, 150], [50] * 4), mode=0, ctx=ctx, lags=lags, dt=10.0)
+    z = np.load(str(d / 'o_noeMap.npz'))
+    assert z['sums'].tobytes() == res['sums'].tobytes() and z['lags'].tolist() == lags
+    for k in ('G', 'Cdd', 'dCdd', 'tau_e', 'dtau_e'):
+        assert z[k].tobytes() == res[k].tobytes(), k
+    tab = noe.read_map_ct(str(d / 'o_noeMapCt.dat'))
+    keep = np.nonzero(res['reff6'] <= 0.7)[0]
+    assert 0 < keep.size < res['reff6'].size
+    assert np.array_equal(tab['i'], indexP[res['pairs'][keep, 0]]) and np.array_equal(tab['j'], indexP[res['pairs'][keep, 1]])
+    assert tab['name_i'] == [names[i] for i in res['pairs'][keep, 0]] and tab['lags'].tolist() == [10.0, 20.0, 40.0, 80.0, 160.0]
+    for key in ('tau_e', 'dtau_e'):
+        assert np.max(np.abs(tab[key] - res[key][keep])) <= 5e-8 * np.max(np.abs(res[key][keep])), key
+    assert np.max(np.abs(tab['Cdd'] - res['Cdd'][:, keep].T)) <= 5e-8 * np.max(np.abs(res['Cdd']))
+    assert tab['tau_e'].max() > 10.0                               # ps: the map's tau_e is in the time unit of the run
+    want = noesy.noesy(dict(res, tau_e=res['tau_e'] * 1e-12), [0.05, 0.2], 600.0, 5e-9, tau_e='map', ctx=ctx)
+    zn = np.load(str(d / 'o_noesy.npz'))
+    for k in ('R', 'A'):
+        assert zn[k].tobytes() == want[k].tobytes(), k
+    other = noesy.noesy(res, [0.05, 0.2], 600.0, 5e-9, tau_e=1e-10, ctx=ctx)
+    assert not np.array_equal(zn['R'], other['R'])
+    nt = noesy.read_noesy(str(d / 'o_noesy.dat'))
+    off = nt['i'] != nt['j']
+    assert np.max(np.abs(nt['sigma'][off] - want['sigma'][keep])) <= 5e-8 * np.max(np.abs(want['sigma']))

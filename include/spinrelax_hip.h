@@ -429,6 +429,38 @@ int sr_noe_lagged_check(sr_ctx *, int64_t nFrames, int64_t nAtoms, const int32_t
                         const int64_t *block_len, int B, const int32_t *lags, int K, int mode);
 int sr_noe_lagged_splits(int64_t P, int64_t longest_block, int B);   /* S of such a call (tests aim at S > 1); 0 for a bad shape */
 
+/* ---- the lagged map split into the five tumbling modes of an anisotropic diffusion tensor (sr_noe_modes.hip; beyond the reference) ----
+ * For the same atoms, blocks, lags and pair order as sr_noe_lagged_*, six sums per (block, lag, pair).  With F = R(frame_quat), the
+ * constant rotation into the principal-axis frame of the diffusion tensor, d"(t) = F R(quat[t]) d(t), u = d"(t) / r(t),
+ * v = d"(t + k) / r(t + k), w = r(t)^-3 r(t + k)^-3, qz(u) = u_z^2 - 1/3 and dl(u) = u_x^2 - u_y^2:
+ *     H[b][q][k(i, j)][0 .. 5] = sum over the origins t of block b with t + k inside the block of
+ *         w qz(u) qz(v),   w dl(u) dl(v),   w [qz(u) dl(v) + dl(u) qz(v)] / 2,   w u_y u_z v_y v_z,   w u_x u_z v_x v_z,   w u_x u_y v_x v_y
+ * They do not depend on the tensor: one H serves any D.  2.25 H0 + 0.75 H1 + 3 (H3 + H4 + H5) is G of sr_noe_lagged_* whatever the
+ * frame; the amplitudes of the five modes are host work (spinrelax_amd/noe.py: mode_amplitudes).
+ *   mode 0: float32 per pair, frame and lag: d, e, r2, s2, ri, si, d', e' as in k_noe_lagged with the matrix F R(quat[t]), formed in
+ *           float64 and rounded to float32; u_a = d'_a ri, v_a = e'_a si; a0 = fma(uz, uz, -1/3), a1 = fma(ux, ux, -(uy uy)), b0, b1
+ *           of v likewise; g = ri si; g3 = (g g) g; the six terms (a0 b0) g3, (a1 b1) g3, (0.5 fma(a0, b1, a1 b0)) g3,
+ *           ((uy uz) (vy vz)) g3, ((ux uz) (vx vz)) g3, ((ux uy) (vx vy)) g3; float32 partial sums of at most 8 origins, then float64.
+ *   mode 1: the same sequence in float64 with 1 / sqrt.
+ * k_noe_modes and k_noe_modes_finish: the workgroups, tiles, windows, origin ranges and the split count S = sr_noe_lagged_splits(...)
+ * of k_noe_lagged; the partial tiles are added in the order s = 0 .. S-1.  No atomics: equal input gives bit-equal H, and a lag has
+ * the same bits alone and in any list.  With S > 1 the partial tiles are a work area of about S times the bytes of H.
+ *   quat: DEVICE (nFrames, 4) float64 or NULL (R(quat[t]) = 1); frame_quat_host: HOST (4) float64 (w, x, y, z), a unit quaternion
+ *   (normalised again in float64 before use), or NULL (F = 1); with both NULL no rotation is applied at all.
+ *   H: DEVICE (B, K, P (P - 1) / 2, 6) float64.  Asynchronous on the context's stream.
+ * Refused with -3, before anything is queued: everything sr_noe_lagged_check refuses, the byte counts taken six times; a frame
+ * quaternion that is not finite or whose squared norm is farther than 1e-6 from 1. */
+int sr_noe_modes_f32_dev(sr_ctx *, const float *xyz, int64_t nFrames, int64_t nAtoms, const int32_t *index_host, int64_t P,
+                         const double *quat, const double *frame_quat_host, const int64_t *block_start_host,
+                         const int64_t *block_len_host, int B, const int32_t *lags_host, int K, int mode, double *H);
+/* the same with xyz, quat (may be NULL) and H on the HOST.  Blocks until H is there. */
+int sr_noe_modes_f32(sr_ctx *, const float *xyz, int64_t nFrames, int64_t nAtoms, const int32_t *index, int64_t P, const double *quat,
+                     const double *frame_quat, const int64_t *block_start, const int64_t *block_len, int B, const int32_t *lags, int K,
+                     int mode, double *H);
+/* What the two calls above refuse with -3, with their message, and nothing else: all host work, nothing allocated or queued. */
+int sr_noe_modes_check(sr_ctx *, int64_t nFrames, int64_t nAtoms, const int32_t *index, int64_t P, const int64_t *block_start,
+                       const int64_t *block_len, int B, const int32_t *lags, int K, const double *frame_quat, int mode);
+
 /* ---- NOESY intensities from the dipolar map: the full relaxation matrix (sr_noesy.hip; beyond the reference) -------------------------
  * Macura & Ernst, Mol. Phys. 41, 95 (1980); Keepers & James, J. Magn. Reson. 57, 404 (1984); the model-free rates from <r^-6> and S2:
  * Brueschweiler et al., JACS 114, 2289 (1992).  Isotropic tumbling, one kind of spin.  With A6 and S2 (P (P - 1) / 2 each) in the pair
@@ -447,6 +479,25 @@ int sr_noesy_rates_f64_dev(sr_ctx *, const double *A6_host, const double *S2_hos
 /* the same with R on the HOST.  Blocks until R is there. */
 int sr_noesy_rates_f64(sr_ctx *, const double *A6, const double *S2, const double *tau_e_pair, const double *leak_spin, int64_t P,
                        double omega_H, double tau_c, double tau_e, double leak, double prefactor, double *R);
+/* The same matrix under anisotropic tumbling: the diffusion tensor's five rates E[0 .. 4] (1 / s, the order of
+ * _hostmath.D_coefficients_ellipsoid) and per pair the mode amplitudes a[k][m] at lag 0 and their plateaus c[k][m] (units of A6:
+ * sum_m a = A6, sum_m c = S2 A6; spinrelax_amd/noe.py: mode_amplitudes, mode_plateau), g(x, y) = x / (x^2 + y^2):
+ *     J(w)     = sum_m [ c_m g(E_m, w) + max(a_m - c_m, 0) g(E_m + 1 / tau_e, w) ]
+ *     R_ij     = prefactor [6 J(2 omega_H) - J(0)],      R_ii = sum_j prefactor [J(0) + 3 J(omega_H) + 6 J(2 omega_H)] + leak_i
+ * With E_m = 1 / tau_c for all m this is the formula above.  tau_e: tau_e_mode (one per pair and mode), else tau_e_pair (one per
+ * pair), else the scalar.  k_noesy_rates_modes: one workgroup per row, the row sum in a fixed order, R_ij and R_ji the same bits.
+ *   a, c (P (P - 1) / 2, 5), E (5), tau_e_pair, tau_e_mode (P (P - 1) / 2, 5), leak: HOST arrays, checked before anything is queued
+ *   and consumed on return; R_dev: DEVICE (P, P) float64.
+ * Refused with -3, before anything is queued: P < 2 or P > 32768, tables beyond the device's memory, a negative a or c,
+ * c_m > a_m (1 + 1e-6) where a_m > 0 (c_m > 0 where a_m = 0), E_m <= 0, a tau_e <= 0, a negative leak, a prefactor <= 0, a negative
+ * omega_H, anything not finite. */
+int sr_noesy_rates_modes_f64_dev(sr_ctx *, const double *a_host, const double *c_host, const double *E_host, const double *tau_e_pair_host,
+                                 const double *tau_e_mode_host, const double *leak_host, int64_t P, double omega_H, double tau_e,
+                                 double leak, double prefactor, double *R_dev);
+/* the same with R on the HOST.  Blocks until R is there. */
+int sr_noesy_rates_modes_f64(sr_ctx *, const double *a, const double *c, const double *E, const double *tau_e_pair,
+                             const double *tau_e_mode, const double *leak_spin, int64_t P, double omega_H, double tau_e, double leak,
+                             double prefactor, double *R);
 /* C = alpha A B + beta I for symmetric (P, P) float64 DEVICE matrices A and B that commute; C may be A or B.  Only the 64 x 64 tiles
  * with tile row <= tile column are computed (k_symm_mul: v_mfma_f64_16x16x4_f64, both operands read as rows, k split over S
  * workgroups, S a function of P alone) and k_symm_mul_finish writes C[i][j] and C[j][i] from one value: C == C^T bit for bit, equal

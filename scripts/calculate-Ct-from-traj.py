@@ -7,7 +7,7 @@ also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat; with the [ext
 and <o>_crossPairs.dat; with the [extension] --dipolarCt also <o>_dipolarCtint.dat and <o>_dipolarDist.dat; with the
 [extension] --dipolarCrossCt --pairs FILE also <o>_dipolarCrossCtint.dat and <o>_dipolarCrossPairs.dat; with the [extension] --noeMap
 also <o>_noeMap.dat and, with --binary, <o>_noeMap.npz, with --noeLags / --noeLagMax on top of it <o>_noeMapCt.dat, and with --noesy on top of it <o>_noesy.dat and, with --binary,
-<o>_noesy.npz).  C(t), the rotation into
+<o>_noesy.npz; --noesyD in the place of --noesyTauC: the same files under anisotropic tumbling, --vecRot as the tensor's frame).  C(t), the rotation into
 the PAF, the spherical histogram, the mean vector and S2 are computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
 Several GPUs: run under torchrun (`torchrun --nproc-per-node N scripts/calculate-Ct-from-traj.py ...`): rank r computes the
@@ -138,11 +138,17 @@ def build_parser():
                         '(Macura & Ernst 1980; Keepers & James 1984; model-free rates from <r^-6> and S2, Brueschweiler et al. 1992), spin '
                         'diffusion included: A(tau_m) = exp(-R tau_m) at the mixing times of --noesyMix.  <o>_noesy.dat with the columns '
                         'i j name_i name_j sigma and one column per mixing time, the diagonal rows i = j included (--noeCutoff applies to '
-                        'the pairs); with --binary also <o>_noesy.npz.  Needs --noesyMix, --noesyField and --noesyTauC.  Isotropic tumbling, '
+                        'the pairs); with --binary also <o>_noesy.npz.  Needs --noesyMix, --noesyField and --noesyTauC (isotropic tumbling) or --noesyD (anisotropic), '
                         'protons only, single process only.')
     p.add_argument('--noesyMix', type=str, dest='noesy_mix', default=None, help='[extension] --noesy: the mixing times in seconds, e.g. "0.05 0.1 0.2".')
     p.add_argument('--noesyField', type=float, dest='noesy_field', default=None, help='[extension] --noesy: the proton frequency of the spectrometer in MHz.')
     p.add_argument('--noesyTauC', type=float, dest='noesy_tauc', default=None, help='[extension] --noesy: the overall correlation time tau_c in seconds.')
+    p.add_argument('--noesyD', type=str, dest='noesy_D', default=None,
+                   help='[extension] --noesy under anisotropic tumbling, in the place of --noesyTauC: the rotational diffusion tensor as '
+                        '"Diso aniso [rhomb]", Diso in 1/s (the convention of calculate-relaxations-from-Ct.py).  The map then also holds the '
+                        'mode sums of every pair in the frame of --vecRot, the quaternion into the tensor\'s principal-axis frame (identity '
+                        'without it), lag 0 is put in front of the lags, and with --noesyTauEMap every mode of every pair has its own tau_e.  '
+                        'With --binary H, H_blocks and frame also go into <o>_noeMap.npz.')
     p.add_argument('--noesyTauE', type=float, dest='noesy_taue', default=None,
                    help='[extension] --noesy: the correlation time of the internal motion tau_e in seconds (default 1e-10).')
     p.add_argument('--noesyTauEMap', dest='noesy_taue_map', action='store_true', default=False,
@@ -192,10 +198,23 @@ def check_noe_lag_args(args):
     return lags
 
 
+def noesy_tensor(args):
+    """--noesyD "Diso aniso [rhomb]" -> (Dx, Dy, Dz) in 1/s through _hostmath.ellipsoid_from_iso; None for anything else"""
+    from spinrelax_amd._hostmath import ellipsoid_from_iso
+    try:
+        w = [float(v) for v in args.noesy_D.split()]
+    except ValueError:
+        return None
+    if len(w) not in (2, 3) or not np.all(np.isfinite(w)) or not w[0] > 0 or not w[1] > 0:
+        return None
+    D = np.array(ellipsoid_from_iso(w[0], w[1], w[2] if len(w) == 3 else 0.0), dtype=np.float64)
+    return D if np.all(np.isfinite(D)) and np.all(D > 0) else None
+
+
 def check_noesy_args(args):
     """the --noesy* flags that do not fit together: an error message and exit, before any GPU work; returns the mixing times"""
     given = [n for n, v in (('--noesyMix', args.noesy_mix), ('--noesyField', args.noesy_field), ('--noesyTauC', args.noesy_tauc),
-                            ('--noesyTauE', args.noesy_taue), ('--noesyLeak', args.noesy_leak), ('--noesyUnit', args.noesy_unit),
+                            ('--noesyD', args.noesy_D), ('--noesyTauE', args.noesy_taue), ('--noesyLeak', args.noesy_leak), ('--noesyUnit', args.noesy_unit),
                             ('--noesyGroups', args.noesy_groups), ('--noesyTauEMap', args.noesy_taue_map or None)) if v is not None]
     if not args.bDoNoesy:
         if given:
@@ -205,9 +224,26 @@ def check_noesy_args(args):
     if not args.bDoNoeMap:
         print("= = = ERROR: --noesy works on the map of --noeMap; give both.", file=sys.stderr)
         sys.exit(1)
-    for name, v in (('--noesyMix', args.noesy_mix), ('--noesyField', args.noesy_field), ('--noesyTauC', args.noesy_tauc)):
+    if args.noesy_D is not None and args.noesy_tauc is not None:
+        print("= = = ERROR: --noesyD and --noesyTauC both describe the tumbling; give one of them.", file=sys.stderr)
+        sys.exit(1)
+    for name, v in (('--noesyMix', args.noesy_mix), ('--noesyField', args.noesy_field),
+                    ('--noesyTauC' if args.noesy_D is None else '--noesyD', args.noesy_tauc if args.noesy_D is None else args.noesy_D)):
         if v is None:
             print("= = = ERROR: --noesy needs %s." % name, file=sys.stderr)
+            sys.exit(1)
+    if args.noesy_D is not None and noesy_tensor(args) is None:
+        print("= = = ERROR: --noesyD must be \"Diso aniso [rhomb]\" with Diso > 0 in 1/s and a tensor with Dx, Dy, Dz > 0; got '%s'."
+              % args.noesy_D, file=sys.stderr)
+        sys.exit(1)
+    if args.noesy_D is not None and args.vecRotQ != '':
+        try:
+            q = np.array([float(v) for v in args.vecRotQ.split()])
+        except ValueError:
+            q = np.zeros(0)
+        if q.shape != (4,) or not np.all(np.isfinite(q)) or abs(np.dot(q, q) - 1.0) > 1e-6:
+            print("= = = ERROR: --noesyD takes --vecRot as the unit quaternion \"w x y z\" into the tensor's frame; got '%s'." % args.vecRotQ,
+                  file=sys.stderr)
             sys.exit(1)
     try:
         mix = np.array([float(w) for w in args.noesy_mix.split()])
@@ -216,7 +252,7 @@ def check_noesy_args(args):
     if mix.size < 1 or not np.all(np.isfinite(mix)) or np.any(mix < 0):
         print("= = = ERROR: --noesyMix must list mixing times in seconds, finite and >= 0; got '%s'." % args.noesy_mix, file=sys.stderr)
         sys.exit(1)
-    if not args.noesy_field > 0 or not args.noesy_tauc > 0 or (args.noesy_taue is not None and not args.noesy_taue > 0) \
+    if not args.noesy_field > 0 or (args.noesy_tauc is not None and not args.noesy_tauc > 0) or (args.noesy_taue is not None and not args.noesy_taue > 0) \
             or (args.noesy_leak is not None and not args.noesy_leak >= 0):
         print("= = = ERROR: --noesyField, --noesyTauC and --noesyTauE must be > 0 and --noesyLeak >= 0.", file=sys.stderr)
         sys.exit(1)
@@ -239,12 +275,13 @@ def run_noesy(args, out_pref, res, names):
     mix = check_noesy_args(args)
     print("= = = Conducting the relaxation-matrix NOESY calculation of %i spins at %i mixing times." % (res['index'].size, mix.size))
     tau_e = 1e-10 if args.noesy_taue is None else args.noesy_taue
+    D = None if args.noesy_D is None else noesy_tensor(args)
     if args.noesy_taue_map:
-        # the map's tau_e is in the time unit of the run
-        res = dict(res, tau_e=res['tau_e'] * TIME_UNIT_S)
-        tau_e = 'map'
+        # the map's tau_e and dt are in the time unit of the run
+        res = dict(res, tau_e=res['tau_e'] * TIME_UNIT_S, dt=res['dt'] * TIME_UNIT_S)
+        tau_e = 'map' if D is None else 'modes'
     try:
-        out = noesy.noesy(res, mix, args.noesy_field, args.noesy_tauc, tau_e=tau_e,
+        out = noesy.noesy(res, mix, args.noesy_field, args.noesy_tauc, tau_e=tau_e, D=D,
                           leak=0.0 if args.noesy_leak is None else args.noesy_leak, unit=args.noesy_unit or 'nm')
         rows = noesy.write_noesy(out_pref + '_noesy.dat', out, names=names, reff6=res['reff6'], cutoff=args.noe_cutoff)
         if args.noesy_groups is not None:
@@ -266,6 +303,12 @@ def run_noe_map(args, out_pref):
     correlation functions and tau_e of every pair"""
     from spinrelax_amd import ired, noe
     lags = check_noe_lag_args(args)
+    modes = dict()
+    if args.bDoNoesy and args.noesy_D is not None:
+        # anisotropic tumbling: the mode sums in the frame of --vecRot, from lag 0 on
+        modes = dict(modes=True, frame=np.array([float(v) for v in args.vecRotQ.split()]) if args.vecRotQ != '' else None)
+        if lags is not None and lags[0] != 0:
+            lags = np.concatenate([[0], lags])
     xyz, frames, first = [], [], None
     for fn in args.infn:
         z = np.load(fn, allow_pickle=True) if fn.endswith('.npz') else {}
@@ -298,11 +341,11 @@ def run_noe_map(args, out_pref):
     print("= = = Conducting the all-pairs dipolar map of %i atoms (%i pairs) over %i blocks." % (index.size, noe.n_pairs(index.size), blocks[0].size))
     try:
         if 'ref_xyz' in z and 'fit_indices' in z:
-            res = noe.dipolar_map_superposed(allxyz, z['ref_xyz'], z['fit_indices'], index, blocks=blocks, mode=mode, lags=lags, dt=dt)
+            res = noe.dipolar_map_superposed(allxyz, z['ref_xyz'], z['fit_indices'], index, blocks=blocks, mode=mode, lags=lags, dt=dt, **modes)
         else:
             print("= = = WARNING: no `ref_xyz` / `fit_indices` in the input: the map is computed in the lab frame and its S2 includes "
                   "overall tumbling.", file=sys.stderr)
-            res = noe.dipolar_map(allxyz, index, blocks=blocks, mode=mode, lags=lags, dt=dt)
+            res = noe.dipolar_map(allxyz, index, blocks=blocks, mode=mode, lags=lags, dt=dt, **modes)
         rows = noe.write_map(out_pref + '_noeMap.dat', res, names=names, cutoff=args.noe_cutoff)
         if lags is not None:
             noe.write_map_ct(out_pref + '_noeMapCt.dat', res, names=names, cutoff=args.noe_cutoff)
@@ -314,6 +357,8 @@ def run_noe_map(args, out_pref):
                 'reff6_b', 'reff3_b', 'S2_b', 'S2rad_b', 'block_len', 'sums')
         if lags is not None:
             keep += ('lags', 'G', 'Cdd', 'dCdd', 'tau_e', 'dtau_e')
+        if modes:
+            keep += ('H', 'H_blocks', 'frame')
         np.savez(out_pref + '_noeMap.npz', block_start=blocks[0], **{k: res[k] for k in keep})
     print("      ...%i of %i pairs written; complete." % (rows, res['reff6'].size))
     if args.bDoNoesy:

@@ -1,5 +1,5 @@
 // Developer tool: sweeps the pure host helpers of the lagged dipolar map (spinrelax_amd/csrc/sr_noe_host.h: split rule, lag list check,
-// origin ranges, byte counts, grid sizes) against plain restatements of their definitions, under the sanitizers.  No HIP, no GPU:
+// origin ranges, byte counts, grid sizes, and those of its mode-resolved form: byte counts, grid sizes, frame matrix) against plain restatements of their definitions, under the sanitizers.  No HIP, no GPU:
 //
 //     c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I spinrelax_amd/csrc \
 //         scripts/dev/noe_lagged_host_sweep.cpp -o /tmp/noe_lagged_host_sweep && /tmp/noe_lagged_host_sweep
@@ -7,6 +7,7 @@
 // Prints the number of comparisons and exits 0, or names the first disagreement and exits 1.
 #include "sr_noe_host.h"
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
@@ -102,7 +103,60 @@ int main()
                     const unsigned __int128 wg = (unsigned __int128)B * K * S * NP, fin = (unsigned __int128)B * K * NP * 4;
                     const bool ok = wg < ((unsigned __int128)1 << 31) && fin < ((unsigned __int128)1 << 31);
                     EXPECT(noe_lagged_grid_ok(B, K, S, NP) == ok, "grid(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
+                    // the mode-resolved map: six sums per pair, the same grids
+                    unsigned __int128 mout, mpart;
+                    noe_modes_bytes(B, K, npairs, S, NP, mout, mpart);
+                    EXPECT(mout == 6 * want_out && mpart == 6 * want_part, "modes bytes(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
+                    EXPECT(noe_modes_grid_ok(B, K, S, NP) == ok, "modes grid(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
                 }
+
+    // ---- the frame matrix: the identity for NULL; orthogonal with determinant 1, R(q) v = q (0, v) q*, R(-q) = R(q), a scaling
+    // inside the tolerance taken out; refusals ----
+    {
+        double Fm[9];
+        EXPECT(noe_frame_matrix(nullptr, Fm, msg, sizeof msg) == 0, "NULL frame");
+        for (int k = 0; k < 9; ++k) EXPECT(Fm[k] == (k % 4 == 0 ? 1.0 : 0.0), "identity[%d] = %g", k, Fm[k]);
+        unsigned seed = 12345;
+        auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (double)(seed >> 8) / (double)(1u << 24) - 0.5; };
+        for (int n = 0; n < 2000; ++n) {
+            double q[4] = {rnd(), rnd(), rnd(), rnd()};
+            const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+            if (nq < 1e-3) continue;
+            const double scale = 1.0 + 4e-7 * rnd();                // squared norm within 1e-6 of 1
+            double qs[4], qn[4];
+            for (int k = 0; k < 4; ++k) { q[k] /= nq; qs[k] = q[k] * scale; qn[k] = -q[k]; }
+            double Fs[9], Fn[9];
+            EXPECT(noe_frame_matrix(q, Fm, msg, sizeof msg) == 0 && noe_frame_matrix(qs, Fs, msg, sizeof msg) == 0 &&
+                   noe_frame_matrix(qn, Fn, msg, sizeof msg) == 0, "unit quaternion %d refused: %s", n, msg);
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) {
+                    double dot = 0.0;
+                    for (int c = 0; c < 3; ++c) dot += Fm[3 * a + c] * Fm[3 * b + c];
+                    EXPECT(std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-14, "rows %d, %d of frame %d: %g", a, b, n, dot);
+                    EXPECT(std::fabs(Fs[3 * a + b] - Fm[3 * a + b]) <= 1e-14 && Fn[3 * a + b] == Fm[3 * a + b], "frame %d entry %d %d", n, a, b);
+                }
+            const double det = Fm[0] * (Fm[4] * Fm[8] - Fm[5] * Fm[7]) - Fm[1] * (Fm[3] * Fm[8] - Fm[5] * Fm[6]) + Fm[2] * (Fm[3] * Fm[7] - Fm[4] * Fm[6]);
+            EXPECT(std::fabs(det - 1.0) <= 1e-14, "det of frame %d: %g", n, det);
+            // q (0, v) q* by the quaternion product
+            const double v[3] = {rnd(), rnd(), rnd()};
+            const double w = q[0], x = q[1], y = q[2], z = q[3];
+            const double tw = -x * v[0] - y * v[1] - z * v[2], tx = w * v[0] + y * v[2] - z * v[1], ty = w * v[1] + z * v[0] - x * v[2],
+                         tz = w * v[2] + x * v[1] - y * v[0];
+            const double rx = -tw * x + tx * w - ty * z + tz * y, ry = -tw * y + ty * w - tz * x + tx * z, rz = -tw * z + tz * w - tx * y + ty * x;
+            for (int a = 0; a < 3; ++a) {
+                const double got = Fm[3 * a] * v[0] + Fm[3 * a + 1] * v[1] + Fm[3 * a + 2] * v[2];
+                EXPECT(std::fabs(got - (a == 0 ? rx : a == 1 ? ry : rz)) <= 1e-14, "frame %d rotates component %d to %g", n, a, got);
+            }
+        }
+        const double bad[][4] = {{1.0, 0.1, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {1.0 + 1e-6, 0.0, 0.0, 0.0}, {0.999999, 0.0, 0.0, 0.0}};
+        for (const auto &qb : bad) EXPECT(noe_frame_matrix(qb, Fm, msg, sizeof msg) == -3 && strstr(msg, "not a unit quaternion"), "norm: %s", msg);
+        for (int k = 0; k < 4; ++k)
+            for (double v : {(double)NAN, (double)INFINITY, -(double)INFINITY}) {
+                double qb[4] = {1.0, 0.0, 0.0, 0.0};
+                qb[k] = v;
+                EXPECT(noe_frame_matrix(qb, Fm, msg, sizeof msg) == -3 && strstr(msg, "is not finite"), "component %d = %g: %s", k, v, msg);
+            }
+    }
     printf("noe_lagged_host_sweep: %ld comparisons, no disagreement\n", checks);
     return 0;
 }

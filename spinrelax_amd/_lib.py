@@ -212,6 +212,20 @@ SIGNATURES = {
                                   c_int, c_void_p]),
     'sr_noe_lagged_check': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int]),
     'sr_noe_lagged_splits': (c_int, [c_int64, c_int64, c_int]),
+    # the lagged map split into tumbling modes (sr_noe_modes.hip): (ctx, xyz, nFrames, nAtoms, index_host, P, quat, frame_quat_host | NULL,
+    # block_start_host, block_len_host, B, lags_host, K, mode, H), xyz / quat / H on the device or all three on the host; the check
+    # takes no xyz, quat and H: (ctx, nFrames, nAtoms, index, P, block_start, block_len, B, lags, K, frame_quat | NULL, mode)
+    'sr_noe_modes_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_int, c_int, c_void_p]),
+    'sr_noe_modes_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_void_p, c_int, c_int, c_void_p]),
+    'sr_noe_modes_check': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int]),
+    # (ctx, a_host, c_host, E_host, tau_e_pair_host | NULL, tau_e_mode_host | NULL, leak_host | NULL, P, omega_H, tau_e, leak, prefactor, R),
+    # R on the device or on the host
+    'sr_noesy_rates_modes_f64_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double,
+                                             c_double, c_double, c_void_p]),
+    'sr_noesy_rates_modes_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double,
+                                         c_double, c_double, c_void_p]),
     # NOESY from the map (sr_noesy.hip): (ctx, A6_host, S2_host, tau_e_host | NULL, leak_host | NULL, P, omega_H, tau_c, tau_e, leak, prefactor, R),
     # R on the device or on the host
     'sr_noesy_rates_f64_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double, c_double,
@@ -235,7 +249,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long, sr_noe, sr_noe_lagged and sr_noesy entry points, sr_vechist_plan and the sr_ct_palmer_sums_pack_* / sr_ct_pack_fused / sr_pack_reg_tiles group: they only add symbols, and load() fails at a missing one
+ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long, sr_noe, sr_noe_lagged, sr_noe_modes and sr_noesy entry points, sr_vechist_plan and the sr_ct_palmer_sums_pack_* / sr_ct_pack_fused / sr_pack_reg_tiles group: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -61,7 +61,7 @@ enum {
     SR_WS_CTLONG_TAB,   // twiddles of its float64 inverse transform
     SR_WS_IRED,         // iRED matrix (sr_ired.hip): partial tiles of the frame split, (W, tile pairs, S, 64 x 64) float64
     SR_WS_IRED_AMP,     // iRED mode correlation functions (sr_ired_modes.hip): amplitudes of one batch of windows, (m, 6, F_w) float64 each
-    SR_WS_NOE,          // all-pairs dipolar map (sr_noe.hip): partial tiles of the frame split, (B, S, tile pairs, T x T, 7) float64
+    SR_WS_NOE,          // all-pairs dipolar map (sr_noe.hip): partial tiles of the frame split, (B, S, tile pairs, T x T, 7) float64; those of its lagged and mode-resolved forms
     SR_WS_SYMM,         // symmetric product (sr_noesy.hip): partial tiles of the k split, (S, tile pairs, 64 x 64) float64
     SR_WS_EXPM          // matrix exponential (sr_noesy.hip): the scaled matrix Y (P, P) and the P row sums of |R|
 };

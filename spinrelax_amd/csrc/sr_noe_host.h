@@ -1,7 +1,9 @@
-// sr_noe_host.h -- the pure host arithmetic of the all-pairs dipolar map and its lagged form (sr_noe.hip, sr_noe_lagged.hip): split
-// rule, lag list check, origin ranges, byte counts, grid sizes.  Nothing here needs HIP: scripts/dev/noe_lagged_host_sweep.cpp compiles
+// sr_noe_host.h -- the pure host arithmetic of the all-pairs dipolar map, its lagged form and the lagged form's split into tumbling
+// modes (sr_noe.hip, sr_noe_lagged.hip, sr_noe_modes.hip): split rule, lag list check, origin ranges, byte counts, grid sizes, frame
+// matrix.  Nothing here needs HIP: scripts/dev/noe_lagged_host_sweep.cpp compiles
 // this header alone, with -fsanitize=address,undefined, and sweeps it.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 
@@ -77,4 +79,45 @@ inline bool noe_lagged_grid_ok(int B, int K, int S, int64_t NP)
 {
     const unsigned __int128 bk = (unsigned __int128)B * (unsigned)K * (unsigned __int128)NP, lim = (unsigned __int128)1 << 31;
     return bk * (unsigned)S < lim && bk * 4u < lim;
+}
+
+// ---- the mode-resolved lagged map (sr_noe_modes.hip) ----
+constexpr int kNoeModeSums = 6;                     // sums per (block, lag, pair): H0 .. H5
+
+// bytes of the result H (B, K, npairs, 6) float64 and of the partial tiles (B, K, S, NP, 6, T x T) float64 (none with S = 1): the
+// lagged map's, six times; inside 128 bits by the same margin
+inline void noe_modes_bytes(int B, int K, int64_t npairs, int S, int64_t NP, unsigned __int128 &out_bytes, unsigned __int128 &part_bytes)
+{
+    noe_lagged_bytes(B, K, npairs, S, NP, out_bytes, part_bytes);
+    out_bytes *= (unsigned)kNoeModeSums;
+    part_bytes *= (unsigned)kNoeModeSums;
+}
+
+// k_noe_modes takes B K S NP workgroups, k_noe_modes_finish 4 B K NP (a thread adds the six sums of one pair): the lagged map's grids
+inline bool noe_modes_grid_ok(int B, int K, int S, int64_t NP) { return noe_lagged_grid_ok(B, K, S, NP); }
+
+// the frame quaternion (w, x, y, z) -> F = R(q / |q|), row-major 3 x 3 in float64; 0, or -3 with the reason in msg: a component that
+// is not finite, a squared norm farther than 1e-6 from 1.  NULL: the identity.
+inline int noe_frame_matrix(const double *q, double *F, char *msg, size_t nmsg)
+{
+    for (int k = 0; k < 9; ++k) F[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    if (!q) return 0;
+    double n2 = 0.0;
+    for (int k = 0; k < 4; ++k) {
+        if (!(q[k] - q[k] == 0.0)) {                // NaN or infinite
+            snprintf(msg, nmsg, "frame quaternion component %d = %g is not finite", k, q[k]);
+            return -3;
+        }
+        n2 += q[k] * q[k];
+    }
+    if (!(n2 >= 1.0 - 1e-6 && n2 <= 1.0 + 1e-6)) {
+        snprintf(msg, nmsg, "frame quaternion of squared norm %.9g is not a unit quaternion", n2);
+        return -3;
+    }
+    const double n = 1.0 / std::sqrt(n2);
+    const double w = q[0] * n, x = q[1] * n, y = q[2] * n, z = q[3] * n;
+    F[0] = 1 - 2 * (y * y + z * z); F[1] = 2 * (x * y - w * z);     F[2] = 2 * (x * z + w * y);
+    F[3] = 2 * (x * y + w * z);     F[4] = 1 - 2 * (x * x + z * z); F[5] = 2 * (y * z - w * x);
+    F[6] = 2 * (x * z - w * y);     F[7] = 2 * (y * z + w * x);     F[8] = 1 - 2 * (x * x + y * y);
+    return 0;
 }

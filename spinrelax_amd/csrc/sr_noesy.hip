@@ -106,6 +106,46 @@ __global__ __launch_bounds__(256) void k_noesy_rates(const double *__restrict__ 
     if (threadIdx.x == 0) R[(int64_t)i * P + i] = tot + (leak ? leak[i] : leak_all);
 }
 
+struct ModeRates {
+    double E[5];                            // the tensor's five rates, the order of _hostmath.D_coefficients_ellipsoid
+};
+
+__device__ __forceinline__ double noesy_g(double x, double y) { return x / (x * x + y * y); }      // as in sr_relax.hip
+
+// anisotropic tumbling: per pair the amplitudes a[k][m] of the five modes at lag 0 and their plateaus c[k][m], both in units of A6.
+// tau_e per (pair, mode), per pair or one for all.  The structure of k_noesy_rates: the same row sum, R_ij and R_ji from one value.
+__global__ __launch_bounds__(256) void k_noesy_rates_modes(const double *__restrict__ am, const double *__restrict__ cm,
+                                                           const double *__restrict__ tau_e_pair, const double *__restrict__ tau_e_mode,
+                                                           const double *__restrict__ leak, int P, double omega, ModeRates rates,
+                                                           double tau_e_all, double leak_all, double q, double *__restrict__ R)
+{
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    const int i = blockIdx.x;
+    double rho = 0.0;
+    for (int j = threadIdx.x; j < P; j += 256) {
+        if (j == i) continue;
+        const int64_t a = i < j ? i : j, b = i < j ? j : i;
+        const int64_t k = a * (2 * (int64_t)P - a - 1) / 2 + (b - a - 1);
+        const double te = tau_e_pair ? tau_e_pair[k] : tau_e_all;
+        double J0 = 0.0, J1 = 0.0, J2 = 0.0;
+#pragma unroll
+        for (int m = 0; m < 5; ++m) {
+            const double c = cm[5 * k + m];
+            double d = am[5 * k + m] - c;
+            d = d > 0.0 ? d : 0.0;
+            const double E = rates.E[m], Ef = E + 1.0 / (tau_e_mode ? tau_e_mode[5 * k + m] : te);
+            J0 += c * noesy_g(E, 0.0) + d * noesy_g(Ef, 0.0);
+            J1 += c * noesy_g(E, omega) + d * noesy_g(Ef, omega);
+            J2 += c * noesy_g(E, 2.0 * omega) + d * noesy_g(Ef, 2.0 * omega);
+        }
+        R[(int64_t)i * P + j] = q * (6.0 * J2 - J0);
+        rho += q * (J0 + 3.0 * J1 + 6.0 * J2);
+    }
+    const double tot = block_sum_256(rho, red);
+    if (threadIdx.x == 0) R[(int64_t)i * P + i] = tot + (leak ? leak[i] : leak_all);
+}
+
 // sums[i] = sum_j |R_ij|, in a fixed order: a non-finite entry makes its row's sum non-finite
 __global__ __launch_bounds__(256) void k_symm_rowsum(const double *__restrict__ R, int P, double *__restrict__ sums)
 {
@@ -333,9 +373,91 @@ int rates_run(sr_ctx *ctx, sr_stage &st, const double *A6, const double *S2, con
     return sr_launch(ctx, k_noesy_rates, dim3((unsigned)P), dim3(256), 0, a6_d, s2_d, te_d, lk_d, (int)P, omega, tau_c, tau_e_all, leak_all, q, R_dev);
 }
 
+// what the mode-resolved rate entry points refuse, before anything is queued
+int rates_modes_check(sr_ctx *ctx, const char *who, const double *a, const double *c, const double *E, const double *tau_e_pair,
+                      const double *tau_e_mode, const double *leak, int64_t P, double omega, double tau_e_all, double leak_all, double q)
+{
+    SR_REQUIRE(P >= 2, -3, "%s: P=%lld spins; a pair needs two", who, (long long)P);
+    SR_REQUIRE(P <= kMaxP, -3, "%s: P=%lld spins; at most %d", who, (long long)P, kMaxP);
+    const int64_t np = P * (P - 1) / 2;
+    // the staged tables (a, c, tau_e) and R: P <= 32768, below 2^40 bytes
+    const uint64_t bytes = ((uint64_t)np * (10 + (tau_e_mode ? 5 : 0) + (tau_e_pair ? 1 : 0)) + (uint64_t)P + (uint64_t)P * P) * 8u;
+    SR_REQUIRE(bytes <= (uint64_t)ctx->prop.totalGlobalMem, -3, "%s: the tables of %lld pairs and R, %.2f GiB, do not fit the device's %.2f GiB", who,
+               (long long)np, (double)bytes / 1073741824.0, (double)ctx->prop.totalGlobalMem / 1073741824.0);
+    SR_REQUIRE(std::isfinite(omega) && omega >= 0.0, -3, "%s: omega_H = %g rad/s", who, omega);
+    SR_REQUIRE(std::isfinite(q) && q > 0.0, -3, "%s: prefactor %g (finite and > 0)", who, q);
+    for (int m = 0; m < 5; ++m) SR_REQUIRE(std::isfinite(E[m]) && E[m] > 0.0, -3, "%s: E[%d] = %g (finite and > 0)", who, m, E[m]);
+    if (!tau_e_pair && !tau_e_mode) SR_REQUIRE(std::isfinite(tau_e_all) && tau_e_all > 0.0, -3, "%s: tau_e = %g (finite and > 0)", who, tau_e_all);
+    if (!leak) SR_REQUIRE(std::isfinite(leak_all) && leak_all >= 0.0, -3, "%s: leak = %g (finite and >= 0)", who, leak_all);
+    for (int64_t k = 0; k < np; ++k) {
+        for (int m = 0; m < 5; ++m) {
+            const double am = a[5 * k + m], cm = c[5 * k + m];
+            SR_REQUIRE(std::isfinite(am) && am >= 0.0, -3, "%s: a[%lld][%d] = %g (finite and >= 0)", who, (long long)k, m, am);
+            SR_REQUIRE(std::isfinite(cm) && cm >= 0.0, -3, "%s: c[%lld][%d] = %g (finite and >= 0)", who, (long long)k, m, cm);
+            SR_REQUIRE(cm <= am * (1.0 + 1e-6), -3, "%s: c[%lld][%d] = %.17g is above a = %.17g: a plateau lies below its function's start", who,
+                       (long long)k, m, cm, am);
+            if (tau_e_mode)
+                SR_REQUIRE(std::isfinite(tau_e_mode[5 * k + m]) && tau_e_mode[5 * k + m] > 0.0, -3, "%s: tau_e[%lld][%d] = %g (finite and > 0)", who,
+                           (long long)k, m, tau_e_mode[5 * k + m]);
+        }
+        if (tau_e_pair && !tau_e_mode)
+            SR_REQUIRE(std::isfinite(tau_e_pair[k]) && tau_e_pair[k] > 0.0, -3, "%s: tau_e[%lld] = %g (finite and > 0)", who, (long long)k, tau_e_pair[k]);
+    }
+    if (leak)
+        for (int64_t i = 0; i < P; ++i)
+            SR_REQUIRE(std::isfinite(leak[i]) && leak[i] >= 0.0, -3, "%s: leak[%lld] = %g (finite and >= 0)", who, (long long)i, leak[i]);
+    return 0;
+}
+
+// stages the pair and spin arrays (one slot) and queues k_noesy_rates_modes; the caller waits before the host arrays change
+int rates_modes_run(sr_ctx *ctx, sr_stage &st, const double *a, const double *c, const double *E, const double *tau_e_pair, const double *tau_e_mode,
+                    const double *leak, int64_t P, double omega, double tau_e_all, double leak_all, double q, double *R_dev)
+{
+    const size_t np = (size_t)(P * (P - 1) / 2);
+    if (tau_e_mode) tau_e_pair = nullptr;               // the finer table wins
+    st.open(SR_WS_IN0, ((10 + (tau_e_mode ? 5 : 0) + (tau_e_pair ? 1 : 0)) * np + (size_t)P) * sizeof(double));
+    const double *a_d = st.put(a, 5 * np), *c_d = st.put(c, 5 * np), *tp_d = st.put(tau_e_pair, np), *tm_d = st.put(tau_e_mode, 5 * np),
+                 *lk_d = st.put(leak, (size_t)P);
+    if (st.rc) return st.rc;
+    ModeRates rates;
+    for (int m = 0; m < 5; ++m) rates.E[m] = E[m];
+    return sr_launch(ctx, k_noesy_rates_modes, dim3((unsigned)P), dim3(256), 0, a_d, c_d, tp_d, tm_d, lk_d, (int)P, omega, rates, tau_e_all, leak_all, q,
+                     R_dev);
+}
+
 }  // namespace
 
 extern "C" {
+
+int sr_noesy_rates_modes_f64_dev(sr_ctx *ctx, const double *a_host, const double *c_host, const double *E_host, const double *tau_e_pair_host,
+                                 const double *tau_e_mode_host, const double *leak_host, int64_t P, double omega_H, double tau_e, double leak,
+                                 double prefactor, double *R_dev)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(a_host && c_host && E_host && R_dev, -2, "sr_noesy_rates_modes_f64_dev: null pointer");
+    if (int rc = rates_modes_check(ctx, "sr_noesy_rates_modes_f64_dev", a_host, c_host, E_host, tau_e_pair_host, tau_e_mode_host, leak_host, P, omega_H,
+                                   tau_e, leak, prefactor))
+        return rc;
+    sr_stage st(ctx);
+    if (int rc = rates_modes_run(ctx, st, a_host, c_host, E_host, tau_e_pair_host, tau_e_mode_host, leak_host, P, omega_H, tau_e, leak, prefactor, R_dev))
+        return rc;
+    return st.finish();                                 // the caller's arrays are free again when this returns
+}
+
+int sr_noesy_rates_modes_f64(sr_ctx *ctx, const double *a, const double *c, const double *E, const double *tau_e_pair, const double *tau_e_mode,
+                             const double *leak_spin, int64_t P, double omega_H, double tau_e, double leak, double prefactor, double *R)
+{
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(a && c && E && R, -2, "sr_noesy_rates_modes_f64: null pointer");
+    if (int rc = rates_modes_check(ctx, "sr_noesy_rates_modes_f64", a, c, E, tau_e_pair, tau_e_mode, leak_spin, P, omega_H, tau_e, leak, prefactor))
+        return rc;
+    sr_stage st(ctx);
+    double *R_d = st.take<double>(SR_WS_OUT0, (size_t)P * P);
+    if (st.rc) return st.rc;
+    if (int rc = rates_modes_run(ctx, st, a, c, E, tau_e_pair, tau_e_mode, leak_spin, P, omega_H, tau_e, leak, prefactor, R_d)) return rc;
+    st.fetch(R, R_d, (size_t)P * P);
+    return st.finish();
+}
 
 int sr_noesy_rates_f64_dev(sr_ctx *ctx, const double *A6_host, const double *S2_host, const double *tau_e_host, const double *leak_host, int64_t P,
                            double omega_H, double tau_c, double tau_e, double leak, double prefactor, double *R_dev)

@@ -475,7 +475,115 @@ class Context:
         the lags"""
         return int(self.lib.sr_noe_lagged_splits(int(P), int(longest_block), int(B)))
 
+    # ---- the lagged map split into the tumbling modes of an anisotropic tensor (sr_noe_modes.hip) ----
+    @staticmethod
+    def _frame(frame):
+        if frame is None:
+            return None
+        fq = _f64(frame)
+        if fq.shape != (4,):
+            raise ValueError('frame must be a quaternion (w, x, y, z)')
+        return fq
+
+    def noe_modes_dev(self, xyz_ptr, nFrames, nAtoms, index, quat_ptr, block_start, block_len, lags, H_ptr, frame=None, mode=0):
+        """H[b][q][pair][0 .. 5]: the six mode sums of sr_noe_modes.hip (qz qz', dl dl', sym qz dl', yz yz', xz xz', xy xy', each weighted
+        with r(t)^-3 r(t + k)^-3) over the origins t of block b at the lags k = lags[q], of every pair i < j of the atoms `index`, the
+        pair vectors taken into the frame R(frame) R(quat[t]): frame a unit quaternion (w, x, y, z) on the host, None: identity;
+        quat_ptr the device quaternions (nFrames, 4) float64, None: identity.  Into the device array H_ptr (B, K, P (P - 1) / 2, 6)
+        float64 (sr_noe_modes_f32_dev); asynchronous on the context's stream"""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError('index must be 1-D')
+        bs, bl = _windows(block_start, block_len)
+        lg = self._lags(lags)
+        fq = self._frame(frame)
+        check(self.lib.sr_noe_modes_f32_dev(self.h, xyz_ptr, int(nFrames), int(nAtoms), _ptr(idx), idx.size, quat_ptr, _ptr(fq), _ptr(bs),
+                                            _ptr(bl), bs.size, _ptr(lg), lg.size, int(mode), H_ptr), 'sr_noe_modes_f32_dev')
+
+    def noe_modes(self, xyz, index, lags, quat=None, frame=None, block_start=None, block_len=None, mode=0):
+        """The same of host arrays: xyz (nFrames, nAtoms, 3) float32, quat (nFrames, 4) float64 or None -> H (B, K, P (P - 1) / 2, 6)
+        float64; without block tables one block of all frames (sr_noe_modes_f32)"""
+        xyz = _f32(xyz)
+        if xyz.ndim != 3 or xyz.shape[2] != 3:
+            raise ValueError('xyz must be (frames, atoms, 3)')
+        nF, nA, _ = xyz.shape
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError('index must be 1-D')
+        qq = None if quat is None else _f64(quat)
+        if qq is not None and qq.shape != (nF, 4):
+            raise ValueError('quat must be (frames, 4)')
+        if block_start is None:
+            block_start, block_len = [0], [nF]
+        bs, bl = _windows(block_start, block_len)
+        lg = self._lags(lags)
+        fq = self._frame(frame)
+        P = idx.size
+        self.noe_modes_check(nF, nA, idx, bs, bl, lg, frame=fq, mode=mode)   # a result beyond the device's memory is refused before its host array exists
+        H = np.empty((bs.size, lg.size, P * (P - 1) // 2, 6))
+        check(self.lib.sr_noe_modes_f32(self.h, _ptr(xyz), nF, nA, _ptr(idx), P, _ptr(qq), _ptr(fq), _ptr(bs), _ptr(bl), bs.size, _ptr(lg),
+                                        lg.size, int(mode), _ptr(H)), 'sr_noe_modes_f32')
+        return H
+
+    def noe_modes_check(self, nFrames, nAtoms, index, block_start, block_len, lags, frame=None, mode=0):
+        """raises what noe_modes / noe_modes_dev would refuse (-3) for these arguments, the size of the result and the frame quaternion
+        included; allocates and queues nothing (sr_noe_modes_check)"""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError('index must be 1-D')
+        bs, bl = _windows(block_start, block_len)
+        lg = self._lags(lags)
+        fq = self._frame(frame)
+        check(self.lib.sr_noe_modes_check(self.h, int(nFrames), int(nAtoms), _ptr(idx), idx.size, _ptr(bs), _ptr(bl), bs.size, _ptr(lg), lg.size,
+                                          _ptr(fq), int(mode)), 'sr_noe_modes_check')
+
     # ---- NOESY from the dipolar map (sr_noesy.hip) ----
+    @staticmethod
+    def _noesy_modes_args(a, c, E, P, tau_e, leak):
+        a, c, E = _f64(a), _f64(c), _f64(E)
+        P = int(P)
+        npairs = P * (P - 1) // 2
+        if a.shape != (npairs, 5) or c.shape != (npairs, 5) or E.shape != (5,):
+            raise ValueError('a and c must be (P (P - 1) / 2, 5) = (%d, 5) for P = %d spins and E (5)' % (npairs, P))
+        tp_arr = tm_arr = lk_arr = None
+        te = lk = 0.0
+        if np.ndim(tau_e) == 0:
+            te = float(tau_e)
+        else:
+            t = _f64(tau_e)
+            if t.shape == (npairs,):
+                tp_arr = t
+            elif t.shape == (npairs, 5):
+                tm_arr = t
+            else:
+                raise ValueError('tau_e must be a scalar, one value per pair or one per pair and mode')
+        if np.ndim(leak) == 0:
+            lk = float(leak)
+        else:
+            lk_arr = _f64(leak)
+            if lk_arr.shape != (P,):
+                raise ValueError('leak must be a scalar or one value per spin')
+        return a, c, E, P, tp_arr, tm_arr, lk_arr, te, lk
+
+    def noesy_rates_modes_dev(self, a, c, E, P, omega_H, tau_e, leak, prefactor, R_ptr):
+        """The relaxation matrix of P spins under anisotropic tumbling from the host arrays a, c (P (P - 1) / 2, 5), the mode amplitudes
+        at lag 0 and their plateaus in units of <r^-6> (noe.mode_amplitudes, noe.mode_plateau), and the tensor's five rates E (1 / s):
+        J(w) = sum_m [c_m g(E_m, w) + max(a_m - c_m, 0) g(E_m + 1 / tau_e, w)], R_ij = prefactor [6 J(2 omega_H) - J(0)],
+        R_ii = sum_j prefactor [J(0) + 3 J(omega_H) + 6 J(2 omega_H)] + leak_i, into the device array R_ptr (P, P) float64; tau_e a
+        scalar, one per pair or one per pair and mode, leak a scalar or one per spin (sr_noesy_rates_modes_f64_dev); returns when the
+        host arrays are consumed"""
+        a, c, E, P, tp, tm, lk_arr, te, lk = self._noesy_modes_args(a, c, E, P, tau_e, leak)
+        check(self.lib.sr_noesy_rates_modes_f64_dev(self.h, _ptr(a), _ptr(c), _ptr(E), _ptr(tp), _ptr(tm), _ptr(lk_arr), P, float(omega_H), te, lk,
+                                                    float(prefactor), R_ptr), 'sr_noesy_rates_modes_f64_dev')
+
+    def noesy_rates_modes(self, a, c, E, P, omega_H, tau_e, leak, prefactor):
+        """The same with the result on the host: R (P, P) float64 (sr_noesy_rates_modes_f64)"""
+        a, c, E, P, tp, tm, lk_arr, te, lk = self._noesy_modes_args(a, c, E, P, tau_e, leak)
+        R = np.empty((max(P, 0), max(P, 0)))
+        check(self.lib.sr_noesy_rates_modes_f64(self.h, _ptr(a), _ptr(c), _ptr(E), _ptr(tp), _ptr(tm), _ptr(lk_arr), P, float(omega_H), te, lk,
+                                                float(prefactor), _ptr(R)), 'sr_noesy_rates_modes_f64')
+        return R
+
     @staticmethod
     def _noesy_args(A6, S2, P, tau_e, leak):
         A6, S2 = _f64(A6), _f64(S2)

@@ -22,12 +22,23 @@ With lags (dipolar_map(..., lags=...)) the map also holds the dipolar correlatio
 
 from the block sums G_b(k) of csrc/sr_noe_lagged.hip, and from it the internal correlation time of the pair, the Lipari-Szabo integral
 tau_e = int (Cdd - S2) / (1 - S2) dt (tau_e_from_Cdd): what noesy.rate_matrix(..., tau_e='map') takes.  finalize_lagged() is pure numpy.
+
+With modes=True (dipolar_map(..., modes=True, frame=q_F)) the map also holds the split of A6 Cdd(k) into the five tumbling modes of an
+anisotropic rotational diffusion tensor D = (Dx, Dy, Dz), whose principal-axis frame the constant unit quaternion q_F rotates into:
+the six sums H of csrc/sr_noe_modes.hip, which do not depend on D, and from them, host numpy,
+
+    g_m(k), m = 0 .. 4   (mode_amplitudes(H[k], D): sum_m g_m(k) = A6 Cdd(k); rates E_m = _hostmath.D_coefficients_ellipsoid(D))
+    c_m                  (mode_plateau(T, D, q_F): the plateau of g_m, from the map's mean tensor; sum_m c_m = S2 A6)
+    tau_e per mode       (mode_tau_e(result, D): tau_e_from_Cdd of g_m(k) / g_m(0) with the plateau c_m / g_m(0))
+
+what noesy.rate_matrix(..., D=...) takes.
 """
 import warnings
 
 import numpy as np
 
 from . import hip
+from ._hostmath import ellipsoid_R
 from .ired import ired_reduce
 
 # the seven sums per block and pair, in the library's order
@@ -193,7 +204,122 @@ def finalize_lagged(G, block_len, lags, fin, dt=1.0):
                 Cdd_b=Cdd_b, tau_e_b=tau_e_b)
 
 
-def _result(sums, bl, index, G=None, lags=None, dt=1.0):
+def _frame_quat(frame):
+    """None, or the unit quaternion (w, x, y, z) as float64 (4); ValueError for anything else"""
+    if frame is None:
+        return None
+    q = np.asarray(frame, dtype=np.float64)
+    if q.shape != (4,) or not np.all(np.isfinite(q)) or abs(float(q @ q) - 1.0) > 1e-6:
+        raise ValueError('frame must be a unit quaternion (w, x, y, z)')
+    return q
+
+
+def frame_matrix(frame):
+    """R(q_F) (3, 3) of the frame quaternion (normalised), the identity for None: v' = R v is --vecRot's q v q*"""
+    q = _frame_quat(frame)
+    if q is None:
+        return np.eye(3)
+    w, x, y, z = q / np.sqrt(q @ q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _tensor_D(D):
+    D = np.asarray(D, dtype=np.float64)
+    if D.shape != (3,) or not np.all(np.isfinite(D)) or np.any(D <= 0):
+        raise ValueError('D must be (Dx, Dy, Dz), finite and > 0')
+    return D
+
+
+def mode_amplitudes(H, D):
+    """The six mode sums H (..., 6) of csrc/sr_noe_modes.hip (sums or averages: the map is linear) -> the amplitudes (..., 5) of the five
+    rates of D = (Dx, Dy, Dz), in the order of _hostmath.D_coefficients_ellipsoid:
+        g_0 = 3 H3, g_1 = 3 H4, g_2 = 3 H5, g_3 = dd - e, g_4 = dd + e,   dd = 1.125 H0 + 0.375 H1,
+        e = sum_i c_i (3 <q_i q'_i> + 6 sym<q_j q'_k>),   c_i = (D_i - Diso) / (12 R), 0 for the sphere (_hostmath.A_coefficients_ellipsoid),
+    q_i = u_i^2 - 1/3, so that with qz = q_z and dl = q_x - q_y: <q_x q'_x> = (H0 - 2 H2 + H1) / 4, <q_y q'_y> = (H0 + 2 H2 + H1) / 4,
+    <q_z q'_z> = H0, sym<q_x q'_y> = (H0 - H1) / 4, sym<q_x q'_z> = (H2 - H0) / 2, sym<q_y q'_z> = -(H0 + H2) / 2.
+    Their sum is 2.25 H0 + 0.75 H1 + 3 (H3 + H4 + H5) = sum w P2(u . v), the lagged map's G.  For H of one unit vector (u = v, w = 1)
+    they are A_coefficients_ellipsoid(u, D)."""
+    H = np.asarray(H, dtype=np.float64)
+    if H.shape[-1] != 6:
+        raise ValueError('H must be (..., 6), got %s' % (H.shape,))
+    D = _tensor_D(D)
+    R = float(ellipsoid_R(D))
+    s = 1.0 / (12.0 * R) if R > 0.0 else 0.0
+    cx, cy, cz = (D - D.mean()) * s
+    H0, H1, H2, H3, H4, H5 = (H[..., k] for k in range(6))
+    xx, yy, zz = 0.25 * (H0 - 2.0 * H2 + H1), 0.25 * (H0 + 2.0 * H2 + H1), H0
+    xy, xz, yz = 0.25 * (H0 - H1), 0.5 * (H2 - H0), -0.5 * (H0 + H2)
+    dd = 1.125 * H0 + 0.375 * H1
+    e = cx * (3.0 * xx + 6.0 * yz) + cy * (3.0 * yy + 6.0 * xz) + cz * (3.0 * zz + 6.0 * xy)
+    return np.stack((3.0 * H3, 3.0 * H4, 3.0 * H5, dd - e, dd + e), axis=-1)
+
+
+def mode_plateau(T, D, frame=None):
+    """The plateaus c_m (..., 5) of the mode functions from the map's mean tensor T (..., 3, 3) = <d d^T r^-5> (in the frame the map
+    was made in) and the frame quaternion: Qbar = F T F^T - (tr T / 3) 1, F = R(frame), and mode_amplitudes of H0 = Qbar_zz^2,
+    H1 = (Qbar_xx - Qbar_yy)^2, H2 = Qbar_zz (Qbar_xx - Qbar_yy), H3 = Qbar_yz^2, H4 = Qbar_xz^2, H5 = Qbar_xy^2.  sum_m c_m = S2 A6."""
+    T = np.asarray(T, dtype=np.float64)
+    if T.shape[-2:] != (3, 3):
+        raise ValueError('T must be (..., 3, 3), got %s' % (T.shape,))
+    F = frame_matrix(frame)
+    Q = np.einsum('ab,...bc,dc->...ad', F, T, F)
+    tr = (Q[..., 0, 0] + Q[..., 1, 1] + Q[..., 2, 2]) / 3.0
+    qz, dl = Q[..., 2, 2] - tr, Q[..., 0, 0] - Q[..., 1, 1]
+    H = np.stack((qz * qz, dl * dl, qz * dl, Q[..., 1, 2] ** 2, Q[..., 0, 2] ** 2, Q[..., 0, 1] ** 2), axis=-1)
+    return mode_amplitudes(H, D)
+
+
+def mode_tau_e(result, D):
+    """The internal correlation time of every pair and mode (npairs, 5), in the units of the map's dt, of a map made with modes=True and
+    lags beyond 0: tau_e_from_Cdd of g_m(k) / a_m with the plateau c_m / a_m, a_m = g_m(0), c_m = mode_plateau(T, D, frame); 0 for a
+    mode whose a_m - c_m is not positive (no decay to describe)."""
+    if 'H' not in result:
+        raise ValueError('mode_tau_e needs a map made with modes=True (noe.dipolar_map(..., modes=True)): this one holds no H')
+    lg = np.asarray(result['lags'], dtype=np.int64)
+    if lg.size < 2:
+        raise ValueError('mode_tau_e needs a map with lags beyond 0 (noe.dipolar_map(..., modes=True, lags=[0, ...]))')
+    g = mode_amplitudes(result['H'], D)                          # (K, npairs, 5)
+    c = mode_plateau(result['T'], D, result.get('frame'))
+    a = g[0]
+    live = (a > 0) & (a - c > 0)
+    den = np.where(live, a, 1.0)
+    C = np.where(live[None], g / den[None], 1.0).reshape(lg.size, -1)
+    S2 = np.where(live, np.clip(c, 0.0, None) / den, 1.0).reshape(-1)
+    return tau_e_from_Cdd(C, S2, lg, float(result.get('dt', 1.0))).reshape(a.shape)
+
+
+def finalize_modes(Hb, block_len, lags, frame=None):
+    """H_blocks (B, K, npairs, 6) float64 as the library writes it, block_len (B), lags (K) starting at 0 -> dict: H (K, npairs, 6) =
+    sum_b H_b(k) / sum_b (n_b - k), the average over the origins; H_blocks; frame (the quaternion, (1, 0, 0, 0) for None)"""
+    Hb = np.asarray(Hb, dtype=np.float64)
+    lg = _lag_array(lags)
+    bl = np.atleast_1d(np.asarray(block_len, dtype=np.int64))
+    if Hb.ndim != 4 or Hb.shape[:2] != (bl.size, lg.size) or Hb.shape[3] != 6:
+        raise ValueError('H_blocks must be (blocks, lags, pairs, 6), got %s' % (Hb.shape,))
+    terms = bl[:, None] - lg[None, :]
+    if np.any(terms < 1):
+        raise ValueError('every lag must leave a term in every block')
+    q = _frame_quat(frame)
+    return dict(H=Hb.sum(axis=0) / terms.sum(axis=0)[:, None, None].astype(np.float64), H_blocks=Hb,
+                frame=np.array([1.0, 0.0, 0.0, 0.0]) if q is None else q)
+
+
+def _mode_lags(lags, modes, frame):
+    """the lag list of a map with modes (None -> [0]; it must start at 0: a_m is the lag-0 value) and the checked frame quaternion;
+    ValueError before a context is asked for"""
+    if not modes:
+        if frame is not None:
+            raise ValueError('frame belongs to modes=True')
+        return (None if lags is None else _lag_array(lags)), None
+    lg = np.zeros(1, dtype=np.int64) if lags is None else _lag_array(lags)
+    if lg[0] != 0:
+        raise ValueError('a map with modes=True needs lags that start at 0 (the mode amplitudes a_m are the lag-0 values), got %d' % lg[0])
+    return lg, _frame_quat(frame)
+
+
+def _result(sums, bl, index, G=None, lags=None, dt=1.0, Hb=None, mode_lags=None, frame=None):
     index = np.asarray(index)
     out = finalize(sums, bl)
     out['pairs'] = pair_list(index.size)
@@ -201,10 +327,14 @@ def _result(sums, bl, index, G=None, lags=None, dt=1.0):
     out['sums'] = sums
     if G is not None:
         out.update(finalize_lagged(G, bl, lags, out, dt))
+    if Hb is not None:
+        out.update(finalize_modes(Hb, bl, mode_lags, frame))
+        out.setdefault('lags', mode_lags)
+        out.setdefault('dt', float(dt))
     return out
 
 
-def dipolar_map(xyz, index, quat=None, blocks=None, mode=0, ctx=None, lags=None, dt=1.0):
+def dipolar_map(xyz, index, quat=None, blocks=None, mode=0, ctx=None, lags=None, dt=1.0, modes=False, frame=None):
     """The map of every pair of the atoms `index` of the coordinates xyz (frames, atoms, 3) float32.  quat (frames, 4) float64: the
     unit quaternion (w, x, y, z) that takes each frame into the molecule-fixed frame (what ct.superpose_XHvecs(..., want_quat=True)
     returns); None: the lab frame, S2 then includes overall tumbling.  blocks = (block_start, block_len) in frames (ragged lengths
@@ -212,26 +342,35 @@ def dipolar_map(xyz, index, quat=None, blocks=None, mode=0, ctx=None, lags=None,
     Returns finalize()'s dict and pairs (npairs, 2) positions in `index`, index, sums (B, npairs, 7).
     lags: integer lags in frames (strictly increasing, >= 0, below the shortest block, at most 64; log_lags makes such a list), dt the
     time between frames: the dict then also holds finalize_lagged()'s lags, G, Cdd, dCdd, tau_e, dtau_e (tau_e in the units of dt).
-    None: the map alone, as ever."""
+    None: the map alone, as ever.
+    modes=True: also the mode sums of csrc/sr_noe_modes.hip for anisotropic tumbling, in the frame R(frame) R(quat[t]); frame: the
+    constant unit quaternion (w, x, y, z) from the molecule-fixed frame into the diffusion tensor's principal-axis frame (--vecRot's
+    convention), None: identity.  The lags must start at 0 (None: [0]; ValueError otherwise, before a context is asked for).  The
+    dict then also holds finalize_modes()'s H (K, npairs, 6), H_blocks (B, K, npairs, 6) and frame, with lags and dt."""
+    lg, fq = _mode_lags(lags, modes, frame)
     xyz = np.ascontiguousarray(xyz, dtype=np.float32)
     bs, bl = _blocks(blocks, xyz.shape[0])
     c = _ctx(ctx)
-    if lags is None:
+    if lg is None:
         return _result(c.noe_pairs(xyz, index, quat=quat, block_start=bs, block_len=bl, mode=mode), bl, index)
-    lg = _lag_array(lags)
     if xyz.ndim == 3:
-        c.noe_lagged_check(xyz.shape[0], xyz.shape[1], index, bs, bl, lg, mode)     # the lags' refusals before the map is computed
+        if lags is not None:
+            c.noe_lagged_check(xyz.shape[0], xyz.shape[1], index, bs, bl, lg, mode)     # the lags' refusals before the map is computed
+        if modes:
+            c.noe_modes_check(xyz.shape[0], xyz.shape[1], index, bs, bl, lg, frame=fq, mode=mode)
     sums = c.noe_pairs(xyz, index, quat=quat, block_start=bs, block_len=bl, mode=mode)
-    G = c.noe_lagged(xyz, index, lg, quat=quat, block_start=bs, block_len=bl, mode=mode)
-    return _result(sums, bl, index, G, lg, dt)
+    G = c.noe_lagged(xyz, index, lg, quat=quat, block_start=bs, block_len=bl, mode=mode) if lags is not None else None
+    Hb = c.noe_modes(xyz, index, lg, quat=quat, frame=fq, block_start=bs, block_len=bl, mode=mode) if modes else None
+    return _result(sums, bl, index, G, lg, dt, Hb, lg, fq)
 
 
-def dipolar_map_superposed(xyz, ref_xyz, fit_indices, index, blocks=None, mode=0, ctx=None, lags=None, dt=1.0):
+def dipolar_map_superposed(xyz, ref_xyz, fit_indices, index, blocks=None, mode=0, ctx=None, lags=None, dt=1.0, modes=False, frame=None):
     """dipolar_map in the frame of the per-frame least-squares superposition onto ref_xyz (atoms, 3) over fit_indices, the front end's
     (Context.xh_vectors / ct.superpose_XHvecs): the coordinates are uploaded once, the front end's kernel leaves its quaternions on
-    the device and the map reads them there.  The result also holds quat (frames, 4).  lags, dt: as in dipolar_map; the lagged sums
-    read the same device coordinates and quaternions."""
+    the device and the map reads them there.  The result also holds quat (frames, 4).  lags, dt, modes, frame: as in dipolar_map; the
+    lagged and the mode sums read the same device coordinates and quaternions."""
     import torch
+    mlg, fq = _mode_lags(lags, modes, frame)
     c = _ctx(ctx)
     xyz = np.ascontiguousarray(xyz, dtype=np.float32)
     if xyz.ndim != 3 or xyz.shape[2] != 3:
@@ -243,6 +382,8 @@ def dipolar_map_superposed(xyz, ref_xyz, fit_indices, index, blocks=None, mode=0
     lg = None if lags is None else _lag_array(lags)
     if lg is not None:
         c.noe_lagged_check(nF, nA, index, bs, bl, lg, mode)
+    if modes:
+        c.noe_modes_check(nF, nA, index, bs, bl, mlg, frame=fq, mode=mode)
     dev = torch.device('cuda', c.device)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore', UserWarning)    # a read-only array: it is only read
@@ -257,8 +398,14 @@ def dipolar_map_superposed(xyz, ref_xyz, fit_indices, index, blocks=None, mode=0
         G_d = torch.empty((bs.size, lg.size, n_pairs(index.size)), dtype=torch.float64, device=dev)
         torch.cuda.synchronize(dev)
         c.noe_lagged_dev(xyz_d.data_ptr(), nF, nA, index, quat_d.data_ptr(), bs, bl, lg, G_d.data_ptr(), mode=mode)
+    H_d = None
+    if modes:
+        H_d = torch.empty((bs.size, mlg.size, n_pairs(index.size), 6), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        c.noe_modes_dev(xyz_d.data_ptr(), nF, nA, index, quat_d.data_ptr(), bs, bl, mlg, H_d.data_ptr(), frame=fq, mode=mode)
     c.sync()
-    out = _result(sums_d.cpu().numpy(), bl, index, None if G_d is None else G_d.cpu().numpy(), lg, dt)
+    out = _result(sums_d.cpu().numpy(), bl, index, None if G_d is None else G_d.cpu().numpy(), lg, dt,
+                  None if H_d is None else H_d.cpu().numpy(), mlg, fq)
     out['quat'] = quat_d.cpu().numpy()
     return out
 

@@ -18,11 +18,22 @@ sum_groups, write_noesy and read_noesy are host numpy.
 A per-pair tau_e comes from the map itself when it was made with lags (noe.dipolar_map(..., lags=...), csrc/sr_noe_lagged.hip):
 tau_e='map' takes map_result['tau_e'], in seconds, floored at TAU_E_FLOOR.
 
-Not done: anisotropic tumbling (the map keeps no pair orientation in the diffusion frame), other nuclei than protons, more than one GPU.
+Anisotropic tumbling: with D = (Dx, Dy, Dz) in 1 / s in the place of tau_c, and a map made with modes=True in the tensor's
+principal-axis frame (noe.dipolar_map(..., modes=True, frame=q_F), csrc/sr_noe_modes.hip), the five rates E_m of the tensor
+(_hostmath.D_coefficients_ellipsoid) and per pair the mode amplitudes a_m (lag 0) and plateaus c_m (noe.mode_amplitudes,
+noe.mode_plateau; sum_m a_m = A6, sum_m c_m = S2 A6), g(x, y) = x / (x^2 + y^2):
+
+    J(w)     = sum_m [ c_m g(E_m, w) + max(a_m - c_m, 0) g(E_m + 1 / tau_e, w) ]
+    sigma_ij = q [6 J(2 w_H) - J(0)]      rho_ij = q [J(0) + 3 J(w_H) + 6 J(2 w_H)]
+
+With Dx = Dy = Dz = 1 / (6 tau_c) this is the formula above.  tau_e='modes': every mode of every pair with its own tau_e (noe.mode_tau_e).
+
+Not done: other nuclei than protons, more than one GPU.
 """
 import numpy as np
 
-from . import hip
+from . import hip, noe
+from ._hostmath import D_coefficients_ellipsoid
 from .noe import n_pairs, pair_list
 from .spectral_densities import GAMMA
 
@@ -67,33 +78,77 @@ def map_tau_e(map_result):
     return np.maximum(np.asarray(map_result['tau_e'], dtype=np.float64), TAU_E_FLOOR)
 
 
-def _tau_e(map_result, tau_e):
-    """tau_e as the library takes it: a scalar or one value per pair in seconds; 'map': map_tau_e(map_result)"""
+def _tau_e(map_result, tau_e, D=None):
+    """tau_e as the library takes it: a scalar or one value per pair in seconds; 'map': map_tau_e(map_result); with D also one value
+    per pair and mode, or 'modes': mode_tau_e(map_result, D)"""
     if not isinstance(tau_e, str):
         return tau_e
+    if tau_e == 'modes' and D is not None:
+        return mode_tau_e(map_result, D)
     if tau_e != 'map':
-        raise ValueError("tau_e must be a time in seconds, one per pair, or 'map'")
+        raise ValueError("tau_e must be a time in seconds, one per pair, or 'map'" + (" or 'modes'" if D is not None else ''))
     return map_tau_e(map_result)
 
 
-def _rates_dev(c, map_result, field_MHz, tau_c, tau_e, leak, unit):
+def mode_tau_e(map_result, D):
+    """the per-pair, per-mode tau_e (npairs, 5) of a map made with modes=True, lags beyond 0 and dt in seconds per frame as the rate
+    matrix takes it: noe.mode_tau_e, floored at TAU_E_FLOOR (a mode whose a_m - c_m is not positive gets the floor)"""
+    return np.maximum(noe.mode_tau_e(map_result, D), TAU_E_FLOOR)
+
+
+def _check_tumbling(map_result, tau_c, D):
+    """tau_c or D, not both; with D the map must hold the mode sums.  ValueError before a context is asked for"""
+    if D is None:
+        if tau_c is None:
+            raise ValueError('give the overall correlation time tau_c, or the diffusion tensor D = (Dx, Dy, Dz)')
+        return None
+    if tau_c is not None:
+        raise ValueError('tau_c and D both describe the tumbling; with D, tau_c must be None')
+    D = np.asarray(D, dtype=np.float64)
+    if D.shape != (3,) or not np.all(np.isfinite(D)) or np.any(D <= 0):
+        raise ValueError('D must be (Dx, Dy, Dz) in 1 / s, finite and > 0')
+    if 'H' not in map_result:
+        raise ValueError('D needs a map made with modes=True (noe.dipolar_map(..., modes=True, frame=...)): this one holds no H')
+    return D
+
+
+def mode_inputs(map_result, D):
+    """(a, c, E) as the library takes them: a (npairs, 5) = noe.mode_amplitudes of the map's H at lag 0, c (npairs, 5) =
+    noe.mode_plateau of its mean tensor in its frame, E (5) the tensor's rates.  Rounding is taken out as S2 is clipped in the
+    isotropic form: a below 0 becomes 0, c is clipped to [0, a] (exactly, c_m <= a_m: a squared mean is below the mean square)."""
+    a = np.maximum(noe.mode_amplitudes(np.asarray(map_result['H'])[0], D), 0.0)
+    c = np.clip(noe.mode_plateau(map_result['T'], D, map_result.get('frame')), 0.0, a)
+    return a, c, D_coefficients_ellipsoid(D)
+
+
+def _rates_dev(c, map_result, field_MHz, tau_c, tau_e, leak, unit, D=None):
     """R as a torch tensor on the context's device"""
     P = _n_spins(map_result)
-    tau_e = _tau_e(map_result, tau_e)
+    tau_e = _tau_e(map_result, tau_e, D)
     torch, dev = _torch_dev(c)
     R_d = torch.empty((P, P), dtype=torch.float64, device=dev)
     torch.cuda.synchronize(dev)
-    c.noesy_rates_dev(map_result['A6'], map_result['S2'], P, omega_H(field_MHz), tau_c, tau_e, leak, prefactor(unit), R_d.data_ptr())
+    if D is not None:
+        a, cm, E = mode_inputs(map_result, D)
+        c.noesy_rates_modes_dev(a, cm, E, P, omega_H(field_MHz), tau_e, leak, prefactor(unit), R_d.data_ptr())
+    else:
+        c.noesy_rates_dev(map_result['A6'], map_result['S2'], P, omega_H(field_MHz), tau_c, tau_e, leak, prefactor(unit), R_d.data_ptr())
     return R_d
 
 
-def rate_matrix(map_result, field_MHz, tau_c, tau_e=1e-10, leak=0.0, unit='nm', ctx=None):
+def rate_matrix(map_result, field_MHz, tau_c=None, tau_e=1e-10, leak=0.0, unit='nm', ctx=None, D=None):
     """R (P, P) float64 of the P spins of a map: noe.dipolar_map's dict, or anything that holds A6, S2 (P (P - 1) / 2 each, pairs in
     the order of noe.pair_index) and index (P).  field_MHz: the proton frequency; tau_c, tau_e in seconds, tau_e a scalar or one value
     per pair, or 'map': the map's own tau_e (a map made with lags and dt in seconds per frame), floored at TAU_E_FLOOR; leak in 1 / s, a
     scalar or one value per spin; unit: the unit of the coordinates the map was taken from, 'nm' (MDTraj's,
-    the default), 'A', or metres per unit.  R_ij = sigma_ij, R_ii = sum_j rho_ij + leak_i, exactly symmetric."""
-    tau_e = _tau_e(map_result, tau_e)           # a map without tau_e is refused before a context is asked for
+    the default), 'A', or metres per unit.  R_ij = sigma_ij, R_ii = sum_j rho_ij + leak_i, exactly symmetric.
+    D = (Dx, Dy, Dz) in 1 / s: anisotropic tumbling, in the place of tau_c (which must then be None), on a map made with modes=True in
+    the tensor's principal-axis frame; tau_e may then also be one value per pair and mode (npairs, 5), or 'modes' (mode_tau_e)."""
+    D = _check_tumbling(map_result, tau_c, D)
+    tau_e = _tau_e(map_result, tau_e, D)        # a map without tau_e is refused before a context is asked for
+    if D is not None:
+        a, cm, E = mode_inputs(map_result, D)
+        return _ctx(ctx).noesy_rates_modes(a, cm, E, _n_spins(map_result), omega_H(field_MHz), tau_e, leak, prefactor(unit))
     return _ctx(ctx).noesy_rates(map_result['A6'], map_result['S2'], _n_spins(map_result), omega_H(field_MHz), tau_c, tau_e, leak,
                                  prefactor(unit))
 
@@ -129,14 +184,15 @@ def intensities(R, mixing_times, ctx=None):
     return _expm_dev(c, R_d, tau).cpu().numpy()
 
 
-def noesy(map_result, mixing_times, field_MHz, tau_c, tau_e=1e-10, leak=0.0, unit='nm', ctx=None):
+def noesy(map_result, mixing_times, field_MHz, tau_c=None, tau_e=1e-10, leak=0.0, unit='nm', ctx=None, D=None):
     """rate_matrix and intensities in one go, R staying on the device between the two.  Returns dict(R (P, P), sigma (npairs) the
     cross-relaxation rates in the map's pair order, rho (P) the auto-relaxation rates R_ii (leak included), A (n_tau, P, P),
-    mixing_times, index, pairs)."""
-    tau_e = _tau_e(map_result, tau_e)           # a map without tau_e is refused before a context is asked for
+    mixing_times, index, pairs).  tau_c or D, and tau_e: as in rate_matrix."""
+    D = _check_tumbling(map_result, tau_c, D)
+    tau_e = _tau_e(map_result, tau_e, D)        # a map without tau_e is refused before a context is asked for
     c = _ctx(ctx)
     tau = _mixing(mixing_times)
-    R_d = _rates_dev(c, map_result, field_MHz, tau_c, tau_e, leak, unit)
+    R_d = _rates_dev(c, map_result, field_MHz, tau_c, tau_e, leak, unit, D)
     A = _expm_dev(c, R_d, tau).cpu().numpy()
     R = R_d.cpu().numpy()
     P = R.shape[0]

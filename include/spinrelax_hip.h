@@ -398,7 +398,7 @@ int sr_noe_pairs_check(sr_ctx *, int64_t nFrames, int64_t nAtoms, const int32_t 
 int sr_noe_tile(void);          /* T: atoms per tile side (tests aim at tile edges) */
 int sr_noe_frame_batch(void);   /* frames per LDS stage of k_noe_pairs */
 
-/* ---- the all-pairs dipolar map at a few chosen lags (sr_noe_lagged.hip; beyond the reference) ----------------------------------------
+/* ---- the all-pairs dipolar map at a few chosen lags (sr_noe.hip; beyond the reference) ----------------------------------------
  * For the same atoms, blocks and pair order, and K lags k = lags[0] < lags[1] < ...:
  *     G[b][q][k(i, j)] = sum over the origins t of block b with t + k inside the block of
  *                        [1.5 (d'(t) . d'(t + k))^2 / (r(t)^2 r(t + k)^2) - 0.5] r(t)^-3 r(t + k)^-3,      d'(t) = R(quat[t]) d(t)
@@ -410,7 +410,7 @@ int sr_noe_frame_batch(void);   /* frames per LDS stage of k_noe_pairs */
  *   mode 1: the same sequence in float64 with 1 / sqrt.
  * k_noe_lagged: one workgroup per (block, lag, frame split, tile pair), tiles and threads as in k_noe_pairs, two windows of
  * sr_noe_frame_batch() frames in LDS (the origins and the frames one lag later).  A frame split owns a range of origins, runs of
- * ceil((n_b - k) / S); k_noe_lagged_finish adds the S partial tiles in the order s = 0 .. S-1.  No atomics: equal input gives
+ * ceil((n_b - k) / S); k_noe_finish adds the S partial tiles in the order s = 0 .. S-1.  No atomics: equal input gives
  * bit-equal G.  S = sr_noe_lagged_splits(P, longest block, B) is the map's split count and does not depend on the lags: a lag has the
  * same bits alone and in any list.  With S > 1 the partial tiles are a work area of about S times the bytes of G.
  *   lags_host (K) int32: HOST array, like the index and the block tables; G: DEVICE (B, K, P (P - 1) / 2) float64.  Asynchronous on
@@ -429,7 +429,7 @@ int sr_noe_lagged_check(sr_ctx *, int64_t nFrames, int64_t nAtoms, const int32_t
                         const int64_t *block_len, int B, const int32_t *lags, int K, int mode);
 int sr_noe_lagged_splits(int64_t P, int64_t longest_block, int B);   /* S of such a call (tests aim at S > 1); 0 for a bad shape */
 
-/* ---- the lagged map split into the five tumbling modes of an anisotropic diffusion tensor (sr_noe_modes.hip; beyond the reference) ----
+/* ---- the lagged map split into the five tumbling modes of an anisotropic diffusion tensor (sr_noe.hip; beyond the reference) ----
  * For the same atoms, blocks, lags and pair order as sr_noe_lagged_*, six sums per (block, lag, pair).  With F = R(frame_quat), the
  * constant rotation into the principal-axis frame of the diffusion tensor, d"(t) = F R(quat[t]) d(t), u = d"(t) / r(t),
  * v = d"(t + k) / r(t + k), w = r(t)^-3 r(t + k)^-3, qz(u) = u_z^2 - 1/3 and dl(u) = u_x^2 - u_y^2:
@@ -442,7 +442,7 @@ int sr_noe_lagged_splits(int64_t P, int64_t longest_block, int B);   /* S of suc
  *           of v likewise; g = ri si; g3 = (g g) g; the six terms (a0 b0) g3, (a1 b1) g3, (0.5 fma(a0, b1, a1 b0)) g3,
  *           ((uy uz) (vy vz)) g3, ((ux uz) (vx vz)) g3, ((ux uy) (vx vy)) g3; float32 partial sums of at most 8 origins, then float64.
  *   mode 1: the same sequence in float64 with 1 / sqrt.
- * k_noe_modes and k_noe_modes_finish: the workgroups, tiles, windows, origin ranges and the split count S = sr_noe_lagged_splits(...)
+ * k_noe_modes and k_noe_finish: the workgroups, tiles, windows, origin ranges and the split count S = sr_noe_lagged_splits(...)
  * of k_noe_lagged; the partial tiles are added in the order s = 0 .. S-1.  No atomics: equal input gives bit-equal H, and a lag has
  * the same bits alone and in any list.  With S > 1 the partial tiles are a work area of about S times the bytes of H.
  *   quat: DEVICE (nFrames, 4) float64 or NULL (R(quat[t]) = 1); frame_quat_host: HOST (4) float64 (w, x, y, z), a unit quaternion

@@ -1,5 +1,6 @@
-// Developer tool: sweeps the pure host helpers of the lagged dipolar map (spinrelax_amd/csrc/sr_noe_host.h: split rule, lag list check,
-// origin ranges, byte counts, grid sizes, and those of its mode-resolved form: byte counts, grid sizes, frame matrix) against plain restatements of their definitions, under the sanitizers.  No HIP, no GPU:
+// Developer tool: sweeps the pure host helpers of the all-pairs dipolar map, its lagged and its mode-resolved form
+// (spinrelax_amd/csrc/sr_noe_host.h: split rule, lag list check, origin ranges, byte counts, grid sizes, frame matrix) against plain
+// restatements of their definitions, under the sanitizers.  No HIP, no GPU:
 //
 //     c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I spinrelax_amd/csrc \
 //         scripts/dev/noe_lagged_host_sweep.cpp -o /tmp/noe_lagged_host_sweep && /tmp/noe_lagged_host_sweep
@@ -53,6 +54,18 @@ int main()
                 }
                 EXPECT(next == no, "origins(len %lld, k %lld, S %d) end at %lld", (long long)len, (long long)k, S, (long long)next);
             }
+    // the map is lag 0: its frames in runs of ceil(len / S), [min(s per, len), min((s + 1) per, len))
+    for (int64_t len = 1; len <= 700; len += (len < 70 ? 1 : 37))
+        for (int S : {1, 2, 3, 5, 7, 16, 255, 256}) {
+            const int64_t per = (len + S - 1) / S;
+            for (int s = 0; s < S; ++s) {
+                int64_t lo, hi;
+                noe_lag_origins(len, 0, S, s, lo, hi);
+                const int64_t a = (int64_t)s * per, b = a + per;
+                EXPECT(lo == (a < len ? a : len) && hi == (b < len ? b : len), "map frames(len %lld, S %d, s %d) = [%lld, %lld)", (long long)len,
+                       S, s, (long long)lo, (long long)hi);
+            }
+        }
     {   // at the largest values a call can carry
         int64_t lo, hi;
         noe_lag_origins(INT64_MAX / 512, 0, 256, 255, lo, hi);
@@ -94,7 +107,7 @@ int main()
                 for (int S : {1, 2, 256}) {
                     const int64_t nT = (P + kNoeTile - 1) / kNoeTile, NP = nT * (nT + 1) / 2, npairs = P * (P - 1) / 2;
                     unsigned __int128 out, part;
-                    noe_lagged_bytes(B, K, npairs, S, NP, out, part);
+                    noe_bytes(B, K, 1, npairs, S, NP, out, part);
                     unsigned __int128 want_out = 8, want_part = S > 1 ? 8 * 1024 : 0;
                     want_out *= (unsigned __int128)B; want_out *= (unsigned __int128)K; want_out *= (unsigned __int128)npairs;
                     want_part *= (unsigned __int128)B; want_part *= (unsigned __int128)K; want_part *= (unsigned __int128)S;
@@ -102,12 +115,21 @@ int main()
                     EXPECT(out == want_out && part == want_part, "bytes(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
                     const unsigned __int128 wg = (unsigned __int128)B * K * S * NP, fin = (unsigned __int128)B * K * NP * 4;
                     const bool ok = wg < ((unsigned __int128)1 << 31) && fin < ((unsigned __int128)1 << 31);
-                    EXPECT(noe_lagged_grid_ok(B, K, S, NP) == ok, "grid(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
+                    EXPECT(noe_grid_ok(B, K, S, NP) == ok, "grid(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
                     // the mode-resolved map: six sums per pair, the same grids
                     unsigned __int128 mout, mpart;
-                    noe_modes_bytes(B, K, npairs, S, NP, mout, mpart);
+                    noe_bytes(B, K, kNoeModeSums, npairs, S, NP, mout, mpart);
                     EXPECT(mout == 6 * want_out && mpart == 6 * want_part, "modes bytes(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
-                    EXPECT(noe_modes_grid_ok(B, K, S, NP) == ok, "modes grid(B %d, K %d, P %lld, S %d)", B, K, (long long)P, S);
+                    if (K > 1) continue;
+                    // the map: one lag, seven sums per pair: 56 bytes per pair, 7 x 1024 float64 per partial tile
+                    unsigned __int128 pout, ppart, want_pout = 56, want_ppart = S > 1 ? 7 * 8 * 1024 : 0;
+                    want_pout *= (unsigned __int128)B; want_pout *= (unsigned __int128)npairs;
+                    want_ppart *= (unsigned __int128)B; want_ppart *= (unsigned __int128)S; want_ppart *= (unsigned __int128)NP;
+                    noe_bytes(B, 1, kNoeMapSums, npairs, S, NP, pout, ppart);
+                    EXPECT(pout == want_pout && ppart == want_ppart, "map bytes(B %d, P %lld, S %d)", B, (long long)P, S);
+                    const unsigned __int128 pwg = (unsigned __int128)B * S * NP, pfin = (unsigned __int128)B * NP * 4;
+                    EXPECT(noe_grid_ok(B, 1, S, NP) == (pwg < ((unsigned __int128)1 << 31) && pfin < ((unsigned __int128)1 << 31)),
+                           "map grid(B %d, P %lld, S %d)", B, (long long)P, S);
                 }
 
     // ---- the frame matrix: the identity for NULL; orthogonal with determinant 1, R(q) v = q (0, v) q*, R(-q) = R(q), a scaling

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer timing of the lagged dipolar map kernels (k_noe_lagged + k_noe_lagged_finish, sr_noe_lagged_f32_dev, mode 0, with
+"""Developer timing of the lagged dipolar map kernels (k_noe_lagged + k_noe_finish, sr_noe_lagged_f32_dev, mode 0, with
 per-frame quaternions) against the map itself (k_noe_pairs + k_noe_finish, sr_noe_pairs_f32_dev) on the same coordinates in the same
 run: 512 atoms x 100 000 frames as one block, one lag (K = 1, the lag LAG1, default 16) and twelve (noe.log_lags(2048, 12)).
 

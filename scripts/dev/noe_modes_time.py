@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Developer timing of the mode-resolved lagged dipolar map (k_noe_modes + k_noe_modes_finish, sr_noe_modes_f32_dev, mode 0, with
-per-frame quaternions and a frame quaternion) against the lagged map (k_noe_lagged + k_noe_lagged_finish, sr_noe_lagged_f32_dev) on
+"""Developer timing of the mode-resolved lagged dipolar map (k_noe_modes + k_noe_finish, sr_noe_modes_f32_dev, mode 0, with
+per-frame quaternions and a frame quaternion) against the lagged map (k_noe_lagged + k_noe_finish, sr_noe_lagged_f32_dev) on
 the same coordinates, quaternions and lags in the same run: 512 atoms x 100 000 frames as one block, one lag (K = 1, the lag LAG1,
 default 16) and twelve (noe.log_lags(2048, 12)).
 

@@ -204,7 +204,7 @@ SIGNATURES = {
     'sr_noe_pairs_check': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int]),
     'sr_noe_tile': (c_int, []),
     'sr_noe_frame_batch': (c_int, []),
-    # the map at chosen lags (sr_noe_lagged.hip): (ctx, xyz, nFrames, nAtoms, index_host, P, quat, block_start_host, block_len_host, B, lags_host,
+    # the map at chosen lags (sr_noe.hip): (ctx, xyz, nFrames, nAtoms, index_host, P, quat, block_start_host, block_len_host, B, lags_host,
     # K, mode, G), xyz / quat / G on the device or all three on the host; the check takes no xyz, quat and G
     'sr_noe_lagged_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                       c_int, c_void_p]),
@@ -212,7 +212,7 @@ SIGNATURES = {
                                   c_int, c_void_p]),
     'sr_noe_lagged_check': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int]),
     'sr_noe_lagged_splits': (c_int, [c_int64, c_int64, c_int]),
-    # the lagged map split into tumbling modes (sr_noe_modes.hip): (ctx, xyz, nFrames, nAtoms, index_host, P, quat, frame_quat_host | NULL,
+    # the lagged map split into tumbling modes (sr_noe.hip): (ctx, xyz, nFrames, nAtoms, index_host, P, quat, frame_quat_host | NULL,
     # block_start_host, block_len_host, B, lags_host, K, mode, H), xyz / quat / H on the device or all three on the host; the check
     # takes no xyz, quat and H: (ctx, nFrames, nAtoms, index, P, block_start, block_len, B, lags, K, frame_quat | NULL, mode)
     'sr_noe_modes_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libspinrelax_hip.so')
 SOURCES = ['sr_core.hip', 'sr_pack.hip', 'sr_ct.hip', 'sr_ct_direct.hip', 'sr_ct_cross.hip', 'sr_ct_dipolar.hip', 'sr_ct_dipolar_cross.hip', 'sr_ct_fft64.hip', 'sr_ct_rfft64.hip', 'sr_ct32.hip', 'sr_ct_long.hip', 'sr_ct_cross_long.hip', 'sr_ct_dipolar_long.hip',
-           'sr_vechist.hip', 'sr_ired.hip', 'sr_ired_modes.hip', 'sr_noe.hip', 'sr_noe_lagged.hip', 'sr_noe_modes.hip', 'sr_noesy.hip', 'sr_fit.hip', 'sr_relax.hip', 'sr_dq.hip', 'sr_traj.hip', 'sr_vectors.hip', 'sr_textio.hip']
+           'sr_vechist.hip', 'sr_ired.hip', 'sr_ired_modes.hip', 'sr_noe.hip', 'sr_noesy.hip', 'sr_fit.hip', 'sr_relax.hip', 'sr_dq.hip', 'sr_traj.hip', 'sr_vectors.hip', 'sr_textio.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']
 # Kernels 0 and 1, no SLP vectoriser.  sr_ct_direct.hip: it packs the FMAs of the C(t) inner loop into v_pk_fma_f32, whose operand

@@ -1,7 +1,6 @@
 // sr_noe_host.h -- the pure host arithmetic of the all-pairs dipolar map, its lagged form and the lagged form's split into tumbling
-// modes (sr_noe.hip, sr_noe_lagged.hip, sr_noe_modes.hip): split rule, lag list check, origin ranges, byte counts, grid sizes, frame
-// matrix.  Nothing here needs HIP: scripts/dev/noe_lagged_host_sweep.cpp compiles
-// this header alone, with -fsanitize=address,undefined, and sweeps it.
+// modes (sr_noe.hip): split rule, lag list check, origin ranges, byte counts, grid sizes, quaternion and frame matrix.  Nothing here
+// needs HIP: scripts/dev/noe_lagged_host_sweep.cpp compiles this header alone, with -fsanitize=address,undefined, and sweeps it.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -15,7 +14,9 @@
 
 constexpr int kNoeTile = 32;                        // atoms per tile side
 constexpr int kNoeMaxLags = 64;                     // lags per call of the lagged map
-constexpr int kNoeLagPart = kNoeTile * kNoeTile;    // float64 values of one partial tile of the lagged map
+constexpr int kNoeLagPart = kNoeTile * kNoeTile;    // pairs of a tile: float64 values of one sum of one partial tile
+constexpr int kNoeMapSums = 7;                      // sums per (block, pair) of the map: r^-6 and the six tensor components
+constexpr int kNoeModeSums = 6;                     // sums per (block, lag, pair) of the mode-resolved map: H0 .. H5
 
 // the split rule: a function of the shape alone: about sixteen workgroups per CU of a 256-CU part (three fit a SIMD at a time: several
 // rounds of them keep the last round short), each with at least 128 frames, at most 256 partial tiles to add
@@ -66,35 +67,33 @@ SR_NOE_HD void noe_lag_origins(int64_t len, int64_t k, int S, int s, int64_t &lo
     if (hi > no) hi = no;
 }
 
-// bytes of the result G (B, K, npairs) float64 and of the partial tiles (B, K, S, NP, T x T) float64 (none with S = 1).
-// P <= 2^20: npairs < 2^39, NP < 2^29, B < 2^31, K <= 64, S <= 256: inside 128 bits by a wide margin
-inline void noe_lagged_bytes(int B, int K, int64_t npairs, int S, int64_t NP, unsigned __int128 &out_bytes, unsigned __int128 &part_bytes)
+// bytes of the result (B, K, npairs, M) float64 and of the partial tiles (B, K, S, NP, M, T x T) float64 (none with S = 1): the map is
+// K = 1, M = 7, its lagged form M = 1, the mode-resolved form M = kNoeModeSums.
+// P <= 2^20: npairs < 2^39, NP < 2^29, B < 2^31, K <= 64, S <= 256, M <= 7: inside 128 bits by a wide margin
+inline void noe_bytes(int B, int K, int M, int64_t npairs, int S, int64_t NP, unsigned __int128 &out_bytes, unsigned __int128 &part_bytes)
 {
-    out_bytes = (unsigned __int128)B * (unsigned)K * (unsigned __int128)npairs * 8u;
-    part_bytes = S > 1 ? (unsigned __int128)B * (unsigned)K * (unsigned)S * (unsigned __int128)NP * (kNoeLagPart * 8u) : 0;
+    out_bytes = (unsigned __int128)B * (unsigned)K * (unsigned)M * (unsigned __int128)npairs * 8u;
+    part_bytes = S > 1 ? (unsigned __int128)B * (unsigned)K * (unsigned)S * (unsigned)M * (unsigned __int128)NP * (kNoeLagPart * 8u) : 0;
 }
 
-// k_noe_lagged takes B K S NP workgroups, k_noe_lagged_finish 4 B K NP: both in one dimension, below 2^31
-inline bool noe_lagged_grid_ok(int B, int K, int S, int64_t NP)
+// the tile kernels take B K S NP workgroups in one dimension, below 2^31.  4 B K NP was the grid of the lagged map's own finish
+// kernel and stays a refusal; k_noe_finish (4 M B K NP workgroups) runs only with S > 1, that is B NP < 4096 (noe_ksplit)
+inline bool noe_grid_ok(int B, int K, int S, int64_t NP)
 {
     const unsigned __int128 bk = (unsigned __int128)B * (unsigned)K * (unsigned __int128)NP, lim = (unsigned __int128)1 << 31;
     return bk * (unsigned)S < lim && bk * 4u < lim;
 }
 
-// ---- the mode-resolved lagged map (sr_noe_modes.hip) ----
-constexpr int kNoeModeSums = 6;                     // sums per (block, lag, pair): H0 .. H5
-
-// bytes of the result H (B, K, npairs, 6) float64 and of the partial tiles (B, K, S, NP, 6, T x T) float64 (none with S = 1): the
-// lagged map's, six times; inside 128 bits by the same margin
-inline void noe_modes_bytes(int B, int K, int64_t npairs, int S, int64_t NP, unsigned __int128 &out_bytes, unsigned __int128 &part_bytes)
+// the unit quaternion (w, x, y, z) -> R(q), row-major 3 x 3 in float64, each entry as written: no contraction
+SR_NOE_HD void noe_quat_matrix(double w, double x, double y, double z, double *A)
 {
-    noe_lagged_bytes(B, K, npairs, S, NP, out_bytes, part_bytes);
-    out_bytes *= (unsigned)kNoeModeSums;
-    part_bytes *= (unsigned)kNoeModeSums;
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    A[0] = 1 - 2 * (y * y + z * z); A[1] = 2 * (x * y - w * z);     A[2] = 2 * (x * z + w * y);
+    A[3] = 2 * (x * y + w * z);     A[4] = 1 - 2 * (x * x + z * z); A[5] = 2 * (y * z - w * x);
+    A[6] = 2 * (x * z - w * y);     A[7] = 2 * (y * z + w * x);     A[8] = 1 - 2 * (x * x + y * y);
 }
-
-// k_noe_modes takes B K S NP workgroups, k_noe_modes_finish 4 B K NP (a thread adds the six sums of one pair): the lagged map's grids
-inline bool noe_modes_grid_ok(int B, int K, int S, int64_t NP) { return noe_lagged_grid_ok(B, K, S, NP); }
 
 // the frame quaternion (w, x, y, z) -> F = R(q / |q|), row-major 3 x 3 in float64; 0, or -3 with the reason in msg: a component that
 // is not finite, a squared norm farther than 1e-6 from 1.  NULL: the identity.
@@ -115,9 +114,6 @@ inline int noe_frame_matrix(const double *q, double *F, char *msg, size_t nmsg)
         return -3;
     }
     const double n = 1.0 / std::sqrt(n2);
-    const double w = q[0] * n, x = q[1] * n, y = q[2] * n, z = q[3] * n;
-    F[0] = 1 - 2 * (y * y + z * z); F[1] = 2 * (x * y - w * z);     F[2] = 2 * (x * z + w * y);
-    F[3] = 2 * (x * y + w * z);     F[4] = 1 - 2 * (x * x + z * z); F[5] = 2 * (y * z - w * x);
-    F[6] = 2 * (x * z - w * y);     F[7] = 2 * (y * z + w * x);     F[8] = 1 - 2 * (x * x + y * y);
+    noe_quat_matrix(q[0] * n, q[1] * n, q[2] * n, q[3] * n, F);
     return 0;
 }

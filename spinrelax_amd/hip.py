@@ -355,61 +355,7 @@ class Context:
         check(self.lib.sr_ired_mode_ct_f32_dev(self.h, soa_ptr, int(Npad), int(nV), _ptr(ws), _ptr(wl), ws.size, coef_ptr, int(K),
                                                int(n_lags), Cm_ptr), 'sr_ired_mode_ct_f32_dev')
 
-    # ---- all-pairs dipolar map (sr_noe.hip) ----
-    def noe_pairs_dev(self, xyz_ptr, nFrames, nAtoms, index, quat_ptr, block_start, block_len, sums_ptr, mode=0):
-        """Block sums of r^-6 and d'_a d'_b r^-5 (xx, yy, zz, xy, xz, yz) of every pair i < j of the atoms `index` from the device
-        coordinates xyz_ptr (nFrames, nAtoms, 3) float32, d' = d rotated by the frame's unit quaternion of the device array quat_ptr
-        (nFrames, 4) float64 (None: identity), into the device array sums_ptr (B, P (P - 1) / 2, 7) float64, pairs in the order of
-        noe.pair_index (sr_noe_pairs_f32_dev); asynchronous on the context's stream"""
-        idx = np.ascontiguousarray(index, dtype=np.int32)
-        if idx.ndim != 1:
-            raise ValueError('index must be 1-D')
-        bs, bl = _windows(block_start, block_len)
-        check(self.lib.sr_noe_pairs_f32_dev(self.h, xyz_ptr, int(nFrames), int(nAtoms), _ptr(idx), idx.size, quat_ptr, _ptr(bs), _ptr(bl),
-                                            bs.size, int(mode), sums_ptr), 'sr_noe_pairs_f32_dev')
-
-    def noe_pairs(self, xyz, index, quat=None, block_start=None, block_len=None, mode=0):
-        """The same of host arrays: xyz (nFrames, nAtoms, 3) float32, quat (nFrames, 4) float64 or None -> sums (B, P (P - 1) / 2, 7)
-        float64; without block tables one block of all frames (sr_noe_pairs_f32)"""
-        xyz = _f32(xyz)
-        if xyz.ndim != 3 or xyz.shape[2] != 3:
-            raise ValueError('xyz must be (frames, atoms, 3)')
-        nF, nA, _ = xyz.shape
-        idx = np.ascontiguousarray(index, dtype=np.int32)
-        if idx.ndim != 1:
-            raise ValueError('index must be 1-D')
-        qq = None if quat is None else _f64(quat)
-        if qq is not None and qq.shape != (nF, 4):
-            raise ValueError('quat must be (frames, 4)')
-        if block_start is None:
-            block_start, block_len = [0], [nF]
-        bs, bl = _windows(block_start, block_len)
-        P = idx.size
-        self.noe_pairs_check(nF, nA, idx, bs, bl, mode)      # a map beyond the device's memory is refused before its host array exists
-        sums = np.empty((bs.size, P * (P - 1) // 2, 7))
-        check(self.lib.sr_noe_pairs_f32(self.h, _ptr(xyz), nF, nA, _ptr(idx), P, _ptr(qq), _ptr(bs), _ptr(bl), bs.size, int(mode),
-                                        _ptr(sums)), 'sr_noe_pairs_f32')
-        return sums
-
-    def noe_pairs_check(self, nFrames, nAtoms, index, block_start, block_len, mode=0):
-        """raises what noe_pairs / noe_pairs_dev would refuse (-3) for these arguments, the size of the result included; allocates and
-        queues nothing (sr_noe_pairs_check)"""
-        idx = np.ascontiguousarray(index, dtype=np.int32)
-        if idx.ndim != 1:
-            raise ValueError('index must be 1-D')
-        bs, bl = _windows(block_start, block_len)
-        check(self.lib.sr_noe_pairs_check(self.h, int(nFrames), int(nAtoms), _ptr(idx), idx.size, _ptr(bs), _ptr(bl), bs.size, int(mode)),
-              'sr_noe_pairs_check')
-
-    def noe_tile(self):
-        """atoms per tile side of k_noe_pairs"""
-        return int(self.lib.sr_noe_tile())
-
-    def noe_frame_batch(self):
-        """frames per LDS stage of k_noe_pairs"""
-        return int(self.lib.sr_noe_frame_batch())
-
-    # ---- the dipolar map at chosen lags (sr_noe_lagged.hip) ----
+    # ---- all-pairs dipolar map, at chosen lags, split into tumbling modes (sr_noe.hip) ----
     @staticmethod
     def _lags(lags):
         lg = np.ascontiguousarray(np.atleast_1d(lags))
@@ -421,61 +367,6 @@ class Context:
             raise ValueError('lags must fit 32 bits')
         return np.ascontiguousarray(lg, dtype=np.int32)
 
-    def noe_lagged_dev(self, xyz_ptr, nFrames, nAtoms, index, quat_ptr, block_start, block_len, lags, G_ptr, mode=0):
-        """G[b][q][pair] = sum over the origins t of block b of [1.5 cos^2 - 0.5] r(t)^-3 r(t + k)^-3 at the lags k = lags[q] (strictly
-        increasing, >= 0, below the shortest block; at most 64), cos the angle between d'(t) and d'(t + k), of every pair i < j of the
-        atoms `index` from the device coordinates xyz_ptr (nFrames, nAtoms, 3) float32 and the device quaternions quat_ptr (nFrames,
-        4) float64 (None: identity), into the device array G_ptr (B, K, P (P - 1) / 2) float64, pairs in the order of noe.pair_index
-        (sr_noe_lagged_f32_dev); asynchronous on the context's stream"""
-        idx = np.ascontiguousarray(index, dtype=np.int32)
-        if idx.ndim != 1:
-            raise ValueError('index must be 1-D')
-        bs, bl = _windows(block_start, block_len)
-        lg = self._lags(lags)
-        check(self.lib.sr_noe_lagged_f32_dev(self.h, xyz_ptr, int(nFrames), int(nAtoms), _ptr(idx), idx.size, quat_ptr, _ptr(bs), _ptr(bl),
-                                             bs.size, _ptr(lg), lg.size, int(mode), G_ptr), 'sr_noe_lagged_f32_dev')
-
-    def noe_lagged(self, xyz, index, lags, quat=None, block_start=None, block_len=None, mode=0):
-        """The same of host arrays: xyz (nFrames, nAtoms, 3) float32, quat (nFrames, 4) float64 or None -> G (B, K, P (P - 1) / 2)
-        float64; without block tables one block of all frames (sr_noe_lagged_f32)"""
-        xyz = _f32(xyz)
-        if xyz.ndim != 3 or xyz.shape[2] != 3:
-            raise ValueError('xyz must be (frames, atoms, 3)')
-        nF, nA, _ = xyz.shape
-        idx = np.ascontiguousarray(index, dtype=np.int32)
-        if idx.ndim != 1:
-            raise ValueError('index must be 1-D')
-        qq = None if quat is None else _f64(quat)
-        if qq is not None and qq.shape != (nF, 4):
-            raise ValueError('quat must be (frames, 4)')
-        if block_start is None:
-            block_start, block_len = [0], [nF]
-        bs, bl = _windows(block_start, block_len)
-        lg = self._lags(lags)
-        P = idx.size
-        self.noe_lagged_check(nF, nA, idx, bs, bl, lg, mode)    # a result beyond the device's memory is refused before its host array exists
-        G = np.empty((bs.size, lg.size, P * (P - 1) // 2))
-        check(self.lib.sr_noe_lagged_f32(self.h, _ptr(xyz), nF, nA, _ptr(idx), P, _ptr(qq), _ptr(bs), _ptr(bl), bs.size, _ptr(lg), lg.size,
-                                         int(mode), _ptr(G)), 'sr_noe_lagged_f32')
-        return G
-
-    def noe_lagged_check(self, nFrames, nAtoms, index, block_start, block_len, lags, mode=0):
-        """raises what noe_lagged / noe_lagged_dev would refuse (-3) for these arguments, the size of the result included; allocates and
-        queues nothing (sr_noe_lagged_check)"""
-        idx = np.ascontiguousarray(index, dtype=np.int32)
-        if idx.ndim != 1:
-            raise ValueError('index must be 1-D')
-        bs, bl = _windows(block_start, block_len)
-        lg = self._lags(lags)
-        check(self.lib.sr_noe_lagged_check(self.h, int(nFrames), int(nAtoms), _ptr(idx), idx.size, _ptr(bs), _ptr(bl), bs.size, _ptr(lg), lg.size,
-                                           int(mode)), 'sr_noe_lagged_check')
-
-    def noe_lagged_splits(self, P, longest_block, B=1):
-        """frame splits S of a lagged map of P atoms over B blocks, the longest of longest_block frames: the map's own rule, whatever
-        the lags"""
-        return int(self.lib.sr_noe_lagged_splits(int(P), int(longest_block), int(B)))
-
-    # ---- the lagged map split into the tumbling modes of an anisotropic tensor (sr_noe_modes.hip) ----
     @staticmethod
     def _frame(frame):
         if frame is None:
@@ -485,40 +376,118 @@ class Context:
             raise ValueError('frame must be a quaternion (w, x, y, z)')
         return fq
 
-    def noe_modes_dev(self, xyz_ptr, nFrames, nAtoms, index, quat_ptr, block_start, block_len, lags, H_ptr, frame=None, mode=0):
-        """H[b][q][pair][0 .. 5]: the six mode sums of sr_noe_modes.hip (qz qz', dl dl', sym qz dl', yz yz', xz xz', xy xy', each weighted
-        with r(t)^-3 r(t + k)^-3) over the origins t of block b at the lags k = lags[q], of every pair i < j of the atoms `index`, the
-        pair vectors taken into the frame R(frame) R(quat[t]): frame a unit quaternion (w, x, y, z) on the host, None: identity;
-        quat_ptr the device quaternions (nFrames, 4) float64, None: identity.  Into the device array H_ptr (B, K, P (P - 1) / 2, 6)
-        float64 (sr_noe_modes_f32_dev); asynchronous on the context's stream"""
+    @staticmethod
+    def _noe_index(index):
         idx = np.ascontiguousarray(index, dtype=np.int32)
         if idx.ndim != 1:
             raise ValueError('index must be 1-D')
-        bs, bl = _windows(block_start, block_len)
+        return idx
+
+    @classmethod
+    def _noe_host(cls, xyz, index, quat, block_start, block_len):
+        """the host arrays of a noe_* call as the library takes them: xyz (frames, atoms, 3) float32, index 1-D int32, quat (frames, 4)
+        float64 or None, the block table int64 (without one: one block of all frames)"""
+        xyz = _f32(xyz)
+        if xyz.ndim != 3 or xyz.shape[2] != 3:
+            raise ValueError('xyz must be (frames, atoms, 3)')
+        idx = cls._noe_index(index)
+        qq = None if quat is None else _f64(quat)
+        if qq is not None and qq.shape != (xyz.shape[0], 4):
+            raise ValueError('quat must be (frames, 4)')
+        if block_start is None:
+            block_start, block_len = [0], [xyz.shape[0]]
+        return (xyz, idx, qq) + _windows(block_start, block_len)
+
+    def noe_pairs_dev(self, xyz_ptr, nFrames, nAtoms, index, quat_ptr, block_start, block_len, sums_ptr, mode=0):
+        """Block sums of r^-6 and d'_a d'_b r^-5 (xx, yy, zz, xy, xz, yz) of every pair i < j of the atoms `index` from the device
+        coordinates xyz_ptr (nFrames, nAtoms, 3) float32, d' = d rotated by the frame's unit quaternion of the device array quat_ptr
+        (nFrames, 4) float64 (None: identity), into the device array sums_ptr (B, P (P - 1) / 2, 7) float64, pairs in the order of
+        noe.pair_index (sr_noe_pairs_f32_dev); asynchronous on the context's stream"""
+        idx, (bs, bl) = self._noe_index(index), _windows(block_start, block_len)
+        check(self.lib.sr_noe_pairs_f32_dev(self.h, xyz_ptr, int(nFrames), int(nAtoms), _ptr(idx), idx.size, quat_ptr, _ptr(bs), _ptr(bl),
+                                            bs.size, int(mode), sums_ptr), 'sr_noe_pairs_f32_dev')
+
+    def noe_pairs(self, xyz, index, quat=None, block_start=None, block_len=None, mode=0):
+        """The same of host arrays: xyz (nFrames, nAtoms, 3) float32, quat (nFrames, 4) float64 or None -> sums (B, P (P - 1) / 2, 7)
+        float64; without block tables one block of all frames (sr_noe_pairs_f32)"""
+        xyz, idx, qq, bs, bl = self._noe_host(xyz, index, quat, block_start, block_len)
+        nF, nA, P = xyz.shape[0], xyz.shape[1], idx.size
+        self.noe_pairs_check(nF, nA, idx, bs, bl, mode)      # a map beyond the device's memory is refused before its host array exists
+        sums = np.empty((bs.size, P * (P - 1) // 2, 7))
+        check(self.lib.sr_noe_pairs_f32(self.h, _ptr(xyz), nF, nA, _ptr(idx), P, _ptr(qq), _ptr(bs), _ptr(bl), bs.size, int(mode),
+                                        _ptr(sums)), 'sr_noe_pairs_f32')
+        return sums
+
+    def noe_pairs_check(self, nFrames, nAtoms, index, block_start, block_len, mode=0):
+        """raises what noe_pairs / noe_pairs_dev would refuse (-3) for these arguments, the size of the result included; allocates and
+        queues nothing (sr_noe_pairs_check)"""
+        idx, (bs, bl) = self._noe_index(index), _windows(block_start, block_len)
+        check(self.lib.sr_noe_pairs_check(self.h, int(nFrames), int(nAtoms), _ptr(idx), idx.size, _ptr(bs), _ptr(bl), bs.size, int(mode)),
+              'sr_noe_pairs_check')
+
+    def noe_tile(self):
+        """atoms per tile side of k_noe_pairs"""
+        return int(self.lib.sr_noe_tile())
+
+    def noe_frame_batch(self):
+        """frames per LDS stage of k_noe_pairs"""
+        return int(self.lib.sr_noe_frame_batch())
+
+    # the dipolar map at chosen lags
+    def noe_lagged_dev(self, xyz_ptr, nFrames, nAtoms, index, quat_ptr, block_start, block_len, lags, G_ptr, mode=0):
+        """G[b][q][pair] = sum over the origins t of block b of [1.5 cos^2 - 0.5] r(t)^-3 r(t + k)^-3 at the lags k = lags[q] (strictly
+        increasing, >= 0, below the shortest block; at most 64), cos the angle between d'(t) and d'(t + k), of every pair i < j of the
+        atoms `index` from the device coordinates xyz_ptr (nFrames, nAtoms, 3) float32 and the device quaternions quat_ptr (nFrames,
+        4) float64 (None: identity), into the device array G_ptr (B, K, P (P - 1) / 2) float64, pairs in the order of noe.pair_index
+        (sr_noe_lagged_f32_dev); asynchronous on the context's stream"""
+        idx, (bs, bl) = self._noe_index(index), _windows(block_start, block_len)
         lg = self._lags(lags)
-        fq = self._frame(frame)
+        check(self.lib.sr_noe_lagged_f32_dev(self.h, xyz_ptr, int(nFrames), int(nAtoms), _ptr(idx), idx.size, quat_ptr, _ptr(bs), _ptr(bl),
+                                             bs.size, _ptr(lg), lg.size, int(mode), G_ptr), 'sr_noe_lagged_f32_dev')
+
+    def noe_lagged(self, xyz, index, lags, quat=None, block_start=None, block_len=None, mode=0):
+        """The same of host arrays: xyz (nFrames, nAtoms, 3) float32, quat (nFrames, 4) float64 or None -> G (B, K, P (P - 1) / 2)
+        float64; without block tables one block of all frames (sr_noe_lagged_f32)"""
+        xyz, idx, qq, bs, bl = self._noe_host(xyz, index, quat, block_start, block_len)
+        lg = self._lags(lags)
+        nF, nA, P = xyz.shape[0], xyz.shape[1], idx.size
+        self.noe_lagged_check(nF, nA, idx, bs, bl, lg, mode)    # a result beyond the device's memory is refused before its host array exists
+        G = np.empty((bs.size, lg.size, P * (P - 1) // 2))
+        check(self.lib.sr_noe_lagged_f32(self.h, _ptr(xyz), nF, nA, _ptr(idx), P, _ptr(qq), _ptr(bs), _ptr(bl), bs.size, _ptr(lg), lg.size,
+                                         int(mode), _ptr(G)), 'sr_noe_lagged_f32')
+        return G
+
+    def noe_lagged_check(self, nFrames, nAtoms, index, block_start, block_len, lags, mode=0):
+        """raises what noe_lagged / noe_lagged_dev would refuse (-3) for these arguments, the size of the result included; allocates and
+        queues nothing (sr_noe_lagged_check)"""
+        idx, (bs, bl) = self._noe_index(index), _windows(block_start, block_len)
+        lg = self._lags(lags)
+        check(self.lib.sr_noe_lagged_check(self.h, int(nFrames), int(nAtoms), _ptr(idx), idx.size, _ptr(bs), _ptr(bl), bs.size, _ptr(lg), lg.size,
+                                           int(mode)), 'sr_noe_lagged_check')
+
+    def noe_lagged_splits(self, P, longest_block, B=1):
+        """frame splits S of a lagged map of P atoms over B blocks, the longest of longest_block frames: the map's own rule, whatever
+        the lags"""
+        return int(self.lib.sr_noe_lagged_splits(int(P), int(longest_block), int(B)))
+
+    # the lagged map split into the tumbling modes of an anisotropic tensor
+    def noe_modes_dev(self, xyz_ptr, nFrames, nAtoms, index, quat_ptr, block_start, block_len, lags, H_ptr, frame=None, mode=0):
+        """H[b][q][pair][0 .. 5]: the six mode sums of k_noe_modes (sr_noe.hip: qz qz', dl dl', sym qz dl', yz yz', xz xz', xy xy', each
+        weighted with r(t)^-3 r(t + k)^-3) over the origins t of block b at the lags k = lags[q], of every pair i < j of the atoms `index`,
+        the pair vectors taken into the frame R(frame) R(quat[t]): frame a unit quaternion (w, x, y, z) on the host, None: identity;
+        quat_ptr the device quaternions (nFrames, 4) float64, None: identity.  Into the device array H_ptr (B, K, P (P - 1) / 2, 6)
+        float64 (sr_noe_modes_f32_dev); asynchronous on the context's stream"""
+        idx, (bs, bl) = self._noe_index(index), _windows(block_start, block_len)
+        lg, fq = self._lags(lags), self._frame(frame)
         check(self.lib.sr_noe_modes_f32_dev(self.h, xyz_ptr, int(nFrames), int(nAtoms), _ptr(idx), idx.size, quat_ptr, _ptr(fq), _ptr(bs),
                                             _ptr(bl), bs.size, _ptr(lg), lg.size, int(mode), H_ptr), 'sr_noe_modes_f32_dev')
 
     def noe_modes(self, xyz, index, lags, quat=None, frame=None, block_start=None, block_len=None, mode=0):
         """The same of host arrays: xyz (nFrames, nAtoms, 3) float32, quat (nFrames, 4) float64 or None -> H (B, K, P (P - 1) / 2, 6)
         float64; without block tables one block of all frames (sr_noe_modes_f32)"""
-        xyz = _f32(xyz)
-        if xyz.ndim != 3 or xyz.shape[2] != 3:
-            raise ValueError('xyz must be (frames, atoms, 3)')
-        nF, nA, _ = xyz.shape
-        idx = np.ascontiguousarray(index, dtype=np.int32)
-        if idx.ndim != 1:
-            raise ValueError('index must be 1-D')
-        qq = None if quat is None else _f64(quat)
-        if qq is not None and qq.shape != (nF, 4):
-            raise ValueError('quat must be (frames, 4)')
-        if block_start is None:
-            block_start, block_len = [0], [nF]
-        bs, bl = _windows(block_start, block_len)
-        lg = self._lags(lags)
-        fq = self._frame(frame)
-        P = idx.size
+        xyz, idx, qq, bs, bl = self._noe_host(xyz, index, quat, block_start, block_len)
+        lg, fq = self._lags(lags), self._frame(frame)
+        nF, nA, P = xyz.shape[0], xyz.shape[1], idx.size
         self.noe_modes_check(nF, nA, idx, bs, bl, lg, frame=fq, mode=mode)   # a result beyond the device's memory is refused before its host array exists
         H = np.empty((bs.size, lg.size, P * (P - 1) // 2, 6))
         check(self.lib.sr_noe_modes_f32(self.h, _ptr(xyz), nF, nA, _ptr(idx), P, _ptr(qq), _ptr(fq), _ptr(bs), _ptr(bl), bs.size, _ptr(lg),
@@ -528,12 +497,8 @@ class Context:
     def noe_modes_check(self, nFrames, nAtoms, index, block_start, block_len, lags, frame=None, mode=0):
         """raises what noe_modes / noe_modes_dev would refuse (-3) for these arguments, the size of the result and the frame quaternion
         included; allocates and queues nothing (sr_noe_modes_check)"""
-        idx = np.ascontiguousarray(index, dtype=np.int32)
-        if idx.ndim != 1:
-            raise ValueError('index must be 1-D')
-        bs, bl = _windows(block_start, block_len)
-        lg = self._lags(lags)
-        fq = self._frame(frame)
+        idx, (bs, bl) = self._noe_index(index), _windows(block_start, block_len)
+        lg, fq = self._lags(lags), self._frame(frame)
         check(self.lib.sr_noe_modes_check(self.h, int(nFrames), int(nAtoms), _ptr(idx), idx.size, _ptr(bs), _ptr(bl), bs.size, _ptr(lg), lg.size,
                                           _ptr(fq), int(mode)), 'sr_noe_modes_check')
 

@@ -20,12 +20,12 @@ With lags (dipolar_map(..., lags=...)) the map also holds the dipolar correlatio
 
     Cdd(k) = <P2(u(t) . u(t + k)) r(t)^-3 r(t + k)^-3> / A6       (calculate_Ct_dipolar's normalisation: Cdd(0) = 1, plateau S2)
 
-from the block sums G_b(k) of csrc/sr_noe_lagged.hip, and from it the internal correlation time of the pair, the Lipari-Szabo integral
+from the block sums G_b(k) of csrc/sr_noe.hip, and from it the internal correlation time of the pair, the Lipari-Szabo integral
 tau_e = int (Cdd - S2) / (1 - S2) dt (tau_e_from_Cdd): what noesy.rate_matrix(..., tau_e='map') takes.  finalize_lagged() is pure numpy.
 
 With modes=True (dipolar_map(..., modes=True, frame=q_F)) the map also holds the split of A6 Cdd(k) into the five tumbling modes of an
 anisotropic rotational diffusion tensor D = (Dx, Dy, Dz), whose principal-axis frame the constant unit quaternion q_F rotates into:
-the six sums H of csrc/sr_noe_modes.hip, which do not depend on D, and from them, host numpy,
+the six sums H of csrc/sr_noe.hip, which do not depend on D, and from them, host numpy,
 
     g_m(k), m = 0 .. 4   (mode_amplitudes(H[k], D): sum_m g_m(k) = A6 Cdd(k); rates E_m = _hostmath.D_coefficients_ellipsoid(D))
     c_m                  (mode_plateau(T, D, q_F): the plateau of g_m, from the map's mean tensor; sum_m c_m = S2 A6)
@@ -233,7 +233,7 @@ def _tensor_D(D):
 
 
 def mode_amplitudes(H, D):
-    """The six mode sums H (..., 6) of csrc/sr_noe_modes.hip (sums or averages: the map is linear) -> the amplitudes (..., 5) of the five
+    """The six mode sums H (..., 6) of csrc/sr_noe.hip (sums or averages: the map is linear) -> the amplitudes (..., 5) of the five
     rates of D = (Dx, Dy, Dz), in the order of _hostmath.D_coefficients_ellipsoid:
         g_0 = 3 H3, g_1 = 3 H4, g_2 = 3 H5, g_3 = dd - e, g_4 = dd + e,   dd = 1.125 H0 + 0.375 H1,
         e = sum_i c_i (3 <q_i q'_i> + 6 sym<q_j q'_k>),   c_i = (D_i - Diso) / (12 R), 0 for the sphere (_hostmath.A_coefficients_ellipsoid),
@@ -343,7 +343,7 @@ def dipolar_map(xyz, index, quat=None, blocks=None, mode=0, ctx=None, lags=None,
     lags: integer lags in frames (strictly increasing, >= 0, below the shortest block, at most 64; log_lags makes such a list), dt the
     time between frames: the dict then also holds finalize_lagged()'s lags, G, Cdd, dCdd, tau_e, dtau_e (tau_e in the units of dt).
     None: the map alone, as ever.
-    modes=True: also the mode sums of csrc/sr_noe_modes.hip for anisotropic tumbling, in the frame R(frame) R(quat[t]); frame: the
+    modes=True: also the mode sums of csrc/sr_noe.hip for anisotropic tumbling, in the frame R(frame) R(quat[t]); frame: the
     constant unit quaternion (w, x, y, z) from the molecule-fixed frame into the diffusion tensor's principal-axis frame (--vecRot's
     convention), None: identity.  The lags must start at 0 (None: [0]; ValueError otherwise, before a context is asked for).  The
     dict then also holds finalize_modes()'s H (K, npairs, 6), H_blocks (B, K, npairs, 6) and frame, with lags and dt."""

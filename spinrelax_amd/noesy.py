@@ -15,11 +15,11 @@ q = 0.1 (mu0 / 4 pi)^2 hbar^2 gamma_H^4 / u^6 with u the length of one coordinat
 are computed on the MI355X (csrc/sr_noesy.hip) and nowhere else: without a GPU every function that needs them raises SpinRelaxHipError.
 sum_groups, write_noesy and read_noesy are host numpy.
 
-A per-pair tau_e comes from the map itself when it was made with lags (noe.dipolar_map(..., lags=...), csrc/sr_noe_lagged.hip):
+A per-pair tau_e comes from the map itself when it was made with lags (noe.dipolar_map(..., lags=...), csrc/sr_noe.hip):
 tau_e='map' takes map_result['tau_e'], in seconds, floored at TAU_E_FLOOR.
 
 Anisotropic tumbling: with D = (Dx, Dy, Dz) in 1 / s in the place of tau_c, and a map made with modes=True in the tensor's
-principal-axis frame (noe.dipolar_map(..., modes=True, frame=q_F), csrc/sr_noe_modes.hip), the five rates E_m of the tensor
+principal-axis frame (noe.dipolar_map(..., modes=True, frame=q_F), csrc/sr_noe.hip), the five rates E_m of the tensor
 (_hostmath.D_coefficients_ellipsoid) and per pair the mode amplitudes a_m (lag 0) and plateaus c_m (noe.mode_amplitudes,
 noe.mode_plateau; sum_m a_m = A6, sum_m c_m = S2 A6), g(x, y) = x / (x^2 + y^2):
 

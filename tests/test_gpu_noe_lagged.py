@@ -1,5 +1,5 @@
 """
-GPU tests of the lagged all-pairs dipolar map (csrc/sr_noe_lagged.hip) and of everything above it: hip.Context.noe_lagged,
+GPU tests of the lagged all-pairs dipolar map (csrc/sr_noe.hip) and of everything above it: hip.Context.noe_lagged,
 noe.dipolar_map(..., lags=...), noesy's tau_e='map' and the --noeLags / --noesyTauEMap flags of scripts/calculate-Ct-from-traj.py.
 
 Oracle (in this file): the definition in float64 numpy on the same float32 coordinates and the same float64 quaternions:
@@ -13,7 +13,7 @@ units from the origin; the oracle asserts a minimum pair distance of 0.05).
 Bars, u = 2^-24, absolute on G, first order in u.
 Mode 1 (float64 throughout): both sides add n <= 1000 float64 terms of magnitude <= r^-3 s^-3 in different orders, each term after
   some twenty float64 roundings: by the argument of tests/test_gpu_noe.py below 2 * 1020 * 1.1e-16 = 2.3e-13 of W.  BAR1 = 1e-12 W.
-Mode 0 (float32 per pair, frame and lag), the sequence of csrc/sr_noe_lagged.hip; r, s the two distances, |x| <= 1, |p| <= 1:
+Mode 0 (float32 per pair, frame and lag), the sequence of csrc/sr_noe.hip; r, s the two distances, |x| <= 1, |p| <= 1:
   d_a, e_a = differences of float32 coordinates                       u each (relative)
   r2 = fma(dz, dz, fma(dy, dy, dx dx)), s2 likewise                    2u from d, 3 roundings: 5u
   ri = v_rsq_f32(r2), si                                               2.5u from r2, 1 ulp <= 2u: 4.5u

@@ -1,5 +1,5 @@
 """
-GPU tests of NOESY under anisotropic tumbling: the mode-resolved lagged map (csrc/sr_noe_modes.hip), the mode-resolved rate kernel
+GPU tests of NOESY under anisotropic tumbling: the mode-resolved lagged map (csrc/sr_noe.hip), the mode-resolved rate kernel
 (k_noesy_rates_modes, csrc/sr_noesy.hip) and everything above them: hip.Context.noe_modes / noesy_rates_modes,
 noe.dipolar_map(..., modes=True, frame=...), noesy.rate_matrix(..., D=...) and --noesyD of scripts/calculate-Ct-from-traj.py.
 
@@ -13,7 +13,7 @@ Inputs: make_body of tests/test_gpu_noe.py, scrambled as in tests/test_gpu_noe_l
 
 Bars, u = 2^-24, absolute on H per component, first order in u.
 Mode 1 (float64 throughout): the sum-order argument of tests/test_gpu_noe_lagged.py, every term of magnitude <= w: BAR1 = 1e-12 W.
-Mode 0 (float32 per pair, frame and lag), the sequence of csrc/sr_noe_modes.hip; |u_a| <= 1:
+Mode 0 (float32 per pair, frame and lag), the sequence of csrc/sr_noe.hip; |u_a| <= 1:
   d'_a (the matrix F R(q) formed in float64, rounded to float32 once: its rows have unit length)     5u r absolute, ri 4.5u relative
                                                                                      (tests/test_gpu_noe_lagged.py)
   u_a = d'_a ri                                5u + 4.5u |u_a| + 1 rounding: 10.5u absolute; v_a likewise
@@ -145,7 +145,7 @@ def split_case():
 @pytest.mark.parametrize('mode', (0, 1))
 def test_frame_splits(ctx, mode):
     """P = 33, 1000 frames: seven frame splits (asserted > 1: otherwise the case is vacuous), partial tiles added by
-    k_noe_modes_finish; lag 129 reads frames of the next split, lag 700 leaves splits of 43 origins"""
+    k_noe_finish; lag 129 reads frames of the next split, lag 700 leaves splits of 43 origins"""
     xyz, quat, lags, ref, W = split_case()
     assert ctx.noe_lagged_splits(33, 1000, 1) > 1
     got = ctx.noe_modes(xyz, np.arange(33), lags, quat=quat, frame=Q_F, mode=mode)

@@ -1,5 +1,5 @@
 """
-CPU tests of the lagged dipolar map's host side (spinrelax_amd/noe.py, noesy.py, csrc/sr_noe_lagged.hip's symbols): the Lipari-Szabo
+CPU tests of the lagged dipolar map's host side (spinrelax_amd/noe.py, noesy.py, csrc/sr_noe.hip's symbols): the Lipari-Szabo
 integral tau_e_from_Cdd on a known decay and against a plain loop, log_lags, the _noeMapCt.dat round trip, Cdd and dCdd assembled from
 hand-made G with ragged blocks, the tau_e='map' floor and refusal, the script's flag refusals before any GPU work, and the ctypes
 signatures.  Nothing here touches a GPU.

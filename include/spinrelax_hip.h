@@ -661,6 +661,46 @@ int sr_vectors_ct_dipolar_cross_long_f32(sr_ctx *, sr_vectors *, const float *di
                                          const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode, double *P0, double *dP0,
                                          double *Ct, double *dCt, double *reff6);
 
+/* ---- bond-vector correlation function split into the five tumbling modes of an anisotropic diffusion tensor (sr_ct_modes.hip; beyond
+ * the reference) ----
+ * The reference's anisotropic J(w) multiplies a static histogram of the vector's orientation in the principal-axis frame by one internal
+ * C(t) shared by the five modes: exact only if the internal motion decays every mode alike.  This is sr_noe_modes' definition with
+ * w = 1, on the Palmer chunk table of kernel 1 (R chunks of F frames, chunk_start_host as there) and at every lag of a chunk.  With
+ * F = R(frame_quat), the constant rotation into the principal-axis frame of the tensor (--vecRot's convention), u(t) = F v(t) / |v(t)|:
+ *     s0 = u_z^2 - 1/3,  s1 = u_x^2 - u_y^2,  s2 = u_y u_z,  s3 = u_x u_z,  s4 = u_x u_y
+ * and per chunk r and lag k = 0 .. L = F / 2, <.> = sum_t / (F - k) over the origins t with t + k inside the chunk, s' taken at t + k:
+ *     H0 = <s0 s0'>,  H1 = <s1 s1'>,  H2 = <s0 s1' + s1 s0'> / 2,  H3 = <s2 s2'>,  H4 = <s3 s3'>,  H5 = <s4 s4'>
+ * the order of sr_noe_modes.  They do not depend on the tensor: one H serves any D (spinrelax_amd/noe.py: mode_amplitudes;
+ * spinrelax_amd/modes.py: amplitudes, J, relaxation).  2.25 H0 + 0.75 H1 + 3 (H3 + H4 + H5) is kernel 1's C(k) whatever the frame.
+ * H (L + 1, nV, 6) is the mean over the chunks, lag 0 included (a_m(0) is the mode amplitude); dH its std / (sqrt(R) - 1), kernel 1's
+ * convention, so R = 1 gives what it gives; smean (nV, 5) the means of the five signals over the frames of all chunks used, whose
+ * products (m0^2, m1^2, m0 m1, m2^2, m3^2, m4^2) are the six sums of the plateaus.
+ * Arithmetic as the direct form of kernel 1.  mode 0: float32 FMAs, float32 partial sums of at most 16 signed terms started at zero,
+ * folded into float64; mode 1: the same definition in float64 from the planes (the on-device check, not built for speed).  No atomics:
+ * equal input gives bit-equal output, and a vector's bits do not depend on the other vectors of the call.
+ *   sr_pack_modes_f32_dev    frame-major vectors (N, Vtot, 3) float32 of ANY positive length, columns [v0, v0 + nV) -> five planes per
+ *                            vector s0 .. s4 in kernel 0's layout, planes[(v * 5 + c) * Npad + n], zero for n in [N, Npad).  F is formed
+ *                            on the host in float64; F and the normalisation are applied in float64, each value rounded once to float32.
+ *                            frame_quat_host: HOST (4) float64 (w, x, y, z), a unit quaternion (normalised again before use), or NULL
+ *                            (F = 1).  bad_dev (nV) int32: 1 for a vector with a frame that is not finite or of zero length (its planes
+ *                            hold zeros there), else 0.  Asynchronous.  Refused with -3 before anything is queued: a bad shape; a frame
+ *                            quaternion that is not finite or whose squared norm is farther than 1e-6 from 1 (sr_noe_modes' rule).
+ *   sr_ct_modes_f32_dev      those planes -> H, dH (L + 1, nV, 6) and smean (nV, 5), float64 DEVICE arrays; psum_ws (optional, may be
+ *                            NULL): (6 nV, R, sr_ct_psum_stride(F)) float64.  Asynchronous (behind the upload of a chunk table); every
+ *                            argument check comes before the first launch.
+ *   sr_vectors_ct_modes_f32  the same of resident vectors, results on the HOST, blocking.  The pack depends on the frame: it is a work
+ *                            area of the call, not kept on the object.  A vector that the pack marks bad is refused (-3) by name.
+ * One workgroup stages the five series of a (vector, chunk) in LDS, 20 bytes per frame: F up to sr_ct_modes_max_frames() (7968 with the
+ * 160 KiB of gfx950); a longer chunk is refused with -4 before anything is queued (this function has only the staged form); a chunk start outside
+ * what is held, a bad shape or mode: -3.  The context stays usable after every refusal. */
+int64_t sr_ct_modes_max_frames(sr_ctx *);
+int sr_pack_modes_f32_dev(sr_ctx *, const float *vecs_dev, int64_t N, int64_t Vtot, int64_t v0, int64_t nV, const double *frame_quat_host,
+                          float *planes_dev, int64_t Npad, int32_t *bad_dev);
+int sr_ct_modes_f32_dev(sr_ctx *, const float *planes_dev, int64_t Npad, int64_t nV, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                        int mode, double *psum_ws, double *H, double *dH, double *smean);
+int sr_vectors_ct_modes_f32(sr_ctx *, sr_vectors *, const double *frame_quat_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                            int mode, double *H, double *dH, double *smean);
+
 /* ---- kernel 3b: multi-exponential C(t) model --------------------------------------------
  * Model of curvefit_exponential (fitting_Ct_functions.py:419-427): params = [C_1..C_K, tau_1..tau_K
  * (, S2)], P = 2K or 2K+1; even P: S2 = 1 - sum C.  resid = (model - C)/sigma (sigma may be NULL),

@@ -7,7 +7,8 @@ also <o>_iRED_Ctint.dat, <o>_iRED_modeCt.dat and <o>_iRED_tau.dat; with the [ext
 and <o>_crossPairs.dat; with the [extension] --dipolarCt also <o>_dipolarCtint.dat and <o>_dipolarDist.dat; with the
 [extension] --dipolarCrossCt --pairs FILE also <o>_dipolarCrossCtint.dat and <o>_dipolarCrossPairs.dat; with the [extension] --noeMap
 also <o>_noeMap.dat and, with --binary, <o>_noeMap.npz, with --noeLags / --noeLagMax on top of it <o>_noeMapCt.dat, and with --noesy on top of it <o>_noesy.dat and, with --binary,
-<o>_noesy.npz; --noesyD in the place of --noesyTauC: the same files under anisotropic tumbling, --vecRot as the tensor's frame).  C(t), the rotation into
+<o>_noesy.npz; --noesyD in the place of --noesyTauC: the same files under anisotropic tumbling, --vecRot as the tensor's frame; with the [extension] --modeCt also <o>_modeCt.npz, with
+--modeD on top of it <o>_modeAmp.dat and with --modeField on top of that <o>_modeRelax.dat).  C(t), the rotation into
 the PAF, the spherical histogram, the mean vector and S2 are computed on the MI355X (libspinrelax_hip.so); this script only parses arguments and moves files.
 
 Several GPUs: run under torchrun (`torchrun --nproc-per-node N scripts/calculate-Ct-from-traj.py ...`): rank r computes the
@@ -161,10 +162,80 @@ def build_parser():
     p.add_argument('--noesyGroups', type=str, dest='noesy_groups', default=None,
                    help='[extension] --noesy: a file with one group of equivalent or unresolved spins per line (positions in the list of '
                         'selected atoms); the intensities summed over the groups go to <o>_noesyGroups.dat.')
+    p.add_argument('--modeCt', dest='bDoModeCt', action='store_true', default=False,
+                   help='[extension] C(t) of the fitted vectors split into the five tumbling modes of an anisotropic diffusion tensor: the six '
+                        'mode sums of every vector at the lags 0 .. tau/2 in the frame of --vecRot, the quaternion into the tensor\'s '
+                        'principal-axis frame (identity without it), to <o>_modeCt.npz (H, dH, smean, lags, dt, frame).  They do not depend '
+                        'on the tensor.  Needs --tau, chunks of at most 7968 frames.  --exact: float64 throughout.')
+    p.add_argument('--modeD', type=str, dest='mode_D', default=None,
+                   help='[extension] --modeCt: the rotational diffusion tensor as "Diso aniso [rhomb]", Diso in 1/s, parsed like --noesyD; '
+                        'also writes <o>_modeAmp.dat with the amplitudes a_m(0), the plateaus c_m and S2 = sum c_m of every vector.')
+    p.add_argument('--modeField', type=float, dest='mode_field', default=None,
+                   help='[extension] --modeCt --modeD: the proton frequency of the spectrometer in MHz; also writes <o>_modeRelax.dat with '
+                        'R1, R2 and NOE of every vector (15N-1H, the constants of calculate-relaxations-from-Ct.py).')
     return p
 
 
 TIME_UNIT_S = 1e-12       # the times of a run (dt of the input, --dt, --tau) are in ps
+
+
+def mode_tensor(args):
+    """--modeD "Diso aniso [rhomb]" -> (Dx, Dy, Dz) in 1/s, --noesyD's rule (noesy_tensor); None for anything else"""
+    return noesy_tensor(argparse.Namespace(noesy_D=args.mode_D))
+
+
+def check_mode_args(args):
+    """the --mode* flags that do not fit together: an error message and exit, before any GPU work"""
+    def fail(msg):
+        print("= = = ERROR: %s" % msg, file=sys.stderr)
+        sys.exit(1)
+    if not args.bDoModeCt:
+        for name, v in (('--modeD', args.mode_D), ('--modeField', args.mode_field)):
+            if v is not None:
+                fail("%s belongs to --modeCt; give both." % name)
+        return
+    if args.tau is None:
+        fail("--modeCt needs --tau: the functions are block averages over the memory time.")
+    if args.mode_field is not None and args.mode_D is None:
+        fail("--modeField needs --modeD: the rates need the tumbling.")
+    if args.mode_D is not None and mode_tensor(args) is None:
+        fail("--modeD must be \"Diso aniso [rhomb]\" with Diso > 0 in 1/s and a tensor with Dx, Dy, Dz > 0; got '%s'." % args.mode_D)
+    if args.mode_field is not None and not (np.isfinite(args.mode_field) and args.mode_field > 0):
+        fail("--modeField must be > 0.")
+    if args.vecRotQ != '':
+        try:
+            q = np.array([float(v) for v in args.vecRotQ.split()])
+        except ValueError:
+            q = np.zeros(0)
+        if q.shape != (4,) or not np.all(np.isfinite(q)) or abs(float(q @ q) - 1.0) > 1e-6:
+            fail("--modeCt takes --vecRot as the unit quaternion \"w x y z\" into the tensor's frame; got '%s'." % args.vecRotQ)
+
+
+def run_mode_ct(args, out_pref, rv_fit, resXH, R, F, deltaT, q_rot):
+    """--modeCt: the mode-resolved C(t) of the fitted vectors and, with --modeD / --modeField, amplitudes and rates"""
+    from spinrelax_amd import modes
+    print("= = = Conducting mode-resolved C(t) analysis of the fitted vectors using Palmer's approach.")
+    try:
+        res = hostct.calculate_Ct_modes_resident(rv_fit, R, F, frame=q_rot, mode=1 if args.exact else 0)
+    except (ValueError, hostct.hip.SpinRelaxHipError) as exc:      # a zero-length vector, a chunk beyond the staged kernel
+        print("= = = ERROR: %s" % exc, file=sys.stderr)
+        sys.exit(1)
+    np.savez(out_pref + '_modeCt.npz', H=res['H'], dH=res['dH'], smean=res['smean'], lags=res['lags'], dt=float(deltaT), frame=res['frame'],
+             names=np.array(resXH))
+    if args.mode_D is not None:
+        D = mode_tensor(args) * TIME_UNIT_S                         # 1/s -> 1/ps, the unit of dt
+        a, c, _ = modes.amplitudes(res, D)
+        with open(out_pref + '_modeAmp.dat', 'w') as fp:
+            print("# resid a_0(0) .. a_4(0) c_0 .. c_4 S2", file=fp)
+            for n in range(a.shape[1]):
+                print("%s %s %s %.8g" % (resXH[n], ' '.join('%.8g' % x for x in a[0, n]), ' '.join('%.8g' % x for x in c[n]), c[n].sum()), file=fp)
+        if args.mode_field is not None:
+            rel = modes.relaxation(res, D, float(deltaT), args.mode_field)
+            with open(out_pref + '_modeRelax.dat', 'w') as fp:
+                print("# resid R1 R2 NOE", file=fp)
+                for n in range(a.shape[1]):
+                    print("%s %.8g %.8g %.8g" % (resXH[n], rel['R1'][n], rel['R2'][n], rel['NOE'][n]), file=fp)
+    print("      ...complete.")
 
 
 def check_noe_lag_args(args):
@@ -527,8 +598,13 @@ def main():
         sys.exit(1)
     check_noe_lag_args(args)
     check_noesy_args(args)
+    check_mode_args(args)
     time_start = time.time()
     rank, world = srdist.start()
+    if args.bDoModeCt and world > 1:
+        # the ranks hold ranges of vectors; the output is not sharded
+        print("= = = ERROR: --modeCt does not run under torchrun with more than one rank; run it as a single process.", file=sys.stderr)
+        sys.exit(1)
     if args.bDoDipolarCt and world > 1:
         # the ranks hold ranges of vectors; the distances and the output are not sharded
         print("= = = ERROR: --dipolarCt does not run under torchrun with more than one rank; run it as a single process.", file=sys.stderr)
@@ -753,6 +829,9 @@ def main():
                 print("%d %d %d %s %s %.8g %.8g %.8g %.8g" % (ordinals[n], i, j, resXH[i], resXH[j], P0[n], dP0[n], reff6[n, 0], reff6[n, 1]),
                       file=fp)
         print("      ...complete.")
+
+    if args.bDoModeCt:
+        run_mode_ct(args, out_pref, rv_fit, resXH, R, F, deltaT, q_rot)
 
     need_dist = args.bDoVecAverage or args.bDoS2 or (bDoVecDistrib and args.bDoVecHist)
     if need_dist:

@@ -196,6 +196,14 @@ SIGNATURES = {
                                                  c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'sr_vectors_ct_dipolar_cross_long_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the mode-resolved bond-vector correlation function (sr_ct_modes.hip): (ctx, vecs_dev, N, Vtot, v0, nV, frame_quat_host, planes_dev, Npad,
+    # bad_dev) / (ctx, planes, Npad, nV, R, F, chunk_start, mode, psum_ws, H_dev, dH_dev, smean_dev) / (ctx, vectors, frame_quat_host, R, F,
+    # chunk_start, mode, H_host, dH_host, smean_host)
+    'sr_ct_modes_max_frames': (c_int64, [c_void_p]),
+    'sr_pack_modes_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    'sr_ct_modes_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    'sr_vectors_ct_modes_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     # the all-pairs dipolar map (sr_noe.hip): (ctx, xyz, nFrames, nAtoms, index_host, P, quat, block_start_host, block_len_host, B, mode, sums),
     # xyz / quat / sums on the device or all three on the host
     'sr_noe_pairs_f32_dev': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -249,7 +257,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long, sr_noe, sr_noe_lagged, sr_noe_modes and sr_noesy entry points, sr_vechist_plan and the sr_ct_palmer_sums_pack_* / sr_ct_pack_fused / sr_pack_reg_tiles group: they only add symbols, and load() fails at a missing one
+ABI_VERSION = 13      # unchanged by the sr_ct_cross, sr_ct_dipolar, sr_ct_dipolar_cross, sr_ct_dipolar_long, sr_noe, sr_noe_lagged, sr_noe_modes, sr_noesy and sr_ct_modes entry points, sr_vechist_plan and the sr_ct_palmer_sums_pack_* / sr_ct_pack_fused / sr_pack_reg_tiles group: they only add symbols, and load() fails at a missing one
 LIB_PATH = os.environ.get('SPINRELAX_HIP_LIB', LIB_PATH)      # alternative build of the same ABI
 
 

@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libspinrelax_hip.so')
-SOURCES = ['sr_core.hip', 'sr_pack.hip', 'sr_ct.hip', 'sr_ct_direct.hip', 'sr_ct_cross.hip', 'sr_ct_dipolar.hip', 'sr_ct_dipolar_cross.hip', 'sr_ct_fft64.hip', 'sr_ct_rfft64.hip', 'sr_ct32.hip', 'sr_ct_long.hip', 'sr_ct_cross_long.hip', 'sr_ct_dipolar_long.hip',
+SOURCES = ['sr_core.hip', 'sr_pack.hip', 'sr_ct.hip', 'sr_ct_direct.hip', 'sr_ct_cross.hip', 'sr_ct_dipolar.hip', 'sr_ct_dipolar_cross.hip', 'sr_ct_modes.hip', 'sr_ct_fft64.hip', 'sr_ct_rfft64.hip', 'sr_ct32.hip', 'sr_ct_long.hip', 'sr_ct_cross_long.hip', 'sr_ct_dipolar_long.hip',
            'sr_vechist.hip', 'sr_ired.hip', 'sr_ired_modes.hip', 'sr_noe.hip', 'sr_noesy.hip', 'sr_fit.hip', 'sr_relax.hip', 'sr_dq.hip', 'sr_traj.hip', 'sr_vectors.hip', 'sr_textio.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']
@@ -21,6 +21,7 @@ EXTRA = {'sr_pack.hip': ['-fno-slp-vectorize'], 'sr_ct.hip': ['-fno-slp-vectoriz
          'sr_ct_cross.hip': ['-fno-slp-vectorize'],        # the same inner loop (sr_ct_shift.h)
          'sr_ct_dipolar.hip': ['-fno-slp-vectorize'],      # the same again, and a second loop of its shape
          'sr_ct_dipolar_cross.hip': ['-fno-slp-vectorize'],   # both loops, on two series
+         'sr_ct_modes.hip': ['-fno-slp-vectorize'],        # the scalar loop, seven times per lag block
          'sr_ct_fft64.hip': ['-fno-slp-vectorize'], 'sr_ct_rfft64.hip': ['-fno-slp-vectorize'],
          'sr_ct32.hip': ['-fno-slp-vectorize'], 'sr_ct_long.hip': ['-fno-slp-vectorize'],
          'sr_ct_cross_long.hip': ['-fno-slp-vectorize'],   # the kernels of sr_ct_long.h, compiled as in sr_ct_long.hip

@@ -202,6 +202,7 @@ int sr_ct_pack_fused(int formulation, int64_t F, int64_t series, int64_t tiles, 
 const sr_ct_form sr_ct_form_cross = {"two", 24, SR_CT_CROSS_LONG_FLOOR, "sr_ct_cross_long_f32_dev", true};
 const sr_ct_form sr_ct_form_dipolar = {"four", 16, SR_CT_DIPOLAR_LONG_FLOOR, "sr_ct_dipolar_long_f32_dev", false};
 const sr_ct_form sr_ct_form_dipolar_cross = {"eight", 32, SR_CT_DIPOLAR_CROSS_LONG_FLOOR, "sr_ct_dipolar_cross_long_f32_dev", true};
+const sr_ct_form sr_ct_form_modes = {"five", 20, 0, nullptr, false};
 
 size_t sr_ct_lds_bytes(int64_t F, int bytes_per_frame) { return (size_t)ct_Fp(F) * (size_t)bytes_per_frame; }
 
@@ -245,9 +246,10 @@ int sr_ct_rows_check(sr_ctx *ctx, const sr_ct_rows &w, const sr_ct_form &form)
     } else {
         const size_t limit = sr_lds_limit(ctx);
         SR_REQUIRE(sr_ct_lds_bytes(w.F, form.bytes_per_frame) <= limit, -4,
-                   "%s: the %s series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (longer chunks: the blocked form, %s)",
+                   "%s: the %s series of a chunk of F=%lld frames need %zu B of LDS (> %zu); max F is %lld (longer chunks: %s%s)",
                    who, form.series, (long long)w.F, sr_ct_lds_bytes(w.F, form.bytes_per_frame), limit,
-                   (long long)sr_ct_lds_max_frames(form.bytes_per_frame, limit), form.long_name);
+                   (long long)sr_ct_lds_max_frames(form.bytes_per_frame, limit), form.long_name ? "the blocked form, " : "this function has only the staged form",
+                   form.long_name ? form.long_name : "");
     }
     const int64_t rows = form.pairs ? w.nP : w.nV;
     SR_REQUIRE(w.R * rows < (int64_t)1 << 30, -3, "%s: too many series", who);

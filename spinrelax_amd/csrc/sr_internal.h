@@ -145,10 +145,11 @@ struct sr_ct_form {
     const char *series;                         // "two", "four", "eight": the series a workgroup of the staged form holds in LDS,
     int bytes_per_frame;                        // and their bytes per staged frame
     int long_floor;                             // the shortest chunk of the blocked form
-    const char *long_name;                      // and its entry point, for the staged form's -4 message
+    const char *long_name;                      // and its entry point, for the staged form's -4 message; null: the staged form is the only one
     bool pairs;                                 // rows are pairs (a pair table is required) or the vectors themselves
 };
 extern const sr_ct_form sr_ct_form_cross, sr_ct_form_dipolar, sr_ct_form_dipolar_cross;
+extern const sr_ct_form sr_ct_form_modes;       // the mode-resolved function (sr_ct_modes.hip): five signal series, staged form only
 // LDS of a staged chunk of F frames, and the longest chunk that a limit admits (0: none)
 size_t sr_ct_lds_bytes(int64_t F, int bytes_per_frame);
 int64_t sr_ct_lds_max_frames(int bytes_per_frame, size_t lds_limit);

@@ -464,6 +464,36 @@ int sr_vectors_ct_dipolar_long_f32(sr_ctx *ctx, sr_vectors *h, const float *dist
     return vectors_ct_dipolar(ctx, "sr_vectors_ct_dipolar_long_f32", 1, h, dist_host, R, F, chunk_start_host, mode, Ct, dCt, reff6, reff3, S2rad);
 }
 
+int sr_vectors_ct_modes_f32(sr_ctx *ctx, sr_vectors *h, const double *frame_quat_host, int64_t R, int64_t F, const int64_t *chunk_start_host,
+                            int mode, double *H, double *dH, double *smean)
+{
+    const char *who = "sr_vectors_ct_modes_f32";
+    SR_CHECK_CTX(ctx);
+    SR_REQUIRE(h && H && dH && smean, -2, "%s: null pointer", who);
+    // refusals come before the pack: a chunk that does not fit or a bad frame quaternion launches nothing
+    const sr_ct_rows w = {who, h->N, h->nV, R, F, chunk_start_host, nullptr, nullptr, 0, 0, mode, 0};
+    if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_modes)) return rc;
+    if (int rc = wait_ready(ctx, h)) return rc;
+    SR_REQUIRE(h->N > 0, -3, "sr_vectors: no frames appended");
+    // the five planes depend on the frame: a work area of this call, not the object's
+    const int64_t nV = h->nV, Npad = sr_round_up(h->N, 64);
+    float *planes = (float *)sr_workspace(ctx, SR_WS_SOA, (size_t)nV * 5 * Npad * sizeof(float));
+    int32_t *bad_d = (int32_t *)sr_workspace(ctx, SR_WS_IN0, (size_t)nV * sizeof(int32_t));
+    if (!planes || !bad_d) return -5;
+    if (int rc = sr_pack_modes_f32_dev(ctx, h->fm, h->N, nV, 0, nV, frame_quat_host, planes, Npad, bad_d)) return rc;
+    std::vector<int32_t> bad((size_t)nV);
+    SR_HIP(hipMemcpyAsync(bad.data(), bad_d, (size_t)nV * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SR_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t v = 0; v < nV; ++v)
+        SR_REQUIRE(!bad[(size_t)v], -3, "%s: vector %lld has a frame of zero length or one that is not finite", who, (long long)v);
+    const size_t LV = (size_t)((F / 2 + 1) * nV) * 6, V5 = (size_t)nV * 5;
+    const size_t n[] = {LV, LV, V5};                                                                // H, dH, smean
+    const CtDown down[] = {{H, 0, 0, LV, 1}, {dH, 1, 0, LV, 1}, {smean, 2, 0, V5, 1}};
+    return ct_results(ctx, n, down, [&](double *const *d) {
+        return sr_ct_modes_f32_dev(ctx, planes, Npad, nV, R, F, chunk_start_host, mode, nullptr, d[0], d[1], d[2]);
+    });
+}
+
 static int vectors_ct_dipolar_cross(sr_ctx *ctx, const char *who, int blocked, sr_vectors *h, const float *dist_host, int64_t R, int64_t F,
                                     const int64_t *chunk_start_host, const int32_t *pair_i, const int32_t *pair_j, int64_t nP, int sym, int mode,
                                     double *P0, double *dP0, double *Ct, double *dCt, double *reff6)

@@ -260,6 +260,57 @@ def calculate_Ct_dipolar_cross_resident(rv, pairs, R, F, dist=None, symmetric=Tr
     return _ct_dipolar_cross(rv, R, F, pairs, dist=dist, chunk_start=chunk_start, sym=int(bool(symmetric)), mode=mode)
 
 
+def _modes_result(rv, R, F, frame, chunk_start, mode):
+    """the dict of the three calculate_Ct_modes functions; a chunk beyond the staged kernel raises before any device work"""
+    from .noe import _frame_quat
+    q = _frame_quat(frame)
+    fmax = rv.ctx.ct_modes_max_frames()
+    if F > fmax:
+        raise ValueError('mode-resolved C(t): a chunk of %d frames is beyond the staged kernel (%d frames), the only form of this function'
+                         % (F, fmax))
+    H, dH, smean = rv.ct_modes(R, F, frame=q, chunk_start=chunk_start, mode=mode)
+    return dict(H=H, dH=dH, smean=smean, frame=np.array([1.0, 0.0, 0.0, 0.0]) if q is None else q, lags=np.arange(F // 2 + 1))
+
+
+def calculate_Ct_modes(vecs, frame=None, ctx=None, mode=0):
+    """The bond-vector correlation function split into the five tumbling modes of an anisotropic diffusion tensor, an extension beyond
+    the reference (whose anisotropic J(w) multiplies a static orientation histogram by one internal C(t)).  vecs (nReplicates, nFrames,
+    nVectors, 3) as calculate_Ct_Palmer takes them, of any positive length; frame: the unit quaternion (w, x, y, z) that rotates them
+    into the principal-axis frame of the tensor, --vecRot's convention (noe.frame_matrix), or None.  With u the rotated unit vector,
+    s0 = u_z^2 - 1/3, s1 = u_x^2 - u_y^2, s2 = u_y u_z, s3 = u_x u_z, s4 = u_x u_y and s' the signal k frames later, returns a dict:
+    H, dH (nFrames // 2 + 1, nVectors, 6) = <s0 s0'>, <s1 s1'>, <s0 s1' + s1 s0'> / 2, <s2 s2'>, <s3 s3'>, <s4 s4'> at the lags
+    0 .. nFrames // 2 (the order of noe.mode_amplitudes), mean over the replicates and std / (sqrt(nReplicates) - 1) like C(t);
+    smean (nVectors, 5), the means of the five signals over all frames; frame (the quaternion, (1, 0, 0, 0) for None) and lags.
+    They do not depend on the tensor: modes.amplitudes, modes.J and modes.relaxation take this dict and any D.  Replicates of up to
+    Context.ct_modes_max_frames() frames."""
+    sh = np.shape(vecs)
+    if len(sh) != 4 or sh[3] != 3:
+        raise ValueError('vecs must be (replicates, frames, vectors, 3), got %s' % (sh,))
+    R, F, V = sh[0], sh[1], sh[2]
+    flat = np.ascontiguousarray(vecs, dtype=np.float32).reshape(R * F, V, 3)
+    with _ctx(ctx).vectors(V, R * F) as rv:
+        rv.append(flat)
+        return _modes_result(rv, R, F, frame, None, mode)
+
+
+def calculate_Ct_modes_from_files(vec_list, dt, tau, frame=None, ctx=None, mode=0):
+    """calculate_Ct_modes on the chunks reformat_vecs_by_tau would form from the files (concat_with_chunk_starts: the tail of every
+    file that does not fill a chunk of int(tau / dt) frames is skipped, exactly as for C(t))."""
+    F = int(tau / dt)
+    cat, starts, R = concat_with_chunk_starts(vec_list, F)
+    if R < 1:
+        raise ValueError('no trajectory holds a full block of memory time tau')
+    with _ctx(ctx).vectors(cat.shape[1], cat.shape[0]) as rv:
+        rv.append(cat)
+        return _modes_result(rv, R, F, frame, starts, mode)
+
+
+def calculate_Ct_modes_resident(rv, R, F, frame=None, mode=0, chunk_start=None):
+    """calculate_Ct_modes of resident vectors (regular chunks r * F unless chunk_start is given); smean runs over the frames of the
+    chunks used."""
+    return _modes_result(rv, R, F, frame, chunk_start, mode)
+
+
 def upload_shard(vec_list, frames_per_chunk=None, ctx=None):
     """The product path's single upload: this rank's vector range (srdist.my_range; everything in a single process) of the
     files' vectors, each file cut to whole chunks of frames_per_chunk frames when given (reformat_vecs_by_tau,

@@ -300,6 +300,27 @@ class Context:
         (sr_ct_dipolar_f32_dev); asynchronous on the context's stream"""
         self._dipolar_dev('sr_ct_dipolar_f32_dev', planes_ptr, Npad, nV, R, F, chunk_start, mode, psum_ptr, Ct_ptr, dCt_ptr, wmean_ptr)
 
+    # ---- bond-vector correlation function split into the five tumbling modes (sr_ct_modes.hip) ----
+    def ct_modes_max_frames(self):
+        """longest chunk whose five signal series fit the LDS of a workgroup (sr_ct_modes_max_frames)"""
+        return int(self.lib.sr_ct_modes_max_frames(self.h))
+
+    def pack_modes_dev(self, vecs_ptr, N, Vtot, v0, nV, planes_ptr, Npad, bad_ptr, frame=None):
+        """frame-major vectors (N, Vtot, 3) float32 of any positive length -> planes (nV, 5, Npad) float32 of the five signals
+        u_z^2 - 1/3, u_x^2 - u_y^2, u_y u_z, u_x u_z, u_x u_y of u = R(frame) v / |v| and bad (nV) int32, 1 for a vector with a frame that
+        is not finite or of zero length (sr_pack_modes_f32_dev); frame: a unit quaternion (w, x, y, z) or None; asynchronous on the
+        context's stream"""
+        fq = self._frame(frame)
+        check(self.lib.sr_pack_modes_f32_dev(self.h, vecs_ptr, int(N), int(Vtot), int(v0), int(nV), _ptr(fq), planes_ptr, int(Npad), bad_ptr),
+              'sr_pack_modes_f32_dev')
+
+    def ct_modes_dev(self, planes_ptr, Npad, nV, R, F, H_ptr, dH_ptr, smean_ptr, chunk_start=None, mode=0, psum_ptr=None):
+        """the six mode sums H and dH (F//2 + 1, nV, 6), lag 0 first, and smean (nV, 5), the means of the five signals, from the planes of
+        pack_modes_dev into device arrays (sr_ct_modes_f32_dev); asynchronous on the context's stream"""
+        cs = _chunk_starts(chunk_start)
+        check(self.lib.sr_ct_modes_f32_dev(self.h, planes_ptr, int(Npad), int(nV), int(R), int(F), _ptr(cs), int(mode), psum_ptr, H_ptr, dH_ptr,
+                                           smean_ptr), 'sr_ct_modes_f32_dev')
+
     # ---- distance-weighted pair cross-correlation functions (sr_ct_dipolar_cross.hip) ----
     def ct_dipolar_cross_max_frames(self):
         """longest chunk whose eight series (a_x, a_y, a_z, w of both vectors of a pair) fit the LDS of a workgroup
@@ -1186,6 +1207,20 @@ class ResidentVectors:
         check(getattr(self.ctx.lib, name)(self.ctx.h, self.h, _ptr(d), int(R), int(F), _ptr(cs), int(mode), _ptr(Ct), _ptr(dCt), _ptr(reff6),
                                           _ptr(reff3), _ptr(S2rad)), name)
         return Ct, dCt, reff6, reff3, S2rad
+
+    def ct_modes(self, R, F, frame=None, chunk_start=None, mode=0):
+        """the six mode sums of the resident vectors in the frame R(frame) (sr_vectors_ct_modes_f32): H, dH (F//2 + 1, nV, 6) for the
+        lags 0 .. F//2, mean and error over the R chunks like ct(), and smean (nV, 5), the means of the five signals.  frame: a unit
+        quaternion (w, x, y, z), --vecRot's convention, or None.  Chunks of up to Context.ct_modes_max_frames() frames."""
+        fq = Context._frame(frame)
+        L1 = F // 2 + 1
+        H = np.empty((L1, self.nV, 6))
+        dH = np.empty((L1, self.nV, 6))
+        smean = np.empty((self.nV, 5))
+        cs = _chunk_starts(chunk_start, R)
+        check(self.ctx.lib.sr_vectors_ct_modes_f32(self.ctx.h, self.h, _ptr(fq), int(R), int(F), _ptr(cs), int(mode), _ptr(H), _ptr(dH),
+                                                   _ptr(smean)), 'sr_vectors_ct_modes_f32')
+        return H, dH, smean
 
     def ct_dipolar_cross(self, R, F, pairs, dist=None, chunk_start=None, sym=1, mode=0):
         """distance-weighted P2 cross-correlation of the pairs (nP, 2) of resident vectors (sr_vectors_ct_dipolar_cross_f32):

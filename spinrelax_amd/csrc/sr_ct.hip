@@ -40,8 +40,10 @@ namespace {
 // launches behind it.)
 constexpr int kFinV = 16, kFinD = 64;
 constexpr int kFinR = 32;          // replicate chunks a thread keeps in registers (more: two passes over memory)
+// half: what is subtracted from 1.5 S / n per chunk -- 0.5 for unit vectors (P2 = 1.5 cos^2 - 0.5); 0 for the distance-weighted
+// functions, whose raw sums S_a - S_w / 3 carry the whole function (sr_ct_dipolar.hip)
 __global__ __launch_bounds__(256) void k_ct_finalize(const double *__restrict__ psum, int R, int F, int L, int Lp,
-                                                     int64_t nV, double *__restrict__ Ct, double *__restrict__ dCt,
+                                                     int64_t nV, double half, double *__restrict__ Ct, double *__restrict__ dCt,
                                                      double *__restrict__ CtT, double *__restrict__ dCtT)
 {
     __shared__ double tm[kFinV][kFinD + 1], ts[kFinV][kFinD + 1];
@@ -68,7 +70,7 @@ __global__ __launch_bounds__(256) void k_ct_finalize(const double *__restrict__ 
                 for (int r = 0; r < kFinR; ++r) pr[r] = r < R ? p[(int64_t)r * Lp] : 0.0;
 #pragma unroll
                 for (int r = 0; r < kFinR; ++r) {
-                    pr[r] = 1.5 * (pr[r] / n) - 0.5;
+                    pr[r] = 1.5 * (pr[r] / n) - half;
                     if (r < R) m += pr[r];
                 }
                 m /= (double)R;
@@ -78,10 +80,10 @@ __global__ __launch_bounds__(256) void k_ct_finalize(const double *__restrict__ 
                     if (r < R) s += e * e;
                 }
             } else {
-                for (int r = 0; r < R; ++r) m += 1.5 * (p[(int64_t)r * Lp] / n) - 0.5;
+                for (int r = 0; r < R; ++r) m += 1.5 * (p[(int64_t)r * Lp] / n) - half;
                 m /= (double)R;
                 for (int r = 0; r < R; ++r) {
-                    const double e = (1.5 * (p[(int64_t)r * Lp] / n) - 0.5) - m;
+                    const double e = (1.5 * (p[(int64_t)r * Lp] / n) - half) - m;
                     s += e * e;
                 }
             }
@@ -391,8 +393,8 @@ int sr_ct_palmer_sums_pack_plan(sr_ctx *ctx, const float *soa, int64_t Npad, int
     return ct_carries(form, job, ct_next_job(next_vecs, next_N, next_Vtot, next_v0, next_nV, const_cast<float *>(next_soa), next_Npad)) ? 1 : 0;
 }
 
-int sr_ct_finalize_t_f64_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt,
-                             double *CtT, double *dCtT)
+static int ct_finalize(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nV, double half, double *Ct, double *dCt, double *CtT,
+                       double *dCtT)
 {
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(psum && Ct && dCt, -2, "sr_ct_finalize_f64_dev: null pointer");
@@ -403,10 +405,26 @@ int sr_ct_finalize_t_f64_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t
     const int64_t gx = (L + kFinD - 1) / kFinD, gy = (nV + kFinV - 1) / kFinV;
     SR_REQUIRE(gy <= 65535, -3, "sr_ct_finalize_f64_dev: too many vectors in one call (%lld)", (long long)nV);
     hipLaunchKernelGGL(k_ct_finalize, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, ctx->stream, psum, (int)R, (int)F, (int)L,
-                       (int)Lp, nV, Ct, dCt, CtT, dCtT);
+                       (int)Lp, nV, half, Ct, dCt, CtT, dCtT);
     SR_HIP(hipGetLastError());
     return 0;
 }
+
+int sr_ct_finalize_t_f64_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt,
+                             double *CtT, double *dCtT)
+{
+    return ct_finalize(ctx, psum, R, F, nV, 0.5, Ct, dCt, CtT, dCtT);
+}
+
+}  // extern "C"
+
+// internal (sr_internal.h): the finalizer of the distance-weighted functions
+int sr_ct_finalize_weighted_f64_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt)
+{
+    return ct_finalize(ctx, psum, R, F, nV, 0.0, Ct, dCt, nullptr, nullptr);
+}
+
+extern "C" {
 
 int sr_ct_finalize_f64_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt)
 {

@@ -97,22 +97,22 @@ __global__ __launch_bounds__(kCrossWaves * 64, 2) void k_ct_cross(CtCrossArgs a)
     }
 }
 
-// P0[p] = mean over the chunks of 1.5 S[p][r][0] / F - 0.5, summed in chunk order; dP0[p] (may be null) = their two-pass standard
+// P0[p] = mean over the chunks of 1.5 S[p][r][0] / F - half (half: k_ct_finalize's), summed in chunk order; dP0[p] (may be null) = their two-pass standard
 // deviation / (sqrt(R) - 1), the formula of k_ct_finalize
-__global__ __launch_bounds__(256) void k_ct_cross_p0(const double *__restrict__ psum, int R, int F, int Lp, int64_t nP, double *__restrict__ P0,
-                                                     double *__restrict__ dP0)
+__global__ __launch_bounds__(256) void k_ct_cross_p0(const double *__restrict__ psum, int R, int F, int Lp, int64_t nP, double half,
+                                                     double *__restrict__ P0, double *__restrict__ dP0)
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= nP) return;
     const double *s = psum + p * R * Lp;
     double m = 0.0;
-    for (int r = 0; r < R; ++r) m += 1.5 * (s[(int64_t)r * Lp] / (double)F) - 0.5;
+    for (int r = 0; r < R; ++r) m += 1.5 * (s[(int64_t)r * Lp] / (double)F) - half;
     m /= (double)R;
     P0[p] = m;
     if (!dP0) return;
     double v = 0.0;
     for (int r = 0; r < R; ++r) {
-        const double e = (1.5 * (s[(int64_t)r * Lp] / (double)F) - 0.5) - m;
+        const double e = (1.5 * (s[(int64_t)r * Lp] / (double)F) - half) - m;
         v += e * e;
     }
     dP0[p] = sqrt(v / (double)R) / (sqrt((double)R) - 1.0);
@@ -120,10 +120,10 @@ __global__ __launch_bounds__(256) void k_ct_cross_p0(const double *__restrict__ 
 
 }  // namespace
 
-int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nP, double *P0, double *dP0)
+int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nP, double half, double *P0, double *dP0)
 {
     hipLaunchKernelGGL(k_ct_cross_p0, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, ctx->stream, psum, (int)R, (int)F,
-                       (int)sr_ct_psum_stride(F), nP, P0, dP0);
+                       (int)sr_ct_psum_stride(F), nP, half, P0, dP0);
     SR_HIP(hipGetLastError());
     return 0;
 }
@@ -163,7 +163,7 @@ static int cross_f32_dev(sr_ctx *ctx, const char *who, int blocked, const float 
                                sr_ct_lds_bytes(F, sr_ct_form_cross.bytes_per_frame), a))
             return rc;
     }
-    if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, P0, dP0)) return rc;
+    if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, 0.5, P0, dP0)) return rc;
     return sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt);
 }
 

@@ -31,7 +31,7 @@
 //   k_ctlx_cross    per (pair, chunk, 64 frequencies): the block spectra of both series once -> Q_d, float64
 //   k_ctl_inverse   per (pair, chunk, offset): psum completed
 // The distance-weighted pair form (sr_ct_dipolar_long.hip) runs the same launches on the four-plane dipolar pack with traceless = 1: five
-// signals whatever |a| is (k_ctlx_promote is skipped), no eps term, and S_a(0) - S_w(0) / 3 + F / 3 from the a and w planes in slot 0.
+// signals whatever |a| is (k_ctlx_promote is skipped), no eps term, no 1/3 per product, and S_a(0) - S_w(0) / 3 from the a and w planes in slot 0.
 // psum has kernel 1's layout (pair, chunk, sr_ct_psum_stride(F)) with pairs in the place of vectors, so k_ct_cross_p0 and k_ct_finalize
 // follow unchanged (sr_ct_cross_finish).  Mode 1 (float64 validation) is k_ctlx_f64: the definition, lag by lag from the planes.
 #include <algorithm>
@@ -55,7 +55,7 @@ struct CtlxArgs {
     int R, F, L, Lp, nb, nd, sym;
     int p0, r0, nr;                      // the tile: its first pair, first chunk, number of chunks
     int planes;                          // planes per vector in soa: 3, or 4 for the dipolar pack (whose fourth plane is w)
-    int traceless;                       // 1: five traceless signals whatever |a| is, no eps term, S_a - S_w / 3 + F / 3 in slot 0
+    int traceless;                       // 1: five traceless signals whatever |a| is, no eps term, S_a - S_w / 3 in slot 0
 };
 
 // ---- six signals for both series of a pair if one of them is not a unit-vector series --------------------------------------------
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void k_ctlx_scan(CtlxArgs a)
         wj[c] = (double)uniform_f(cj->wm[c]);
     }
     const bool unit = a.traceless || (uniform_f(ci->weps) != 0.f && uniform_f(cj->weps) != 0.f);
-    double K6 = unit ? 2.0 : 0.0;
+    double K6 = unit && !a.traceless ? 2.0 : 0.0;
 #pragma unroll
     for (int c = 0; c < 6; ++c)
         if (c < 5 || !unit) K6 = fma(wi[c], (double)mj[c], K6);
@@ -187,13 +187,13 @@ __global__ __launch_bounds__(256) void k_ctlx_scan(CtlxArgs a)
         }
         return;
     }
-    // the distance-weighted pair: S_a(0) - S_w(0) / 3 + F / 3, the raw sum k_ct_dipolar_cross leaves in slot 0
+    // the distance-weighted pair: S_a(0) - S_w(0) / 3, the raw sum k_ct_dipolar_cross leaves in slot 0
     __syncthreads();
     sw0 = sr_wave_sum_f64(sw0);
     if ((tid & 63) == 0) tot[tid >> 6] = sw0;
     __syncthreads();
     if (tid == 0) {
-        out[0] = s0t - ((tot[0] + tot[1]) + (tot[2] + tot[3])) / 3.0 + (double)F / 3.0;
+        out[0] = s0t - ((tot[0] + tot[1]) + (tot[2] + tot[3])) / 3.0;
         a.pconsts[s].G0 = 0.0;
     }
 }

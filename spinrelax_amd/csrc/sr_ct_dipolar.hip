@@ -10,9 +10,11 @@
 // Per (vector, chunk) two shifted-product sums: S_a(k) = sum_t (a(t) . a(t+k))^2 -- what ct_shift_block (sr_ct_shift.h) accumulates;
 // every term stays in [0, 1], which its centred float32 partial sums rely on: the reason for the r_ref scaling -- and
 // S_w(k) = sum_t w(t) w(t+k).
-// The raw sums leave as S'(k) = S_a(k) - S_w(k) / 3 + (F - k) / 3 in kernel 1's psum layout, so that the unchanged k_ct_finalize
-// (1.5 S' / (F - k) - 0.5 = [1.5 S_a - 0.5 S_w] / (F - k)) gives the chunk mean of the unnormalised function and its
-// std / (sqrt(R) - 1); k_ct_dipolar_norm divides both by the chunk mean of n_r = sum_t w^2 / F.
+// The raw sums leave as S'(k) = S_a(k) - S_w(k) / 3 in kernel 1's psum layout, and k_ct_finalize with nothing subtracted (half = 0:
+// 1.5 S' / (F - k) = [1.5 S_a - 0.5 S_w] / (F - k)) gives the chunk mean of the unnormalised function and its std / (sqrt(R) - 1);
+// k_ct_dipolar_norm divides both by the chunk mean of n_r = sum_t w^2 / F.  (S' carried (F - k) / 3 once, so that the finalizer's
+// 1.5 S' / (F - k) - 0.5 could stay as it was: that rounds the unnormalised function to 1e-16 ABSOLUTE, which the division by n_r turns
+// into 1e-16 / <w^2> -- 3.6e-12 in float64 mode for a pair whose <w^2> is 3e-5, one close frame in 36 000.)
 //
 // Kernels:
 //   k_dipolar_rmin   r_ref per vector: a workgroup min over the frames, no atomics
@@ -27,6 +29,9 @@
 //                    atomics, no scratch: equal input gives bit-equal output
 //   k_ct_dipolar_norm  chunk means of the two sums; Ct and dCt scaled by 1 / mean n_r; <w> and <w^2> per vector
 // A chunk must fit 16 ct_Fp(F) bytes of LDS: F <= 10016 at 160 KiB.  Longer chunks take the blocked form (sr_ct_dipolar_long.hip).
+// Accuracy of mode 0: 2e-8 relative on C_dd was measured on wobbling pairs whose w stays within a factor 3 (C_dd >= 0.66); on mobile pairs
+// whose w spans four decades (tests/test_gpu_ct_dipolar_mobile.py, docs/EXPERIMENTS.md section 38) 1.4e-7 of max(1, max |C_dd|) on C and
+// 1.9e-7 / (sqrt(R) - 1) on dC, the pair form 1.1e-7 and 1.3e-7 / (sqrt(R) - 1); mode 1 1e-15.
 #include "sr_ct_dipolar.h"
 #include <cmath>
 
@@ -200,7 +205,7 @@ __global__ __launch_bounds__(W * 64, SR_CT_DIP_WAVES_EU) void k_ct_dipolar(CtDip
             const int lag0 = dw + kLagsPerLane * l16;
             double *o = out + lag0;
 #pragma unroll
-            for (int d = 0; d < kLagsPerLane; ++d) o[d] = sa[d] - sw[d] / 3.0 + (double)(F - lag0 - d) / 3.0;
+            for (int d = 0; d < kLagsPerLane; ++d) o[d] = sa[d] - sw[d] / 3.0;
         }
     }
 
@@ -216,7 +221,7 @@ __global__ __launch_bounds__(W * 64, SR_CT_DIP_WAVES_EU) void k_ct_dipolar(CtDip
         }
         s = wave_sum_f64(s);
         q = wave_sum_f64(q);
-        if (lane == 0) out[d] = s - q / 3.0 + (double)(F - d) / 3.0;
+        if (lane == 0) out[d] = s - q / 3.0;
     }
 }
 
@@ -332,7 +337,7 @@ int sr_ct_dipolar_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, int64_
         rc = launch_dip<1>(ctx, a, series * a.nslab, lds_bytes);
     }
     if (rc) return rc;
-    if (int rc2 = sr_ct_finalize_f64_dev(ctx, psum, R, F, nV, Ct, dCt)) return rc2;
+    if (int rc2 = sr_ct_finalize_weighted_f64_dev(ctx, psum, R, F, nV, Ct, dCt)) return rc2;
     return sr_ct_dipolar_norm_dev(ctx, a.wsum, R, F, nV, Ct, dCt, wmean);
 }
 

@@ -7,9 +7,10 @@
 //
 // Per (pair, chunk), the later frame from vector j as in k_ct_cross:
 //     S_a(k) = sum_t (a_i(t) . a_j(t+k))^2,   S_w(k) = sum_t w_i(t) w_j(t+k),   k = 0 .. L = F/2
-// (sym = 1: the mean of both directions, summed by the same lane in a fixed order).  The raw sums leave as
-// S'(k) = S_a(k) - S_w(k) / 3 + (F - k) / 3 in kernel 1's psum layout, row (pair, chunk), lag 0 in slot 0: the unchanged k_ct_finalize
-// and k_ct_cross_p0 give the chunk mean of the unnormalised function, its std / (sqrt(R) - 1) and the equal-time value with its error;
+// (sym = 1: the mean of both directions, summed by the same lane in a fixed order, the lower vector of the pair first: (i, j) and
+// (j, i) give the same bytes).  The raw sums leave as S'(k) = S_a(k) - S_w(k) / 3 in kernel 1's psum layout, row (pair, chunk), lag 0 in
+// slot 0: k_ct_finalize and k_ct_cross_p0 with nothing subtracted (half = 0: 1.5 S' / (F - k) is the whole function) give the chunk
+// mean of the unnormalised function, its std / (sqrt(R) - 1) and the equal-time value with its error;
 // k_ct_dipolar_cross_norm scales all four by 1 / sqrt(n_i n_j), n_v the mean over the chunks of sum_t w_v^2 / F (k_ct_dipolar_norm's
 // convention: a ratio of chunk means, the normaliser's own scatter is ignored; the r_ref factors cancel).  For i = j the result is
 // C_dd of k_ct_dipolar with P0 = 1, to rounding.
@@ -51,11 +52,21 @@ __global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtD
     float *ai = lds, *wi = lds + 2 * Hf;
     float *aj = lds + 4 * Fp, *wj = aj + 2 * Hf;
 
+    // sym = 1: the function of (i, j) is that of (j, i).  The pair runs with the lower vector first, so both are the same arithmetic in
+    // the same order and leave the same bytes (the two directions are added into one set of sums, one after the other)
+    int vi = a.pair_i[p], vj = a.pair_j[p];
+    const bool swapped = a.sym && vi > vj;
+    if (swapped) {
+        const int t = vi;
+        vi = vj;
+        vj = t;
+    }
+
     // ---- stage the eight series (coalesced dword loads; zero padding behind frame F) ----
     {
         const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
-        const float *pi = a.soa + (int64_t)a.pair_i[p] * 4 * a.Npad + start;
-        const float *pj = a.soa + (int64_t)a.pair_j[p] * 4 * a.Npad + start;
+        const float *pi = a.soa + (int64_t)vi * 4 * a.Npad + start;
+        const float *pj = a.soa + (int64_t)vj * 4 * a.Npad + start;
         const float *pwi = pi + 3 * a.Npad, *pwj = pj + 3 * a.Npad;
         ct_stage_series<kDipCrossWaves * 64>(ai, pi, pi + a.Npad, pi + 2 * a.Npad, F, Fp, Hf, tid);
         ct_stage_series<kDipCrossWaves * 64>(aj, pj, pj + a.Npad, pj + 2 * a.Npad, F, Fp, Hf, tid);
@@ -88,8 +99,8 @@ __global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtD
         sj = wave_sum_f64(sj);
         if (wave == 0 && lane == 0) {
             double *o = a.wsum2 + ((int64_t)p * a.R + r) * 2;
-            o[0] = si;
-            o[1] = sj;
+            o[swapped ? 1 : 0] = si;
+            o[swapped ? 0 : 1] = sj;
         }
         center = fminf(kCenter, (float)(8.0 * sqrt(si * sj) / (double)F));
     }
@@ -116,7 +127,7 @@ __global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtD
             const int lag0 = dw + kLagsPerLane * l16;
             double *o = out + lag0;
 #pragma unroll
-            for (int d = 0; d < kLagsPerLane; ++d) o[d] = scale * (sa[d] - sw[d] / 3.0) + (double)(F - lag0 - d) / 3.0;
+            for (int d = 0; d < kLagsPerLane; ++d) o[d] = scale * (sa[d] - sw[d] / 3.0);
         }
     }
 
@@ -139,7 +150,7 @@ __global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtD
         }
         s = wave_sum_f64(s);
         q = wave_sum_f64(q);
-        if (lane == 0) out[d] = scale * (s - q / 3.0) + (double)(F - d) / 3.0;
+        if (lane == 0) out[d] = scale * (s - q / 3.0);
     }
 }
 
@@ -222,8 +233,8 @@ int sr_ct_dipolar_cross_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, 
     if (int rc = sr_launch(ctx, k_ct_dipolar_cross, dim3((unsigned)(nP * R)), dim3(kDipCrossWaves * 64),
                            sr_ct_lds_bytes(F, sr_ct_form_dipolar_cross.bytes_per_frame), a))
         return rc;
-    if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, P0, dP0)) return rc;
-    if (int rc = sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt)) return rc;
+    if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, 0.0, P0, dP0)) return rc;
+    if (int rc = sr_ct_finalize_weighted_f64_dev(ctx, psum, R, F, nP, Ct, dCt)) return rc;
     return sr_ct_dipolar_cross_norm_dev(ctx, wsum2, R, F, nP, Ct, dCt, P0, dP0);
 }
 

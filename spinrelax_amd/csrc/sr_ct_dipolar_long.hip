@@ -7,13 +7,15 @@
 //     1.5 (a . a')^2 - 0.5 w w' = 1.5 Q : Q' + 0.5 (|a|^2 |a'|^2 - w w') = 1.5 Q : Q'
 // so the unnormalised function of a chunk is 1.5 sum Q : Q' / (F - k): the five traceless signals that the blocked kernels already
 // transform, and nothing else -- no sixth signal, no eps = |a|^2 - 1 term.  In CtlConst terms nsig = 5, weps = 0 and
-// Kc = 6 (sum_c w_c m_c^2 + 1/3): the 1/3 per product makes the raw sum S' = sum Q : Q' + (F - k) / 3 = S_a - S_w / 3 + (F - k) / 3, what
-// k_ct_dipolar leaves, so the unchanged k_ct_finalize gives [1.5 S_a - 0.5 S_w] / (F - k).  The same holds term by term for a pair:
+// Kc = 6 sum_c w_c m_c^2 without the 1/3 per product of unit vectors: the raw sum is S' = sum Q : Q' = S_a - S_w / 3, what
+// k_ct_dipolar leaves, and k_ct_finalize with half = 0 gives [1.5 S_a - 0.5 S_w] / (F - k).  The same holds term by term for a pair:
 // 1.5 (a_i . a_j')^2 - 0.5 w_i w_j' = 1.5 Q_i : Q_j'.  The shared kernels take this as their "traceless" flag and the plane stride 4
 // (CtlArgs / CtlxArgs, sr_ct_long.h).
 //
 // |a|^2 and w agree to the float32 rounding of the pack only (relative 1e-7 per frame, not systematic): on the test vectors the
-// five-signal form differs from the definition on the same planes by 1.5e-9 of C (docs/EXPERIMENTS.md).  The planes must therefore
+// five-signal form differs from the definition on the same planes by 1.5e-9 of C (docs/EXPERIMENTS.md) -- on wobbling pairs whose w
+// stays within a factor 3; on mobile pairs whose w spans four decades (docs/EXPERIMENTS.md section 38) mode 0 as a whole is within 1.6e-7
+// of max(1, max |C|) on C and 2.1e-7 / (sqrt(R) - 1) on dC, at most 2.3 times an independent float32 emulation.  The planes must therefore
 // come from sr_pack_dipolar_f32_dev; four planes whose first three are not sqrt(w) long give Q : Q', not the definition.
 //
 // What is not a transform stays the definition on the w plane, in float64, in a fixed order: the chunk sums of w and w^2 that
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(256) void k_dipl_wsums(DiplArgs a)
 }
 
 // ---- mode 1: the definition in float64, lag by lag from the planes --------------------------------------------------------------------
-// One thread per lag (slot 0 included), frames in order: S_a - S_w / 3 + (F - k) / 3 with S_w from the w planes (k_ctlx_f64's shape).
+// One thread per lag (slot 0 included), frames in order: S_a - S_w / 3 with S_w from the w planes (k_ctlx_f64's shape).
 __global__ __launch_bounds__(256) void k_dipl_f64(DiplArgs a)
 {
     const int k = blockIdx.y * 256 + threadIdx.x, F = a.F;
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(256) void k_dipl_f64(DiplArgs a)
         }
     }
     const double S = a.sym ? 0.5 * ((sa + ta) - (sw + tw) / 3.0) : sa - sw / 3.0;
-    a.psum[s * a.Lp + k] = S + (double)(F - k) / 3.0;
+    a.psum[s * a.Lp + k] = S;
 }
 
 int launch_wsums(sr_ctx *ctx, const DiplArgs &a, int64_t rows)
@@ -159,7 +161,7 @@ int sr_ct_dipolar_long_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, i
         job.traceless = 1;
         if (int rc = sr_launch_ct_long(ctx, job)) return rc;
     }
-    if (int rc = sr_ct_finalize_f64_dev(ctx, psum, R, F, nV, Ct, dCt)) return rc;
+    if (int rc = sr_ct_finalize_weighted_f64_dev(ctx, psum, R, F, nV, Ct, dCt)) return rc;
     return sr_ct_dipolar_norm_dev(ctx, a.wsum, R, F, nV, Ct, dCt, wmean);
 }
 
@@ -196,8 +198,8 @@ int sr_ct_dipolar_cross_long_f32_dev(sr_ctx *ctx, const float *planes, int64_t N
         const int rc = st.finish();
         if (err || rc) return err ? err : rc;
     }
-    if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, P0, dP0)) return rc;
-    if (int rc = sr_ct_finalize_f64_dev(ctx, psum, R, F, nP, Ct, dCt)) return rc;
+    if (int rc = sr_ct_cross_p0_dev(ctx, psum, R, F, nP, 0.0, P0, dP0)) return rc;
+    if (int rc = sr_ct_finalize_weighted_f64_dev(ctx, psum, R, F, nP, Ct, dCt)) return rc;
     return sr_ct_dipolar_cross_norm_dev(ctx, wsum2, R, F, nP, Ct, dCt, P0, dP0);
 }
 

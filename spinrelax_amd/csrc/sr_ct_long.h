@@ -77,11 +77,11 @@ __global__ __launch_bounds__(256) void k_ctl_consts(CtlArgs a)
         // m_c: the chunk mean with its low four mantissa bits cleared, as in k_ct_rfft32 (3 m_c and 12 m_c exact in float32)
         const float wgt[6] = {1.0f, 3.0f, 12.0f, 12.0f, 12.0f, 2.0f};
         const float invF = 1.0f / (float)F;
-        // traceless: five signals and the constant 1/3 per product as for unit vectors, but no eps term (weps = 0): the caller's
-        // function has no trace part (sr_ct_dipolar_long.hip)
+        // traceless: five signals as for unit vectors, but neither the constant 1/3 per product nor the eps term (weps = 0): the
+        // caller's function has no trace part (sr_ct_dipolar_long.hip)
         const bool unit = a.traceless || fmaxf(fmaxf(red[0][6], red[1][6]), fmaxf(red[2][6], red[3][6])) < kUnitTolF;
         CtlConst c;
-        double Kc = unit ? 2.0 : 0.0;
+        double Kc = unit && !a.traceless ? 2.0 : 0.0;          // 6 x the 1/3 per product of unit vectors; the traceless form has none
         for (int i = 0; i < 6; ++i) {
             const float mean = ((red[0][i] + red[1][i]) + (red[2][i] + red[3][i])) * invF;
             c.m[i] = __builtin_bit_cast(float, __builtin_bit_cast(int, mean) & (int)0xFFFFFFF0);

@@ -162,8 +162,13 @@ int sr_ct_chunks_check(const char *who, int64_t frames, int64_t R, int64_t F, co
 double *sr_ct_psum(sr_ctx *ctx, double *psum_ws, int64_t rows, int64_t R, int64_t F);
 
 // sr_ct_cross.hip: k_ct_cross_p0 on raw sums (nP, R, sr_ct_psum_stride(F)) whose slot 0 holds lag 0: P0 (nP) the chunk mean of
-// 1.5 S / F - 0.5 and, when dP0 is not null, its std / (sqrt(R) - 1); device arrays, asynchronous on ctx->stream
-int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nP, double *P0, double *dP0);
+// 1.5 S / F - half and, when dP0 is not null, its std / (sqrt(R) - 1); device arrays, asynchronous on ctx->stream.  half: 0.5 for unit
+// vectors, 0 for the distance-weighted raw sums S_a - S_w / 3
+int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nP, double half, double *P0, double *dP0);
+
+// sr_ct.hip: sr_ct_finalize_f64_dev for the distance-weighted raw sums S_a - S_w / 3 (sr_ct_dipolar.hip): mean and std / (sqrt(R) - 1)
+// over the chunks of 1.5 S / (F - k), nothing subtracted
+int sr_ct_finalize_weighted_f64_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, int64_t nV, double *Ct, double *dCt);
 
 // sr_ct_cross_long.hip: the blocked form of the pair cross-correlation (raw sums in kernel 1's layout, lag 0 in slot 0), for what
 // sr_ct_rows_check(blocked = 1) admits: the range in which the kernels it shares with sr_ct_long.hip are tested
@@ -172,7 +177,7 @@ int sr_ct_cross_p0_dev(sr_ctx *ctx, const double *psum, int64_t R, int64_t F, in
 // A checked job whose tables the caller has put on `st` (sr_ct_stage_tables with room for 2 nP more int32 behind them): the launcher
 // appends its two slot tables and calls st->finish(), on every path.  ct: psum (nP, R, Lp), series = R nP, and planes = 3,
 // traceless = 0 for unit-vector planes (sr_ct_cross.hip) or planes = 4, traceless = 1 for the dipolar pack: five traceless signals and
-// S_a - S_w / 3 + F / 3 in slot 0 (sr_ct_dipolar_long.hip, mode 0 only)
+// S_a - S_w / 3 in slot 0 (sr_ct_dipolar_long.hip, mode 0 only)
 struct sr_stage;
 struct sr_ct_pair_job {
     sr_ct_job ct;

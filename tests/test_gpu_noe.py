@@ -101,13 +101,13 @@ def make_body(P, F, wobble=True, shift=SHIFT):
     return body, xyz, quat
 
 
-def oracle_sums(xyz, index, quat, blocks):
+def oracle_sums(xyz, index, quat, blocks, min_dist=MIN_DIST):
     """sums (B, npairs, 7) and sum r^-3 (B, npairs) by the definition; asserts the minimum distance"""
     x = np.asarray(xyz[:, index], dtype=np.float64)
     iu, ju = np.triu_indices(len(index), k=1)
     d = x[:, ju] - x[:, iu]
     r = np.sqrt((d * d).sum(axis=-1))
-    assert r.min() >= MIN_DIST, 'oracle: a pair comes as close as %.3g' % r.min()
+    assert r.min() >= min_dist, 'oracle: a pair comes as close as %.3g' % r.min()
     dp = d if quat is None else np.einsum('tab,tpb->tpa', rotmat(np.asarray(quat, dtype=np.float64)), d)
     per = np.empty(d.shape[:2] + (7,))
     per[..., 0] = r ** -6

@@ -64,13 +64,13 @@ def ctx():
     c.close()
 
 
-def oracle_G(xyz, index, quat, blocks, lags):
+def oracle_G(xyz, index, quat, blocks, lags, min_dist=MIN_DIST):
     """G and W (B, K, npairs) by the definition; asserts the minimum distance"""
     x = np.asarray(xyz[:, index], dtype=np.float64)
     iu, ju = np.triu_indices(len(index), k=1)
     d = x[:, ju] - x[:, iu]
     r = np.sqrt((d * d).sum(axis=-1))
-    assert r.min() >= MIN_DIST, 'oracle: a pair comes as close as %.3g' % r.min()
+    assert r.min() >= min_dist, 'oracle: a pair comes as close as %.3g' % r.min()
     dp = d if quat is None else np.einsum('tab,tpb->tpa', rotmat(np.asarray(quat, dtype=np.float64)), d)
     w = r ** -3
     G = np.empty((len(blocks), len(lags), iu.size))

@@ -18,35 +18,28 @@
 //   * lags that do not fill a block, and every lag in the validation mode (mode 1), take a float64 path in the same launch.
 // A chunk whose two series do not fit the LDS is refused here (sr_ct_cross_max_frames); the entry points sr_*ct_cross_long_* give such
 // chunks to the blocked form (sr_ct_cross_long.hip).
-#include "sr_ct_shift.h"
+// The workers, the serpentine, the float64 path and the argument struct: sr_ct_staged.h.
+//
+// Kernels:
+//   k_ct_cross     one (pair, chunk) per workgroup of 8 waves; lags 0 .. L
+//   k_ct_cross_p0  the equal-time value and its error from slot 0 of the raw sums
+#include "sr_ct_staged.h"
 
 namespace {
 
 constexpr int kCrossWaves = 8;
 
-struct CtCrossArgs {
-    const float *soa;
-    int64_t Npad;
-    const int64_t *chunk_start;   // device, may be null
-    const int32_t *pair_i, *pair_j;   // device
-    double *psum;                 // (nP, R, Lp)
-    int R, F, Fp, L, Lp, sym, mode;
-};
-
-__global__ __launch_bounds__(kCrossWaves * 64, 2) void k_ct_cross(CtCrossArgs a)
+__global__ __launch_bounds__(kCrossWaves * 64, 2) void k_ct_cross(CtStagedArgs a)
 {
     extern __shared__ __align__(16) float lds[];
     const int Fp = a.Fp, Hf = (Fp >> 3) * 12, F = a.F;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int p = blockIdx.x / a.R;
-    const int r = blockIdx.x - p * a.R;
+    const CtWorker w = ct_worker<kCrossWaves>(a, 1);
+    const int tid = w.tid, lane = w.lane, p = w.row;
     float *si = lds, *sj = lds + 2 * Hf;
 
     // ---- stage the two series ----
     {
-        const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
+        const int64_t start = ct_chunk_start(a, w);
         const float *pi = a.soa + (int64_t)a.pair_i[p] * 3 * a.Npad + start;
         const float *pj = a.soa + (int64_t)a.pair_j[p] * 3 * a.Npad + start;
         ct_stage_series<kCrossWaves * 64>(si, pi, pi + a.Npad, pi + 2 * a.Npad, F, Fp, Hf, tid);
@@ -54,47 +47,36 @@ __global__ __launch_bounds__(kCrossWaves * 64, 2) void k_ct_cross(CtCrossArgs a)
     }
     __syncthreads();
 
-    double *out = a.psum + ((int64_t)p * a.R + r) * a.Lp;
-    const int nb = (a.mode == 0) ? (a.L + 1) / kLagBlock : 0;
-    const double scale = a.sym ? 0.5 : 1.0;
+    const int NW = ct_workers<kCrossWaves>(1), wid = ct_worker_id<kCrossWaves>(w);
+    double *out = ct_psum_row(a, w, a.Lp);
+    const int nb = ct_full_blocks(a);
+    const int sym = a.sym;
+    const double scale = sym ? 0.5 : 1.0;
 
-    // ---- fast path: full lag blocks (lag 0 included), serpentine assignment balances the (F - lag) work ----
-    int g, l16;
-    lane_to_strip(lane, g, l16);
-    for (int i = 0; i * kCrossWaves < nb; ++i) {
-        const int k = (i & 1) ? i * kCrossWaves + (kCrossWaves - 1 - wave) : i * kCrossWaves + wave;
-        if (k >= nb) continue;
-        const int dw = k * kLagBlock;
+    // ---- fast path: full lag blocks (lag 0 included) ----
+    ct_for_each_lag_block(nb, NW, wid, lane, [=](int dw, int g, int l16) SR_CT_INLINE {
         double acc64[kLagsPerLane];
-#pragma unroll
-        for (int d = 0; d < kLagsPerLane; ++d) acc64[d] = 0.0;
+        ct_zero_lags(acc64);
         ct_shift_block(si, sj, Hf, F, dw, g, l16, acc64);                 // S_ij
-        if (a.sym) ct_shift_block(sj, si, Hf, F, dw, g, l16, acc64);      // + S_ji
+        if (sym) ct_shift_block(sj, si, Hf, F, dw, g, l16, acc64);        // + S_ji
         ct_combine_strips(acc64, l16);
         if (g == 0) {
-            double *o = out + dw + kLagsPerLane * l16;
+            double *o = ct_lag_slots(out, dw, l16);
 #pragma unroll
             for (int d = 0; d < kLagsPerLane; ++d) o[d] = scale * acc64[d];
         }
-    }
+    });
 
     // ---- float64 path: remaining lags (and every lag in validation mode) ----
-    for (int d = nb * kLagBlock + wave; d <= a.L; d += kCrossWaves) {
-        double s = 0.0;
-        for (int t = lane; t + d < F; t += 64) {
-            const int pa = lds_pos(t, 0, Hf), pb = lds_pos(t + d, 0, Hf);
-            const double x = (double)si[pa] * (double)sj[pb] + (double)si[pa + 4] * (double)sj[pb + 4] +
-                             (double)si[pa + 8] * (double)sj[pb + 8];
-            s += x * x;
-            if (a.sym) {
-                const double y = (double)sj[pa] * (double)si[pb] + (double)sj[pa + 4] * (double)si[pb + 4] +
-                                 (double)sj[pa + 8] * (double)si[pb + 8];
-                s += y * y;
-            }
+    ct_tail_lags<1>(nb * kLagBlock, a.L, F, NW, wid, lane, [=](int t, int d, double (&s)[1]) SR_CT_INLINE {
+        const int pa = lds_pos(t, 0, Hf), pb = lds_pos(t + d, 0, Hf);
+        const double x = ct_dot_f64(si, sj, pa, pb);
+        s[0] += x * x;
+        if (sym) {
+            const double y = ct_dot_f64(sj, si, pa, pb);
+            s[0] += y * y;
         }
-        s = wave_sum_f64(s);
-        if (lane == 0) out[d] = scale * s;
-    }
+    }, [=](int d, const double (&s)[1]) SR_CT_INLINE { out[d] = scale * s[0]; });
 }
 
 // P0[p] = mean over the chunks of 1.5 S[p][r][0] / F - half (half: k_ct_finalize's), summed in chunk order; dP0[p] (may be null) = their two-pass standard
@@ -155,10 +137,8 @@ static int cross_f32_dev(sr_ctx *ctx, const char *who, int blocked, const float 
         if (int rc = sr_launch_ct_cross_long(ctx, job)) return rc;
     } else {
         if (int rc = st.finish()) return rc;            // small tables: the caller's arrays are free again when this returns
-        CtCrossArgs a;
-        a.chunk_start = t.chunk_start; a.pair_i = t.pair_i; a.pair_j = t.pair_j;
-        a.soa = soa; a.Npad = Npad; a.psum = psum;
-        a.R = (int)R; a.F = (int)F; a.Fp = (int)ct_Fp(F); a.L = (int)L; a.Lp = (int)Lp; a.sym = sym; a.mode = mode;
+        CtStagedArgs a = ct_staged_args(soa, Npad, t.chunk_start, psum, R, F, mode);
+        a.pair_i = t.pair_i; a.pair_j = t.pair_j; a.sym = sym;
         if (int rc = sr_launch(ctx, k_ct_cross, dim3((unsigned)(nP * R)), dim3(kCrossWaves * 64),
                                sr_ct_lds_bytes(F, sr_ct_form_cross.bytes_per_frame), a))
             return rc;

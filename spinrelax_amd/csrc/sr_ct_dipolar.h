@@ -1,6 +1,7 @@
 // sr_ct_dipolar.h -- the scalar (w) series of the distance-weighted correlation kernels: k_ct_dipolar (sr_ct_dipolar.hip: one series
 // against itself) and k_ct_dipolar_cross (sr_ct_dipolar_cross.hip: the series of two vectors against each other) stage it in the same
-// LDS layout behind the three a planes of sr_ct_shift.h and run the same inner loop on it.
+// LDS layout behind the three a planes of sr_ct_shift.h and run the same inner loop on it; k_ct_modes (sr_ct_modes.hip) stages its five
+// signal series so and runs the loop on pairs of them.  Also the tile of the two normalising kernels (dip_scale_tile).
 //
 // A staged w series: Fp = ct_Fp(F) frames, zero behind frame F, parity-split 16-byte chunks, so that the 16 lag-lanes of a
 // ds_read_b128 group read 256 consecutive bytes; Hw = Fp / 2 floats per half.
@@ -73,6 +74,23 @@ __device__ __forceinline__ void dip_shift_block_w(const float *lwa, const float 
     }
 #undef SR_DIP_STEP
 #undef SR_DIP_LOAD_HALF
+}
+
+// the tile of the two normalising kernels (k_ct_dipolar_norm, k_ct_dipolar_cross_norm), 256 threads: Ct, dCt (L, n) scaled in place,
+// the 64 rows from row0 (vectors or pairs) x the 64 lags of blockIdx.x, row row0 + i by inv[i]
+__device__ __forceinline__ void dip_scale_tile(const double *inv, int L, int64_t n, int64_t row0, double *Ct, double *dCt)
+{
+    const int tid = threadIdx.x;
+    const int vl = tid & 63;
+    const int64_t v = row0 + vl;
+    if (v >= n) return;
+    for (int i = tid >> 6; i < 64; i += 4) {
+        const int d = blockIdx.x * 64 + i;              // lag index - 1
+        if (d >= L) break;
+        const int64_t o = (int64_t)d * n + v;
+        Ct[o] *= inv[vl];
+        dCt[o] *= inv[vl];
+    }
 }
 
 }  // namespace

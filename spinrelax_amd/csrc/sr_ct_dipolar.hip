@@ -19,8 +19,9 @@
 // Kernels:
 //   k_dipolar_rmin   r_ref per vector: a workgroup min over the frames, no atomics
 //   k_pack_dipolar   frame-major vectors (and optional distances) -> four planes per vector a_x, a_y, a_z, w in kernel 0's layout
-//                    (soa[(v * 4 + c) * Npad + n], zero for n in [N, Npad)); float64 arithmetic, rounded once to float32
-//   k_ct_dipolar<W>  one (vector, chunk) per workgroup or per slab of one, the dispatch of sr_launch_ct_direct: the three a planes staged
+//                    (soa[(v * 4 + c) * Npad + n], zero for n in [N, Npad)); float64 arithmetic, rounded once to float32; the tile
+//                    transpose is pack_planes_tile (sr_pack_planes.h)
+//   k_ct_dipolar<W>  one (vector, chunk) per workgroup or per slab of one (the scaffold and the launch ladder of sr_ct_staged.h): the three a planes staged
 //                    as the direct kernel stages them, the w series behind them (parity-split 16-byte chunks, so that the 16 lag-lanes
 //                    of a ds_read_b128 group read 256 consecutive bytes), 16 bytes per frame in all; per lag block ct_shift_block for
 //                    S_a and the same (strip, lag-lane) partition, 8-frame window rotation and float32 partial sums of at most 16 terms
@@ -33,6 +34,8 @@
 // whose w spans four decades (tests/test_gpu_ct_dipolar_mobile.py, docs/EXPERIMENTS.md section 38) 1.4e-7 of max(1, max |C_dd|) on C and
 // 1.9e-7 / (sqrt(R) - 1) on dC, the pair form 1.1e-7 and 1.3e-7 / (sqrt(R) - 1); mode 1 1e-15.
 #include "sr_ct_dipolar.h"
+#include "sr_ct_staged.h"
+#include "sr_pack_planes.h"
 #include <cmath>
 
 namespace {
@@ -40,9 +43,8 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // r_ref and the four-plane pack
 // ------------------------------------------------------------------------------------------
-constexpr int kDipVecs = 32;            // vectors per tile: a frame's 32 vectors are 96 consecutive floats
+constexpr int kDipVecs = kPlaneVecs;    // vectors per workgroup of k_dipolar_rmin: those of a tile of the pack, whose grid.y it is launched with
 constexpr int kDipRows = 32;            // frame rows of k_dipolar_rmin
-constexpr int kDipFrames = 64;          // frames per tile of k_pack_dipolar
 
 // min that keeps a NaN once it has one (a frame that is not finite must reach the host)
 __device__ __forceinline__ double min_nan(double m, double r) { return (r < m || r != r) ? r : m; }
@@ -82,75 +84,38 @@ __global__ __launch_bounds__(256) void k_pack_dipolar(const float *__restrict__ 
                                                       int64_t v0, int64_t nV, const double *__restrict__ rref, float *__restrict__ soa,
                                                       int64_t Npad)
 {
+    pack_planes_tile<4>(vecs, N, Vtot, v0, nV, soa, Npad, [=](const float *p, int64_t di, int64_t v, float (&o)[4]) {
 #pragma clang fp contract(off)
-    __shared__ float tile[kDipVecs * 4][kDipFrames + 1];
-    const int64_t n0 = (int64_t)blockIdx.x * kDipFrames;
-    const int64_t vb = (int64_t)blockIdx.y * kDipVecs;
-    const int nvec = (int)min((int64_t)kDipVecs, nV - vb);
-    const int tid = threadIdx.x;
-    for (int idx = tid; idx < kDipFrames * nvec; idx += 256) {
-        const int n = idx / nvec, k = idx - n * nvec;
-        const int64_t fr = n0 + n;
-        float ox = 0.f, oy = 0.f, oz = 0.f, ow = 0.f;
-        if (fr < N) {
-            const float *p = vecs + (fr * Vtot + v0 + vb + k) * 3;
-            double len;
-            const double r = dip_distance(p, dist, fr * Vtot + v0 + vb + k, len);
-            const double q = rref[vb + k] / r;
-            const double w = q * q * q;
-            const double s = sqrt(w) / len;
-            ox = (float)((double)p[0] * s);
-            oy = (float)((double)p[1] * s);
-            oz = (float)((double)p[2] * s);
-            ow = (float)w;
-        }
-        tile[k * 4 + 0][n] = ox;
-        tile[k * 4 + 1][n] = oy;
-        tile[k * 4 + 2][n] = oz;
-        tile[k * 4 + 3][n] = ow;
-    }
-    __syncthreads();
-    const int row = nvec * 4;
-    for (int idx = tid; idx < kDipFrames * row; idx += 256) {
-        const int k = idx / kDipFrames, n = idx - k * kDipFrames;
-        const int64_t fr = n0 + n;
-        if (fr < Npad) soa[(vb * 4 + k) * Npad + fr] = tile[k][n];
-    }
+        double len;
+        const double r = dip_distance(p, dist, di, len);
+        const double q = rref[v] / r;
+        const double w = q * q * q;
+        const double s = sqrt(w) / len;
+        o[0] = (float)((double)p[0] * s);
+        o[1] = (float)((double)p[1] * s);
+        o[2] = (float)((double)p[2] * s);
+        o[3] = (float)w;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
 // the correlation kernel
 // ------------------------------------------------------------------------------------------
-struct CtDipArgs {
-    const float *soa;             // (nV, 4, Npad)
-    int64_t Npad;
-    const int64_t *chunk_start;   // device, may be null
-    double *psum;                 // (nV, R, Lp)
-    double *wsum;                 // (nV, R, 2): sum of w and of w^2 over the chunk
-    int R, F, Fp, L, Lp, nslab, mode;
-};
-
 #ifndef SR_CT_DIP_WAVES_EU
 #define SR_CT_DIP_WAVES_EU 3
 #endif
 template <int W>
-__global__ __launch_bounds__(W * 64, SR_CT_DIP_WAVES_EU) void k_ct_dipolar(CtDipArgs a)
+__global__ __launch_bounds__(W * 64, SR_CT_DIP_WAVES_EU) void k_ct_dipolar(CtStagedArgs a)     // soa (nV, 4, Npad); sums (nV, R, 2): the sum of w and of w^2 over the chunk
 {
     extern __shared__ __align__(16) float lds[];
     const int Fp = a.Fp, Hf = (Fp >> 3) * 12, Hw = Fp >> 1, F = a.F;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int series = blockIdx.x / a.nslab;
-    const int slab = blockIdx.x - series * a.nslab;
-    const int v = series / a.R;
-    const int r = series - v * a.R;
+    const CtWorker w = ct_worker<W>(a, a.nslab);
+    const int tid = w.tid, lane = w.lane, wave = w.wave, slab = w.slab, v = w.row, r = w.r;
     float *lw = lds + 2 * Hf;              // the w series, behind the 3 Fp floats of the a planes
 
     // ---- stage the four series (coalesced dword loads; zero padding behind frame F) ----
     {
-        const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
-        const float *px = a.soa + ((int64_t)v * 4 + 0) * a.Npad + start;
+        const float *px = a.soa + ((int64_t)v * 4 + 0) * a.Npad + ct_chunk_start(a, w);
         const float *py = px + a.Npad;
         const float *pz = py + a.Npad;
         const float *pw = pz + a.Npad;
@@ -159,7 +124,7 @@ __global__ __launch_bounds__(W * 64, SR_CT_DIP_WAVES_EU) void k_ct_dipolar(CtDip
     }
     __syncthreads();
 
-    const int nb = (a.mode == 0) ? (a.L + 1) / kLagBlock : 0;
+    const int nb = ct_full_blocks(a);
 
     // ---- sum of w and of w^2 over the chunk, float64, fixed order: wave 0 of slab 0 writes them out; every wave with a lag block takes
     // the centre of its float32 partial sums from them.  The terms of both sums are about w w' <= 1, on average <w^2> of the chunk, which
@@ -176,53 +141,38 @@ __global__ __launch_bounds__(W * 64, SR_CT_DIP_WAVES_EU) void k_ct_dipolar(CtDip
         s1 = wave_sum_f64(s1);
         s2 = wave_sum_f64(s2);
         if (slab == 0 && wave == 0 && lane == 0) {
-            double *o = a.wsum + ((int64_t)v * a.R + r) * 2;
+            double *o = a.sums + ((int64_t)v * a.R + r) * 2;
             o[0] = s1;
             o[1] = s2;
         }
         center = fminf(kCenter, (float)(8.0 * s2 / (double)F));
     }
 
-    const int NW = a.nslab * W;            // workers (waves) per series
-    const int wid = slab * W + wave;
-    double *out = a.psum + ((int64_t)v * a.R + r) * a.Lp;
+    const int NW = ct_workers<W>(a.nslab), wid = ct_worker_id<W>(w);
+    double *out = ct_psum_row(a, w, a.Lp);
 
     // ---- fast path: full lag blocks (lag 0 included), serpentine assignment balances the (F - lag) work ----
-    int g, l16;
-    lane_to_strip(lane, g, l16);
-    for (int i = 0; i * NW < nb; ++i) {
-        const int k = (i & 1) ? i * NW + (NW - 1 - wid) : i * NW + wid;
-        if (k >= nb) continue;
-        const int dw = k * kLagBlock;
+    ct_for_each_lag_block(nb, NW, wid, lane, [=](int dw, int g, int l16) SR_CT_INLINE {
         double sa[kLagsPerLane], sw[kLagsPerLane];
-#pragma unroll
-        for (int d = 0; d < kLagsPerLane; ++d) sa[d] = sw[d] = 0.0;
+        ct_zero_lags(sa);
+        ct_zero_lags(sw);
         ct_shift_block(lds, lds, Hf, F, dw, g, l16, sa, center);
         ct_combine_strips(sa, l16);
         dip_shift_block_w(lw, lw, Hw, F, dw, g, l16, sw, center);
         ct_combine_strips(sw, l16);
         if (g == 0) {
-            const int lag0 = dw + kLagsPerLane * l16;
-            double *o = out + lag0;
+            double *o = ct_lag_slots(out, dw, l16);
 #pragma unroll
             for (int d = 0; d < kLagsPerLane; ++d) o[d] = sa[d] - sw[d] / 3.0;
         }
-    }
+    });
 
     // ---- float64 path: remaining lags (and every lag in validation mode) ----
-    for (int d = nb * kLagBlock + wid; d <= a.L; d += NW) {
-        double s = 0.0, q = 0.0;
-        for (int j = lane; j + d < F; j += 64) {
-            const int pa = lds_pos(j, 0, Hf), pb = lds_pos(j + d, 0, Hf);
-            const double x = (double)lds[pa] * (double)lds[pb] + (double)lds[pa + 4] * (double)lds[pb + 4] +
-                             (double)lds[pa + 8] * (double)lds[pb + 8];
-            s += x * x;
-            q += (double)lw[lds_wpos(j, Hw)] * (double)lw[lds_wpos(j + d, Hw)];
-        }
-        s = wave_sum_f64(s);
-        q = wave_sum_f64(q);
-        if (lane == 0) out[d] = s - q / 3.0;
-    }
+    ct_tail_lags<2>(nb * kLagBlock, a.L, F, NW, wid, lane, [=](int j, int d, double (&s)[2]) SR_CT_INLINE {
+        const double x = ct_dot_f64(lds, lds, lds_pos(j, 0, Hf), lds_pos(j + d, 0, Hf));
+        s[0] += x * x;
+        s[1] += (double)lw[lds_wpos(j, Hw)] * (double)lw[lds_wpos(j + d, Hw)];
+    }, [=](int d, const double (&s)[2]) SR_CT_INLINE { out[d] = s[0] - s[1] / 3.0; });
 }
 
 // Ct, dCt (L, nV) of k_ct_finalize scaled in place by 1 / (mean over the chunks of n_r = sum_t w^2 / F); wmean (nV, 2) = <w>, <w^2> over
@@ -248,22 +198,7 @@ __global__ __launch_bounds__(256) void k_ct_dipolar_norm(const double *__restric
         }
     }
     __syncthreads();
-    const int vl = tid & 63;
-    const int64_t v = v0 + vl;
-    if (v >= nV) return;
-    for (int i = tid >> 6; i < 64; i += 4) {
-        const int d = blockIdx.x * 64 + i;              // lag index - 1
-        if (d >= L) break;
-        const int64_t o = (int64_t)d * nV + v;
-        Ct[o] *= inv[vl];
-        dCt[o] *= inv[vl];
-    }
-}
-
-template <int W>
-int launch_dip(sr_ctx *ctx, const CtDipArgs &a, int64_t nblocks, size_t lds_bytes)
-{
-    return sr_launch(ctx, k_ct_dipolar<W>, dim3((unsigned)nblocks), dim3(W * 64), lds_bytes, a);
+    dip_scale_tile(inv, L, nV, v0, Ct, dCt);
 }
 
 }  // namespace
@@ -290,15 +225,11 @@ int sr_pack_dipolar_f32_dev(sr_ctx *ctx, const float *vecs, const float *dist, i
 {
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(vecs && planes && rref, -2, "sr_pack_dipolar_f32_dev: null pointer");
-    SR_REQUIRE(N > 0 && Vtot > 0 && nV > 0 && v0 >= 0 && v0 + nV <= Vtot, -3, "sr_pack_dipolar_f32_dev: bad shape N=%lld Vtot=%lld v0=%lld nV=%lld",
-               (long long)N, (long long)Vtot, (long long)v0, (long long)nV);
-    SR_REQUIRE(Npad >= N && Npad % 4 == 0, -3, "sr_pack_dipolar_f32_dev: Npad=%lld must be >= N and a multiple of 4", (long long)Npad);
-    const int64_t gx = (Npad + kDipFrames - 1) / kDipFrames;
-    const int64_t gy = (nV + kDipVecs - 1) / kDipVecs;
-    SR_REQUIRE(gy <= 65535, -3, "sr_pack_dipolar_f32_dev: too many vectors in one call (%lld)", (long long)nV);
-    hipLaunchKernelGGL(k_dipolar_rmin, dim3((unsigned)gy), dim3(kDipVecs * kDipRows), 0, ctx->stream, vecs, dist, N, Vtot, v0, nV, rref);
+    dim3 grid;
+    if (int rc = pack_planes_grid("sr_pack_dipolar_f32_dev", N, Vtot, v0, nV, Npad, grid)) return rc;
+    hipLaunchKernelGGL(k_dipolar_rmin, dim3(grid.y), dim3(kDipVecs * kDipRows), 0, ctx->stream, vecs, dist, N, Vtot, v0, nV, rref);
     SR_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_pack_dipolar, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, ctx->stream, vecs, dist, N, Vtot, v0, nV, rref, planes, Npad);
+    hipLaunchKernelGGL(k_pack_dipolar, grid, dim3(256), 0, ctx->stream, vecs, dist, N, Vtot, v0, nV, rref, planes, Npad);
     SR_HIP(hipGetLastError());
     return 0;
 }
@@ -310,35 +241,17 @@ int sr_ct_dipolar_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, int64_
     SR_REQUIRE(planes && Ct && dCt && wmean, -2, "sr_ct_dipolar_f32_dev: null pointer");
     const sr_ct_rows w = {"sr_ct_dipolar_f32_dev", Npad, nV, R, F, chunk_start_host, nullptr, nullptr, 0, 0, mode, 0};
     if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_dipolar)) return rc;
-    const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
     double *psum = sr_ct_psum(ctx, psum_ws, nV, R, F);
     if (!psum) return -5;
     // ---- stage the chunk starts; the chunk sums of w and w^2 live behind them ----
     sr_stage st(ctx);
-    CtDipArgs a;
-    a.chunk_start = sr_ct_stage_tables(st, w, 2 * (size_t)(nV * R) * sizeof(double)).chunk_start;
-    a.wsum = st.take<double>(2 * (size_t)(nV * R));
+    const int64_t *cs_dev = sr_ct_stage_tables(st, w, 2 * (size_t)(nV * R) * sizeof(double)).chunk_start;
+    CtStagedArgs a = ct_staged_args(planes, Npad, cs_dev, psum, R, F, mode);
+    a.sums = st.take<double>(2 * (size_t)(nV * R));
     if (int rc = chunk_start_host ? st.finish() : st.rc) return rc;     // tiny table: the caller's array is free again when this returns
-    // ---- launch: the dispatch of sr_launch_ct_direct ----
-    a.soa = planes; a.Npad = Npad; a.psum = psum;
-    a.R = (int)R; a.F = (int)F; a.Fp = (int)ct_Fp(F); a.L = (int)L; a.Lp = (int)Lp; a.mode = mode;
-    const size_t lds_bytes = sr_ct_lds_bytes(F, sr_ct_form_dipolar.bytes_per_frame);
-    const int nb = mode == 0 ? (int)((L + 1) / kLagBlock) : 0;
-    const int64_t series = R * nV;
-    int rc;
-    if (mode == 1) {
-        a.nslab = 1;
-        rc = launch_dip<4>(ctx, a, series, lds_bytes);
-    } else if (nb >= 16) {
-        a.nslab = nb >= 64 ? nb / 32 : 1;            // about 4-8 lag blocks per wave
-        rc = launch_dip<4>(ctx, a, series * a.nslab, lds_bytes);
-    } else {
-        a.nslab = nb > 0 ? nb : 1;                   // one wave per workgroup, one lag block per wave
-        rc = launch_dip<1>(ctx, a, series * a.nslab, lds_bytes);
-    }
-    if (rc) return rc;
-    if (int rc2 = sr_ct_finalize_weighted_f64_dev(ctx, psum, R, F, nV, Ct, dCt)) return rc2;
-    return sr_ct_dipolar_norm_dev(ctx, a.wsum, R, F, nV, Ct, dCt, wmean);
+    if (int rc = ct_launch_slabs(ctx, k_ct_dipolar<1>, k_ct_dipolar<4>, a, R * nV, sr_ct_form_dipolar.bytes_per_frame)) return rc;
+    if (int rc = sr_ct_finalize_weighted_f64_dev(ctx, psum, R, F, nV, Ct, dCt)) return rc;
+    return sr_ct_dipolar_norm_dev(ctx, a.sums, R, F, nV, Ct, dCt, wmean);
 }
 
 }  // extern "C"

@@ -15,7 +15,8 @@
 // convention: a ratio of chunk means, the normaliser's own scatter is ignored; the r_ref factors cancel).  For i = j the result is
 // C_dd of k_ct_dipolar with P0 = 1, to rounding.
 //
-// Kernel: one workgroup of 8 waves per (pair, chunk) (k_ct_cross's shape) stages eight series in LDS: for i and for j the three a planes
+// Kernels: k_ct_dipolar_cross_norm, the scaling above (its tile: dip_scale_tile, sr_ct_dipolar.h), and k_ct_dipolar_cross, on the
+// scaffold of sr_ct_staged.h: one workgroup of 8 waves per (pair, chunk) (k_ct_cross's shape) stages eight series in LDS: for i and for j the three a planes
 // (ct_stage_series) and the w series behind them (lds_wpos), 32 bytes per frame, 138 240 B at F = 4096: one workgroup per CU.  Per
 // block of 128 lags a wave runs ct_shift_block(a_i, a_j) and dip_shift_block_w(w_i, w_j), with sym both again with the series
 // exchanged; the float32 partial sums start at -min(kCenter, 8 sqrt(sum w_i^2 sum w_j^2) / F), the adaptive centre of k_ct_dipolar
@@ -23,31 +24,19 @@
 // w_j^2 of the chunk in float64 and wave 0 writes them out.  No atomics, no scratch: equal input gives bit-equal output.
 // A chunk must fit 32 ct_Fp(F) bytes of LDS: F <= 4896 at 160 KiB.  Longer chunks take the blocked form (sr_ct_dipolar_long.hip).
 #include "sr_ct_dipolar.h"
+#include "sr_ct_staged.h"
 #include <cmath>
 
 namespace {
 
 constexpr int kDipCrossWaves = 8;
 
-struct CtDipCrossArgs {
-    const float *soa;             // (nV, 4, Npad)
-    int64_t Npad;
-    const int64_t *chunk_start;   // device, may be null
-    const int32_t *pair_i, *pair_j;   // device
-    double *psum;                 // (nP, R, Lp)
-    double *wsum2;                // (nP, R, 2): sum of w_i^2 and of w_j^2 over the chunk
-    int R, F, Fp, L, Lp, sym, mode;
-};
-
-__global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtDipCrossArgs a)
+__global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtStagedArgs a)     // soa (nV, 4, Npad); sums = wsum2 (nP, R, 2): the sum of w_i^2 and of w_j^2 over the chunk
 {
     extern __shared__ __align__(16) float lds[];
     const int Fp = a.Fp, Hf = (Fp >> 3) * 12, Hw = Fp >> 1, F = a.F;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int p = blockIdx.x / a.R;
-    const int r = blockIdx.x - p * a.R;
+    const CtWorker w = ct_worker<kDipCrossWaves>(a, 1);
+    const int tid = w.tid, lane = w.lane, wave = w.wave, p = w.row, r = w.r;
     // per vector 4 Fp floats: the three a planes (2 Hf = 3 Fp floats) and the w series behind them
     float *ai = lds, *wi = lds + 2 * Hf;
     float *aj = lds + 4 * Fp, *wj = aj + 2 * Hf;
@@ -64,7 +53,7 @@ __global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtD
 
     // ---- stage the eight series (coalesced dword loads; zero padding behind frame F) ----
     {
-        const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
+        const int64_t start = ct_chunk_start(a, w);
         const float *pi = a.soa + (int64_t)vi * 4 * a.Npad + start;
         const float *pj = a.soa + (int64_t)vj * 4 * a.Npad + start;
         const float *pwi = pi + 3 * a.Npad, *pwj = pj + 3 * a.Npad;
@@ -79,9 +68,11 @@ __global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtD
     }
     __syncthreads();
 
-    double *out = a.psum + ((int64_t)p * a.R + r) * a.Lp;
-    const int nb = (a.mode == 0) ? (a.L + 1) / kLagBlock : 0;
-    const double scale = a.sym ? 0.5 : 1.0;
+    const int NW = ct_workers<kDipCrossWaves>(1), wid = ct_worker_id<kDipCrossWaves>(w);
+    double *out = ct_psum_row(a, w, a.Lp);
+    const int nb = ct_full_blocks(a);
+    const int sym = a.sym;
+    const double scale = sym ? 0.5 : 1.0;
 
     // ---- sum of w_i^2 and of w_j^2 over the chunk, float64, fixed order: wave 0 writes them out; every wave with a lag block takes the
     // centre of its float32 partial sums from them (k_ct_dipolar's adaptive centre: the terms of both sums are <= w_i w_j', on average
@@ -98,60 +89,46 @@ __global__ __launch_bounds__(kDipCrossWaves * 64, 2) void k_ct_dipolar_cross(CtD
         si = wave_sum_f64(si);
         sj = wave_sum_f64(sj);
         if (wave == 0 && lane == 0) {
-            double *o = a.wsum2 + ((int64_t)p * a.R + r) * 2;
+            double *o = a.sums + ((int64_t)p * a.R + r) * 2;
             o[swapped ? 1 : 0] = si;
             o[swapped ? 0 : 1] = sj;
         }
         center = fminf(kCenter, (float)(8.0 * sqrt(si * sj) / (double)F));
     }
 
-    // ---- fast path: full lag blocks (lag 0 included), serpentine assignment balances the (F - lag) work ----
-    int g, l16;
-    lane_to_strip(lane, g, l16);
-    for (int i = 0; i * kDipCrossWaves < nb; ++i) {
-        const int k = (i & 1) ? i * kDipCrossWaves + (kDipCrossWaves - 1 - wave) : i * kDipCrossWaves + wave;
-        if (k >= nb) continue;
-        const int dw = k * kLagBlock;
+    // ---- fast path: full lag blocks (lag 0 included) ----
+    ct_for_each_lag_block(nb, NW, wid, lane, [=](int dw, int g, int l16) SR_CT_INLINE {
         double sa[kLagsPerLane], sw[kLagsPerLane];
-#pragma unroll
-        for (int d = 0; d < kLagsPerLane; ++d) sa[d] = sw[d] = 0.0;
+        ct_zero_lags(sa);
+        ct_zero_lags(sw);
         ct_shift_block(ai, aj, Hf, F, dw, g, l16, sa, center);                 // S_a of (i, j)
         dip_shift_block_w(wi, wj, Hw, F, dw, g, l16, sw, center);              // S_w of (i, j)
-        if (a.sym) {
+        if (sym) {
             ct_shift_block(aj, ai, Hf, F, dw, g, l16, sa, center);             // + (j, i)
             dip_shift_block_w(wj, wi, Hw, F, dw, g, l16, sw, center);
         }
         ct_combine_strips(sa, l16);
         ct_combine_strips(sw, l16);
         if (g == 0) {
-            const int lag0 = dw + kLagsPerLane * l16;
-            double *o = out + lag0;
+            double *o = ct_lag_slots(out, dw, l16);
 #pragma unroll
             for (int d = 0; d < kLagsPerLane; ++d) o[d] = scale * (sa[d] - sw[d] / 3.0);
         }
-    }
+    });
 
     // ---- float64 path: remaining lags (and every lag in validation mode) ----
-    for (int d = nb * kLagBlock + wave; d <= a.L; d += kDipCrossWaves) {
-        double s = 0.0, q = 0.0;
-        for (int t = lane; t + d < F; t += 64) {
-            const int pa = lds_pos(t, 0, Hf), pb = lds_pos(t + d, 0, Hf);
-            const int wa = lds_wpos(t, Hw), wb = lds_wpos(t + d, Hw);
-            const double x = (double)ai[pa] * (double)aj[pb] + (double)ai[pa + 4] * (double)aj[pb + 4] +
-                             (double)ai[pa + 8] * (double)aj[pb + 8];
-            s += x * x;
-            q += (double)wi[wa] * (double)wj[wb];
-            if (a.sym) {
-                const double y = (double)aj[pa] * (double)ai[pb] + (double)aj[pa + 4] * (double)ai[pb + 4] +
-                                 (double)aj[pa + 8] * (double)ai[pb + 8];
-                s += y * y;
-                q += (double)wj[wa] * (double)wi[wb];
-            }
+    ct_tail_lags<2>(nb * kLagBlock, a.L, F, NW, wid, lane, [=](int t, int d, double (&s)[2]) SR_CT_INLINE {
+        const int pa = lds_pos(t, 0, Hf), pb = lds_pos(t + d, 0, Hf);
+        const int wa = lds_wpos(t, Hw), wb = lds_wpos(t + d, Hw);
+        const double x = ct_dot_f64(ai, aj, pa, pb);
+        s[0] += x * x;
+        s[1] += (double)wi[wa] * (double)wj[wb];
+        if (sym) {
+            const double y = ct_dot_f64(aj, ai, pa, pb);
+            s[0] += y * y;
+            s[1] += (double)wj[wa] * (double)wi[wb];
         }
-        s = wave_sum_f64(s);
-        q = wave_sum_f64(q);
-        if (lane == 0) out[d] = scale * (s - q / 3.0);
-    }
+    }, [=](int d, const double (&s)[2]) SR_CT_INLINE { out[d] = scale * (s[0] - s[1] / 3.0); });
 }
 
 // Ct, dCt (L, nP) of k_ct_finalize and P0, dP0 (nP; dP0 may be null) of k_ct_cross_p0 scaled in place by 1 / sqrt(n_i n_j), n_v the mean
@@ -178,16 +155,7 @@ __global__ __launch_bounds__(256) void k_ct_dipolar_cross_norm(const double *__r
         }
     }
     __syncthreads();
-    const int pl = tid & 63;
-    const int64_t p = p0 + pl;
-    if (p >= nP) return;
-    for (int i = tid >> 6; i < 64; i += 4) {
-        const int d = blockIdx.x * 64 + i;              // lag index - 1
-        if (d >= L) break;
-        const int64_t o = (int64_t)d * nP + p;
-        Ct[o] *= inv[pl];
-        dCt[o] *= inv[pl];
-    }
+    dip_scale_tile(inv, L, nP, p0, Ct, dCt);
 }
 
 }  // namespace
@@ -219,17 +187,14 @@ int sr_ct_dipolar_cross_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, 
     SR_REQUIRE(planes && P0 && Ct && dCt && wsum2, -2, "%s: null pointer", who);
     const sr_ct_rows w = {who, Npad, nV, R, F, chunk_start_host, pair_i_host, pair_j_host, nP, sym, mode, 0};
     if (int rc = sr_ct_rows_check(ctx, w, sr_ct_form_dipolar_cross)) return rc;
-    const int64_t L = F / 2, Lp = sr_ct_psum_stride(F);
     double *psum = sr_ct_psum(ctx, psum_ws, nP, R, F);
     if (!psum) return -5;
     sr_stage st(ctx);
     const sr_ct_tables t = sr_ct_stage_tables(st, w, 0);
     if (int rc = st.finish()) return rc;            // small tables: the caller's arrays are free again when this returns
     // ---- launch ----
-    CtDipCrossArgs a;
-    a.chunk_start = t.chunk_start; a.pair_i = t.pair_i; a.pair_j = t.pair_j;
-    a.soa = planes; a.Npad = Npad; a.psum = psum; a.wsum2 = wsum2;
-    a.R = (int)R; a.F = (int)F; a.Fp = (int)ct_Fp(F); a.L = (int)L; a.Lp = (int)Lp; a.sym = sym; a.mode = mode;
+    CtStagedArgs a = ct_staged_args(planes, Npad, t.chunk_start, psum, R, F, mode);
+    a.pair_i = t.pair_i; a.pair_j = t.pair_j; a.sym = sym; a.sums = wsum2;
     if (int rc = sr_launch(ctx, k_ct_dipolar_cross, dim3((unsigned)(nP * R)), dim3(kDipCrossWaves * 64),
                            sr_ct_lds_bytes(F, sr_ct_form_dipolar_cross.bytes_per_frame), a))
         return rc;

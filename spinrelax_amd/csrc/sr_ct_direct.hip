@@ -24,66 +24,56 @@
 //     float64 every 8 steps; strips are combined with two float64 wave shuffles; no atomics;
 //   * lags that do not fill a 128-lag block (for F = 4096 only lag 2048) and the validation mode run
 //     through a simple float64 path in the same launch.
-// The layout, the lane map and the lag-block loop are in sr_ct_shift.h: k_ct_cross (sr_ct_cross.hip) runs them on two series.
-#include "sr_ct_shift.h"
+// The layout, the lane map and the lag-block loop are in sr_ct_shift.h; the workers, the serpentine, the float64 path and the launch
+// ladder, which the other staged kernels share, in sr_ct_staged.h.
+//
+// Kernels:
+//   k_ct_palmer<W>  one (vector, chunk) per workgroup of W waves or per slab of one; lags 1 .. L (slot 0 of a psum row stays unused)
+#include "sr_ct_staged.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------
 // kernel 1
 // ------------------------------------------------------------------------------------------
-struct CtArgs {
-    const float *soa;
-    int64_t Npad;
-    const int64_t *chunk_start;   // device, may be null
-    double *psum;                 // (nV, R, Lp)
-    int R, F, Fp, L, Lp, nslab, mode;
-};
-
 #ifndef SR_CT_WAVES_EU
 #define SR_CT_WAVES_EU 3
 #endif
 template <int W>
-__global__ __launch_bounds__(W * 64, SR_CT_WAVES_EU) void k_ct_palmer(CtArgs a)
+__global__ __launch_bounds__(W * 64, SR_CT_WAVES_EU) void k_ct_palmer(CtStagedArgs a)
 {
     extern __shared__ __align__(16) float lds[];
     // This is the throughput kernel of the pipeline; the fit wavefronts of the previous batch share its SIMDs.  Raised
     // issue priority makes them fill the slots this kernel leaves idle instead of taking turns with it.
     __builtin_amdgcn_s_setprio(3);
     const int Fp = a.Fp, Hf = (Fp >> 3) * 12, F = a.F;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int series = blockIdx.x / a.nslab;
-    const int slab = blockIdx.x - series * a.nslab;
-    const int v = series / a.R;
-    const int r = series - v * a.R;
+    const CtWorker w = ct_worker<W>(a, a.nslab);
+    const int tid = w.tid, lane = w.lane;
 
     // ---- stage the series (coalesced dword loads; zero padding behind frame F) ----
     {
-        const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
-        const float *px = a.soa + ((int64_t)v * 3 + 0) * a.Npad + start;
+        const float *px = a.soa + ((int64_t)w.row * 3 + 0) * a.Npad + ct_chunk_start(a, w);
         const float *py = px + a.Npad;
         const float *pz = py + a.Npad;
         ct_stage_series<W * 64>(lds, px, py, pz, F, Fp, Hf, tid);
     }
     __syncthreads();
 
-    const int NW = a.nslab * W;            // workers (waves) per series
-    const int wid = slab * W + wave;
-    double *out = a.psum + ((int64_t)v * a.R + r) * a.Lp;
-    const int nb = (a.mode == 0) ? (a.L + 1) / kLagBlock : 0;
+    const int NW = ct_workers<W>(a.nslab), wid = ct_worker_id<W>(w);
+    double *out = ct_psum_row(a, w, a.Lp);
+    const int nb = ct_full_blocks(a);
 
-    // ---- fast path: full lag blocks, serpentine assignment balances the (F - lag) work ----
+    // ---- fast path: full lag blocks, serpentine assignment balances the (F - lag) work.  This loop and the next are those of
+    // ct_for_each_lag_block and ct_tail_lags (sr_ct_staged.h), written out: through the helpers the compiler lays the same instructions
+    // out in another order, and this kernel's code object is held to "same" from revision to revision (scripts/dev/isa_diff.py) ----
     int g, l16;
     lane_to_strip(lane, g, l16);
     for (int i = 0; i * NW < nb; ++i) {
-        const int k = (i & 1) ? i * NW + (NW - 1 - wid) : i * NW + wid;
+        const int k = ct_serpentine(i, NW, wid);
         if (k >= nb) continue;
         const int dw = k * kLagBlock;
         double acc64[kLagsPerLane];
-#pragma unroll
-        for (int d = 0; d < kLagsPerLane; ++d) acc64[d] = 0.0;
+        ct_zero_lags(acc64);
         ct_shift_block(lds, lds, Hf, F, dw, g, l16, acc64);
         ct_combine_strips(acc64, l16);
         if (g == 0) {
@@ -93,28 +83,17 @@ __global__ __launch_bounds__(W * 64, SR_CT_WAVES_EU) void k_ct_palmer(CtArgs a)
         }
     }
 
-    // ---- float64 path: remaining lags (and every lag in validation mode) ----
-    {
-        int lo = nb * kLagBlock;
-        if (lo < 1) lo = 1;
-        for (int d = lo + wid; d <= a.L; d += NW) {
-            double s = 0.0;
-            for (int j = lane; j + d < F; j += 64) {
-                const int pa = lds_pos(j, 0, Hf), pb = lds_pos(j + d, 0, Hf);
-                const double x = (double)lds[pa] * (double)lds[pb] + (double)lds[pa + 4] * (double)lds[pb + 4] +
-                                 (double)lds[pa + 8] * (double)lds[pb + 8];
-                s += x * x;
-            }
-            s = wave_sum_f64(s);
-            if (lane == 0) out[d] = s;
+    // ---- float64 path: remaining lags (and every lag in validation mode), from lag 1: slot 0 of a psum row stays unused ----
+    for (int d = max(nb * kLagBlock, 1) + wid; d <= a.L; d += NW) {
+        double s = 0.0;
+        for (int j = lane; j + d < F; j += 64) {
+            const int pa = lds_pos(j, 0, Hf), pb = lds_pos(j + d, 0, Hf);
+            const double x = ct_dot_f64(lds, lds, pa, pb);
+            s += x * x;
         }
+        s = wave_sum_f64(s);
+        if (lane == 0) out[d] = s;
     }
-}
-
-template <int W>
-int launch_ct(sr_ctx *ctx, const CtArgs &a, int64_t nblocks, size_t lds_bytes)
-{
-    return sr_launch(ctx, k_ct_palmer<W>, dim3((unsigned)nblocks), dim3(W * 64), lds_bytes, a);
 }
 
 }  // namespace
@@ -131,19 +110,6 @@ int64_t sr_ct_direct_max_frames(size_t lds_limit)
 // Called by sr_ct_palmer_sums_f32_dev (sr_ct.hip), which has checked that the series fits the LDS.
 int sr_launch_ct_direct(sr_ctx *ctx, const sr_ct_job &j, int mode)
 {
-    CtArgs a;
-    a.soa = j.soa; a.Npad = j.Npad; a.chunk_start = j.cs_dev; a.psum = j.psum;
-    a.R = j.R; a.F = j.F; a.Fp = (int)ct_Fp(j.F); a.L = j.L; a.Lp = j.Lp; a.mode = mode;
-    const size_t lds_bytes = sr_ct_direct_lds_bytes(j.F);
-    const int nb = mode == 0 ? (j.L + 1) / kLagBlock : 0;
-    if (mode == 1) {
-        a.nslab = 1;
-        return launch_ct<4>(ctx, a, j.series, lds_bytes);
-    }
-    if (nb >= 16) {
-        a.nslab = nb >= 64 ? nb / 32 : 1;            // about 4-8 lag blocks per wave
-        return launch_ct<4>(ctx, a, j.series * a.nslab, lds_bytes);
-    }
-    a.nslab = nb > 0 ? nb : 1;                       // one wave per workgroup, one lag block per wave
-    return launch_ct<1>(ctx, a, j.series * a.nslab, lds_bytes);
+    CtStagedArgs a = ct_staged_args(j.soa, j.Npad, j.cs_dev, j.psum, j.R, j.F, mode);
+    return ct_launch_slabs(ctx, k_ct_palmer<1>, k_ct_palmer<4>, a, j.series, 12);
 }

@@ -14,8 +14,8 @@
 //   k_pack_modes        frame-major vectors of any positive length -> five planes per vector s0 .. s4 in kernel 0's layout
 //                       (soa[(v * 5 + c) * Npad + n], zero for n in [N, Npad)); F and the normalisation in float64, each value rounded
 //                       once to float32; a vector with a frame that is not finite or of zero length gets bad[v] = 1 (a plain store of
-//                       the same value by whoever meets one: no atomics)
-//   k_ct_modes<W>       one (vector, chunk) per workgroup or per slab of one, the dispatch of sr_launch_ct_direct: the five series staged
+//                       the same value by whoever meets one: no atomics); the tile transpose is pack_planes_tile (sr_pack_planes.h)
+//   k_ct_modes<W>       one (vector, chunk) per workgroup or per slab of one (the scaffold and the launch ladder of sr_ct_staged.h): the five series staged
 //                       as k_ct_dipolar stages its w series (sr_ct_dipolar.h), 20 bytes per frame; per lag block the seven shifted-product
 //                       sums (0,0) (1,1) (0,1) (1,0) (2,2) (3,3) (4,4) by seven calls of dip_shift_block_w, one sum at a time so that
 //                       only one set of float64 accumulators lives beside the inner loop: float32 FMAs, float32 partial sums of at most
@@ -27,6 +27,8 @@
 // Why seven calls and not one fused block: docs/EXPERIMENTS.md section 37.
 // A chunk must fit 20 ct_Fp(F) bytes of LDS: F <= 7968 at 160 KiB.  Longer chunks would take a blocked form.
 #include "sr_ct_dipolar.h"
+#include "sr_ct_staged.h"
+#include "sr_pack_planes.h"
 #include "sr_noe_host.h"
 #include <cmath>
 
@@ -35,8 +37,6 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // the five-plane pack
 // ------------------------------------------------------------------------------------------
-constexpr int kModeVecs = 32;           // vectors per tile: a frame's 32 vectors are 96 consecutive floats
-constexpr int kModeFrames = 64;         // frames per tile
 constexpr int kModeSig = 5;             // signals per vector
 constexpr int kModeSums = 6;            // sums per (vector, chunk, lag)
 constexpr int kModeFinV = 16;           // vectors per workgroup of k_ct_modes_finalize: k_ct_finalize's, whose grid sr_ct_rows_check bounds
@@ -48,77 +48,42 @@ struct ModeFrame {
 __global__ __launch_bounds__(256) void k_pack_modes(const float *__restrict__ vecs, int64_t N, int64_t Vtot, int64_t v0, int64_t nV,
                                                     const ModeFrame fr, float *__restrict__ soa, int64_t Npad, int32_t *__restrict__ bad)
 {
+    pack_planes_tile<kModeSig>(vecs, N, Vtot, v0, nV, soa, Npad, [=](const float *p, int64_t, int64_t v, float (&o)[kModeSig]) {
 #pragma clang fp contract(off)
-    __shared__ float tile[kModeVecs * kModeSig][kModeFrames + 1];
-    const int64_t n0 = (int64_t)blockIdx.x * kModeFrames;
-    const int64_t vb = (int64_t)blockIdx.y * kModeVecs;
-    const int nvec = (int)min((int64_t)kModeVecs, nV - vb);
-    const int tid = threadIdx.x;
-    for (int idx = tid; idx < kModeFrames * nvec; idx += 256) {
-        const int n = idx / nvec, k = idx - n * nvec;
-        const int64_t f = n0 + n;
-        float o[kModeSig] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        if (f < N) {
-            const float *p = vecs + (f * Vtot + v0 + vb + k) * 3;
-            const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
-            const double len = sqrt(x * x + y * y + z * z);
-            if (!(len > 0.0) || isinf(len)) {
-                bad[vb + k] = 1;
-            } else {
-                const double ux = (fr.m[0] * x + fr.m[1] * y + fr.m[2] * z) / len;
-                const double uy = (fr.m[3] * x + fr.m[4] * y + fr.m[5] * z) / len;
-                const double uz = (fr.m[6] * x + fr.m[7] * y + fr.m[8] * z) / len;
-                o[0] = (float)(uz * uz - 1.0 / 3.0);
-                o[1] = (float)(ux * ux - uy * uy);
-                o[2] = (float)(uy * uz);
-                o[3] = (float)(ux * uz);
-                o[4] = (float)(ux * uy);
-            }
+        const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+        const double len = sqrt(x * x + y * y + z * z);
+        if (!(len > 0.0) || isinf(len)) {
+            bad[v] = 1;
+        } else {
+            const double ux = (fr.m[0] * x + fr.m[1] * y + fr.m[2] * z) / len;
+            const double uy = (fr.m[3] * x + fr.m[4] * y + fr.m[5] * z) / len;
+            const double uz = (fr.m[6] * x + fr.m[7] * y + fr.m[8] * z) / len;
+            o[0] = (float)(uz * uz - 1.0 / 3.0);
+            o[1] = (float)(ux * ux - uy * uy);
+            o[2] = (float)(uy * uz);
+            o[3] = (float)(ux * uz);
+            o[4] = (float)(ux * uy);
         }
-#pragma unroll
-        for (int c = 0; c < kModeSig; ++c) tile[k * kModeSig + c][n] = o[c];
-    }
-    __syncthreads();
-    const int row = nvec * kModeSig;
-    for (int idx = tid; idx < kModeFrames * row; idx += 256) {
-        const int k = idx / kModeFrames, n = idx - k * kModeFrames;
-        const int64_t f = n0 + n;
-        if (f < Npad) soa[(vb * kModeSig + k) * Npad + f] = tile[k][n];
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------
 // the correlation kernel
 // ------------------------------------------------------------------------------------------
-struct CtModesArgs {
-    const float *soa;             // (nV, 5, Npad)
-    int64_t Npad;
-    const int64_t *chunk_start;   // device, may be null
-    double *psum;                 // (nV, R, 6, Lp): slot k holds lag k
-    double *ssum;                 // (nV, R, 5): the sums of the five signals over the chunk
-    int R, F, Fp, L, Lp, nslab, mode;
-};
-
 #ifndef SR_CT_MODES_WAVES_EU
 #define SR_CT_MODES_WAVES_EU 3
 #endif
 template <int W>
-__global__ __launch_bounds__(W * 64, SR_CT_MODES_WAVES_EU) void k_ct_modes(CtModesArgs a)
+__global__ __launch_bounds__(W * 64, SR_CT_MODES_WAVES_EU) void k_ct_modes(CtStagedArgs a)     // soa (nV, 5, Npad); psum (nV, R, 6, Lp): slot k holds lag k; sums = ssum (nV, R, 5)
 {
     extern __shared__ __align__(16) float lds[];
-    const int Fp = a.Fp, Hw = Fp >> 1, F = a.F;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int series = blockIdx.x / a.nslab;
-    const int slab = blockIdx.x - series * a.nslab;
-    const int v = series / a.R;
-    const int r = series - v * a.R;
+    const int Fp = a.Fp, Hw = Fp >> 1, F = a.F, Lp = a.Lp;
+    const CtWorker w = ct_worker<W>(a, a.nslab);
+    const int tid = w.tid, lane = w.lane;
 
     // ---- stage the five series, series c at lds + c Fp (coalesced dword loads; zero padding behind frame F) ----
     {
-        const int64_t start = a.chunk_start ? a.chunk_start[r] : (int64_t)r * F;
-        const float *p = a.soa + (int64_t)v * kModeSig * a.Npad + start;
+        const float *p = a.soa + (int64_t)w.row * kModeSig * a.Npad + ct_chunk_start(a, w);
         for (int e = tid; e < Fp; e += W * 64) {
             const int pos = lds_wpos(e, Hw);
             const bool in = e < F;
@@ -129,7 +94,7 @@ __global__ __launch_bounds__(W * 64, SR_CT_MODES_WAVES_EU) void k_ct_modes(CtMod
     __syncthreads();
 
     // ---- the sums of the five signals over the chunk, float64, fixed order ----
-    if (slab == 0 && wave == 0) {
+    if (w.slab == 0 && w.wave == 0) {
         double s[kModeSig];
 #pragma unroll
         for (int c = 0; c < kModeSig; ++c) s[c] = 0.0;
@@ -141,67 +106,52 @@ __global__ __launch_bounds__(W * 64, SR_CT_MODES_WAVES_EU) void k_ct_modes(CtMod
 #pragma unroll
         for (int c = 0; c < kModeSig; ++c) {
             s[c] = wave_sum_f64(s[c]);
-            if (lane == 0) a.ssum[((int64_t)v * a.R + r) * kModeSig + c] = s[c];
+            if (lane == 0) a.sums[((int64_t)w.row * a.R + w.r) * kModeSig + c] = s[c];
         }
     }
 
-    const int nb = (a.mode == 0) ? (a.L + 1) / kLagBlock : 0;
-    const int NW = a.nslab * W;            // workers (waves) per series
-    const int wid = slab * W + wave;
-    double *out = a.psum + ((int64_t)v * a.R + r) * kModeSums * a.Lp;
+    const int nb = ct_full_blocks(a);
+    const int NW = ct_workers<W>(a.nslab), wid = ct_worker_id<W>(w);
+    double *out = ct_psum_row(a, w, kModeSums * Lp);
 
-    // ---- fast path: full lag blocks (lag 0 included), serpentine assignment balances the (F - lag) work ----
-    int g, l16;
-    lane_to_strip(lane, g, l16);
-    for (int i = 0; i * NW < nb; ++i) {
-        const int k = (i & 1) ? i * NW + (NW - 1 - wid) : i * NW + wid;
-        if (k >= nb) continue;
-        const int dw = k * kLagBlock;
-        const int lag0 = dw + kLagsPerLane * l16;
+    // ---- fast path: full lag blocks (lag 0 included) ----
+    ct_for_each_lag_block(nb, NW, wid, lane, [=](int dw, int g, int l16) SR_CT_INLINE {
         // one sum at a time: (0,0) | (1,1) | (0,1) + (1,0) | (2,2) | (3,3) | (4,4)
 #pragma unroll 1
         for (int c = 0; c < kModeSums; ++c) {
             double acc[kLagsPerLane];
-#pragma unroll
-            for (int d = 0; d < kLagsPerLane; ++d) acc[d] = 0.0;
+            ct_zero_lags(acc);
             const int sa = c < 2 ? c : (c == 2 ? 0 : c - 1), sb = c < 2 ? c : (c == 2 ? 1 : c - 1);     // earlier and later series
             dip_shift_block_w(lds + sa * Fp, lds + sb * Fp, Hw, F, dw, g, l16, acc, 0.f);
             if (c == 2) dip_shift_block_w(lds + Fp, lds, Hw, F, dw, g, l16, acc, 0.f);
             ct_combine_strips(acc, l16);
             if (g == 0) {
-                double *o = out + (int64_t)c * a.Lp + lag0;
+                double *o = ct_lag_slots(out + (int64_t)c * Lp, dw, l16);
 #pragma unroll
                 for (int d = 0; d < kLagsPerLane; ++d) o[d] = c == 2 ? 0.5 * acc[d] : acc[d];
             }
         }
-    }
+    });
 
     // ---- float64 path: remaining lags (and every lag in validation mode) ----
-    for (int d = nb * kLagBlock + wid; d <= a.L; d += NW) {
-        double s[kModeSums];
+    ct_tail_lags<kModeSums>(nb * kLagBlock, a.L, F, NW, wid, lane, [=](int j, int d, double (&s)[kModeSums]) SR_CT_INLINE {
+        const int pa = lds_wpos(j, Hw), pb = lds_wpos(j + d, Hw);
+        double x[kModeSig], y[kModeSig];
 #pragma unroll
-        for (int c = 0; c < kModeSums; ++c) s[c] = 0.0;
-        for (int j = lane; j + d < F; j += 64) {
-            const int pa = lds_wpos(j, Hw), pb = lds_wpos(j + d, Hw);
-            double x[kModeSig], y[kModeSig];
-#pragma unroll
-            for (int c = 0; c < kModeSig; ++c) {
-                x[c] = (double)lds[c * Fp + pa];
-                y[c] = (double)lds[c * Fp + pb];
-            }
-            s[0] += x[0] * y[0];
-            s[1] += x[1] * y[1];
-            s[2] += x[0] * y[1] + x[1] * y[0];
-            s[3] += x[2] * y[2];
-            s[4] += x[3] * y[3];
-            s[5] += x[4] * y[4];
+        for (int c = 0; c < kModeSig; ++c) {
+            x[c] = (double)lds[c * Fp + pa];
+            y[c] = (double)lds[c * Fp + pb];
         }
+        s[0] += x[0] * y[0];
+        s[1] += x[1] * y[1];
+        s[2] += x[0] * y[1] + x[1] * y[0];
+        s[3] += x[2] * y[2];
+        s[4] += x[3] * y[3];
+        s[5] += x[4] * y[4];
+    }, [=](int d, const double (&s)[kModeSums]) SR_CT_INLINE {
 #pragma unroll
-        for (int c = 0; c < kModeSums; ++c) {
-            s[c] = wave_sum_f64(s[c]);
-            if (lane == 0) out[(int64_t)c * a.Lp + d] = c == 2 ? 0.5 * s[c] : s[c];
-        }
-    }
+        for (int c = 0; c < kModeSums; ++c) out[(int64_t)c * Lp + d] = c == 2 ? 0.5 * s[c] : s[c];
+    });
 }
 
 // H, dH (L + 1, nV, 6): mean over the R chunks of S / (F - k) and its std / (sqrt(R) - 1), numpy.std's two passes in chunk order as
@@ -244,12 +194,6 @@ __global__ __launch_bounds__(256) void k_ct_modes_finalize(const double *__restr
     }
 }
 
-template <int W>
-int launch_modes(sr_ctx *ctx, const CtModesArgs &a, int64_t nblocks, size_t lds_bytes)
-{
-    return sr_launch(ctx, k_ct_modes<W>, dim3((unsigned)nblocks), dim3(W * 64), lds_bytes, a);
-}
-
 }  // namespace
 
 extern "C" {
@@ -265,12 +209,8 @@ int sr_pack_modes_f32_dev(sr_ctx *ctx, const float *vecs, int64_t N, int64_t Vto
 {
     SR_CHECK_CTX(ctx);
     SR_REQUIRE(vecs && planes && bad, -2, "sr_pack_modes_f32_dev: null pointer");
-    SR_REQUIRE(N > 0 && Vtot > 0 && nV > 0 && v0 >= 0 && v0 + nV <= Vtot, -3, "sr_pack_modes_f32_dev: bad shape N=%lld Vtot=%lld v0=%lld nV=%lld",
-               (long long)N, (long long)Vtot, (long long)v0, (long long)nV);
-    SR_REQUIRE(Npad >= N && Npad % 4 == 0, -3, "sr_pack_modes_f32_dev: Npad=%lld must be >= N and a multiple of 4", (long long)Npad);
-    const int64_t gx = (Npad + kModeFrames - 1) / kModeFrames;
-    const int64_t gy = (nV + kModeVecs - 1) / kModeVecs;
-    SR_REQUIRE(gy <= 65535, -3, "sr_pack_modes_f32_dev: too many vectors in one call (%lld)", (long long)nV);
+    dim3 grid;
+    if (int rc = pack_planes_grid("sr_pack_modes_f32_dev", N, Vtot, v0, nV, Npad, grid)) return rc;
     ModeFrame fr;
     char msg[160];
     if (int rc = noe_frame_matrix(frame_quat_host, fr.m, msg, sizeof msg)) {
@@ -278,7 +218,7 @@ int sr_pack_modes_f32_dev(sr_ctx *ctx, const float *vecs, int64_t N, int64_t Vto
         return rc;
     }
     SR_HIP(hipMemsetAsync(bad, 0, (size_t)nV * sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(k_pack_modes, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, ctx->stream, vecs, N, Vtot, v0, nV, fr, planes, Npad, bad);
+    hipLaunchKernelGGL(k_pack_modes, grid, dim3(256), 0, ctx->stream, vecs, N, Vtot, v0, nV, fr, planes, Npad, bad);
     SR_HIP(hipGetLastError());
     return 0;
 }
@@ -295,29 +235,12 @@ int sr_ct_modes_f32_dev(sr_ctx *ctx, const float *planes, int64_t Npad, int64_t 
     if (!psum) return -5;
     // ---- stage the chunk starts; the chunk sums of the five signals live behind them ----
     sr_stage st(ctx);
-    CtModesArgs a;
-    a.chunk_start = sr_ct_stage_tables(st, w, kModeSig * (size_t)(nV * R) * sizeof(double)).chunk_start;
-    a.ssum = st.take<double>(kModeSig * (size_t)(nV * R));
+    const int64_t *cs_dev = sr_ct_stage_tables(st, w, kModeSig * (size_t)(nV * R) * sizeof(double)).chunk_start;
+    CtStagedArgs a = ct_staged_args(planes, Npad, cs_dev, psum, R, F, mode);
+    a.sums = st.take<double>(kModeSig * (size_t)(nV * R));
     if (int rc = chunk_start_host ? st.finish() : st.rc) return rc;     // tiny table: the caller's array is free again when this returns
-    // ---- launch: the dispatch of sr_launch_ct_direct ----
-    a.soa = planes; a.Npad = Npad; a.psum = psum;
-    a.R = (int)R; a.F = (int)F; a.Fp = (int)ct_Fp(F); a.L = (int)L; a.Lp = (int)Lp; a.mode = mode;
-    const size_t lds_bytes = sr_ct_lds_bytes(F, sr_ct_form_modes.bytes_per_frame);
-    const int nb = mode == 0 ? (int)((L + 1) / kLagBlock) : 0;
-    const int64_t series = R * nV;
-    int rc;
-    if (mode == 1) {
-        a.nslab = 1;
-        rc = launch_modes<4>(ctx, a, series, lds_bytes);
-    } else if (nb >= 16) {
-        a.nslab = 1;                                 // 4-8 lag blocks per wave: a chunk that fits has at most 31 blocks
-        rc = launch_modes<4>(ctx, a, series, lds_bytes);
-    } else {
-        a.nslab = nb > 0 ? nb : 1;                   // one wave per workgroup, one lag block per wave
-        rc = launch_modes<1>(ctx, a, series * a.nslab, lds_bytes);
-    }
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_ct_modes_finalize, dim3((unsigned)((L + 1 + 63) / 64), (unsigned)((nV + kModeFinV - 1) / kModeFinV)), dim3(256), 0, ctx->stream, psum, a.ssum,
+    if (int rc = ct_launch_slabs(ctx, k_ct_modes<1>, k_ct_modes<4>, a, R * nV, sr_ct_form_modes.bytes_per_frame)) return rc;
+    hipLaunchKernelGGL(k_ct_modes_finalize, dim3((unsigned)((L + 1 + 63) / 64), (unsigned)((nV + kModeFinV - 1) / kModeFinV)), dim3(256), 0, ctx->stream, psum, a.sums,
                        (int)R, (int)F, (int)L, (int)Lp, nV, H, dH, smean);
     SR_HIP(hipGetLastError());
     return 0;

@@ -1,5 +1,8 @@
-// sr_ct_shift.h -- the shifted-product lag block of the direct kernels: k_ct_palmer (sr_ct_direct.hip: one series against itself) and
-// k_ct_cross (sr_ct_cross.hip: two series against each other) stage their series in the same LDS layout and run the same inner loop.
+// sr_ct_shift.h -- the shifted-product lag block of the staged correlation kernels on xyz series: k_ct_palmer (sr_ct_direct.hip: one
+// series against itself), k_ct_cross (sr_ct_cross.hip: two series against each other), k_ct_dipolar (sr_ct_dipolar.hip: the a planes
+// against themselves) and k_ct_dipolar_cross (sr_ct_dipolar_cross.hip: the a planes of two vectors) stage their series in the same LDS
+// layout and run the same inner loop; the lane map and ct_combine_strips also serve the scalar series of sr_ct_dipolar.h, which
+// k_ct_modes (sr_ct_modes.hip) uses alone.  What the five kernels share around the inner loop: sr_ct_staged.h.
 //
 // A staged series: Fp = ct_Fp(F) frames, zero behind frame F, "chunk-parity split, xyz-interleaved": 16-byte
 // chunk c (4 frames of one component) lives in half (c & 1) at slot (c >> 1); a slot is 48 bytes = [x-chunk | y-chunk | z-chunk];
